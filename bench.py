@@ -11,20 +11,22 @@ contract; `--frames-from-host` and the `frames_from_pinned_host` leg time the sa
 The geometry consumes exactly what the network emitted (data-dependent keypoint counts and graphs): the weights are random (no
 checkpoint ships) with the classifier bias raised and T-LESS-like thresholds so that the masks pass -- the keypoints are then
 meaningless as measurements, which makes this the WORST case for the geometry (RANSAC runs to its 1000-iteration cap, LM works
-on poorly conditioned graphs); that geometry is right on good measurements is checked after the timed region (`pose_check`:
+on poorly conditioned graphs); that geometry is right on good measurements is checked after the timed region under --full (`pose_check`:
 the same chain on projected ground-truth keypoints + noise, the reference's --debug_gt_kp mode, against the ground truth and
 the CPU oracle).  `value` is frames/s = steps * frames_per_step * n_gpus / elapsed; every network call processes exactly the
 frames that are counted.  Frames of the single-view stream are independent (evaluate.py:345-346), which is what allows
-batching them; the reference's own call shape (one frame per call) is timed separately (`latency`).
+batching them; the reference's own call shape (one frame per call) is timed separately (`latency`, under --full).
 
-Legs after the timed region, never part of `value` and each fenced (an exception or a time-out in one costs only that leg):
+A plain run sets up, warms up, times the steps, writes the last timed step's outputs (--dump-outputs DIR) and prints the line.
+Everything else it can measure runs only with --full: the power / clock sample beside the timed region, the whole-call HBM accounting,
+and the legs after the timed region, never part of `value` and each fenced (an exception or a time-out in one costs only that leg):
 `roofline` (dominant kernel + the largest 1x1 GEMM + the latency-mode launch under HIP events), `frames_from_pinned_host`, `pose_check`, `latency`,
 `drop_in` (ObjectSLAM.process_view, the thing evaluate.py calls, one frame per call), `slam` (BASELINE configs[2]: a 60-view
 sequence through ObjectSLAM.process_view, the reference's two timing meters), `global_ba` (BASELINE configs[4]'s exchange
 step over RCCL -- on one GPU over a ONE-rank RCCL group with every collective issued), `fp32_pipe` (the same timed region with every
 product on the fp32 matrix pipe, in a child process, + the dominant kernel's error against fp64 for both pipes), `cpu_baseline` (the oracle on the host cores, best of a thread sweep; rank 0 at N=1 only).
 
-    python bench.py --gpus N --steps K --warmup W
+    python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR] [--full]
 N > 1 without a launcher: this process starts `python -m torch.distributed.run --nproc-per-node N bench.py ...` as a child
 (before anything touches the GPU), relays its output and exit code.  Under a launcher (WORLD_SIZE set) it is one rank.
 """
@@ -66,7 +68,10 @@ def parse():
                     help="frames of the stream batched into one network call = one step (--objects crops each)")
     ap.add_argument("--only", choices=["all", "cnn"], default="all", help="diagnostic: network half of the step only")
     ap.add_argument("--frames-from-host", action="store_true", help="frames in pinned host memory, uploaded inside the timed region (rounds 1-4's `value`); default: resident in HBM")
-    ap.add_argument("--no-legs", action="store_true", help="timed region only (profiling runs)")
+    ap.add_argument("--full", action="store_true", help="also the power sample beside the timed region, the whole-call roofline and the legs after it "
+                                                        "(off: set-up, warm-up, the timed steps, --dump-outputs and the line)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None, help="write what the last timed step returned as DIR/<name>.npy (float32 / float64)")
+    ap.add_argument("--no-legs", action="store_true", help="with --full: timed region only (profiling runs)")
     ap.add_argument("--no-latency-leg", action="store_true")
     ap.add_argument("--no-global-ba-leg", action="store_true")
     ap.add_argument("--no-slam-leg", action="store_true")
@@ -92,6 +97,26 @@ def spawn_ranks(args):
     env.setdefault("HSA_ENABLE_IPC_MODE_LEGACY", "0")
     env.setdefault("OMP_NUM_THREADS", str(max(1, len(os.sched_getaffinity(0)) // args.gpus)))
     return subprocess.call(cmd, env=env)
+
+
+DUMP_LIMIT_BYTES = 64 << 20
+
+
+def dump_outputs(d, pipe, last_step):
+    """--dump-outputs: what the caller of the timed path received in the last timed step, one DIR/<name>.npy per array (float32 / float64).  The
+    pool, the weights and the RANSAC seeds follow from the arguments, so two builds run with the same arguments can be compared array for array.
+    Above DUMP_LIMIT_BYTES a fixed, seeded sample of the crops is kept (`crop_index` names them)."""
+    i, outs = pipe.last_outputs()
+    assert i == last_step, (i, last_step)
+    n = outs["uv"].shape[0]
+    total = sum(a.nbytes for a in outs.values())
+    if total > DUMP_LIMIT_BYTES:
+        keep = np.sort(np.random.default_rng(0).choice(n, max(1, int(n * DUMP_LIMIT_BYTES * 0.9 / total)), replace=False))
+        outs = {k: (a[keep] if a.shape[0] == n else a) for k, a in outs.items()}
+        outs["crop_index"] = keep.astype(np.float64)
+    os.makedirs(d, exist_ok=True)
+    for k, a in outs.items():
+        np.save(os.path.join(d, k + ".npy"), np.ascontiguousarray(a))
 
 
 _LINE_FD = None
@@ -147,7 +172,8 @@ def main():
         dist.all_reduce(seen)
     n_ranks_seen = int(seen.item())
     rccl_backend = (dist.get_backend() if world > 1 else None)
-    if world == 1 and on_gpu and backend == "nccl" and not args.no_legs and not args.no_global_ba_leg and not args.dry_run:
+    legs = args.full and not args.no_legs
+    if world == 1 and on_gpu and backend == "nccl" and legs and not args.no_global_ba_leg and not args.dry_run:
         # one GPU: a ONE-rank RCCL group, so that the global_ba leg issues the collectives of the multi-GPU schedule for real
         try:
             sk = socket.socket()
@@ -187,7 +213,8 @@ def main():
     pipe.reset_metrics()
     barrier()
     power = {}
-    if rank == 0 and not args.no_power_sample:
+    sample = rank == 0 and args.full and not args.no_power_sample
+    if sample:
         # package power / shader clock WHILE the timed region runs (rocm-smi in a child process started now; it answers ~0.3 s in): the call runs
         # at the package power cap (profiles/r04_power_trace.txt), which is what bounds its matrix-pipe utilisation
         import threading as _th
@@ -206,7 +233,7 @@ def main():
     pipe.drain(args.warmup + args.steps)        # every timed step's read-back is fetched inside the timed region
     barrier()
     dt = time.perf_counter() - t0
-    if rank == 0 and not args.no_power_sample:
+    if sample:
         power_stop.set()
         power_thread.join(timeout=2.0)
         if "t_done" in power:                                # (the rocm-smi route: keep the reading only if it came back inside the region)
@@ -219,6 +246,8 @@ def main():
     from suo_slam_amd import sharding
     dt, (n_kp, n_pose, n_inl, n_trials) = sharding.reduce_metrics(dt, [pipe.n_kp, pipe.n_pose, pipe.n_inl, pipe.n_trials],
                                                                    device="cuda" if backend == "nccl" else "cpu")
+    if rank == 0 and args.dump_outputs:
+        dump_outputs(args.dump_outputs, pipe, args.warmup + args.steps - 1)
     # ---- the line: the timed region first; then the legs, each fenced.  Legs write into `extra` under a lock; the watchdog prints
     # a snapshot of what exists and leaves if they do not finish in time: they are reported beside `value`, they never cost it.
     import threading
@@ -296,7 +325,7 @@ def main():
         with lock:
             (extra if into is None else extra.setdefault(into, {}))[name] = val
 
-    if rank == 0:
+    if rank == 0 and args.full:
         # the whole call against the HBM roof: algorithmic bytes of every launch of one step's network call (a dry run of the schedule that just ran) / step time
         try:
             from bench_legs.roofline import whole_call
@@ -306,7 +335,7 @@ def main():
         except Exception as e:
             with lock:
                 extra.setdefault("roofline_all", {})["whole_call"] = {"error": repr(e)[:300]}
-    if not args.no_legs and args.only == "all":
+    if legs and args.only == "all":
         del pipe                                  # free the timed region's slots before the legs build their own
         if not args.no_global_ba_leg:
             # BASELINE configs[4]'s exchange step, on every rank.  The ranks agree that set-up succeeded before the first

@@ -48,6 +48,7 @@ class FramePipeline:
                  "h_kps": torch.empty((LF, 41, 3)).pin_memory()}
             self.slots.append(S)
         self.first = np.arange(F + 1, dtype=np.int32) * L
+        self.last = None
         self.reset_metrics()
 
     def reset_metrics(self):
@@ -119,8 +120,10 @@ class FramePipeline:
         if self.only == "cnn":
             S["ev"].synchronize()
             self.check_range(S)
+            self.last = (i, S, None)
             return None
         r = S["fg"].fetch(copy=False)
+        self.last = (i, S, r)          # the newest retired step (views into the slot's pinned block: valid until the slot's next launch)
         self.check_range(S)
         assert np.isfinite(r["uv"]).all() and np.isfinite(r["T_opt"][r["accepted"]]).all()
         self.n_kp += int(r["n_kp"].sum())
@@ -147,3 +150,18 @@ class FramePipeline:
         """Retire every step still in flight, oldest first."""
         for k in range(self.depth):
             self.retire(self.slots[(next_step + k) % self.depth])
+
+    def last_outputs(self):
+        """What the caller of the path received for the newest retired step, as float arrays (call after drain, before any further step): the
+        read-back of suo_frame_geom_fetch, or the network's uv / cov / kp under --only cnn.  Slots of chi2 / inlier past a crop's n_kp hold no
+        keypoint (include/suo_hip.h: suo_frame_geom_fetch) and are zeroed."""
+        i, S, r = self.last
+        if r is None:
+            self.torch.cuda.synchronize()
+            out = {k: S[k].cpu().numpy() for k in ("uv", "cov", "kp")}
+        else:
+            out = {k: np.array(v) for k, v in r.items()}
+            past = np.arange(out["chi2"].shape[1])[None, :] >= out["n_kp"][:, None]
+            out["chi2"][past] = 0.0
+            out["inlier"][past] = False
+        return i, {k: v if v.dtype in (np.float32, np.float64) else v.astype(np.float64) for k, v in out.items()}

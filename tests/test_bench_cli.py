@@ -93,3 +93,61 @@ def test_line_bookkeeping_of_round_6():
     import json
     rec = json.load(open(os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "profiles", "pmc_dominant_conv.json")))
     assert rec["kernel"].replace(" ", "").startswith(bench.dominant_kernel_name())
+
+
+def test_full_and_dump_outputs_flags():
+    """A plain run (the driver's flags) does only the headline's work: the legs, the power sample and the whole-call roofline need --full."""
+    _, args = _bench(["--gpus", "1", "--steps", "20", "--warmup", "5"])
+    assert args.full is False and args.dump_outputs is None
+    _, args = _bench(["--full", "--dump-outputs", "out_dir"])
+    assert args.full is True and args.dump_outputs == "out_dir"
+
+
+def _fake_pipeline(step, n_crops=6, n_frames=2):
+    from bench_legs.pipeline import FramePipeline
+    import numpy as np
+    rng = np.random.default_rng(0)
+    n_kp = np.array([0, 4, 41, 7, 12, 5][:n_crops], np.int32)
+    r = {"T_pnp": rng.standard_normal((n_crops, 4, 4)), "T_opt": rng.standard_normal((n_crops, 3, 4)), "chi2": rng.uniform(0, 9, (n_crops, 41)),
+         "pnp_status": np.zeros(n_crops, np.int32), "pnp_best_inliers": n_kp.copy(), "pnp_iterations": np.full(n_crops, 1000, np.int32), "n_kp": n_kp,
+         "lm_stats": np.ones((n_frames, 4), np.int32), "accepted": n_kp >= 4, "inlier": np.ones((n_crops, 41), bool),
+         "uv": rng.standard_normal((n_crops, 41, 2)).astype(np.float32), "cov": rng.standard_normal((n_crops, 41, 2, 2)).astype(np.float32),
+         "mask": np.ones((n_crops, 41), bool)}
+    p = object.__new__(FramePipeline)
+    p.last = (step, None, r)
+    return p, r
+
+
+def test_dump_outputs_writes_the_last_step_as_floats(tmp_path):
+    import numpy as np
+    bench, _ = _bench([])
+    p, r = _fake_pipeline(11)
+    bench.dump_outputs(str(tmp_path), p, 11)
+    got = {f[:-4]: np.load(os.path.join(str(tmp_path), f)) for f in os.listdir(str(tmp_path))}
+    assert set(got) == set(r)
+    assert all(a.dtype in (np.float32, np.float64) for a in got.values())
+    assert got["uv"].dtype == np.float32 and got["T_opt"].dtype == np.float64 and np.array_equal(got["T_opt"], r["T_opt"])
+    assert np.array_equal(got["accepted"], r["accepted"].astype(np.float64)) and np.array_equal(got["pnp_iterations"], np.full(6, 1000.0))
+    # slots past a crop's n_kp hold no keypoint: zeroed, the rest untouched
+    past = np.arange(41)[None, :] >= r["n_kp"][:, None]
+    assert not got["chi2"][past].any() and np.array_equal(got["chi2"][~past], r["chi2"][~past])
+    assert not got["inlier"][past].any() and got["inlier"][~past].all()
+    import pytest
+    with pytest.raises(AssertionError):
+        bench.dump_outputs(str(tmp_path), _fake_pipeline(10)[0], 11)          # a dump that is not of the last timed step is refused
+
+
+def test_dump_outputs_samples_crops_above_the_limit(tmp_path, monkeypatch):
+    import numpy as np
+    bench, _ = _bench([])
+    p, r = _fake_pipeline(3)
+    monkeypatch.setattr(bench, "DUMP_LIMIT_BYTES", 6000)           # 11.5 kB in all
+    bench.dump_outputs(str(tmp_path), p, 3)
+    names = os.listdir(str(tmp_path))
+    assert sum(os.path.getsize(os.path.join(str(tmp_path), f)) for f in names) < 6000 + 200 * len(names)       # (+ the .npy headers)
+    idx = np.load(os.path.join(str(tmp_path), "crop_index.npy")).astype(int)
+    assert 1 <= len(idx) < 6 and np.all(np.diff(idx) > 0)
+    assert np.array_equal(np.load(os.path.join(str(tmp_path), "T_pnp.npy")), r["T_pnp"][idx])
+    again = tmp_path / "again"
+    bench.dump_outputs(str(again), _fake_pipeline(3)[0], 3)                    # the sample is fixed
+    assert np.array_equal(np.load(str(again / "crop_index.npy")), idx)

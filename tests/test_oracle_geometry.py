@@ -1,7 +1,7 @@
 """Pin the geometry oracle (oracle/pnp_oracle.c, oracle/lm_oracle.c).  CPU only.
 
 P3P/P4P: bit-exact against golden vectors produced by the reference's own p4p.cpp
-(tests/golden/make_pnp_golden.py) and, when oracle/_ref is present, against that library live;
+(tests/golden/make_pnp_golden.py, make_ref_live_golden.py) and, when oracle/_ref is present, against that library live;
 the reference's known-answer vector (thirdparty/lambdatwist/test_pnp.py:5-14) to its printed
 precision.  RANSAC/refine and the g2o-style LM cannot be pinned by execution (Ceres / Eigen /
 CHOLMOD are absent): property tests follow thirdparty/lambdatwist/test_pnp.cpp:68-147 and
@@ -9,7 +9,6 @@ thirdparty/g2opy/python/examples/object_slam_demo.py:49-178."""
 import os
 
 import numpy as np
-import pytest
 
 from oracle import geometry as G
 from suo_slam_amd import geometry as geo
@@ -33,16 +32,17 @@ def test_p4p_p3p_bit_exact_vs_reference_vectors():
 
 
 def test_p4p_live_reference_library():
-    if G.ref() is None:
-        pytest.skip("oracle/_ref not built (needs /root/reference)")
-    rng = np.random.default_rng(5)
-    for _ in range(300):
-        x = rng.uniform(-100, 100, (6, 3))
-        Q = S.random_rotation(rng)
-        X = x @ Q.T + np.array([rng.uniform(-50, 50), rng.uniform(-50, 50), rng.uniform(400, 1200)])
-        y = X[:, :2] / X[:, 2:3] + rng.normal(0, 1e-3, (6, 2))
-        idx = sorted(rng.choice(6, 4, replace=False).tolist())
-        assert np.array_equal(G.p4p(x, y, idx), G.ref_p4p(x, y, idx))
+    """Bit-exact against what the reference's compiled p4p.cpp returned on these inputs (tests/golden/make_ref_live_golden.py), and against that
+    library itself when oracle/_ref is built."""
+    from tests.golden import ref_live_cases
+    want = np.load(os.path.join(os.path.dirname(__file__), "golden", "ref_live_golden.npz"))["p4p_T"]
+    live = G.ref() is not None
+    for k, (x, y, idx) in enumerate(ref_live_cases.p4p_cases()):
+        got = G.p4p(x, y, idx)
+        assert np.array_equal(got, want[k]), k
+        if live:
+            assert np.array_equal(got, G.ref_p4p(x, y, idx)), k
+    assert k == len(want) - 1
 
 
 def test_known_answer_vector():

@@ -2,7 +2,8 @@
 std::uniform_int_distribution and a std::set (/root/reference/thirdparty/lambdatwist/utils/random.h:65-116, pnp_ransac.cpp:161-183).  Both restatements --
 the oracle's C (oracle/pnp_oracle.c: orc_ref_*) and the product's host-side table generator (suo_slam_amd/lambdatwist.py: ReferenceSampler, what feeds
 suo_pnp_replay) -- must reproduce the reference's sequence BIT FOR BIT: against tests/golden/sampler_golden.npz (generated from the reference's header compiled
-in the build container, tests/golden/make_sampler_golden.py) and, where oracle/_ref/librandom_ref.so is present, against that library directly."""
+in the build container, tests/golden/make_sampler_golden.py and make_ref_live_golden.py) and, where oracle/_ref/librandom_ref.so is present, against that
+library directly."""
 import os
 
 import numpy as np
@@ -29,23 +30,27 @@ def test_both_restatements_reproduce_the_golden_stream():
 
 
 def test_restatement_equals_the_compiled_reference_header():
+    """Interleaved raw draws and samples on one continuing stream: against what the reference's compiled random.h returned for them
+    (tests/golden/make_ref_live_golden.py), and against that library itself when oracle/_ref is built."""
+    from tests.golden import ref_live_cases
+    g = np.load(os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "ref_live_golden.npz"))
+    draws, offs = g["sampler_draws"], g["sampler_offsets"]
     R = G.ref_random()
-    if R is None:
-        pytest.skip("oracle/_ref/librandom_ref.so not built (`make -C oracle ref` needs /root/reference)")
-    R.ref_rng_reset()
+    if R is not None:
+        R.ref_rng_reset()
     o = G.RefSampler()
-    rng = np.random.default_rng(0)
-    for _ in range(40):                                                     # interleaved raw draws and samples on one continuing stream
-        n = int(rng.integers(4, 64))
-        k = int(rng.integers(1, 200))
-        if rng.random() < 0.5:
-            a = np.zeros(k, np.int32)
-            R.ref_randui(n, k, a)
-            assert [o.randui(0, n - 1) for _ in range(k)] == a.tolist()
+    for j, (kind, n, k) in enumerate(ref_live_cases.sampler_ops()):
+        want = draws[offs[j]:offs[j + 1]]
+        if kind == "randui":
+            got = np.array([o.randui(0, n - 1) for _ in range(k)], np.int32)
         else:
-            a = np.zeros((k, 4), np.int32)
-            R.ref_get4(n, k, a.reshape(-1))
-            assert np.array_equal(o.get4(n, k), a)
+            got = o.get4(n, k)
+        assert np.array_equal(got.reshape(-1), want), j
+        if R is not None:
+            a = np.zeros(len(want), np.int32)
+            (R.ref_randui if kind == "randui" else R.ref_get4)(n, k, a)
+            assert np.array_equal(a, want), j
+    assert j == len(offs) - 2
 
 
 def test_oracle_ransac_under_a_draw_table():

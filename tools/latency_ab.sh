@@ -3,5 +3,5 @@
 R=${GRAFT_REPO_ROOT:-$(cd "$(dirname "$0")/.." && pwd)}
 for c in "$@"; do
   echo "== $c"
-  env $c python3 $R/bench.py --no-cpu-baseline --no-slam-leg --no-global-ba-leg --steps 2 --warmup 1 2>/dev/null | python3 -c "import sys, json; d = json.loads(sys.stdin.readline()); print(json.dumps(d.get('latency')))"
+  env $c python3 $R/bench.py --full --no-cpu-baseline --no-slam-leg --no-global-ba-leg --steps 2 --warmup 1 2>/dev/null | python3 -c "import sys, json; d = json.loads(sys.stdin.readline()); print(json.dumps(d.get('latency')))"
 done

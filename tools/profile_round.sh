@@ -17,9 +17,9 @@ run_traced() {   # name, then the program and its arguments
 }
 if [ -z "${SUO_PROFILE_ONLY_PMC:-}" ]; then
 # 1. the bench line itself (all legs), and at the driver's flags
-python3 $R/bench.py > $OUT/bench_line.json 2> $OUT/bench.err
-python3 $R/bench.py --gpus 1 --steps 20 --warmup 5 > $OUT/bench_line_driver_flags.json 2>> $OUT/bench.err
-python3 $R/bench.py --no-cpu-baseline --no-slam-leg --no-latency-leg --objects 16 --frames-per-step 16 > $OUT/bench_line_objects16.json 2>> $OUT/bench.err
+python3 $R/bench.py --full > $OUT/bench_line.json 2> $OUT/bench.err
+python3 $R/bench.py --full --gpus 1 --steps 20 --warmup 5 > $OUT/bench_line_driver_flags.json 2>> $OUT/bench.err
+python3 $R/bench.py --full --no-cpu-baseline --no-slam-leg --no-latency-leg --objects 16 --frames-per-step 16 > $OUT/bench_line_objects16.json 2>> $OUT/bench.err
 # 2. kernel trace of the timed region (two steps in flight: per-kernel durations are concurrent-execution times)
 run_traced bench $R/bench.py --no-legs --steps 20 --warmup 5
 # 3. the same network calls one at a time (one stream, no graph): non-overlapped per-kernel durations at 256 crops per call
