@@ -77,15 +77,25 @@ int suo_net_schedule_bytes(suo_net* net, int L, int n_frames, int H, int W, int 
  *   SUO_PIPE_F16X2   operands as two fp16 terms, 3 of 4 cross products, fp32 accumulate (csrc/f16x2.h): half the matrix-pipe work, fp16's RANGE --
  *                    activations enter times 16, so a forward in which some |activation| >= 4094 is not computable in this form.  The kernels detect
  *                    that (they never write inf silently) and raise a flag:
- * suo_net_range_exceeded() returns 1 when a forward since its last call left the range -- the outputs of that forward are INVALID -- and clears the flag;
- * the network has then already been moved to SUO_PIPE_BF16X3 and the caller re-issues the call.  Call it after synchronising the stream and before
- * using the outputs.  Forwards on the NULL stream (blocking) check and re-issue by themselves. */
+ * Validity is PER CALL: a forward's outputs are invalid if and only if its own activations left the range.  Every forward is numbered 1, 2, ... in issue order
+ * (suo_net_last_call() returns the number of the last one issued); on SUO_PIPE_F16X2 it ends with a one-lane launch on its stream that moves the kernels'
+ * flag into that call's word (mapped host memory) and clears it for the next call, so a later call still running cannot mark an earlier one.
+ * suo_net_call_range_exceeded(net, call) returns 1 when that call left the range -- its outputs are INVALID; the network has then already been moved to
+ * SUO_PIPE_BF16X3 and the caller re-issues it (and whatever it enqueued behind it that consumed its outputs) --, 0 when its outputs are valid, -1 when it
+ * cannot tell (the call has not finished, or is older than the network's last 64 calls; suo_last_error() says which).  Call it after synchronising on the
+ * call's outputs and before using them.  The network moves to SUO_PIPE_BF16X3 when a query reports an invalid call, not before: calls issued meanwhile
+ * still run on SUO_PIPE_F16X2 and are queried like any other.
+ * suo_net_range_exceeded() returns 1 when a forward since its last call left the range (whether or not suo_net_call_range_exceeded reported it) and clears
+ * that record; on 1 the network has been moved to SUO_PIPE_BF16X3.  Call it after synchronising the stream.  Forwards on the NULL stream (blocking) check
+ * their own call and re-issue it by themselves. */
 #define SUO_PIPE_F32 0
 #define SUO_PIPE_BF16X3 1
 #define SUO_PIPE_F16X2 2
 int suo_net_get_pipe(const suo_net* net);
 int suo_net_set_pipe(suo_net* net, int pipe);
 int suo_net_range_exceeded(suo_net* net);
+uint64_t suo_net_last_call(const suo_net* net);
+int suo_net_call_range_exceeded(suo_net* net, uint64_t call);
 
 /* One frame: image either SUO_IMG_U8_HWC = uint8 [H,W,3] as cv2.imread gives it (scaled by 1/255 on
  * device: object_slam.py:1092 fused) or SUO_IMG_F32_CHW = float32 [3,H,W] already scaled (the tensor

@@ -54,6 +54,8 @@ SIGNATURES = {
     "suo_net_get_pipe": (C.c_int, [VP]),
     "suo_net_set_pipe": (C.c_int, [VP, C.c_int]),
     "suo_net_range_exceeded": (C.c_int, [VP]),
+    "suo_net_last_call": (C.c_uint64, [VP]),
+    "suo_net_call_range_exceeded": (C.c_int, [VP, C.c_uint64]),
     "suo_pack_gemm_weight_f16x2": (C.c_int, [VP, C.c_int, C.c_int, VP, VP]),
     "suo_conv1x1_f16x2_ex": (C.c_int, [VP, C.c_int, C.c_int, VP, VP, VP, C.c_int, C.c_int, VP, VP, VP, VP, C.c_int, VP, C.c_int, C.c_int, C.c_int, C.c_int, VP, VP]),
     "suo_conv1x1_f16x2_pool": (C.c_int, [VP, C.c_int, C.c_int, VP, VP, VP, C.c_int, C.c_int, VP, VP, VP, VP, C.c_int, VP, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, VP, VP, VP]),

@@ -67,6 +67,11 @@ int suo_net_schedule_bytes(suo_net* net, int L, int n_frames, int H, int W, int 
 int suo_net_get_pipe(const suo_net* net) { return net ? net->impl->pipe() : -1; }
 int suo_net_set_pipe(suo_net* net, int pipe) { return net ? net->impl->set_pipe(pipe) : SUO_ERR_ARG; }
 int suo_net_range_exceeded(suo_net* net) { return net ? net->impl->range_exceeded() : 0; }
+uint64_t suo_net_last_call(const suo_net* net) { return net ? net->impl->last_call() : 0; }
+int suo_net_call_range_exceeded(suo_net* net, uint64_t call) {
+    if (!net) { suo_set_error("suo_net_call_range_exceeded: null net"); return -1; }
+    return net->impl->call_range_exceeded(call);
+}
 
 int suo_net_forward(suo_net* net, const void* img, int img_format, int H, int W, const float* boxes, int L, const float* priors,
                     float* uv, float* cov, float* kp_mask, float* kp_logits, float* logits, void* stream) {

@@ -403,4 +403,23 @@ int launch_upload(void* dst_dev, const void* src_host, size_t bytes, hipStream_t
     return SUO_OK;
 }
 
+// The range guard's per-call result (csrc/net.hip: Net::commit_call), stream-ordered behind the last kernel of a forward on the fp16 form: the live flag -- raised by
+// THIS call's kernels, which have all finished -- goes into the call's slot as tag * 2 + raised; when raised, the sticky word (suo_net_range_exceeded) is set and the
+// live flag cleared for the next call.  The words are mapped host memory: plain system-scope loads and stores from one lane, no read-modify-write.
+__global__ void range_commit_kernel(unsigned* live, unsigned* sticky, unsigned* slot, unsigned tag) {
+    if (threadIdx.x != 0) return;
+    const unsigned f = __hip_atomic_load(live, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM) ? 1u : 0u;
+    if (f) {
+        __hip_atomic_store(sticky, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
+        __hip_atomic_store(live, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
+    }
+    __hip_atomic_store(slot, (tag << 1) | f, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
+}
+
+int launch_range_commit(unsigned* live, unsigned* sticky, unsigned* slot, unsigned tag, hipStream_t s) {
+    hipLaunchKernelGGL(range_commit_kernel, dim3(1), dim3(64), 0, s, live, sticky, slot, tag);
+    SUO_HIP_CHECK(hipGetLastError());
+    return SUO_OK;
+}
+
 }  // namespace suo

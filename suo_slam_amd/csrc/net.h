@@ -56,6 +56,10 @@ public:
     int set_pipe(int p);
     // 1 when a forward since the last call of this function left the fp16 range (its outputs are invalid); clears the flag.  The caller has synchronised.
     int range_exceeded();
+    // per-call validity: the number of the last forward issued (1, 2, ...), and whether THAT call left the fp16 range (1), did not (0), or cannot be answered (-1:
+    // not finished, or older than the last kCallRing calls).  On 1 the network has moved to the bf16 form.  The caller has synchronised on the call's outputs.
+    uint64_t last_call() const { return calls_; }
+    int call_range_exceeded(uint64_t call);
     int max_crops() const { return max_crops_; }
     size_t workspace_bytes() const { return ws_floats_ * sizeof(float); }
     int schedule_bytes(int L, int n_frames, int H, int W, int with_priors, double* out, int* n_launches);
@@ -63,6 +67,12 @@ public:
 
 private:
     static constexpr int kNumSide = 4, kNumEvents = 32;
+    // the range guard's words in mapped host memory (range_flag_): [kLiveWord] raised by the fp16 kernels of the call that is running; [kStickyWord] set when a
+    // committed call had raised it, cleared by range_exceeded(); [kSlotWord + i] the result of call c with c % kCallRing == i, as (c mod 2^31) * 2 + raised
+    static constexpr int kCallRing = 64, kLiveWord = 0, kStickyWord = 16, kSlotWord = 32;
+    int commit_call(hipStream_t s);
+    void leave_fp16_form();
+    bool own_call_invalid();
     float* upload(const std::vector<float>& v);
     void make_gemm(const std::string& conv, const std::string& bn_after, const std::string& conv2, GemmW& g);
     void make_conv(const std::string& conv, const std::string& bn_after, int CK, ConvW& c, int c_used = 0);
@@ -113,6 +123,8 @@ private:
     std::vector<PreConv1> pre_;                                              // (several can be pending: up1[0]'s for up1[1] waits while the low branch runs)
     int pipe_ = 1, pipe_built_ = 1;                      // the pipe in use / the best one the weights were packed for
     unsigned* range_flag_ = nullptr;                     // mapped host memory: the f16x2 kernels raise it, the host reads it after any synchronisation
+    uint64_t calls_ = 0;                                 // forwards issued (commit_call numbers them)
+    int call_pipe_[kCallRing] = {};                      // ... and the pipe each of the last kCallRing ran on
     // two executables per captured graph, launched alternately: hipGraphLaunch of an executable whose previous launch is still running blocks the host until
     // that one ends (measured: 14 ms per call with a second batch in flight behind ObjectSLAM.submit_views_single) -- with two, the host runs ahead by one call
     struct GraphEntry { hipGraph_t graph = nullptr; hipGraphExec_t exec[2] = {nullptr, nullptr}; int next = 0; };

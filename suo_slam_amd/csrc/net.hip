@@ -441,10 +441,11 @@ Net::Net(int n, const char* const* names, const float* const* data, const int64_
     tensors_.clear();   // host pointers are not retained past construction
     pipe_built_ = pipe_f16x2() ? 2 : (wino_bf16x3() ? 1 : 0);
     pipe_ = pipe_built_;
-    // the range guard's flag: host memory mapped into the device's address space -- the kernels store to it (rarely: only beyond fp16's range), the host
-    // reads a plain word after whatever synchronisation its results needed anyway
-    if (hipHostMalloc(reinterpret_cast<void**>(&range_flag_), 64, hipHostMallocMapped) != hipSuccess) throw std::runtime_error("hipHostMalloc(range flag) failed");
-    *range_flag_ = 0;
+    // the range guard's words: host memory mapped into the device's address space -- the kernels store to the live flag (rarely: only beyond fp16's range), each
+    // forward's commit launch moves it into the call's slot, the host reads plain words after whatever synchronisation its results needed anyway
+    const size_t guard_bytes = (size_t)(kSlotWord + kCallRing) * sizeof(unsigned);
+    if (hipHostMalloc(reinterpret_cast<void**>(&range_flag_), guard_bytes, hipHostMallocMapped) != hipSuccess) throw std::runtime_error("hipHostMalloc(range flag) failed");
+    memset(range_flag_, 0, guard_bytes);
 
     // ---- workspace: every intermediate gets its own slab (288 GB of HBM: no aliasing games).
     // Size it with a dry run of the launch schedule at max_crops.
@@ -923,17 +924,59 @@ int Net::set_pipe(int p) {
     return SUO_OK;
 }
 
-// The contract of the fp16 form (csrc/f16x2.h): a forward whose activations left fp16's range has INVALID outputs.  Whoever synchronised on them asks here
-// before using them; on 1 the network has already been moved to the bf16 form (which has fp32's range) and the caller re-issues the call.  The blocking
-// entries (stream == NULL) do this themselves.
+// The contract of the fp16 form (csrc/f16x2.h): a forward whose activations left fp16's range has INVALID outputs.  Whoever synchronised on them asks before
+// using them -- per call (call_range_exceeded) or for every forward since the last time it asked (range_exceeded); on 1 the network has already been moved to
+// the bf16 form (which has fp32's range) and the caller re-issues the call.  The blocking entries (stream == NULL) do this themselves.
+void Net::leave_fp16_form() {
+    if (pipe_ != 2) return;
+    pipe_ = 1;
+    fprintf(stderr, "libsuo_hip: an activation left the fp16 range (|x| >= %g); this network now runs the three-term bf16 form -- re-issue the call\n", (double)(S2_LIMIT / S2_XSCALE));
+}
+
 int Net::range_exceeded() {
-    const unsigned f = __atomic_exchange_n(range_flag_, 0u, __ATOMIC_RELAXED);
+    const unsigned f = __atomic_exchange_n(range_flag_ + kStickyWord, 0u, __ATOMIC_RELAXED);
     if (!f) return 0;
-    if (pipe_ == 2) {
-        pipe_ = 1;
-        fprintf(stderr, "libsuo_hip: an activation left the fp16 range (|x| >= %g); this network now runs the three-term bf16 form -- re-issue the call\n", (double)(S2_LIMIT / S2_XSCALE));
-    }
+    leave_fp16_form();
     return 1;
+}
+
+static unsigned call_tag(uint64_t call) { return (unsigned)(call & 0x7fffffffu); }
+
+// Ends every forward, behind its last launch on its stream: numbers the call and, on the fp16 form, enqueues the one-lane launch that moves the live flag into
+// the call's slot (csrc/misc.hip: range_commit_kernel).  In stream order the slot holds exactly this call's raises -- a later call still running cannot reach it.
+// The other forms cannot leave the range: their calls get no launch, the host remembers the pipe.
+int Net::commit_call(hipStream_t s) {
+    const uint64_t c = ++calls_;
+    const int i = (int)(c % kCallRing);
+    call_pipe_[i] = pipe_;
+    if (pipe_ != 2) return SUO_OK;
+    return launch_range_commit(range_flag_ + kLiveWord, range_flag_ + kStickyWord, range_flag_ + kSlotWord + i, call_tag(c), s);
+}
+
+int Net::call_range_exceeded(uint64_t call) {
+    if (call == 0 || call > calls_ || calls_ - call >= (uint64_t)kCallRing) {
+        suo_set_error("suo_net_call_range_exceeded: call %llu is not one of the last %d forwards of this network (calls issued: %llu)", (unsigned long long)call,
+                      kCallRing, (unsigned long long)calls_);
+        return -1;
+    }
+    const int i = (int)(call % kCallRing);
+    if (call_pipe_[i] != 2) return 0;
+    const unsigned v = __atomic_load_n(range_flag_ + kSlotWord + i, __ATOMIC_ACQUIRE);
+    if ((v >> 1) != call_tag(call)) {
+        suo_set_error("suo_net_call_range_exceeded: call %llu has not finished -- synchronise on its outputs first", (unsigned long long)call);
+        return -1;
+    }
+    if (!(v & 1u)) return 0;
+    leave_fp16_form();
+    return 1;
+}
+
+// A blocking entry (synchronised) asks about its own call; it re-issues an invalid one itself, so the raise is answered for range_exceeded()'s readers as well
+// (as it always was).
+bool Net::own_call_invalid() {
+    if (call_range_exceeded(calls_) != 1) return false;
+    (void)range_exceeded();
+    return true;
 }
 
 // The launch schedule of ONE call of L crops cut from n_frames frames of H x W (with_priors: the 48-channel staging + full stem) walked as a dry run (nothing is
@@ -1021,13 +1064,14 @@ int Net::forward_staged(const float* in0_user, int L, float* logits_out, hipStre
         SUO_TRY(run_backbone(in0, IN_C, logits, L, s));
         if (logits_out)
             SUO_HIP_CHECK(hipMemcpyAsync(logits_out, logits, (size_t)L * NUM_KP * HEAT * HEAT * sizeof(float), hipMemcpyDeviceToDevice, s));
+        SUO_TRY(commit_call(s));
     } catch (const std::exception& e) {
         suo_set_error("suo_net_backbone: %s", e.what());
         return SUO_ERR_ARG;
     }
     if (own) {
         SUO_HIP_CHECK(hipStreamSynchronize(s));
-        if (range_exceeded()) return forward_staged(in0_user, L, logits_out, nullptr);      // (now on the bf16 form: cannot recurse twice)
+        if (own_call_invalid()) return forward_staged(in0_user, L, logits_out, nullptr);      // (now on the bf16 form: cannot recurse twice)
     }
     return SUO_OK;
 }
@@ -1067,13 +1111,14 @@ int Net::forward(const void* img, int fmt, int H, int W, const float* boxes, con
         SUO_LAUNCH(launch_classifier(d_mean_logit_, cls_w_, cls_b_, L, kp_logit, kp_prob, s));
         if (logits_out)
             SUO_HIP_CHECK(hipMemcpyAsync(logits_out, logits, (size_t)L * NUM_KP * HEAT * HEAT * sizeof(float), hipMemcpyDeviceToDevice, s));
+        SUO_TRY(commit_call(s));
     } catch (const std::exception& e) {
         suo_set_error("suo_net_forward: %s", e.what());
         return SUO_ERR_ARG;
     }
     if (own) {
         SUO_HIP_CHECK(hipStreamSynchronize(s));
-        if (range_exceeded()) return forward(img, fmt, H, W, boxes, box_img, L, priors, prior_uv, prior_mask, uv, cov, kp_prob, kp_logit, logits_out, nullptr);
+        if (own_call_invalid()) return forward(img, fmt, H, W, boxes, box_img, L, priors, prior_uv, prior_mask, uv, cov, kp_prob, kp_logit, logits_out, nullptr);
     }
     return SUO_OK;
 }

@@ -152,6 +152,7 @@ int launch_stem_x3(const void* img, int fmt, int H, int W, const float* boxes, c
                    float* out, hipStream_t s, const float* osc = nullptr, unsigned* range_flag = nullptr, const StemNext* next = nullptr);
 void pack_stem_weight_f16x2(const float* W, int Cw, const float* out_scale, uint16_t* out, float* oscale_out);
 int launch_upload(void* dst_dev, const void* src_host, size_t bytes, hipStream_t s);
+int launch_range_commit(unsigned* live, unsigned* sticky, unsigned* slot, unsigned tag, hipStream_t s);
 int launch_decode(const float* logits, int L, float* uv, float* cov, float* mean_logit, int* argmax_idx, float* prob, hipStream_t s);
 int launch_classifier(const float* mean_logit, const float* Wc, const float* bc, int L,
                       float* kp_logit, float* kp_prob, hipStream_t s);

@@ -413,7 +413,7 @@ class ObjectSLAM:
             self._fg.launch([0, L], pred["uv"], pred["cov"], masks_dev, kps_dev, kinv, camk, min_depth, seed=self._pnp_seed,
                             use_cov=not self.no_network_cov, do_lm=True, its=its)
             r = self._fg.fetch(copy=True)
-            if not self.model.range_exceeded():               # (fp16 form only: an activation left its range -> the network is on bf16x3 now, once more)
+            if not self.model.call_range_exceeded(pred.call):  # (fp16 form only: an activation of this call left its range -> the network is on bf16x3 now, once more)
                 break
             self.fp16_range_reissues += 1
         self._pnp_seed += int(np.count_nonzero(r["n_kp"] >= 4))
@@ -522,7 +522,7 @@ class ObjectSLAM:
         its = (10, 10, 40, 40) if self.sfm_mode else (10, 10, 10, 10)
         fg.launch(ff, pred["uv"], pred["cov"], masks_dev, kps_dev, kinv, camk, min_depth, seed=self._seed_base, seed_dev=self._seed_run,
                   use_cov=not self.no_network_cov, do_lm=True, its=its)
-        return fg, pred
+        return fg, pred, self.model.last_call()           # (the network call whose validity decides the batch's: PkpNet.call_range_exceeded)
 
     @_on_stream
     def submit_views_single(self, views):
@@ -547,30 +547,30 @@ class ObjectSLAM:
             prep.append((view_id, img, K, obj_ids, bboxes, np.asarray(model_kps), np.asarray(model_kps_masks, dtype=bool), K_bbox))
             ff.append(ff[-1] + len(obj_ids))
         assert ff[-1] <= self.model.max_crops, f"{ff[-1]} crops in one call, the network was built for {self.model.max_crops} (ObjectSLAM(max_crops=...))"
-        fg, pred = self._enqueue_views(prep, ff)
+        fg, pred, call = self._enqueue_views(prep, ff)
         if not hasattr(self, "_tickets"):
             self._tickets = []
-        self._tickets.append({"prep": prep, "ff": ff, "fg": fg, "pred": pred, "t0": time()})
+        self._tickets.append({"prep": prep, "ff": ff, "fg": fg, "pred": pred, "call": call, "t0": time()})
 
     @_on_stream
     def collect_views_single(self):
         """Second half: wait for the OLDEST batch in flight, install its state view by view and return [collect_results() per view]."""
         tk = self._tickets[0]
         r = tk["fg"].fetch(copy=True)
-        if self.model.range_exceeded():
-            # fp16 form only: an activation left its range -- every batch enqueued and not yet checked is invalid (and so is what they added to the running
-            # key).  The network is on bf16x3 now: re-issue all of them in order from the host's seed, which only ever counted valid batches.
+        if self.model.call_range_exceeded(tk["call"]):
+            # fp16 form only: this batch's own call left the range (a batch still in flight behind it cannot mark it) -- its results are invalid, and so are those
+            # of every batch enqueued after it: their PnP keys continue from its counts on the running key.  The network is on bf16x3 now: re-issue them all in
+            # order from the host's seed, which only ever counted valid batches.  Batches collected before it were valid and stay.
             redo = self._tickets
             self._tickets = []
             self.fp16_range_reissues += len(redo)
             import torch
-            torch.cuda.synchronize()
-            self.model.range_exceeded()
+            torch.cuda.synchronize()                          # (the batches behind it drain before their contexts and the key are reused)
             self._seed_run.zero_()
             self._seed_base, self._seed_expect = self._pnp_seed, 0
             for t in redo:
-                fg, pred = self._enqueue_views(t["prep"], t["ff"])
-                self._tickets.append({"prep": t["prep"], "ff": t["ff"], "fg": fg, "pred": pred, "t0": t["t0"]})
+                fg, pred, call = self._enqueue_views(t["prep"], t["ff"])
+                self._tickets.append({"prep": t["prep"], "ff": t["ff"], "fg": fg, "pred": pred, "call": call, "t0": t["t0"]})
             tk = self._tickets[0]
             r = tk["fg"].fetch(copy=True)
         self._tickets.pop(0)
@@ -720,7 +720,7 @@ class ObjectSLAM:
                 kp_masks = masks_dev.cpu().numpy().astype(bool)
                 if not self.no_network_cov or self.run_network_in_debug:
                     cov_uv = pred["cov"].cpu().numpy()
-                if not self.model.range_exceeded():           # (fp16 form only: the read-backs above synchronised; on True the network is on bf16x3 now)
+                if not self.model.call_range_exceeded(pred.call):     # (fp16 form only: the read-backs above synchronised; on True the network is on bf16x3 now)
                     break
                 self.fp16_range_reissues += 1
         if self.debug_gt_kp:
@@ -813,7 +813,7 @@ class ObjectSLAM:
             self._fg.launch([0, L], uv_dev, pred["cov"], masks_dev, kps_dev, kinv, camk, min_depth, seed=self._pnp_seed,
                             use_cov=not self.no_network_cov, do_lm=False)
             r = self._fg.fetch(copy=True)
-            if not self.model.range_exceeded():               # (fp16 form only: the fetch synchronised; on True the network is on bf16x3 now, once more)
+            if not self.model.call_range_exceeded(pred.call):  # (fp16 form only: the fetch synchronised; on True the network is on bf16x3 now, once more)
                 break
             self.fp16_range_reissues += 1
         self._pnp_seed += int(np.count_nonzero(r["n_kp"] >= 4))
@@ -936,12 +936,11 @@ class ObjectSLAM:
             v_ev.synchronize()
             vote = v_pin.numpy().copy()
             prior_uv_h, prior_mask_h = puv_pin[:Lb].numpy().copy(), pmk_pin[:Lb].numpy().copy()
-            if not self.model.range_exceeded():
+            if not self.model.call_range_exceeded(pa.call):   # (pass A's own call: pass B, still running, cannot mark it)
                 break
             # (fp16 form only) pass A left the range: its results -- and the priors pass B is running on -- are invalid.  Let pass B drain, then both again on bf16x3
             self._fg2.fetch(copy=False)
-            self.model.range_exceeded()
-            self.fp16_range_reissues += 1
+            self.fp16_range_reissues += 2
         assert vote[31] == 0.0, "NaN in information matrix"
         n_solv_a = int(np.count_nonzero(ra["n_kp"] >= 4))
         best = int(vote[12])
@@ -957,7 +956,7 @@ class ObjectSLAM:
                                     if hyp_ids else None)
         self._install_kp_detections(view_id, ids_a, bb_a, mm_a, det_a, None, cam_vote=cam)
         rb = self._fg2.fetch(copy=False)
-        b_invalid = self.model.range_exceeded()               # (fp16 form only: pass B alone left the range)
+        b_invalid = self.model.call_range_exceeded(pb.call)   # (fp16 form only: pass B left the range, pass A did not -- its results stand)
         if b_invalid:
             self.fp16_range_reissues += 1
         if cam is None or b_invalid:

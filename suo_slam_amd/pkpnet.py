@@ -25,6 +25,12 @@ def _stream():
     return C.c_void_p(_lib.current_stream_ptr())
 
 
+class NetOutputs(dict):
+    """What forward / forward_frames return: the reference's dict, plus `.call` -- the number of the network call that produced it (suo_net_last_call),
+    for PkpNet.call_range_exceeded."""
+    call = 0
+
+
 class PkpNet:
     """Keypoint / uncertainty network (eval mode only)."""
 
@@ -124,10 +130,31 @@ class PkpNet:
         _lib.check(_lib.lib().suo_net_set_pipe(self._h, int(pipe)), "suo_net_set_pipe")
 
     def range_exceeded(self):
-        """True when a forward since the last call of this method left the fp16 range: every forward of this network that was enqueued and not yet
-        checked is INVALID and must be re-issued (the network is on the bf16x3 form from now on).  The caller has synchronised on the outputs.
-        forward(..., check=True) -- the default -- does all of this itself."""
+        """True when some forward since the last call of this method left the fp16 range (which one: call_range_exceeded); the network is on the bf16x3 form
+        from now on.  The caller has synchronised on everything it enqueued.  forward(..., check=True) -- the default -- checks its own call itself."""
         return bool(_lib.lib().suo_net_range_exceeded(self._h))
+
+    def last_call(self):
+        """The number of the last forward this network issued (suo_net_last_call): what forward(...).call holds."""
+        return int(_lib.lib().suo_net_last_call(self._h))
+
+    def call_range_exceeded(self, call):
+        """True when THE call numbered `call` (forward(...).call) left the fp16 range: its outputs are INVALID and must be re-issued; the network is on the
+        bf16x3 form from now on.  False: its outputs are valid, whatever later calls did.  The caller has synchronised on that call's outputs
+        (suo_net_call_range_exceeded; raises when the call has not finished or is older than the network's last 64 calls)."""
+        rc = int(_lib.lib().suo_net_call_range_exceeded(self._h, C.c_uint64(int(call))))
+        if rc < 0:
+            raise _lib.SuoError("suo_net_call_range_exceeded: " + (_lib.lib().suo_last_error() or b"").decode())
+        return bool(rc)
+
+    def _checked(self, call):
+        """forward(check=True): the call's own validity once the stream has run it.  An invalid call is re-issued by the caller here, so the raise is also
+        answered for range_exceeded()'s readers (as the blocking C entries do)."""
+        torch.cuda.current_stream().synchronize()
+        if not self.call_range_exceeded(call):
+            return True
+        self.range_exceeded()
+        return False
 
     def forward(self, images, boxes, prior_kp=None, want_prob=False, prior_uv=None, prior_mask=None, check=True, out_slot=None):
         """images: uint8 [H,W,3] (cv2 layout) or float32 [1,3,H,W] device/host tensor; boxes: list with
@@ -135,7 +162,8 @@ class PkpNet:
         Returns the reference's dict: uv, cov, prob_logits, kp_mask_logits, kp_mask (+ prob if asked).
         check: on the fp16 form, wait for the call and re-issue it on bf16x3 if an activation left the range (the reference's callers read the
         outputs back right away, lib/object_slam.py:1100-1111, so the wait costs them nothing); check=False returns at once -- the caller then
-        asks range_exceeded() after its own synchronisation and re-issues (what ObjectSLAM's device chains do).
+        asks call_range_exceeded(ret.call) after its own synchronisation and re-issues (what ObjectSLAM's device chains do).
+        ret.call: the number of the network call that produced these outputs (NetOutputs).
         out_slot: any hashable -- the output tensors of (crop count, slot) are allocated once and handed out again by later calls naming the same slot (a caller that
         has consumed the previous call's outputs: five allocations per call saved on a path whose host time is on the critical path)."""
         assert self._h is not None, "load_state_dict first"
@@ -186,11 +214,11 @@ class PkpNet:
         else:
             _lib.check(_lib.lib().suo_net_forward(self._h, _ptr(img), fmt, H, W, _ptr(bx), L, _ptr(pr), _ptr(uv), _ptr(cov),
                                                   _ptr(kpm), _ptr(kpl), _ptr(logits), _stream()), "suo_net_forward")
-        if check and self.pipe() == 2:
-            torch.cuda.current_stream().synchronize()
-            if self.range_exceeded():
-                return self.forward(images, boxes, prior_kp, want_prob, prior_uv, prior_mask, check=False, out_slot=out_slot)     # (now on bf16x3: fp32's range)
-        ret = {"uv": uv, "cov": cov, "prob_logits": logits, "kp_mask_logits": kpl, "kp_mask": kpm}
+        call = self.last_call()
+        if check and self.pipe() == 2 and not self._checked(call):
+            return self.forward(images, boxes, prior_kp, want_prob, prior_uv, prior_mask, check=False, out_slot=out_slot)     # (now on bf16x3: fp32's range)
+        ret = NetOutputs(uv=uv, cov=cov, prob_logits=logits, kp_mask_logits=kpl, kp_mask=kpm)
+        ret.call = call
         if want_prob:
             ret.update(decode_extras(logits))
         return ret
@@ -252,7 +280,7 @@ class PkpNet:
 
     def forward_frames(self, images, boxes_per_frame, check=True, extra=None):
         """Several independent frames in one call: images uint8 [B,H,W,3] (or a list of B frames), boxes_per_frame list of B arrays [L_b,4].
-        Returns the same dict with the crops of all frames concatenated in frame order.  check: as forward().
+        Returns the same dict with the crops of all frames concatenated in frame order (and .call).  check: as forward().
         extra: host arrays to put on the device with the same upload (returned as ret["extra"], device tensors): what the caller's next kernels need."""
         assert self._h is not None, "load_state_dict first"
         dev = self.device
@@ -277,11 +305,12 @@ class PkpNet:
         _lib.check(_lib.lib().suo_net_forward_frames(self._h, _ptr(imgs), 0, int(imgs.shape[1]), int(imgs.shape[2]), _ptr(bx), _ptr(idx), L,
                                                      None, _ptr(uv), _ptr(cov), _ptr(kpm), _ptr(kpl), _ptr(logits), _stream()),
                    "suo_net_forward_frames")
-        if check and self.pipe() == 2:
-            torch.cuda.current_stream().synchronize()
-            if self.range_exceeded():
-                return self.forward_frames(images, boxes_per_frame, check=False, extra=extra)
-        return {"uv": uv, "cov": cov, "prob_logits": logits, "kp_mask_logits": kpl, "kp_mask": kpm, "extra": extra_dev}
+        call = self.last_call()
+        if check and self.pipe() == 2 and not self._checked(call):
+            return self.forward_frames(images, boxes_per_frame, check=False, extra=extra)
+        ret = NetOutputs(uv=uv, cov=cov, prob_logits=logits, kp_mask_logits=kpl, kp_mask=kpm, extra=extra_dev)
+        ret.call = call
+        return ret
 
 
 def decode_extras(logits):
