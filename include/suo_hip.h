@@ -430,6 +430,21 @@ int suo_optimize(suo_ba_problem* problem);
  *                                                                       (round 6; 60 cameras x 8 objects: 6.8 ms, 10.5 through the grid-barrier kernel of rounds 4-5)
  *   more than 16 free objects next to free cameras                      the same phases under the host-driven schedule (the reduced system then lives in HBM) */
 int suo_optimize_batch(suo_ba_problem* problems, int n_problems);
+/* Test entry: the kernel suo_optimize_batch runs each problem of this batch on, decided on the host exactly as the dispatcher decides (same thresholds, same
+ * SUO_LM_CAM2); launches nothing and needs no device.  A batch runs on ONE kernel, except that a batch holding a PHASEWISE graph runs its other problems one by
+ * one, each on the route it takes alone.  route_out[i] is a SUO_LM_ROUTE_* code; lds_need_out (may be NULL) [i] is, on the LM / LM_BIG routes, the dynamic LDS
+ * in bytes that a fully resident problem asks for BEFORE the 150 KiB cap (the kernel relocates arrays into LDS while they fit), -1 on the others. */
+#define SUO_LM_ROUTE_LM 0          /* lm_kernel, 256 threads (csrc/lm.hip): what no route below takes, < 512 edges */
+#define SUO_LM_ROUTE_LM_BIG 1      /* lm_kernel, 1024 threads (csrc/lm_big.hip): the same with >= 512 edges in some problem */
+#define SUO_LM_ROUTE_FRAME2 2      /* lm_frame2_kernel: one fixed camera, <= 16 objects, one wave per frame */
+#define SUO_LM_ROUTE_FRAME8 3      /* lm_frame_kernel<8>: no free camera, one wave per object, <= 8 objects in every problem */
+#define SUO_LM_ROUTE_FRAME16 4     /* lm_frame_kernel<16>: the same with 9-16 objects in some problem */
+#define SUO_LM_ROUTE_CAM2 5        /* lm_cam2_kernel: one free camera alone in its graph, every object fixed, <= 1024 edges */
+#define SUO_LM_ROUTE_CAM 6         /* lm_cam_kernel: one free camera, every object fixed, otherwise */
+#define SUO_LM_ROUTE_PHASES 7      /* csrc/lm_dist.hip phases, device-resident schedule: ONE graph of >= 512 edges, free cameras and free objects */
+#define SUO_LM_ROUTE_PHASEWISE 8   /* the same phases under the host schedule: > 16 free objects next to free cameras */
+#define SUO_LM_ROUTE_GRID 9        /* lm_grid_kernel: tuning builds only (-DSUO_TUNING) */
+int suo_debug_lm_routes(const suo_ba_problem* problems, int n_problems, int* route_out, int* lds_need_out);
 
 /* ---- phase-wise bundle adjustment for the multi-GPU global pose graph ------------------------
  * Cameras are partitioned across GPUs; each rank builds a context over ITS cameras' edges and ALL objects, and

@@ -35,6 +35,7 @@ int lm_frame2_max_edges();
 size_t lm_grid_scratch_bytes();
 #endif
 int lm_lds_bytes(int C, int O, int E, int NP, int n_free_obj_schur);
+size_t lm_lds_bytes_uncapped(int C, int O, int E, int NP, int n_free_obj_schur);
 int launch_debug_cholesky(const double* A, const double* b, int ns, double* x, int* ok, hipStream_t s);
 size_t lm_problem_struct_size();
 int launch_ba_init(const void* P, hipStream_t s);
@@ -403,46 +404,37 @@ static bool frame2_takes(const suo_ba_problem& q) {
     return true;
 }
 
-int suo_optimize_batch(suo_ba_problem* probs, int n_prob) {
-    if (n_prob <= 0) return SUO_OK;
-    if (!probs) { suo_set_error("suo_optimize_batch: null argument"); return SUO_ERR_ARG; }
-    // more than 16 free objects next to free cameras (T-LESS scenes): the reduced system outgrows the single-kernel paths;
-    // those graphs run the phase kernels under the host schedule, one by one, the rest of the batch as usual
-    {
-        std::vector<int> small;
-        bool any_big = false;
-        for (int i = 0; i < n_prob; ++i) {
-            int nfo = 0, nfc = 0;
-            for (int o = 0; o < probs[i].n_obj; ++o) nfo += probs[i].obj_fixed[o] ? 0 : 1;
-            for (int c = 0; c < probs[i].n_cam; ++c) nfc += probs[i].cam_fixed[c] ? 0 : 1;
-            if (nfo > 16 && nfc > 0) any_big = true; else small.push_back(i);
-        }
-        if (any_big) {
-            for (int i = 0, k = 0; i < n_prob; ++i) {
-                if (k < (int)small.size() && small[k] == i) { ++k; int rc = suo_optimize_batch(&probs[i], 1); if (rc != SUO_OK) return rc; }
-                else { int rc = optimize_phasewise(&probs[i]); if (rc != SUO_OK) return rc; }
-            }
-            return SUO_OK;
-        }
-    }
-    // ONE large graph with free cameras and free objects (the global SLAM adjustment): the phase kernels of csrc/lm_dist.hip under the device-resident LM schedule,
-    // driven from here (round 6).  Measured at 60 cameras x 8 objects: 106 us per LM trial against 129 for lm_grid_kernel's grid barriers; the Python-driven form of
-    // this very schedule (suo_slam_amd/ba_dist.py, one rank) was already the faster route and ObjectSLAM.optimize could not reach it through one C call.
-    // SUO_LM_PHASES (tuning builds, which also link csrc/lm_grid.hip): 0 = lm_grid_kernel as in rounds 4-5.
-    {
-        static const int phases = (int)SUO_TUNE("SUO_LM_PHASES", 1);
-        static const int big_from_ph = (int)SUO_TUNE("SUO_LM_BIG_EDGES", 512);
-        if (phases && n_prob == 1 && probs[0].n_edge >= big_from_ph) {
-            int nfo = 0, nfc = 0;
-            for (int o = 0; o < probs[0].n_obj; ++o) nfo += probs[0].obj_fixed[o] ? 0 : 1;
-            for (int c = 0; c < probs[0].n_cam; ++c) nfc += probs[0].cam_fixed[c] ? 0 : 1;
-            if (nfo > 0 && nfc > 0) return optimize_phases_one_rank(&probs[0]);
-        }
-    }
-    std::lock_guard<std::mutex> lock(g_arena.mu);
-    Staged st;
-    int rc = stage_problems(probs, n_prob, g_arena, st);
-    if (rc != SUO_OK) return rc;
+static int count_free(const suo_ba_problem& q, int* nfc_out) {
+    int nfo = 0, nfc = 0;
+    for (int o = 0; o < q.n_obj; ++o) nfo += q.obj_fixed[o] ? 0 : 1;
+    for (int c = 0; c < q.n_cam; ++c) nfc += q.cam_fixed[c] ? 0 : 1;
+    *nfc_out = nfc;
+    return nfo;
+}
+
+// more than 16 free objects next to free cameras (T-LESS scenes): the reduced system outgrows the single-kernel paths;
+// those graphs run the phase kernels under the host schedule, one by one, the rest of the batch as usual
+static bool takes_phasewise(const suo_ba_problem& q) {
+    int nfc = 0;
+    const int nfo = count_free(q, &nfc);
+    return nfo > 16 && nfc > 0;
+}
+
+// ONE large graph with free cameras and free objects (the global SLAM adjustment): the phase kernels of csrc/lm_dist.hip under the device-resident LM schedule,
+// driven from here (round 6).  Measured at 60 cameras x 8 objects: 106 us per LM trial against 129 for lm_grid_kernel's grid barriers; the Python-driven form of
+// this very schedule (suo_slam_amd/ba_dist.py, one rank) was already the faster route and ObjectSLAM.optimize could not reach it through one C call.
+// SUO_LM_PHASES (tuning builds, which also link csrc/lm_grid.hip): 0 = lm_grid_kernel as in rounds 4-5.
+static bool takes_phases(const suo_ba_problem* probs, int n_prob) {
+    static const int phases = (int)SUO_TUNE("SUO_LM_PHASES", 1);
+    static const int big_from_ph = (int)SUO_TUNE("SUO_LM_BIG_EDGES", 512);
+    if (!phases || n_prob != 1 || probs[0].n_edge < big_from_ph) return false;
+    int nfc = 0;
+    const int nfo = count_free(probs[0], &nfc);
+    return nfo > 0 && nfc > 0;
+}
+
+// The one kernel a batch that neither route above takes runs on (SUO_LM_ROUTE_*); *frame_max_obj / *max_edges: what its launcher is sized by.
+static int single_launch_route(const suo_ba_problem* probs, int n_prob, int* frame_max_obj_out, int* max_edges_out) {
     // frame-sized graphs: one 256-thread workgroup each (csrc/lm.hip); large graphs that the phase route above does not take (several in one call, or no free
     // object / no free camera): the 1024-thread single-workgroup build (csrc/lm_big.hip).  Tuning builds with SUO_LM_PHASES=0: ONE large graph spread over up
     // to 32 workgroups with grid barriers (csrc/lm_grid.hip), rounds 4-5's route.
@@ -456,52 +448,135 @@ int suo_optimize_batch(suo_ba_problem* probs, int n_prob) {
     static const int cam_kernel = (int)SUO_TUNE("SUO_LM_CAM", 1);                    // 0: general kernel (A/B)
     bool cam_only = cam_kernel != 0;
     for (int i = 0; i < n_prob && cam_only; ++i) {
-        int nfc = 0, nfo = 0;
-        for (int c = 0; c < probs[i].n_cam; ++c) nfc += probs[i].cam_fixed[c] ? 0 : 1;
-        for (int o = 0; o < probs[i].n_obj; ++o) nfo += probs[i].obj_fixed[o] ? 0 : 1;
+        int nfc = 0;
+        const int nfo = count_free(probs[i], &nfc);
         cam_only = nfc == 1 && nfo == 0;
     }
     // single-view frames (evaluate.py --nviews 1): no free camera -> block-diagonal system, one wave per object (csrc/lm_frame.hip)
     static const int frame_kernel = (int)SUO_TUNE("SUO_LM_FRAME", 8);             // max objects per frame it takes; 0: off (A/B)
+    static const int frame2 = (int)SUO_TUNE("SUO_LM_FRAME2", 1);                  // 0: one wave per object (A/B)
     bool frame_only = frame_kernel > 0 && !cam_only;
     int frame_max_obj = 0;
     for (int i = 0; i < n_prob && frame_only; ++i) {
         int nfc = 0;
-        for (int c = 0; c < probs[i].n_cam; ++c) nfc += probs[i].cam_fixed[c] ? 0 : 1;
+        count_free(probs[i], &nfc);
         // (one wave per object takes <= SUO_LM_FRAME objects: the 16-wave build spills; one wave per frame takes 16)
-        const bool f2 = ((int)SUO_TUNE("SUO_LM_FRAME2", 1) != 0 && frame2_takes(probs[i]));
+        const bool f2 = frame2 != 0 && frame2_takes(probs[i]);
         frame_only = nfc == 0 && probs[i].n_obj >= 1 && probs[i].n_obj <= (f2 ? 16 : frame_kernel) && probs[i].n_obj <= 16;
         frame_max_obj = std::max(frame_max_obj, probs[i].n_obj);
     }
+    if (frame_max_obj_out) *frame_max_obj_out = frame_max_obj;
+    if (max_edges_out) *max_edges_out = max_edges;
     if (cam_only) {
         // the camera alone in its graph (what ObjectSLAM.optimize(curr_only=True) builds): registers / LDS only (csrc/lm_cam2.hip)
         static const int cam2 = (int)suo::env_switch("SUO_LM_CAM2", 1);                  // 0: csrc/lm_cam.hip (A/B)
         bool alone = cam2 != 0;
         for (int i = 0; i < n_prob && alone; ++i) alone = probs[i].n_cam == 1 && probs[i].n_edge <= lm_cam2_max_edges();
-        if (alone) rc = launch_lm_cam2(g_arena.dev + st.o_structs, n_prob, max_edges, g_arena.stream);
-        else rc = launch_lm_cam(g_arena.dev + st.o_structs, n_prob, g_arena.stream);
-    } else if (frame_only) {
+        return alone ? SUO_LM_ROUTE_CAM2 : SUO_LM_ROUTE_CAM;
+    }
+    if (frame_only) {
         // one fixed camera (the single-view frame of evaluate.py): one WAVE per frame, the objects side by side (csrc/lm_frame2.hip)
-        static const int frame2 = (int)SUO_TUNE("SUO_LM_FRAME2", 1);              // 0: one wave per object (A/B)
         bool one_cam = frame2 != 0;
         for (int i = 0; i < n_prob && one_cam; ++i) one_cam = frame2_takes(probs[i]);
-        if (one_cam) rc = launch_lm_frame2(g_arena.dev + st.o_structs, n_prob, frame_max_obj, max_edges, g_arena.stream);
-        else rc = launch_lm_frame(g_arena.dev + st.o_structs, n_prob, frame_max_obj, g_arena.stream);
+        if (one_cam) return SUO_LM_ROUTE_FRAME2;
+        return frame_max_obj <= 8 ? SUO_LM_ROUTE_FRAME8 : SUO_LM_ROUTE_FRAME16;       // (launch_lm_frame's two builds)
+    }
 #ifdef SUO_TUNING
-    } else if (max_edges >= big_from && n_prob == 1 && grid_wgs > 0) {
+    if (max_edges >= big_from && n_prob == 1 && grid_wgs > 0) return SUO_LM_ROUTE_GRID;
+#endif
+    return max_edges >= big_from ? SUO_LM_ROUTE_LM_BIG : SUO_LM_ROUTE_LM;
+}
+
+// The route of every problem of a batch, as suo_optimize_batch takes it: a batch with a PHASEWISE graph runs its other problems one by one, each on the
+// route it takes alone.
+static void lm_routes(const suo_ba_problem* probs, int n_prob, int* route) {
+    bool any_big = false;
+    for (int i = 0; i < n_prob; ++i) any_big = any_big || takes_phasewise(probs[i]);
+    if (any_big) {
+        for (int i = 0; i < n_prob; ++i) {
+            if (takes_phasewise(probs[i])) route[i] = SUO_LM_ROUTE_PHASEWISE;
+            else lm_routes(&probs[i], 1, &route[i]);
+        }
+        return;
+    }
+    if (takes_phases(probs, n_prob)) { route[0] = SUO_LM_ROUTE_PHASES; return; }
+    const int r = single_launch_route(probs, n_prob, nullptr, nullptr);
+    for (int i = 0; i < n_prob; ++i) route[i] = r;
+}
+
+int suo_optimize_batch(suo_ba_problem* probs, int n_prob) {
+    if (n_prob <= 0) return SUO_OK;
+    if (!probs) { suo_set_error("suo_optimize_batch: null argument"); return SUO_ERR_ARG; }
+    {
+        bool any_big = false;
+        for (int i = 0; i < n_prob; ++i) any_big = any_big || takes_phasewise(probs[i]);
+        if (any_big) {
+            for (int i = 0; i < n_prob; ++i) {
+                int rc = takes_phasewise(probs[i]) ? optimize_phasewise(&probs[i]) : suo_optimize_batch(&probs[i], 1);
+                if (rc != SUO_OK) return rc;
+            }
+            return SUO_OK;
+        }
+    }
+    if (takes_phases(probs, n_prob)) return optimize_phases_one_rank(&probs[0]);
+    std::lock_guard<std::mutex> lock(g_arena.mu);
+    Staged st;
+    int rc = stage_problems(probs, n_prob, g_arena, st);
+    if (rc != SUO_OK) return rc;
+    int frame_max_obj = 0, max_edges = 0;
+    switch (single_launch_route(probs, n_prob, &frame_max_obj, &max_edges)) {
+    case SUO_LM_ROUTE_CAM2: rc = launch_lm_cam2(g_arena.dev + st.o_structs, n_prob, max_edges, g_arena.stream); break;
+    case SUO_LM_ROUTE_CAM: rc = launch_lm_cam(g_arena.dev + st.o_structs, n_prob, g_arena.stream); break;
+    case SUO_LM_ROUTE_FRAME2: rc = launch_lm_frame2(g_arena.dev + st.o_structs, n_prob, frame_max_obj, max_edges, g_arena.stream); break;
+    case SUO_LM_ROUTE_FRAME8:
+    case SUO_LM_ROUTE_FRAME16: rc = launch_lm_frame(g_arena.dev + st.o_structs, n_prob, frame_max_obj, g_arena.stream); break;
+#ifdef SUO_TUNING
+    case SUO_LM_ROUTE_GRID: {
         static void* grid_scratch = nullptr;
         if (!grid_scratch) SUO_HIP_CHECK(hipMalloc(&grid_scratch, lm_grid_scratch_bytes()));
         SUO_HIP_CHECK(hipMemsetAsync(grid_scratch, 0, 64, g_arena.stream));
+        static const int grid_wgs = (int)SUO_TUNE("SUO_LM_GRID_WGS", 32);
         const int wgs = std::max(1, std::min(grid_wgs, (max_edges + 255) / 256));
         rc = launch_lm_grid(g_arena.dev + st.o_structs, grid_scratch, wgs, g_arena.stream);
+        break;
+    }
 #endif
-    } else if (max_edges >= big_from) {
-        rc = launch_lm_big(g_arena.dev + st.o_structs, n_prob, st.lds_need, g_arena.stream);
-    } else {
-        rc = launch_lm(g_arena.dev + st.o_structs, n_prob, st.lds_need, g_arena.stream);
+    case SUO_LM_ROUTE_LM_BIG: rc = launch_lm_big(g_arena.dev + st.o_structs, n_prob, st.lds_need, g_arena.stream); break;
+    default: rc = launch_lm(g_arena.dev + st.o_structs, n_prob, st.lds_need, g_arena.stream); break;
     }
     if (rc != SUO_OK) return rc;
     return fetch_results(probs, n_prob, g_arena, st);
+}
+
+// Test entry: see include/suo_hip.h.  Host only: the same decisions as suo_optimize_batch, and the pair count stage_problems would find.
+int suo_debug_lm_routes(const suo_ba_problem* probs, int n_prob, int* route_out, int* lds_need_out) {
+    if (n_prob <= 0) return SUO_OK;
+    if (!probs || !route_out) { suo_set_error("suo_debug_lm_routes: null argument"); return SUO_ERR_ARG; }
+    for (int i = 0; i < n_prob; ++i) {
+        const suo_ba_problem& q = probs[i];
+        if (q.n_cam < 0 || q.n_obj < 0 || q.n_edge < 0) { suo_set_error("suo_debug_lm_routes: bad sizes"); return SUO_ERR_ARG; }
+        for (int e = 0; e < q.n_edge; ++e)
+            if (q.edge_cam[e] < 0 || q.edge_cam[e] >= q.n_cam || q.edge_obj[e] < 0 || q.edge_obj[e] >= q.n_obj) {
+                suo_set_error("suo_debug_lm_routes: edge %d of problem %d references a missing vertex", e, i);
+                return SUO_ERR_ARG;
+            }
+    }
+    lm_routes(probs, n_prob, route_out);
+    if (!lds_need_out) return SUO_OK;
+    for (int i = 0; i < n_prob; ++i) {
+        const suo_ba_problem& q = probs[i];
+        lds_need_out[i] = -1;
+        if (route_out[i] != SUO_LM_ROUTE_LM && route_out[i] != SUO_LM_ROUTE_LM_BIG) continue;
+        std::vector<long long> keys(q.n_edge);
+        for (int e = 0; e < q.n_edge; ++e) keys[e] = (long long)q.edge_cam[e] * q.n_obj + q.edge_obj[e];
+        std::sort(keys.begin(), keys.end());
+        const int np = (int)(std::unique(keys.begin(), keys.end()) - keys.begin());
+        int nfc = 0;
+        const int nfo = count_free(q, &nfc);
+        const size_t need = lm_lds_bytes_uncapped(q.n_cam, q.n_obj, q.n_edge, np, (nfo > 0 && nfc > 0) ? nfo : 0);
+        lds_need_out[i] = need > (size_t)INT32_MAX ? INT32_MAX : (int)need;
+    }
+    return SUO_OK;
 }
 
 int suo_optimize(suo_ba_problem* problem) { return suo_optimize_batch(problem, 1); }

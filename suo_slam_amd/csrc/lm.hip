@@ -454,7 +454,8 @@ int launch_lm_big(const void* problems_dev, int n_problems, int lds_bytes, hipSt
 #else
 // Dynamic LDS a problem of this size wants (everything resident), capped at LM_LDS_BYTES.  Small problems ask
 // for little, so their workgroup can share a CU with the CNN's workgroups instead of waiting for an empty one.
-int lm_lds_bytes(int C, int O, int E, int NP, int n_free_obj_schur) {
+// (uncapped: what the arithmetic asks for; suo_debug_lm_routes reports it)
+size_t lm_lds_bytes_uncapped(int C, int O, int E, int NP, int n_free_obj_schur) {
     size_t b = 0;
     const size_t ns = 6 * (size_t)n_free_obj_schur;
     b += 8 * (ns * (ns + 1) + 8 + ns) + 48;
@@ -463,7 +464,10 @@ int lm_lds_bytes(int C, int O, int E, int NP, int n_free_obj_schur) {
     b += 4 * (3 * (size_t)NP + 1) + 4 * ((size_t)C + 1 + NP) + 4 * ((size_t)O + 1 + NP);
     b += (4 + 1 + 8 * 12 + 16) * (size_t)E + 720 * (size_t)NP + 232 * (size_t)E + 288 * (size_t)C + 288 * (size_t)NP;
     b += 16 * 40;                                    // per-array alignment slack
-    b = (b + 1023) & ~(size_t)1023;
+    return (b + 1023) & ~(size_t)1023;
+}
+int lm_lds_bytes(int C, int O, int E, int NP, int n_free_obj_schur) {
+    const size_t b = lm_lds_bytes_uncapped(C, O, E, NP, n_free_obj_schur);
     return (int)(b > (size_t)LM_LDS_BYTES ? (size_t)LM_LDS_BYTES : b);
 }
 

@@ -49,6 +49,21 @@ def test_kernel_jacobians_match_finite_differences_of_the_kernel_error():
     rng = np.random.default_rng(31)
     P = S.make_pose_graph(rng, 4, 3, kp_per_obj=6, miss=0.0, outlier_frac=0.0)
     P["cam_fixed"][:] = 0
+    _check_kernel_jacobians(P)
+
+
+def test_kernel_jacobians_match_finite_differences_with_anisotropic_information():
+    """The same check on a graph whose information is a full 2x2 inverse covariance per edge (tests/ba_route_cases.py: xy of both signs, xx != yy):
+    the w*info and gradient columns jac[:, 24:29] are then checked with the off-diagonal term live."""
+    from tests import ba_route_cases as RC
+    rng = np.random.default_rng(32)
+    P = RC.graph(rng, np.full((4, 3), 6), np.zeros(4), np.zeros(3), outlier_frac=0.0)
+    assert (P["edge_info"][:, 1] > 0).any() and (P["edge_info"][:, 1] < 0).any()
+    assert np.abs(P["edge_info"][:, 0] - P["edge_info"][:, 2]).min() > 0
+    _check_kernel_jacobians(P)
+
+
+def _check_kernel_jacobians(P):
     jac, err0 = _kernel_linearisation(P)
     E = len(P["edge_cam"])
     assert np.abs(jac[:, :24]).max() > 0
