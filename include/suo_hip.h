@@ -75,7 +75,8 @@ int suo_net_schedule_bytes(suo_net* net, int L, int n_frames, int H, int W, int 
  *   SUO_PIPE_F32     v_mfma_f32_32x32x2_f32, exact fp32 products
  *   SUO_PIPE_BF16X3  operands as three bf16 terms, 6 of 9 cross products, fp32 accumulate (csrc/bf16x3.h): fp32's range
  *   SUO_PIPE_F16X2   operands as two fp16 terms, 3 of 4 cross products, fp32 accumulate (csrc/f16x2.h): half the matrix-pipe work, fp16's RANGE --
- *                    activations enter times 16, so a forward in which some |activation| >= 4094 is not computable in this form.  The kernels detect
+ *                    activations enter times 2^s (s = 4 unless calibrated, see suo_net_calibrate), so a forward in which some |activation| >= 65504 / 2^s is not
+ *                    computable in this form.  The kernels detect
  *                    that (they never write inf silently) and raise a flag:
  * Validity is PER CALL: a forward's outputs are invalid if and only if its own activations left the range.  Every forward is numbered 1, 2, ... in issue order
  * (suo_net_last_call() returns the number of the last one issued); on SUO_PIPE_F16X2 it ends with a one-lane launch on its stream that moves the kernels'
@@ -96,6 +97,28 @@ int suo_net_set_pipe(suo_net* net, int pipe);
 int suo_net_range_exceeded(suo_net* net);
 uint64_t suo_net_last_call(const suo_net* net);
 int suo_net_call_range_exceeded(suo_net* net, uint64_t call);
+
+/* Per-site activation exponents of SUO_PIPE_F16X2 (csrc/f16x2.h).  A SITE is the input operand of one convolution that has fp16 planes, whichever kernel
+ * computes it; it enters the two-term split times 2^s.  A network starts with s = 4 at every site (the fixed factor 16 above: outputs bit-identical to
+ * an uncalibrated network); the image stem keeps 2^4 and is no site.  Weights whose activations reach thousands (trained checkpoints can) leave the range at
+ * s = 4 and cost the network its fp16 form; calibration picks s per site from the data instead:
+ *   suo_net_calibrate      one probe forward of the frames and boxes given (the inputs of suo_net_forward_frames, prior-less) on SUO_PIPE_BF16X3, every block on
+ *                          its per-layer launches so each site's operand is measured whatever the crop count routes where; per site the largest s with
+ *                          2^s k max|x| <= 4094 (suo_f16x2_shift_for).  The probe is not a numbered call and leaves the range record alone.  Fails, leaving the
+ *                          network unchanged, when a site is unmeasured or its max is not finite.  Blocks until done (stream: where the probe runs; NULL: own).
+ *   suo_net_f16x2_sites    the number of sites; suo_net_f16x2_site_name(net, i) its convolution's state-dict prefix ("backbone.Residual.3.conv2")
+ *   suo_net_get_f16x2_shifts / suo_net_set_f16x2_shifts   all n sites' s (set: each in [-26, 26]) -- to store a calibration with its checkpoint, or share it
+ * calibrate and set wait for the device's work in flight, then rewrite the factors in place (captured graphs stay valid).  After either succeeds a network built
+ * for SUO_PIPE_F16X2 that had fallen back to SUO_PIPE_BF16X3 runs SUO_PIPE_F16X2 again (the only way up; suo_net_set_pipe only lowers).  Networks built without
+ * the fp16 form have no sites: calibrate / set fail.
+ * suo_f16x2_shift_for: the rule, host only -- the largest s with 2^s k amax <= 65504 / 16 (k = 4 for ksize 3: the Winograd transform's bound; k = 1 for ksize 1),
+ * clamped to [-26, 26] (2^s and every 2^-(t_n + s) stay normal fp32); amax = 0 gives 4; amax negative, inf or nan, or ksize not 1 or 3: SUO_ERR_ARG. */
+int suo_net_calibrate(suo_net* net, const void* imgs_dev, int img_format, int H, int W, const float* boxes_dev, const int* box_img_dev, int L, void* stream);
+int suo_net_f16x2_sites(const suo_net* net);
+const char* suo_net_f16x2_site_name(const suo_net* net, int i);
+int suo_net_get_f16x2_shifts(const suo_net* net, int* out, int n);
+int suo_net_set_f16x2_shifts(suo_net* net, const int* shifts, int n);
+int suo_f16x2_shift_for(float amax, int ksize, int* out);
 
 /* One frame: image either SUO_IMG_U8_HWC = uint8 [H,W,3] as cv2.imread gives it (scaled by 1/255 on
  * device: object_slam.py:1092 fused) or SUO_IMG_F32_CHW = float32 [3,H,W] already scaled (the tensor

@@ -56,6 +56,12 @@ SIGNATURES = {
     "suo_net_range_exceeded": (C.c_int, [VP]),
     "suo_net_last_call": (C.c_uint64, [VP]),
     "suo_net_call_range_exceeded": (C.c_int, [VP, C.c_uint64]),
+    "suo_net_calibrate": (C.c_int, [VP, VP, C.c_int, C.c_int, C.c_int, VP, VP, C.c_int, VP]),
+    "suo_net_f16x2_sites": (C.c_int, [VP]),
+    "suo_net_f16x2_site_name": (C.c_char_p, [VP, C.c_int]),
+    "suo_net_get_f16x2_shifts": (C.c_int, [VP, c_i32p, C.c_int]),
+    "suo_net_set_f16x2_shifts": (C.c_int, [VP, c_i32p, C.c_int]),
+    "suo_f16x2_shift_for": (C.c_int, [C.c_float, C.c_int, c_i32p]),
     "suo_pack_gemm_weight_f16x2": (C.c_int, [VP, C.c_int, C.c_int, VP, VP]),
     "suo_conv1x1_f16x2_ex": (C.c_int, [VP, C.c_int, C.c_int, VP, VP, VP, C.c_int, C.c_int, VP, VP, VP, VP, C.c_int, VP, C.c_int, C.c_int, C.c_int, C.c_int, VP, VP]),
     "suo_conv1x1_f16x2_pool": (C.c_int, [VP, C.c_int, C.c_int, VP, VP, VP, C.c_int, C.c_int, VP, VP, VP, VP, C.c_int, VP, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, VP, VP, VP]),

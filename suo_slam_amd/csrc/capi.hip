@@ -4,6 +4,7 @@
 
 #include "../../include/suo_hip.h"
 #include "net.h"
+#include "f16x2.h"
 
 static thread_local char g_err[1024] = "";
 
@@ -71,6 +72,26 @@ uint64_t suo_net_last_call(const suo_net* net) { return net ? net->impl->last_ca
 int suo_net_call_range_exceeded(suo_net* net, uint64_t call) {
     if (!net) { suo_set_error("suo_net_call_range_exceeded: null net"); return -1; }
     return net->impl->call_range_exceeded(call);
+}
+
+int suo_net_calibrate(suo_net* net, const void* imgs, int img_format, int H, int W, const float* boxes, const int* box_img, int L, void* stream) {
+    if (!net || !imgs || !boxes || !box_img) { suo_set_error("suo_net_calibrate: null argument"); return SUO_ERR_ARG; }
+    if (img_format != SUO_IMG_U8_HWC && img_format != SUO_IMG_F32_CHW) { suo_set_error("suo_net_calibrate: unknown image format %d", img_format); return SUO_ERR_ARG; }
+    return net->impl->calibrate(imgs, img_format, H, W, boxes, box_img, L, (hipStream_t)stream);
+}
+int suo_net_f16x2_sites(const suo_net* net) { return net ? net->impl->f16x2_sites() : -1; }
+const char* suo_net_f16x2_site_name(const suo_net* net, int i) { return net ? net->impl->f16x2_site_name(i) : nullptr; }
+int suo_net_get_f16x2_shifts(const suo_net* net, int* out, int n) {
+    if (!net) { suo_set_error("suo_net_get_f16x2_shifts: null net"); return SUO_ERR_ARG; }
+    return net->impl->get_f16x2_shifts(out, n);
+}
+int suo_net_set_f16x2_shifts(suo_net* net, const int* shifts, int n) {
+    if (!net) { suo_set_error("suo_net_set_f16x2_shifts: null net"); return SUO_ERR_ARG; }
+    return net->impl->set_f16x2_shifts(shifts, n);
+}
+int suo_f16x2_shift_for(float amax, int ksize, int* out) {
+    if (!suo::s2_site_shift(amax, ksize, out)) { suo_set_error("suo_f16x2_shift_for: amax %g / ksize %d not accepted (finite amax >= 0, ksize 1 or 3)", (double)amax, ksize); return SUO_ERR_ARG; }
+    return SUO_OK;
 }
 
 int suo_net_forward(suo_net* net, const void* img, int img_format, int H, int W, const float* boxes, int L, const float* priors,

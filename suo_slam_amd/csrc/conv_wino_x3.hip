@@ -123,7 +123,7 @@ void pack_tail_weight_f16x2(const float* W3, int N2, int K, uint16_t* out, float
 // the 8 components of rows xi = 2 wc, 2 wc + 1 -- one accumulator each, no fold; the two halves meet through LDS before the epilogue, as in
 // csrc/conv_wino.hip).
 // NP = operand planes: 3 = three bf16 terms, six MFMAs per product block (csrc/bf16x3.h); 2 = two fp16 terms, three MFMAs (csrc/f16x2.h: the staged input times
-// 2^S2_XSHIFT, U's rows times 2^t_n, accumulators back to scale by a.oscale / a.oscale3 in the epilogues, a.range_flag raised beyond fp16's range)
+// its site's 2^s (a.xscale), U's rows times 2^t_n, accumulators back to scale by a.oscale / a.oscale3 in the epilogues, a.range_flag raised beyond fp16's range)
 // NEXT (fp16 form of the fused tail only): the block's output never comes back for the NEXT block's conv1 -- relu(bn_next(out2)) of the tile is split into LDS
 // right where out2 is stored and multiplied by the next block's W1 (256 -> 128) here: the 256-channel tensor is written once and not re-read by a GEMM launch
 // (csrc/net.hip: residual(..., next)).  Same products in the same order as gemm_bf16x3_kernel<NP = 2> forms them: bit-identical to the separate launch.
@@ -187,12 +187,13 @@ __global__ __launch_bounds__(W8 ? 512 : 256) __attribute__((amdgpu_waves_per_eu(
         for (int i = 0; i < NLD; ++i) areg[i] = buf_load(in_srd, avoff[i], c * X_CK * 4);
     };
     float dmax = 0.f;                                         // NP = 2: largest scaled input magnitude this lane staged (range guard)
+    const float xs = NP == 2 ? s2_xscale(a.xscale) : 1.f;    // NP = 2: the input site's factor 2^s (uniform)
     auto sstore = [&](int buf) {
 #pragma unroll
         for (int i = 0; i < NLD; ++i) {
             const int idx = tid + i * NTHR;
             if constexpr (NP == 2) {                              // the activation scale (exact) and the guard's running max ride on the staging copy
-                areg[i] *= S2_XSCALE;
+                areg[i] *= xs;
                 dmax = s2_track(s2_track(dmax, areg[i][0], areg[i][1]), areg[i][2], areg[i][3]);
             }
             if (idx < NF4) *(x_f32x4*)&Hin[buf][(idx >> 2) * X_PKH + (idx & 3) * 4] = areg[i];
@@ -431,9 +432,11 @@ __global__ __launch_bounds__(W8 ? 512 : 256) __attribute__((amdgpu_waves_per_eu(
         const __amdgpu_buffer_rsrc_t o2_srd = make_srd(a.out2 + (size_t)l * crop2, crop2 * sizeof(float));
         constexpr bool has_up = UP;
         const __amdgpu_buffer_rsrc_t up_srd = make_srd(has_up ? a.up + (size_t)l * (crop2 / 4) : a.R, has_up ? crop2 / 4 * sizeof(float) : 0);
-        // NP = 2: the conv2 accumulator carries 2^(t_n + S2_XSHIFT); conv3's operand is 2^S2_XSHIFT relu(conv2 + b2) = relu(acc 2^-t_n + 2^S2_XSHIFT b2): one fma
-        const float b2v = NP == 2 ? a.bias[wn * 32 + (lane & 31)] * S2_XSCALE : a.bias[wn * 32 + (lane & 31)];
-        const float c2v = NP == 2 ? a.oscale[wn * 32 + (lane & 31)] * S2_XSCALE : 1.f;
+        // NP = 2: the conv2 accumulator carries 2^(t_n + s); conv3's operand is 2^s3 relu(conv2 + b2) = relu(acc 2^-(t_n + s) 2^s3 + 2^s3 b2): one fma
+        // (s, s3: the sites of conv2's and conv3's inputs; both factors exact powers of two)
+        const float xs3 = NP == 2 ? s2_xscale(a.xscale3) : 1.f;
+        const float b2v = NP == 2 ? a.bias[wn * 32 + (lane & 31)] * xs3 : a.bias[wn * 32 + (lane & 31)];
+        const float c2v = NP == 2 ? a.oscale[wn * 32 + (lane & 31)] * xs3 : 1.f;
         float tmax = 0.f;
         // store address of the lane's channel n = 32 w + (lane & 31): k-step n >> 4, half (n >> 3) & 1 (swapped for pixels 8-15: = lane >> 5, see m below),
         // element n & 7; pixel m = 16 (r >> 2) + 2 (r & 3) + 8 (lane >> 5) + pj for accumulator row r (tile (r & 3) + 8 (r >> 2) + 4 (lane >> 5))
@@ -514,7 +517,7 @@ __global__ __launch_bounds__(W8 ? 512 : 256) __attribute__((amdgpu_waves_per_eu(
                     x_f32x4 osc3 = x_f32x4{1.f, 1.f, 1.f, 1.f};
                     if constexpr (NP == 2) osc3 = *(const x_f32x4*)(a.oscale3 + col);
                     x_f32x4 nsc, nsh;
-                    if constexpr (NEXT) { nsc = *(const x_f32x4*)(a.n_scale + col) * S2_XSCALE; nsh = *(const x_f32x4*)(a.n_shift + col) * S2_XSCALE; }
+                    if constexpr (NEXT) { const float nxs = s2_xscale(a.n_xscale); nsc = *(const x_f32x4*)(a.n_scale + col) * nxs; nsh = *(const x_f32x4*)(a.n_shift + col) * nxs; }
                     int off[4];
                     x_f32x4 rv[4], uv[UP ? 4 : 1];
 #pragma unroll
@@ -542,7 +545,7 @@ __global__ __launch_bounds__(W8 ? 512 : 256) __attribute__((amdgpu_waves_per_eu(
                         if constexpr (UP) o += uv[NEXT ? 0 : k];
                         buf_store(o, o2_srd, off[k]);
                         if constexpr (NEXT) {
-                            // the next block's operand: 2^S2_XSHIFT relu(bn_next(o)) of this pixel's 4 channels (local channel 32 w + 4 (lane & 7) of K half j) as
+                            // the next block's operand: 2^s_next relu(bn_next(o)) of this pixel's 4 channels (local channel 32 w + 4 (lane & 7) of K half j) as
                             // two fp16 planes in A-operand order -- k-step 2 w + ((lane & 7) >> 2), pixel m, 16-byte half ((lane & 3) >> 1) swapped for pixels 8-15
                             const int m = 32 * i + (lane >> 3) + 8 * k;
                             float xn[4];

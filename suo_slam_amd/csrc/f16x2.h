@@ -10,8 +10,13 @@
 //     one-signed data       fp32 pipe std 4.12 max 19.6 | bf16 x 3 std 3.34 max 15.9 | this split std 2.46 max 11.3   (3 K / 16 roundings against 6 K / 16 against K)
 // What fp16 does NOT have is bf16's range, so both operands are brought into it by EXACT powers of two:
 //   * weights: row n (one output channel) times 2^t_n with max_k |w_nk| 2^t_n in [2^12, 2^13)  (host, when a network is built)
-//   * activations: times 2^S2_XSHIFT (folded into the BN prologue's scale / shift where there is one -- fmaf(x, 16 a, 16 b) = 16 fmaf(x, a, b) exactly)
-//   * the epilogue multiplies the accumulator by 2^-(t_n + S2_XSHIFT) (one fused multiply-add with the bias instead of an add)
+//   * activations: times 2^s, s chosen PER SITE -- a site is the input operand of one convolution with fp16 planes, whichever kernel computes it (folded into
+//     the BN prologue's scale / shift where there is one -- fmaf(x, 2^s a, 2^s b) = 2^s fmaf(x, a, b) exactly).  The kernels read 2^s through a pointer to
+//     device memory (GemmArgs.xscale and its kin); a network starts with s = S2_XSHIFT = 4 at every site, and suo_net_calibrate picks s from one probe forward
+//     on the range-safe bf16x3 form (the largest s with 2^s k max|x| <= S2_SITE_BOUND: s2_site_shift), suo_net_set_f16x2_shifts restores stored ones.  The image
+//     stem's own site keeps 2^S2_XSHIFT (its input is the frame).
+//   * the epilogue multiplies the accumulator by 2^-(t_n + s) (one fused multiply-add with the bias instead of an add): the per-channel factor arrays are
+//     rewritten in place with the site's s, so captured graphs stay valid
 // Small values: v_mfma_f32_32x32x16_f16 HONOURS subnormal fp16 inputs and v_cvt_pk_f16_f32 produces them (probed: tools/micro/f16_split.hip, part A), so a
 // residual below 2^-14 keeps an absolute precision of 2^-25: an activation loses relative accuracy only below ~2^-7 / 16, where its product no longer
 // matters to a sum of O(1) terms (measured: activations of 1e-3 -> std 1.8 units; the bf16 split 0.4; gate 2 sqrt(K) = 32).
@@ -28,9 +33,11 @@
 
 namespace suo {
 
-constexpr int S2_XSHIFT = 4;                      // activations enter the split times 16: range guard at |x| >= 4094
-constexpr float S2_XSCALE = 16.f;
+constexpr int S2_XSHIFT = 4;                      // the default site shift: activations enter the split times 16 (range guard at |x| >= 4094)
+constexpr float S2_XSCALE = 16.f;                 // 2^S2_XSHIFT (and the image stem's fixed factor)
 constexpr float S2_LIMIT = 65504.f;               // largest finite fp16
+constexpr float S2_SITE_BOUND = S2_LIMIT / 16.f;  // calibration: 2^s k max |x| <= 4094 leaves at least 16x of headroom below the guard
+constexpr int S2_SHIFT_MIN = -26, S2_SHIFT_MAX = 26;      // |t_n| <= 100 (s2_row_shift): 2^s and every 2^-(t_n + s) stay normal fp32 numbers
 
 typedef _Float16 s2_f16x2 __attribute__((ext_vector_type(2)));
 typedef float s2_f32x2 __attribute__((ext_vector_type(2)));
@@ -58,6 +65,8 @@ __device__ __forceinline__ unsigned s2_lo_pack(float a, float b, unsigned h) {
 }
 // running max of magnitudes for the range guard: m <- max(m, |a|, |b|) (one v_max3_f32 with source modifiers)
 __device__ __forceinline__ float s2_track(float m, float a, float b) { return fmaxf(fmaxf(m, fabsf(a)), fabsf(b)); }
+// a site's activation factor 2^s, read from device memory (a uniform scalar load); nullptr: the default 2^S2_XSHIFT
+__device__ __forceinline__ float s2_xscale(const float* p) { return p ? *p : S2_XSCALE; }
 // raise the flag when the lane saw a value at or beyond the fp16 range
 __device__ __forceinline__ void s2_raise(unsigned* flag, float m) {
     if (!(m < S2_LIMIT) && flag) __hip_atomic_store(flag, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
@@ -92,13 +101,27 @@ static inline void s2_split_host(float x, uint16_t out[2]) {
     out[0] = s2_rn_host(x);
     out[1] = s2_rn_host(x - s2_to_float_host(out[0]));                     // the subtraction is exact
 }
+// the calibration rule: the largest s with 2^s k amax <= S2_SITE_BOUND, k = 4 for a 3x3 (Winograd) input (|B^T d B| <= 4 max |d|, the guard's own bound),
+// k = 1 for a 1x1 input; clamped to [S2_SHIFT_MIN, S2_SHIFT_MAX]; amax = 0 keeps S2_XSHIFT.  false: amax negative, inf or nan, or ksize not 1 or 3
+static inline bool s2_site_shift(float amax, int ksize, int* out) {
+    if (!out || (ksize != 1 && ksize != 3) || !(amax >= 0.f) || !isfinite(amax)) return false;
+    if (amax == 0.f) { *out = S2_XSHIFT; return true; }
+    const double v = (ksize == 3 ? 4.0 : 1.0) * (double)amax;             // exact
+    int e;
+    (void)frexp((double)S2_SITE_BOUND / v, &e);
+    int s = e - 1;                                                         // within one of the answer; the comparisons below are exact
+    while (ldexp(v, s + 1) <= (double)S2_SITE_BOUND) ++s;
+    while (ldexp(v, s) > (double)S2_SITE_BOUND) --s;
+    *out = s < S2_SHIFT_MIN ? S2_SHIFT_MIN : (s > S2_SHIFT_MAX ? S2_SHIFT_MAX : s);
+    return true;
+}
 // exponent t with max 2^t in [2^12, 2^13) (0 for an all-zero row): the per-output-channel weight scale
 static inline int s2_row_shift(float max_abs) {
     if (!(max_abs > 0.f) || !isfinite(max_abs)) return 0;
     int e;
     (void)frexpf(max_abs, &e);                                             // max_abs = f 2^e, f in [0.5, 1): max_abs in [2^(e-1), 2^e)
     int t = 13 - e;
-    if (t > 100) t = 100;                                                  // (keeps 2^-(t + S2_XSHIFT) a normal fp32 number)
+    if (t > 100) t = 100;                                                  // (keeps 2^-(t + s) a normal fp32 number for every s of S2_SHIFT_MIN ... MAX)
     if (t < -100) t = -100;
     return t;
 }

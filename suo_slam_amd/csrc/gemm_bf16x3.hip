@@ -109,9 +109,10 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(NP == 2 ? S
     const int w = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int wm = w >> 1, wn = w & 1;
     const int M = g.M, K = g.K1 + (DUAL ? g.K2 : 0), ldo = g.ldo;
+    const float xs = NP == 2 ? s2_xscale(g.xscale) : 1.f;                   // the site's activation factor 2^s (csrc/f16x2.h)
     if (PRO) {
-        // (NP = 2: the activation scale rides in the prologue -- fmaf(x, 16 a, 16 b) = 16 fmaf(x, a, b) exactly, and relu commutes with it)
-        for (int k = tid; k < g.K1; k += 256) { P[0][k] = NP == 2 ? g.pro_scale[k] * S2_XSCALE : g.pro_scale[k]; P[1][k] = NP == 2 ? g.pro_shift[k] * S2_XSCALE : g.pro_shift[k]; }
+        // (NP = 2: the activation scale rides in the prologue -- fmaf(x, 2^s a, 2^s b) = 2^s fmaf(x, a, b) exactly, and relu commutes with it)
+        for (int k = tid; k < g.K1; k += 256) { P[0][k] = NP == 2 ? g.pro_scale[k] * xs : g.pro_scale[k]; P[1][k] = NP == 2 ? g.pro_shift[k] * xs : g.pro_shift[k]; }
     }
     // tile = (row tile, column tile of 128); the column tiles of a row tile are neighbours (the second one finds the activations in L2)
     int bid = blockIdx.x;
@@ -188,7 +189,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(NP == 2 ? S
             } else {
                 if (!PRO) {
 #pragma unroll
-                    for (int t = 0; t < 4; ++t) x[t] *= S2_XSCALE;            // (exact; with a prologue the scale is in sc / sh)
+                    for (int t = 0; t < 4; ++t) x[t] *= xs;                   // (exact; with a prologue the scale is in sc / sh)
                 }
                 xmax = s2_track(s2_track(xmax, x[0], x[1]), x[2], x[3]);
                 const unsigned h0 = s2_pack_rn(x[0], x[1]), h1 = s2_pack_rn(x[2], x[3]);
@@ -346,6 +347,7 @@ struct GemmChainArgs {
     const float* bias2; const float* osc2;                // [64]
     float* out; int n_valid, hw;                          // out[(row / hw) * n_valid * hw + ch * hw + row % hw], ch < n_valid
     unsigned* range_flag;
+    const float* xs1; const float* xs2;                   // the activation factors 2^s of the two sites (lin's input, tmpOut's input; nullptr: 2^S2_XSHIFT)
 };
 
 __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(3))) void gemm_chain_head_kernel(const GemmChainArgs g, const uint16_t* __restrict__ W1, const uint16_t* __restrict__ W2) {
@@ -360,6 +362,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(3))) void g
     const int w = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int wm = w >> 1, wn = w & 1;
     const int M = g.M;
+    const float xs1 = s2_xscale(g.xs1), xs2 = s2_xscale(g.xs2);
     int bid = blockIdx.x;
     if ((gridDim.x & 7) == 0) bid = (bid & 7) * (gridDim.x >> 3) + (bid >> 3);          // XCD-aware tile order
     const int m0 = bid * BM;
@@ -393,7 +396,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(3))) void g
             uint16_t* As = &S[stage][0];
             float x[4];
 #pragma unroll
-            for (int t = 0; t < 4; ++t) x[t] = araw[slot][t] * S2_XSCALE;
+            for (int t = 0; t < 4; ++t) x[t] = araw[slot][t] * xs1;
             xmax = s2_track(s2_track(xmax, x[0], x[1]), x[2], x[3]);
             const unsigned h0 = s2_pack_rn(x[0], x[1]), h1 = s2_pack_rn(x[2], x[3]);
             *(u32x2*)&As[ar * X3_PITCH + 4 * aq] = u32x2{h0, h1};
@@ -460,7 +463,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(3))) void g
                 o += bv;
                 float y[4];
 #pragma unroll
-                for (int q = 0; q < 4; ++q) y[q] = fmaxf(o[q], 0.f) * S2_XSCALE;       // what the separate launch stores, times 2^S2_XSHIFT for the split
+                for (int q = 0; q < 4; ++q) y[q] = fmaxf(o[q], 0.f) * xs2;             // what the separate launch stores, times the head site's 2^s for the split
                 xmax = s2_track(s2_track(xmax, y[0], y[1]), y[2], y[3]);
                 const unsigned h0 = s2_pack_rn(y[0], y[1]), h1 = s2_pack_rn(y[2], y[3]);
                 const unsigned l0 = s2_lo_pack(y[0], y[1], h0), l1 = s2_lo_pack(y[2], y[3], h1);
@@ -511,12 +514,12 @@ bool gemm_chain_head_takes(int M, int lda, int n_valid, int hw) {
 
 // logits (NCHW, n_valid channels) = W2 relu(W1 A^T + bias1) + bias2 for A [M, 256]; W1h / W2h = pack_gemm_weight_f16x2 of [256][256] / [64][256] (rows beyond n_valid zero)
 int launch_gemm_chain_head(const float* A, int lda, int M, const uint16_t* W1h, const float* osc1, const float* bias1, const uint16_t* W2h, const float* osc2, const float* bias2,
-                           float* out, int n_valid, int hw, unsigned* range_flag, hipStream_t s) {
+                           float* out, int n_valid, int hw, unsigned* range_flag, hipStream_t s, const float* xs1, const float* xs2) {
     if (!A || !W1h || !osc1 || !bias1 || !W2h || !osc2 || !bias2 || !out || !range_flag || !gemm_chain_head_takes(M, lda, n_valid, hw)) {
         suo_set_error("gemm_chain_head: unsupported arguments (M=%d lda=%d n_valid=%d hw=%d)", M, lda, n_valid, hw);
         return SUO_ERR_ARG;
     }
-    GemmChainArgs g = {A, lda, M, bias1, osc1, bias2, osc2, out, n_valid, hw, range_flag};
+    GemmChainArgs g = {A, lda, M, bias1, osc1, bias2, osc2, out, n_valid, hw, range_flag, xs1, xs2};
     hipLaunchKernelGGL(gemm_chain_head_kernel, dim3(M / 64), dim3(256), 0, s, g, W1h, W2h);
     SUO_HIP_CHECK(hipGetLastError());
     return SUO_OK;

@@ -17,9 +17,10 @@ struct HostTensor {
 };
 
 // Wx3: bf16x3 planes (N a multiple of 128, K segments multiples of 64; csrc/gemm_bf16x3.hip); W16 / osc16: the two fp16 planes and the per-column factors (csrc/f16x2.h)
-struct GemmW { float* Wp = nullptr; float* bias = nullptr; int N = 0, n_valid = 0, K1 = 0, K2 = 0; float* Wx3 = nullptr; float* W16 = nullptr; float* osc16 = nullptr; };
+// site / xs16: the fp16 form's activation site of this convolution's input (Net::sites_ index, -1: none) and its factor 2^s in device memory
+struct GemmW { float* Wp = nullptr; float* bias = nullptr; int N = 0, n_valid = 0, K1 = 0, K2 = 0; float* Wx3 = nullptr; float* W16 = nullptr; float* osc16 = nullptr; int site = -1; const float* xs16 = nullptr; };
 // Wq: Winograd-packed (3x3, 128 -> 128 / 64 -> 64); Wq3: its bf16x3 planes (csrc/conv_wino_x3.hip); Wq16 / osc16: its fp16 planes and per-channel factors
-struct ConvW { float* Wp = nullptr; float* bias = nullptr; int N = 0, C = 0, KS = 0; float* Wq = nullptr; float* Wq3 = nullptr; float* Wq16 = nullptr; float* osc16 = nullptr; };
+struct ConvW { float* Wp = nullptr; float* bias = nullptr; int N = 0, C = 0, KS = 0; float* Wq = nullptr; float* Wq3 = nullptr; float* Wq16 = nullptr; float* osc16 = nullptr; int site = -1; const float* xs16 = nullptr; };
 struct ResidualW {
     float* pro_scale = nullptr; float* pro_shift = nullptr;
     GemmW c1; ConvW c2; GemmW c3;
@@ -61,6 +62,13 @@ public:
     uint64_t last_call() const { return calls_; }
     int call_range_exceeded(uint64_t call);
     int max_crops() const { return max_crops_; }
+    // per-site activation exponents of the fp16 form (csrc/f16x2.h): sites in a fixed order, named by their convolution's state-dict prefix
+    int f16x2_sites() const { return (int)sites_.size(); }
+    const char* f16x2_site_name(int i) const { return i >= 0 && i < (int)sites_.size() ? sites_[i].name.c_str() : nullptr; }
+    int get_f16x2_shifts(int* out, int n) const;
+    int set_f16x2_shifts(const int* s, int n);
+    // one probe forward of the prior-less pass on the bf16x3 form, max |operand| per site, s by the rule; not a numbered call, the range record untouched
+    int calibrate(const void* img, int fmt, int H, int W, const float* boxes, const int* box_img, int L, hipStream_t s);
     size_t workspace_bytes() const { return ws_floats_ * sizeof(float); }
     int schedule_bytes(int L, int n_frames, int H, int W, int with_priors, double* out, int* n_launches);
     const HostTensor& T(const std::string& name) const;
@@ -97,6 +105,24 @@ private:
     int ensure_graph(float* in0, int in_c, float* logits, int L, hipStream_t s, hipGraphExec_t* exec, bool stem_done = false);
     bool fused_stem() const;
     int follow_null_stream();
+
+    // ---- fp16 activation sites
+    static constexpr int kMaxSites = 256;
+    struct Site {
+        std::string name; int ksize = 1; int shift = 4;
+        std::vector<std::pair<float*, std::vector<float>>> osc;       // the device factor arrays of the site's convolution and their values at s = S2_XSHIFT
+    };
+    std::vector<Site> sites_;
+    float* site_xs_ = nullptr;                           // [kMaxSites] device: 2^s per site (the kernels read it through GemmW / ConvW::xs16)
+    unsigned* probe_max_ = nullptr;                      // [kMaxSites] device: the probe's max |operand| per site (float bits)
+    bool probe_ = false;                                 // the schedule of the calibration probe: per-layer launches on the bf16x3 / fp32 forms, every operand materialised
+    std::vector<char> probed_;                           // ... which sites it measured
+    int add_site(const std::string& name, int ksize);
+    void site_osc(int site, float* dev, int n);
+    void register_residual_sites(const std::string& p, ResidualW& r);
+    void register_gemm_site(const std::string& p, GemmW& g);
+    int apply_shifts(const std::vector<int>& s);
+    int probe_site(int site, const float* x, long rows, int C, int ld, const float* scale, const float* shift, int relu, hipStream_t s);
 
     std::map<std::string, HostTensor> tensors_;
     std::vector<float*> owned_;

@@ -311,6 +311,52 @@ void Net::make_residual(const std::string& p, ResidualW& r) {
             }
         }
     }
+    register_residual_sites(p, r);
+}
+
+// ------------------------------------------------------------------------------------------------
+// fp16 activation sites (csrc/f16x2.h): one per convolution with fp16 planes, whichever kernel computes it.  Its factor 2^s lives at site_xs_[i], which every
+// fp16 launch splitting that operand reads; the per-channel factors 2^-(t_n + s) of the convolution's epilogues are kept at s = S2_XSHIFT on the host as well,
+// so a new s rewrites them in place (no pointer changes: captured graphs stay valid).
+int Net::add_site(const std::string& name, int ksize) {
+    if ((int)sites_.size() >= kMaxSites) throw std::runtime_error("too many fp16 activation sites");
+    Site st;
+    st.name = name; st.ksize = ksize; st.shift = S2_XSHIFT;
+    sites_.push_back(st);
+    return (int)sites_.size() - 1;
+}
+void Net::site_osc(int site, float* dev, int n) {
+    if (!dev) return;
+    std::vector<float> h(n);
+    if (hipMemcpy(h.data(), dev, (size_t)n * sizeof(float), hipMemcpyDeviceToHost) != hipSuccess) throw std::runtime_error("hipMemcpy(factors) failed");
+    sites_[site].osc.emplace_back(dev, std::move(h));
+}
+void Net::register_gemm_site(const std::string& p, GemmW& g) {
+    if (!g.W16) return;
+    g.site = add_site(p, 1);
+    g.xs16 = site_xs_ + g.site;
+    site_osc(g.site, g.osc16, g.N);
+}
+void Net::register_residual_sites(const std::string& p, ResidualW& r) {
+    if (r.c1.W16 || r.rbh_w[0]) {                           // relu(bn(x)): the GEMM's prologue, the one-launch block's staging, the stem's / a fused tail's NEXT
+        r.c1.site = add_site(p + ".conv1", 1);
+        r.c1.xs16 = site_xs_ + r.c1.site;
+        site_osc(r.c1.site, r.c1.osc16, r.c1.N);
+        site_osc(r.c1.site, r.rbh_osc[0], 128);
+    }
+    if (r.c2.Wq16 || r.rbh_w[1]) {                          // conv1's output: the Winograd staging, the one-launch block's conv1 epilogue
+        r.c2.site = add_site(p + ".conv2", 3);
+        r.c2.xs16 = site_xs_ + r.c2.site;
+        site_osc(r.c2.site, r.c2.osc16, r.c2.N);
+        site_osc(r.c2.site, r.rbh_osc[1], 128);
+    }
+    if (r.c3.W16 || r.c3x16 || r.rbh_w[2]) {                // conv2's output (+ the block input of a skip conv4): the GEMM, the fused tail, the one-launch block
+        r.c3.site = add_site(p + ".conv3", 1);
+        r.c3.xs16 = site_xs_ + r.c3.site;
+        site_osc(r.c3.site, r.c3.osc16, r.c3.N);
+        site_osc(r.c3.site, r.c3osc16, 256);
+        site_osc(r.c3.site, r.rbh_osc[2], 256);
+    }
 }
 
 void Net::make_hourglass(const std::string& p, int n, HourglassW& h) {
@@ -362,6 +408,8 @@ Net::Net(int n, const char* const* names, const float* const* data, const int64_
     expect_conv(*this, b + ".tmpOut_.0", 256, NUM_KP, 1);
     expect_shape(*this, "classifier.2.weight", {NUM_KP, NUM_KP});
     expect_shape(*this, "classifier.2.bias", {NUM_KP});
+    site_xs_ = upload(std::vector<float>(kMaxSites, S2_XSCALE));
+    probe_max_ = reinterpret_cast<unsigned*>(upload(std::vector<float>(kMaxSites, 0.f)));
     make_conv(b + ".conv1_", b + ".bn1", 16, stem_);
     // Without priors (every single-view pass and the first SLAM pass, lib/object_slam.py:1094-1097) the 41 prior
     // channels are zeros: multiply only the 3 image channels.  Same taps, same order, so the result is bit-identical
@@ -392,6 +440,8 @@ Net::Net(int n, const char* const* names, const float* const* data, const int64_
         for (int j = 0; j < 2; ++j) make_residual(b + ".Residual." + std::to_string(i * 2 + j), post_[i][j]);
         make_gemm(b + ".lin_." + std::to_string(i) + ".0", b + ".lin_." + std::to_string(i) + ".1", "", lin_[i]);
         make_gemm(b + ".tmpOut." + std::to_string(i), "", "", head_[i]);
+        register_gemm_site(b + ".lin_." + std::to_string(i) + ".0", lin_[i]);
+        register_gemm_site(b + ".tmpOut." + std::to_string(i), head_[i]);
     }
     // inter-stack re-injection (hg.py:112-117): x + ll_(ll) + tmpOut_(tmpOut(ll)).  tmpOut and tmpOut_ are both plain 1x1
     // convolutions with nothing between them, so the sum is ONE 256 -> 256 GEMM on ll with
@@ -431,6 +481,7 @@ Net::Net(int n, const char* const* names, const float* const* data, const int64_
                 reinject_.osc16 = upload(osc);
             }
         }
+        register_gemm_site(b + ".ll_.0", reinject_);          // (ll_ + tmpOut_ tmpOut folded: one operand, ll)
     }
     {
         const HostTensor& w = T("classifier.2.weight");
@@ -548,7 +599,7 @@ bool Net::residual_tail_is_fused(const ResidualW& r, int L, int H, int W) const 
     ConvArgs c2 = {};
     c2.L = L; c2.H = H; c2.W = W; c2.C = r.c2.C; c2.OH = H; c2.OW = W; c2.N = r.c2.N;
     const long tiles = (long)((W + 15) / 16) * ((H + 7) / 8) * L;
-    return r.c2.Wq && conv3x3_wino_pays(c2, pipe_ == 2 ? 32 : -1) && fuse_tiles > 0 && tiles >= fuse_tiles && !r.has_skip_conv && r.c3.N == 256 && r.c3.n_valid == 256 &&
+    return !probe_ && r.c2.Wq && conv3x3_wino_pays(c2, pipe_ == 2 ? 32 : -1) && fuse_tiles > 0 && tiles >= fuse_tiles && !r.has_skip_conv && r.c3.N == 256 && r.c3.n_valid == 256 &&
            r.c3.K1 == 128 && r.cin == 256;
 }
 
@@ -562,7 +613,7 @@ int Net::residual_in_one_launch(const ResidualW& r, int L, int H, int W) const {
     static const int mode = (int)SUO_TUNE("SUO_RES_FUSED", 2);
     static const long max_tiles = (long)SUO_TUNE("SUO_RES_FUSED_MAX_TILES", 768);
     static const int min_side = (int)SUO_TUNE("SUO_RES_FUSED_MIN_SIDE", 16);
-    if (mode <= 0 || !r.rb_w[0] || H > 32 || W > 32) return 0;
+    if (probe_ || mode <= 0 || !r.rb_w[0] || H > 32 || W > 32) return 0;
     const long t32 = (long)L * ((H + 3) / 4) * ((W + 7) / 8);
     // Half a round to three rounds of 4 x 8 pixel tiles (one workgroup per CU): the bf16x3 kernel, whatever the map (one frame at 32x32; batched frames at 8x8
     // and 4x4, where it replaces three launches of 17-47 us by one or two rounds of 30).  Fewer tiles than CUs on a map of >= 16 pixels a
@@ -589,6 +640,7 @@ int Net::residual_one_launch(const ResidualW& r, const float* x, float* out, int
     if (kind == 2 && pipe_ == 2 && r.rbh_w[0]) {                      // two fp16 planes: a third less weight traffic per workgroup, half the MFMAs
         a.W1 = r.rbh_w[0]; a.W2 = r.rbh_w[1]; a.W3 = r.rbh_w[2];
         a.osc1 = r.rbh_osc[0]; a.osc2 = r.rbh_osc[1]; a.osc3 = r.rbh_osc[2]; a.range_flag = range_flag_;
+        a.xs1 = r.c1.xs16; a.xs2 = r.c2.xs16; a.xs3 = r.c3.xs16;
         acct(ACCT_BLOCK, block_bytes(a, 4));
         SUO_LAUNCH(launch_res_block_f16x2(a, s));
     } else if (kind == 2) {
@@ -621,7 +673,7 @@ int Net::gemm_maybe_pooled(GemmArgs& g, int L, int H, int W, float* pool_out, hi
         GemmArgs gx = g;
         gx.pool_out = pool_out; gx.pool_H = H; gx.pool_W = W;                  // the pool in the epilogue (maps of 64-column multiples), `out` optional
         const bool f16 = pipe_ == 2 && gw->W16;                              // the two-term fp16 form of the same kernel (csrc/f16x2.h)
-        if (f16) { gx.oscale = gw->osc16; gx.range_flag = range_flag_; }
+        if (f16) { gx.oscale = gw->osc16; gx.range_flag = range_flag_; gx.xscale = gw->xs16; }
         auto launch = [&](const GemmArgs& a) { return f16 ? launch_gemm_f16x2_args(a, reinterpret_cast<const uint16_t*>(gw->W16), s) : launch_gemm_bf16x3_args(a, reinterpret_cast<const uint16_t*>(Wx3), s); };
         if (gemm_bf16x3_takes(gx)) { acct(ACCT_GEMM, gemm_bytes(gx, f16 ? 4 : 6)); SUO_LAUNCH(launch(gx)); return SUO_OK; }
         gx.pool_out = nullptr;                                                // else the pool as its own launch
@@ -681,7 +733,7 @@ int Net::residual(const ResidualW& r, const float* x, float* out, int L, int H, 
     c2.in = mid1; c2.L = L; c2.H = H; c2.W = W; c2.C = r.c2.C; c2.Wp = r.c2.Wp; c2.bias = r.c2.bias;
     c2.out = mid2; c2.OH = H; c2.OW = W; c2.N = r.c2.N; c2.relu = 1;
     const bool wino = r.c2.Wq && conv3x3_wino_pays(c2, pipe_ == 2 ? 32 : -1);       // 2.25x fewer MFMA MACs (csrc/conv_wino.hip)
-    if (!wino && !r.has_skip_conv && r.c3.N == 256 && r.c3.n_valid == 256 && r.c3.K1 == 128 && r.cin == 256 && conv3x3_fusable(c2)) {
+    if (!probe_ && !wino && !r.has_skip_conv && r.c3.N == 256 && r.c3.n_valid == 256 && r.c3.K1 == 128 && r.cin == 256 && conv3x3_fusable(c2)) {
         // conv2 -> conv3 + skip in one launch: the 128-channel tensor between them never leaves the CU (csrc/conv.hip: FUSE)
         if (!out) out = alloc((size_t)M * 256);
         c2.W3p = r.c3.Wp; c2.bias3 = r.c3.bias; c2.R = x; c2.out2 = out; c2.N2 = 256;
@@ -694,17 +746,17 @@ int Net::residual(const ResidualW& r, const float* x, float* out, int L, int H, 
         c2.Wp = r.c2.Wq;
         const long fuse_tiles = wino_min_tiles();
         const long tiles = (long)((W + 15) / 16) * ((H + 7) / 8) * L;
-        if (fuse_tiles > 0 && tiles >= fuse_tiles && !r.has_skip_conv && r.c3.N == 256 && r.c3.n_valid == 256 && r.c3.K1 == 128 && r.cin == 256) {
+        if (!probe_ && fuse_tiles > 0 && tiles >= fuse_tiles && !r.has_skip_conv && r.c3.N == 256 && r.c3.n_valid == 256 && r.c3.K1 == 128 && r.cin == 256) {
             // conv2 -> conv3 + skip in one launch (933 vs 713 + 346 us at 64x64 / 128 crops, 257 vs 195 + 91 at 32x32)
             if (!out) out = alloc((size_t)M * 256);
             c2.W3p = r.c3.Wp; c2.bias3 = r.c3.bias; c2.R = x; c2.out2 = out; c2.N2 = 256; c2.up = up;
             if (pipe_ == 2 && r.c2.Wq16 && r.c3x16) {        // both products as two fp16 terms (csrc/f16x2.h)
-                c2.Wp = r.c2.Wq16; c2.W3p = r.c3x16; c2.oscale = r.c2.osc16; c2.oscale3 = r.c3osc16; c2.range_flag = range_flag_;
+                c2.Wp = r.c2.Wq16; c2.W3p = r.c3x16; c2.oscale = r.c2.osc16; c2.oscale3 = r.c3osc16; c2.range_flag = range_flag_; c2.xscale = r.c2.xs16; c2.xscale3 = r.c3.xs16;
                 // the next block's conv1 on the tile while it is in the CU: its 256-channel input is written once and not re-read by a GEMM launch.
                 // (Not with an up-sampled addend: that variant has no registers left -- measured no gain, tools/bench_f16x2.py.)
                 if (next && !up && !pool_out && next_conv1_fusable(*next, L, H, W)) {
                     float* nm = alloc((size_t)M * 128);
-                    c2.n_scale = next->pro_scale; c2.n_shift = next->pro_shift; c2.n_W1 = next->c1.W16; c2.n_osc1 = next->c1.osc16; c2.n_b1 = next->c1.bias; c2.n_out = nm;
+                    c2.n_scale = next->pro_scale; c2.n_shift = next->pro_shift; c2.n_W1 = next->c1.W16; c2.n_osc1 = next->c1.osc16; c2.n_b1 = next->c1.bias; c2.n_out = nm; c2.n_xscale = next->c1.xs16;
                     pre_.push_back({out, next, nm});
                 }
                 acct(ACCT_CONV3, conv_bytes(c2, 4, 16, true));
@@ -720,7 +772,7 @@ int Net::residual(const ResidualW& r, const float* x, float* out, int L, int H, 
             if (pool_out) SUO_TRY(maxpool(out, pool_out, L, H, W, 256, s));
             return SUO_OK;
         }
-        if (pipe_ == 2 && r.c2.Wq16) { c2.Wp = r.c2.Wq16; c2.oscale = r.c2.osc16; c2.range_flag = range_flag_; acct(ACCT_CONV3, conv_bytes(c2, 4, 16, false)); SUO_LAUNCH(launch_conv3x3_wino_f16x2(c2, s)); }
+        if (pipe_ == 2 && r.c2.Wq16) { c2.Wp = r.c2.Wq16; c2.oscale = r.c2.osc16; c2.range_flag = range_flag_; c2.xscale = r.c2.xs16; acct(ACCT_CONV3, conv_bytes(c2, 4, 16, false)); SUO_LAUNCH(launch_conv3x3_wino_f16x2(c2, s)); }
         else if (r.c2.Wq3) { c2.Wp = r.c2.Wq3; acct(ACCT_CONV3, conv_bytes(c2, 6, 16, false)); SUO_LAUNCH(launch_conv3x3_wino_x3(c2, s)); }
         else { acct(ACCT_CONV3, conv_bytes(c2, 4, 16, false)); SUO_LAUNCH(launch_conv3x3_wino(c2, s)); }
     } else {
@@ -733,6 +785,12 @@ int Net::residual(const ResidualW& r, const float* x, float* out, int L, int H, 
     if (r.has_skip_conv) { g3.A2 = x; g3.lda2 = r.cin; g3.K2 = r.c3.K2; }
     else { g3.R = x; g3.ldr = r.cin; }
     g3.Wp = r.c3.Wp; g3.bias = r.c3.bias; g3.out = out; g3.ldo = r.cout; g3.M = M; g3.N = r.c3.N; g3.n_valid = r.c3.n_valid;
+    if (probe_) {                                             // the calibration probe: every operand of the block's three sites is in memory here
+        SUO_TRY(probe_site(r.c1.site, x, M, r.cin, r.cin, r.pro_scale, r.pro_shift, 1, s));
+        SUO_TRY(probe_site(r.c2.site, mid1, M, r.c1.N, r.c1.N, nullptr, nullptr, 0, s));
+        SUO_TRY(probe_site(r.c3.site, mid2, M, r.c2.N, r.c2.N, nullptr, nullptr, 0, s));
+        if (r.has_skip_conv) SUO_TRY(probe_site(r.c3.site, x, M, r.cin, r.cin, nullptr, nullptr, 0, s));      // (conv4's segment of the same split operand)
+    }
     return gemm_maybe_pooled(g3, L, H, W, pool_out, s, &r.c3);
 }
 
@@ -841,7 +899,7 @@ int Net::backbone(const float* in0, int in_c, float* logits, int L, hipStream_t 
             gemm_chain_head_takes(M, 256, NUM_KP, HEAT * HEAT)) {
             acct(ACCT_GEMM, 4.0 * M * 256 + 4.0 * M * NUM_KP + 4.0 * (256.0 * 256 + 64.0 * 256));
             SUO_LAUNCH(launch_gemm_chain_head(rb, 256, M, reinterpret_cast<const uint16_t*>(lin_[i].W16), lin_[i].osc16, lin_[i].bias, reinterpret_cast<const uint16_t*>(head_[i].W16),
-                                              head_[i].osc16, head_[i].bias, logits, NUM_KP, HEAT * HEAT, range_flag_, s));
+                                              head_[i].osc16, head_[i].bias, logits, NUM_KP, HEAT * HEAT, range_flag_, s, lin_[i].xs16, head_[i].xs16));
             continue;
         }
         float* ll = alloc((size_t)M * 256);
@@ -849,6 +907,11 @@ int Net::backbone(const float* in0, int in_c, float* logits, int L, hipStream_t 
         gl.A1 = rb; gl.lda1 = 256; gl.K1 = 256; gl.Wp = lin_[i].Wp; gl.bias = lin_[i].bias; gl.out = ll; gl.ldo = 256;
         gl.M = M; gl.N = 256; gl.n_valid = 256; gl.relu = 1;
         SUO_TRY(gemm_maybe_pooled(gl, L, 64, 64, nullptr, s, &lin_[i]));
+        if (probe_) {
+            SUO_TRY(probe_site(lin_[i].site, rb, M, 256, 256, nullptr, nullptr, 0, s));
+            SUO_TRY(probe_site(head_[i].site, ll, M, 256, 256, nullptr, nullptr, 0, s));
+            if (i == 0) SUO_TRY(probe_site(reinject_.site, ll, M, 256, 256, nullptr, nullptr, 0, s));
+        }
         GemmArgs gh = {};
         gh.A1 = ll; gh.lda1 = 256; gh.K1 = 256; gh.Wp = head_[i].Wp; gh.bias = head_[i].bias; gh.M = M; gh.N = 64;
         if (i == 0) {
@@ -924,13 +987,123 @@ int Net::set_pipe(int p) {
     return SUO_OK;
 }
 
+// ---- per-site activation exponents (csrc/f16x2.h) ----------------------------------------------------------------------------------------------------------
+int Net::get_f16x2_shifts(int* out, int n) const {
+    if (!out || n != (int)sites_.size()) { suo_set_error("suo_net_get_f16x2_shifts: %d entries asked, the network has %d sites", n, (int)sites_.size()); return SUO_ERR_ARG; }
+    for (int i = 0; i < n; ++i) out[i] = sites_[i].shift;
+    return SUO_OK;
+}
+
+// Rewrites every site's 2^s and its convolution's per-channel factors 2^-(t_n + s) in place, after the device has finished whatever used them.  A network built for
+// the fp16 form returns to it (the only way up: the factors now fit the data the caller calibrated on / vouches for).
+int Net::apply_shifts(const std::vector<int>& sh) {
+    SUO_HIP_CHECK(hipDeviceSynchronize());
+    std::vector<float> xs(kMaxSites, S2_XSCALE);
+    for (size_t i = 0; i < sites_.size(); ++i) xs[i] = ldexpf(1.f, sh[i]);
+    SUO_HIP_CHECK(hipMemcpy(site_xs_, xs.data(), xs.size() * sizeof(float), hipMemcpyHostToDevice));
+    for (size_t i = 0; i < sites_.size(); ++i) {
+        for (auto& o : sites_[i].osc) {
+            std::vector<float> v(o.second.size());
+            for (size_t k = 0; k < v.size(); ++k) v[k] = ldexpf(o.second[k], S2_XSHIFT - sh[i]);      // exact: 2^-(t_n + 4) -> 2^-(t_n + s), both normal
+            SUO_HIP_CHECK(hipMemcpy(o.first, v.data(), v.size() * sizeof(float), hipMemcpyHostToDevice));
+        }
+        sites_[i].shift = sh[i];
+    }
+    if (pipe_built_ == 2) pipe_ = 2;
+    return SUO_OK;
+}
+
+int Net::set_f16x2_shifts(const int* s, int n) {
+    if (sites_.empty()) { suo_set_error("suo_net_set_f16x2_shifts: this network has no fp16 form (built with SUO_F16X2=0 or SUO_WINO_BF16X3=0)"); return SUO_ERR_ARG; }
+    if (!s || n != (int)sites_.size()) { suo_set_error("suo_net_set_f16x2_shifts: %d shifts given, the network has %d sites", n, (int)sites_.size()); return SUO_ERR_ARG; }
+    for (int i = 0; i < n; ++i)
+        if (s[i] < S2_SHIFT_MIN || s[i] > S2_SHIFT_MAX) {
+            suo_set_error("suo_net_set_f16x2_shifts: shift %d of site %s outside [%d, %d]", s[i], sites_[i].name.c_str(), S2_SHIFT_MIN, S2_SHIFT_MAX);
+            return SUO_ERR_ARG;
+        }
+    return apply_shifts(std::vector<int>(s, s + n));
+}
+
+int Net::probe_site(int site, const float* x, long rows, int C, int ld, const float* scale, const float* shift, int relu, hipStream_t s) {
+    if (site < 0) return SUO_OK;
+    if (!dry_run_) probed_[site] = 1;
+    SUO_LAUNCH(launch_absmax(x, rows, C, ld, scale, shift, relu, probe_max_ + site, s));
+    return SUO_OK;
+}
+
+// The probe: the prior-less pass of suo_net_forward_frames on the bf16x3 form (fp32's range: an operand far beyond fp16's cannot corrupt what follows it) with
+// every block on its per-layer launches, so each site's operand is in memory once -- whichever kernel would compute it on the fp16 form at whatever crop count --
+// and one reduction per site measures it.  Its intermediates get a workspace of their own; nothing of the network's numbered calls or range record changes.
+int Net::calibrate(const void* img, int fmt, int H, int W, const float* boxes, const int* box_img, int L, hipStream_t s) {
+    if (sites_.empty()) { suo_set_error("suo_net_calibrate: this network has no fp16 form (built with SUO_F16X2=0 or SUO_WINO_BF16X3=0)"); return SUO_ERR_ARG; }
+    if (L <= 0 || L > max_crops_) { suo_set_error("suo_net_calibrate: L=%d outside [1,%d]", L, max_crops_); return SUO_ERR_ARG; }
+    const bool own = (s == nullptr);
+    if (own) { s = own_stream_; SUO_TRY(follow_null_stream()); }
+    SUO_HIP_CHECK(hipDeviceSynchronize());                    // the network's calls in flight have finished with the factors and the slabs
+    float* const ws = ws_; const size_t ws_floats = ws_floats_, ws_used = ws_used_, ws_mark = ws_mark_;
+    float* const stem_slab = stem_slab_; float* const mid1_slab = stem_mid1_slab_;
+    const int pipe = pipe_;
+    float* pws = nullptr;
+    auto restore = [&]() {
+        ws_ = ws; ws_floats_ = ws_floats; ws_used_ = ws_used; ws_mark_ = ws_mark; stem_slab_ = stem_slab; stem_mid1_slab_ = mid1_slab;
+        pipe_ = pipe; probe_ = false; dry_run_ = false;
+        if (pws) { (void)hipStreamSynchronize(s); (void)hipFree(pws); }
+    };
+    std::vector<unsigned> bits(sites_.size(), 0u);
+    auto run = [&]() -> int {
+        probe_ = true;
+        pipe_ = 1;
+        probed_.assign(sites_.size(), 0);
+        for (int pass = 0; pass < 2; ++pass) {                // pass 0: a dry run sizes the workspace; pass 1 runs
+            dry_run_ = pass == 0;
+            if (pass == 0) ws_floats_ = (size_t)-1 / sizeof(float) / 2;
+            else {
+                const size_t need = ws_used_;
+                SUO_HIP_CHECK(hipMalloc(&pws, need * sizeof(float)));
+                ws_ = pws; ws_floats_ = need;
+            }
+            ws_used_ = 0;
+            float* in0 = alloc((size_t)L * CROP * CROP * IN_C);
+            float* logits = alloc((size_t)L * NUM_KP * HEAT * HEAT);
+            stem_slab_ = alloc((size_t)L * 128 * 128 * 64);
+            stem_mid1_slab_ = nullptr;
+            ws_mark_ = ws_used_;
+            if (pass == 1) {
+                SUO_HIP_CHECK(hipMemsetAsync(probe_max_, 0, sites_.size() * sizeof(unsigned), s));
+                SUO_TRY(launch_roi_align_concat(img, fmt, H, W, boxes, box_img, L, IMG_C, nullptr, nullptr, nullptr, in0, s));
+            }
+            SUO_TRY(backbone(in0, IMG_C, logits, L, s, false));
+        }
+        SUO_HIP_CHECK(hipMemcpyAsync(bits.data(), probe_max_, bits.size() * sizeof(unsigned), hipMemcpyDeviceToHost, s));
+        SUO_HIP_CHECK(hipStreamSynchronize(s));
+        return SUO_OK;
+    };
+    int rc;
+    try {
+        rc = run();
+    } catch (const std::exception& e) {
+        suo_set_error("suo_net_calibrate: %s", e.what());
+        rc = SUO_ERR_ARG;
+    }
+    restore();
+    if (rc != SUO_OK) return rc;
+    std::vector<int> sh(sites_.size());
+    for (size_t i = 0; i < sites_.size(); ++i) {
+        float m;
+        memcpy(&m, &bits[i], sizeof(float));
+        if (!probed_[i]) { suo_set_error("suo_net_calibrate: the probe did not measure site %s", sites_[i].name.c_str()); return SUO_ERR_ARG; }
+        if (!s2_site_shift(m, sites_[i].ksize, &sh[i])) { suo_set_error("suo_net_calibrate: site %s has max |x| = %g", sites_[i].name.c_str(), (double)m); return SUO_ERR_ARG; }
+    }
+    return apply_shifts(sh);
+}
+
 // The contract of the fp16 form (csrc/f16x2.h): a forward whose activations left fp16's range has INVALID outputs.  Whoever synchronised on them asks before
 // using them -- per call (call_range_exceeded) or for every forward since the last time it asked (range_exceeded); on 1 the network has already been moved to
 // the bf16 form (which has fp32's range) and the caller re-issues the call.  The blocking entries (stream == NULL) do this themselves.
 void Net::leave_fp16_form() {
     if (pipe_ != 2) return;
     pipe_ = 1;
-    fprintf(stderr, "libsuo_hip: an activation left the fp16 range (|x| >= %g); this network now runs the three-term bf16 form -- re-issue the call\n", (double)(S2_LIMIT / S2_XSCALE));
+    fprintf(stderr, "libsuo_hip: an activation left the fp16 range of its site; this network now runs the three-term bf16 form -- re-issue the call\n");
 }
 
 int Net::range_exceeded() {
@@ -1096,7 +1269,7 @@ int Net::forward(const void* img, int fmt, int H, int W, const float* boxes, con
             // the boxes are the caller's buffers: their addresses change from call to call, a captured launch could not take them)
             if (stem_computes_r1_conv1()) {
                 // r1's conv1 on the tile while the stem has it (the stem's output is read by r1's skip convolution only)
-                const StemNext nx = {r1_.pro_scale, r1_.pro_shift, reinterpret_cast<const uint16_t*>(r1_.c1.W16), r1_.c1.osc16, r1_.c1.bias, stem_mid1_slab_};
+                const StemNext nx = {r1_.pro_scale, r1_.pro_shift, reinterpret_cast<const uint16_t*>(r1_.c1.W16), r1_.c1.osc16, r1_.c1.bias, stem_mid1_slab_, r1_.c1.xs16};
                 SUO_LAUNCH(launch_stem_x3(img, fmt, H, W, boxes, box_img, L, reinterpret_cast<const uint16_t*>(stem_h2_w_), stem_x3_bias_, stem_slab_, s, stem_h2_osc_, range_flag_, &nx));
             } else if (pipe_ == 2 && stem_h2_w_)
                 SUO_LAUNCH(launch_stem_x3(img, fmt, H, W, boxes, box_img, L, reinterpret_cast<const uint16_t*>(stem_h2_w_), stem_x3_bias_, stem_slab_, s, stem_h2_osc_, range_flag_));

@@ -95,7 +95,7 @@ __device__ __forceinline__ bool r3_hyhx(int row, int& hy, int& hx) {
 #define R3_T(i) do { } while (0)
 #endif
 
-// NP = operand planes: 3 = three bf16 terms, six MFMAs per product block; 2 = two fp16 terms, three MFMAs (csrc/f16x2.h: every activation tile times 2^S2_XSHIFT on its
+// NP = operand planes: 3 = three bf16 terms, six MFMAs per product block; 2 = two fp16 terms, three MFMAs (csrc/f16x2.h: every activation tile times its site's 2^s on its
 // way into LDS, weight rows times 2^t_n, accumulators back to scale with a.osc1 / osc2 / osc3, a.range_flag raised beyond fp16's range) -- a third less weight
 // traffic per workgroup (0.85 MB instead of 1.28), which is what bounds this kernel
 template <bool POOL_IN, bool UP, int NP = 3>
@@ -161,7 +161,7 @@ __global__ __launch_bounds__(256) void res_block_x3_kernel(const ResBlockArgs a)
     const int q = tid & 63;
     {
         r3_f32x4 sc = *(const r3_f32x4*)(a.pro_scale + 4 * q), sh = *(const r3_f32x4*)(a.pro_shift + 4 * q);
-        if constexpr (NP == 2) { sc *= S2_XSCALE; sh *= S2_XSCALE; }      // fmaf(x, 16 a, 16 b) = 16 fmaf(x, a, b) exactly
+        if constexpr (NP == 2) { const float xs1 = s2_xscale(a.xs1); sc *= xs1; sh *= xs1; }      // fmaf(x, 2^s a, 2^s b) = 2^s fmaf(x, a, b) exactly
         constexpr int NB = POOL_IN ? 4 : 16;                    // rows per thread in flight (every request before the first use)
 #pragma unroll
         for (int i0 = 0; i0 < 16; i0 += NB) {
@@ -269,9 +269,10 @@ __global__ __launch_bounds__(256) void res_block_x3_kernel(const ResBlockArgs a)
     for (int g = 0; g < R2 - 2; ++g) load2(g, ring2[g]);        // conv2's first weights travel under the epilogue + barrier
     {   // relu(acc + b1) -> M1 planes (zeros outside the map: Conv2d(padding=1) pads conv2's INPUT)
         const int ch = 32 * w + lr;
-        // NP = 2: the accumulator carries 2^(t_n + S2_XSHIFT); conv2's operand is 2^S2_XSHIFT relu(conv1 + b1) = relu(acc 2^-t_n + 2^S2_XSHIFT b1): one fma
-        const float b1 = NP == 2 ? a.b1[ch] * S2_XSCALE : a.b1[ch];
-        const float c1 = NP == 2 ? a.osc1[ch] * S2_XSCALE : 1.f;
+        // NP = 2: the accumulator carries 2^(t_n + s1); conv2's operand is 2^s2 relu(conv1 + b1) = relu(acc 2^-(t_n + s1) 2^s2 + 2^s2 b1): one fma
+        const float xs2 = NP == 2 ? s2_xscale(a.xs2) : 1.f;
+        const float b1 = NP == 2 ? a.b1[ch] * xs2 : a.b1[ch];
+        const float c1 = NP == 2 ? a.osc1[ch] * xs2 : 1.f;
 #pragma unroll
         for (int m = 0; m < 2; ++m)
 #pragma unroll
@@ -327,8 +328,9 @@ __global__ __launch_bounds__(256) void res_block_x3_kernel(const ResBlockArgs a)
     for (int g = 0; g < R3 - 1; ++g) load3(g, ring3[g]);
     {   // relu(acc + b2) -> M2 planes (the x tile is dead: every wave is past conv1)
         const int ch = 32 * w + lr;
-        const float b2 = NP == 2 ? a.b2[ch] * S2_XSCALE : a.b2[ch];
-        const float c2 = NP == 2 ? a.osc2[ch] * S2_XSCALE : 1.f;
+        const float xs3 = NP == 2 ? s2_xscale(a.xs3) : 1.f;
+        const float b2 = NP == 2 ? a.b2[ch] * xs3 : a.b2[ch];
+        const float c2 = NP == 2 ? a.osc2[ch] * xs3 : 1.f;
 #pragma unroll
         for (int r = 0; r < 16; ++r) {
             float v = NP == 2 ? fmaxf(fmaf(acc2[r], c2, b2), 0.f) : fmaxf(acc2[r] + b2, 0.f);

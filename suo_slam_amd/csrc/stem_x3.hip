@@ -89,6 +89,7 @@ struct StemArgs {
     const float* osc; unsigned* range_flag;             // NP = 2: per-channel factors 2^-(t_n + S2_XSHIFT), range-guard flag (a float frame may hold anything)
     // NEXT (NP = 2 only): the first Residual block's conv1 on the tile while it is in the CU -- relu(bn(out)) x W1 (64 -> 64, BatchNorm folded) + b1, ReLU -> n_out [L,128,128,64]
     const float* n_scale; const float* n_shift; const uint16_t* n_W1; const float* n_osc1; const float* n_b1; float* n_out;
+    const float* n_xscale;                              // NEXT: conv1's site factor 2^s (nullptr: 2^S2_XSHIFT)
 };
 
 // NP = operand planes: 3 = three bf16 terms (six MFMAs per product block), 2 = two fp16 terms (three; csrc/f16x2.h: samples times 2^S2_XSHIFT, weight rows times 2^t_n)
@@ -287,6 +288,7 @@ __global__ __launch_bounds__(256) void stem_x3_kernel(const StemArgs a) {
 #pragma unroll
             for (int r = 0; r < 16; ++r) acc2[n][r] = 0.f;
         float gmax2 = 0.f;
+        const float nxs = s2_xscale(a.n_xscale);
         const float* prow = P + (32 * w + (lane & 31)) * PP + 8 * (lane >> 5);
 #pragma unroll
         for (int ks = 0; ks < 4; ++ks) {
@@ -297,7 +299,7 @@ __global__ __launch_bounds__(256) void stem_x3_kernel(const StemArgs a) {
                 const sx_f32x4 x = *(const sx_f32x4*)(prow + 16 * ks + 4 * q);
                 const sx_f32x4 sc = *(const sx_f32x4*)(a.n_scale + c0 + 4 * q), sh = *(const sx_f32x4*)(a.n_shift + c0 + 4 * q);
 #pragma unroll
-                for (int j = 0; j < 4; ++j) v[4 * q + j] = fmaxf(fmaf(x[j], sc[j] * S2_XSCALE, sh[j] * S2_XSCALE), 0.f);      // (the GEMM's prologue, scale folded in the same way)
+                for (int j = 0; j < 4; ++j) v[4 * q + j] = fmaxf(fmaf(x[j], sc[j] * nxs, sh[j] * nxs), 0.f);      // (the GEMM's prologue, scale folded in the same way)
             }
             sx_u32x4 hi, lo;
 #pragma unroll
@@ -338,8 +340,8 @@ int launch_stem_x3(const void* img, int fmt, int H, int W, const float* boxes, c
                    float* out, hipStream_t s, const float* osc, unsigned* range_flag, const StemNext* next) {
     if (L <= 0 || H <= 1 || W <= 1 || !img || !boxes || !Wx || !bias || !out || ((osc == nullptr) != (range_flag == nullptr))) { suo_set_error("stem_x3: bad arguments"); return SUO_ERR_ARG; }
     if (next && (!osc || !next->scale || !next->shift || !next->W1 || !next->osc1 || !next->b1 || !next->out)) { suo_set_error("stem_x3: the next block's conv1 needs the fp16 form and all of its operands"); return SUO_ERR_ARG; }
-    StemArgs a = {img, fmt, H, W, boxes, box_img, L, Wx, bias, out, osc, range_flag, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
-    if (next) { a.n_scale = next->scale; a.n_shift = next->shift; a.n_W1 = next->W1; a.n_osc1 = next->osc1; a.n_b1 = next->b1; a.n_out = next->out; }
+    StemArgs a = {img, fmt, H, W, boxes, box_img, L, Wx, bias, out, osc, range_flag, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
+    if (next) { a.n_scale = next->scale; a.n_shift = next->shift; a.n_W1 = next->W1; a.n_osc1 = next->osc1; a.n_b1 = next->b1; a.n_out = next->out; a.n_xscale = next->xscale; }
     if (fmt != 0 && fmt != 1) { suo_set_error("stem_x3: unknown image format %d", fmt); return SUO_ERR_ARG; }
     if (osc && next) {
         if (fmt == 0) hipLaunchKernelGGL((stem_x3_kernel<0, 2, true>), dim3(L * 128), dim3(256), 0, s, a);

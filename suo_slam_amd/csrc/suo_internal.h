@@ -54,8 +54,10 @@ struct GemmArgs {
     // optional fused 2x2 max-pool of the result (nn.MaxPool2d(2, 2) after a block, hg.py:41 / pkpnet.py stem): the M pixels are
     // images of pool_H x pool_W, pool_out is [M / 4, ldo]; `out` may then be nullptr (only the pooled tensor is wanted)
     float* pool_out; int pool_H; int pool_W;
-    // f16x2 form only (csrc/f16x2.h): per-column factor 2^-(t_n + S2_XSHIFT) that brings the accumulator back to scale, and the range-guard flag
+    // f16x2 form only (csrc/f16x2.h): per-column factor 2^-(t_n + s) that brings the accumulator back to scale, and the range-guard flag;
+    // xscale: the site's activation factor 2^s in device memory (nullptr: 2^S2_XSHIFT)
     const float* oscale; unsigned* range_flag;
+    const float* xscale;
 };
 int launch_gemm1x1(const GemmArgs& a, hipStream_t s);
 bool gemm1x1_can_pool(const GemmArgs& a);                // shapes the fused pool takes (128 x 128 tiles of 2 image rows x 64 columns)
@@ -70,11 +72,13 @@ struct ConvArgs {
     const float* W3p; const float* bias3; const float* R; float* out2; int N2;
     const float* up;                                     // optional [L,OH/2,OW/2,N2]: out2 += nearest-neighbour 2x up-sampling of it (hg.py:56-58)
     int w3_bf16x3;                                       // csrc/conv_wino_x3.hip only: W3p holds pack_tail_weight_bf16x3's uint16 planes
-    // f16x2 form only (csrc/f16x2.h): per-channel factors 2^-(t_n + S2_XSHIFT) of the 3x3 convolution [N] and of the tail's conv3 [N2], range-guard flag
+    // f16x2 form only (csrc/f16x2.h): per-channel factors 2^-(t_n + s) of the 3x3 convolution [N] and of the tail's conv3 [N2], range-guard flag
     const float* oscale; const float* oscale3; unsigned* range_flag;
     // ... and, optional, the NEXT block's conv1 in the same launch (csrc/conv_wino_x3.hip, NEXT): its BatchNorm prologue [256], its weights as two fp16 planes
     // (pack_gemm_weight_f16x2 of W1 [128][256]) with their factors [128], its folded bias [128]; n_out [L,OH,OW,128] = relu(bn1(conv1(relu(bn(out2)))))
     const float* n_scale; const float* n_shift; const float* n_W1; const float* n_osc1; const float* n_b1; float* n_out;
+    // f16x2 form: the activation factors 2^s of the sites this launch splits -- the 3x3's input, the tail's conv3 input, the next block's conv1 input (nullptr: 2^S2_XSHIFT)
+    const float* xscale; const float* xscale3; const float* n_xscale;
 };
 int launch_conv3x3(const ConvArgs& a, hipStream_t s);
 bool conv3x3_fusable(const ConvArgs& a);
@@ -99,8 +103,9 @@ struct ResBlockArgs {
     const float* W3; const float* b3;                    // pack_res16_gemm(W3 [256][128]), [256]
     const float* up;                                     // optional [L,H/2,W/2,256]: out += its nearest-neighbour 2x up-sampling (hg.py:56-58)
     float* out;                                          // [L,H,W,256]
-    // f16x2 form only (csrc/f16x2.h): per-channel factors 2^-(t_n + S2_XSHIFT) of conv1 [128], conv2 [128], conv3 [256]; the range-guard flag
+    // f16x2 form only (csrc/f16x2.h): per-channel factors 2^-(t_n + s) of conv1 [128], conv2 [128], conv3 [256]; the range-guard flag
     const float* osc1; const float* osc2; const float* osc3; unsigned* range_flag;
+    const float* xs1; const float* xs2; const float* xs3;   // ... and the activation factors 2^s of conv1's, conv2's and conv3's inputs (nullptr: 2^S2_XSHIFT)
 };
 void pack_res16_gemm(const float* W, int N, int K, float* out);
 void pack_res16_conv3x3(const float* W, int N, int C, const float* out_scale, float* out);
@@ -131,7 +136,7 @@ int launch_gemm_f16x2_args(const GemmArgs& g, const uint16_t* W16, hipStream_t s
 // two 1x1 convolutions in one launch, the 256-channel tensor between them kept in LDS (csrc/gemm_bf16x3.hip: gemm_chain_head_kernel): NCHW logits = W2 relu(W1 A + b1) + b2
 bool gemm_chain_head_takes(int M, int lda, int n_valid, int hw);
 int launch_gemm_chain_head(const float* A, int lda, int M, const uint16_t* W1h, const float* osc1, const float* bias1, const uint16_t* W2h, const float* osc2, const float* bias2,
-                           float* out, int n_valid, int hw, unsigned* range_flag, hipStream_t s);
+                           float* out, int n_valid, int hw, unsigned* range_flag, hipStream_t s, const float* xs1 = nullptr, const float* xs2 = nullptr);
 // experimental: Winograd 3x3 with its products on the bf16 matrix pipe at fp32 accuracy (csrc/conv_wino_x3.hip); ConvArgs.Wp = packed uint16
 void pack_tail_weight_bf16x3(const float* W3, int N2, int K, uint16_t* out);
 void pack_wino_weight_bf16x3(const float* W, int N, int C, int Np, int Cp, const float* out_scale, uint16_t* out);
@@ -147,12 +152,14 @@ bool conv3x3_wino_f16x2_w8(long tiles);                // launches of <= one wor
 void pack_stem_weight_bf16x3(const float* W, int Cw, const float* out_scale, uint16_t* out);
 // osc / range_flag: both null = Wx holds three bf16 planes; both set = two fp16 planes (pack_stem_weight_f16x2) with their per-channel factors and the guard flag
 // next (fp16 form only): the first Residual block's conv1 on the tile -- relu(scale x + shift) W1^T (64 -> 64, pack_gemm_weight_f16x2 planes) * osc1 + b1, ReLU -> out
-struct StemNext { const float* scale; const float* shift; const uint16_t* W1; const float* osc1; const float* b1; float* out; };
+struct StemNext { const float* scale; const float* shift; const uint16_t* W1; const float* osc1; const float* b1; float* out; const float* xscale = nullptr; };   // xscale: conv1's site factor 2^s
 int launch_stem_x3(const void* img, int fmt, int H, int W, const float* boxes, const int* box_img, int L, const uint16_t* Wx, const float* bias,
                    float* out, hipStream_t s, const float* osc = nullptr, unsigned* range_flag = nullptr, const StemNext* next = nullptr);
 void pack_stem_weight_f16x2(const float* W, int Cw, const float* out_scale, uint16_t* out, float* oscale_out);
 int launch_upload(void* dst_dev, const void* src_host, size_t bytes, hipStream_t s);
 int launch_range_commit(unsigned* live, unsigned* sticky, unsigned* slot, unsigned tag, hipStream_t s);
+// calibration probe (csrc/calibrate.hip): *out <- max(*out, bits of max |relu(scale x + shift)|) over x [rows, C] (row stride ld; scale / shift optional, [C])
+int launch_absmax(const float* x, long rows, int C, int ld, const float* scale, const float* shift, int relu, unsigned* out, hipStream_t s);
 int launch_decode(const float* logits, int L, float* uv, float* cov, float* mean_logit, int* argmax_idx, float* prob, hipStream_t s);
 int launch_classifier(const float* mean_logit, const float* Wc, const float* bc, int L,
                       float* kp_logit, float* kp_prob, hipStream_t s);

@@ -147,6 +147,48 @@ class PkpNet:
             raise _lib.SuoError("suo_net_call_range_exceeded: " + (_lib.lib().suo_last_error() or b"").decode())
         return bool(rc)
 
+    # -- per-site activation exponents of the fp16 form (include/suo_hip.h: suo_net_calibrate) --------------------------------------------------------------
+    def f16x2_sites(self):
+        """The fp16 form's activation sites in the network's order, named by their convolution's state-dict prefix (empty without the fp16 form)."""
+        lib = _lib.lib()
+        return [lib.suo_net_f16x2_site_name(self._h, i).decode() for i in range(int(lib.suo_net_f16x2_sites(self._h)))]
+
+    def f16x2_shifts(self):
+        """{site name: s}: each site's activations enter the fp16 split times 2^s (4 until calibrated)."""
+        names = self.f16x2_sites()
+        out = (C.c_int * max(len(names), 1))()
+        _lib.check(_lib.lib().suo_net_get_f16x2_shifts(self._h, out, len(names)), "suo_net_get_f16x2_shifts")
+        return {n: int(out[i]) for i, n in enumerate(names)}
+
+    def set_f16x2_shifts(self, shifts):
+        """Restore shifts stored with a checkpoint (or calibrated on another rank): a dict naming every site.  The network runs the fp16 form afterwards."""
+        names = self.f16x2_sites()
+        missing = [n for n in names if n not in shifts]
+        extra = [n for n in shifts if n not in set(names)]
+        if missing or extra:
+            raise ValueError(f"set_f16x2_shifts: missing sites {missing[:4]}, unknown sites {extra[:4]}")
+        arr = (C.c_int * max(len(names), 1))(*[int(shifts[n]) for n in names])
+        _lib.check(_lib.lib().suo_net_set_f16x2_shifts(self._h, arr, len(names)), "suo_net_set_f16x2_shifts")
+
+    def calibrate(self, images, boxes):
+        """Pick each site's activation exponent from one probe forward (suo_net_calibrate) on frames as forward_frames takes them: images uint8 [B,H,W,3]
+        (or a list of B frames) or [H,W,3] for one frame, boxes a list of B arrays [L_b,4] (or one array for one frame).  Call once after loading a checkpoint,
+        with a representative frame, and keep the result with the checkpoint (set_f16x2_shifts).  Returns {site name: s}; the network runs the fp16 form afterwards."""
+        assert self._h is not None, "load_state_dict first"
+        dev = self.device
+        if isinstance(images, np.ndarray) and images.ndim == 3:
+            images = images[None]
+        if not isinstance(boxes, (list, tuple)):
+            boxes = [boxes]
+        frames = np.stack([np.asarray(f) for f in images]) if isinstance(images, (list, tuple)) else np.asarray(images)
+        assert frames.dtype == np.uint8 and frames.ndim == 4 and frames.shape[3] == 3 and frames.shape[0] == len(boxes)
+        imgs = torch.from_numpy(np.ascontiguousarray(frames)).to(dev)
+        bx = torch.from_numpy(np.concatenate([np.asarray(b, np.float32).reshape(-1, 4) for b in boxes])).to(dev).contiguous()
+        idx = torch.from_numpy(np.concatenate([np.full(len(b), i, np.int32) for i, b in enumerate(boxes)])).to(dev).contiguous()
+        _lib.check(_lib.lib().suo_net_calibrate(self._h, _ptr(imgs), 0, int(frames.shape[1]), int(frames.shape[2]), _ptr(bx), _ptr(idx), int(bx.shape[0]), _stream()),
+                   "suo_net_calibrate")
+        return self.f16x2_shifts()
+
     def _checked(self, call):
         """forward(check=True): the call's own validity once the stream has run it.  An invalid call is re-issued by the caller here, so the raise is also
         answered for range_exceeded()'s readers (as the blocking C entries do)."""
