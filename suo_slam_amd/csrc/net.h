@@ -4,6 +4,7 @@
 #include <memory>
 #include <stdexcept>
 #include <string>
+#include <utility>
 #include <vector>
 
 #include "suo_internal.h"
@@ -87,18 +88,33 @@ private:
     void make_residual(const std::string& p, ResidualW& r);
     void make_hourglass(const std::string& p, int n, HourglassW& h);
     float* alloc(size_t floats);
+    // How one Residual block runs at one call shape: the route (which launches), the form each launch runs on (0 = fp32 MFMA, 1 = three bf16 terms, 2 = two
+    // fp16 terms) and what the route can do for its neighbours.  Net::plan_block is the only place that decides any of it; residual() and hourglass() read it.
+    struct BlockPlan {
+        enum Route { ONE_LAUNCH,       // the whole block in one launch (csrc/res_small.hip: form 0; csrc/res_small_x3.hip: forms 1 and 2)
+                     DIRECT_FUSED,     // conv1 | direct 3x3 + conv3 + skip (csrc/conv.hip: FUSE)
+                     WINO_FUSED,       // conv1 | Winograd 3x3 + conv3 + skip [+ up-sampled addend] [+ the next block's conv1]
+                     PER_LAYER };      // conv1 | 3x3 | conv3 (+ conv4)
+        Route route = PER_LAYER;
+        bool wino = false;                     // the 3x3 on the Winograd kernels (else the direct kernel, fp32 pipe)
+        int form = 0;                          // of the one-launch block / the Winograd 3x3 and its tail
+        int form1 = 0, form3 = 0;              // of conv1 / conv3 as launches of their own (gemm_form)
+        bool takes_up = false;                 // the route adds an up-sampled addend itself (residual() refuses `up` on any other before it enqueues anything)
+        bool can_carry_next_conv1 = false;     // its tail can also compute the conv1 of the block that follows at this resolution (without `up` / `pool_out`)
+        bool uses_producer_conv1 = false;      // as a consumer: the route takes a conv1 its producer computed (pre_) -- a fused fp16 tail's, or the fused stem's for r1
+    };
+    BlockPlan plan_block(const ResidualW& r, int L, int H, int W) const;
     // pool_out: also produce max_pool2d(out, 2, 2) (fused into the last GEMM where it can be, else a separate launch); `out` may then be nullptr
-    // next: the Residual block that consumes `out` next at this resolution (or nullptr): where this block ends in the fused fp16 Winograd tail, that launch
-    // also computes next's conv1 (csrc/conv_wino_x3.hip, NEXT) and residual(*next, out, ...) finds it done (pre_*)
+    // next: the Residual block that consumes `out` next at this resolution (or nullptr): where this block's plan can carry next's conv1 and next's plan uses
+    // it, the tail launch also computes it (csrc/conv_wino_x3.hip, NEXT) and residual(*next, out, ...) finds it done (pre_*)
     int residual(const ResidualW& r, const float* x, float* out, int L, int H, int W, hipStream_t s, const float* up = nullptr, float* pool_out = nullptr,
                  const ResidualW* next = nullptr);
     long wino_min_tiles() const;
     long x3_min_rows() const;
-    bool next_conv1_fusable(const ResidualW& next, int L, int H, int W) const;
-    int gemm_maybe_pooled(GemmArgs& g, int L, int H, int W, float* pool_out, hipStream_t s, const GemmW* gw = nullptr);
-    bool residual_tail_is_fused(const ResidualW& r, int L, int H, int W) const;
-    int residual_in_one_launch(const ResidualW& r, int L, int H, int W) const;      // 0: no; 1: csrc/res_small.hip; 2: csrc/res_small_x3.hip
-    int residual_one_launch(const ResidualW& r, const float* x, float* out, int L, int H, int W, hipStream_t s, const float* up, bool pool_in);
+    int gemm_form(const GemmW& gw, long M) const;
+    int gemm_maybe_pooled(GemmArgs& g, int L, int H, int W, float* pool_out, hipStream_t s, const GemmW& gw, int form);
+    int residual_one_launch(const ResidualW& r, const BlockPlan& p, const float* x, float* out, int L, int H, int W, hipStream_t s, const float* up, bool pool_in);
+    std::pair<float*, float*> layout_slabs();      // {staged input, logits}
     int hourglass(const HourglassW& h, const float* x, float* out, int L, int H, int W, hipStream_t s, int depth_idx, const float* x_pooled = nullptr);
     int backbone(const float* in0, int in_c, float* logits, int L, hipStream_t s, bool stem_done = false);
     int run_backbone(float* in0, int in_c, float* logits, int L, hipStream_t s, bool stem_done = false);

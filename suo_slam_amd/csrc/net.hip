@@ -502,12 +502,7 @@ Net::Net(int n, const char* const* names, const float* const* data, const int64_
     // Size it with a dry run of the launch schedule at max_crops.
     dry_run_ = true;
     ws_floats_ = (size_t)-1 / sizeof(float) / 2;
-    ws_used_ = 0;
-    (void)alloc((size_t)max_crops_ * CROP * CROP * IN_C);
-    (void)alloc((size_t)max_crops_ * NUM_KP * HEAT * HEAT);
-    stem_slab_ = alloc((size_t)max_crops_ * 128 * 128 * 64);
-    stem_mid1_slab_ = alloc((size_t)max_crops_ * 128 * 128 * 64);
-    ws_mark_ = ws_used_;
+    (void)layout_slabs();
     // (every pipe this network can run on: the forms pick different kernels -- per-layer launches with their intermediate tensors where another form
     //  takes a one-launch block -- and a network that falls back to bf16x3 must find its workspace large enough)
     size_t need = 0;
@@ -539,6 +534,18 @@ Net::~Net() {
     for (int i = 0; i < kNumSide; ++i) if (side_[i]) (void)hipStreamDestroy(side_[i]);
     if (own_stream_) (void)hipStreamDestroy(own_stream_);
     for (int i = 0; i < kNumEvents; ++i) if (ev_[i]) (void)hipEventDestroy(ev_[i]);
+}
+
+// The persistent slabs at the bottom of the workspace, the same for every call (captured graphs hold their addresses); the schedule's intermediates follow ws_mark_.
+// (calibrate lays out its own: sized by its crop count, without r1's conv1 slab)
+std::pair<float*, float*> Net::layout_slabs() {
+    ws_used_ = 0;
+    float* in0 = alloc((size_t)max_crops_ * CROP * CROP * IN_C);      // the staged input
+    float* logits = alloc((size_t)max_crops_ * NUM_KP * HEAT * HEAT);
+    stem_slab_ = alloc((size_t)max_crops_ * 128 * 128 * 64);          // the stem's output: persistent, the fused stem writes it OUTSIDE the captured graph
+    stem_mid1_slab_ = alloc((size_t)max_crops_ * 128 * 128 * 64);     // ... and r1's conv1 of it, when the stem launch computes that too
+    ws_mark_ = ws_used_;
+    return {in0, logits};
 }
 
 float* Net::alloc(size_t floats) {
@@ -578,8 +585,8 @@ static double block_bytes(const ResBlockArgs& a, double wb) {
     return 4.0 * px * 256 * (a.pool_in ? 4 : 1) + 4.0 * px * 256 + (a.up ? 4.0 * (px / 4) * 256 : 0.0) + wb * (256.0 * 128 + 128.0 * 128 * 9 + 128.0 * 256);
 }
 
-// Residual.forward: three fused launches
-// true when residual() ends in the fused Winograd tail (the only epilogue that can add an up-sampled tensor)
+static double weight_bytes(int form) { return form == 1 ? 6 : 4; }      // per element: fp32 or two fp16 planes | three bf16 planes
+
 // Launch-size thresholds of the split-operand kernels.  The Winograd kernels and the bf16x3 GEMM were introduced for batched calls and measured against the fp32-pipe
 // kernels' smaller tiles: from 256 tiles of 8 x 16 pixels / 32768 rows up.  The fp16 forms changed the balance for calls of FEW crops (SLAM passes run 2-7): a fused fp16
 // tail takes ~50 us whatever the crop count below 8 (one workgroup per CU) where direct 3x3 + conv3 take 84-106; measured per network call of L crops (bench.py --only cnn
@@ -593,28 +600,30 @@ long Net::x3_min_rows() const {
     static const long env = (long)SUO_TUNE("SUO_GEMM_X3_MIN_ROWS", -1);
     return env >= 0 ? env : (pipe_ == 2 ? 4096 : 32768);
 }
-
-bool Net::residual_tail_is_fused(const ResidualW& r, int L, int H, int W) const {
-    const long fuse_tiles = wino_min_tiles();
-    ConvArgs c2 = {};
-    c2.L = L; c2.H = H; c2.W = W; c2.C = r.c2.C; c2.OH = H; c2.OW = W; c2.N = r.c2.N;
-    const long tiles = (long)((W + 15) / 16) * ((H + 7) / 8) * L;
-    return !probe_ && r.c2.Wq && conv3x3_wino_pays(c2, pipe_ == 2 ? 32 : -1) && fuse_tiles > 0 && tiles >= fuse_tiles && !r.has_skip_conv && r.c3.N == 256 && r.c3.n_valid == 256 &&
-           r.c3.K1 == 128 && r.cin == 256;
+// a 1x1 convolution of M rows as a launch of its own: large launches with a bf16x3 form of the weights run on the bf16 pipe (csrc/gemm_bf16x3.hip; 464 vs 595 us at
+// 256 crops / 64 x 64; below ~256 tiles the fp32 kernels' smaller tiles win), as two fp16 terms where the network is on that form (csrc/f16x2.h)
+int Net::gemm_form(const GemmW& gw, long M) const {
+    return !gw.Wx3 || M < x3_min_rows() ? 0 : (pipe_ == 2 && gw.W16 ? 2 : 1);
 }
 
-// A 256 -> 256 block on a small map in ONE launch (csrc/res_small_x3.hip / csrc/res_small.hip) instead of three: the call shape of the
-// reference (one frame = 8 crops per call, lib/object_slam.py:1099).  Measured per block at 8 crops (tools/bench_res_block.py, us; per-layer
-// launches -> one launch on the bf16 pipe): 32x32 47 -> 29.6, 16x16 26.6 -> 25.0; at 8x8 and 4x4 the three per-layer launches (13.5) stay
-// faster -- a workgroup streams all 0.85 / 1.28 MB of the block's weights through ONE CU whatever its tile, 20-24 us at 35 bytes per clock.
-//   SUO_RES_FUSED = 0: never; 1: the fp32-pipe kernel (bit-identical to the per-layer launches); 2 (default with SUO_WINO_BF16X3): the bf16x3 kernel
-//   SUO_RES_FUSED_MAX_TILES: largest launch (4 x 8 pixel tiles) that takes it; beyond that the Winograd kernels' larger tiles win
-int Net::residual_in_one_launch(const ResidualW& r, int L, int H, int W) const {
+// conv2 of a block at L x H x W, on the direct kernel's operands: what the kernels' shape predicates look at; residual() adds the tensors
+static ConvArgs conv2_args(const ResidualW& r, int L, int H, int W) {
+    ConvArgs c2 = {};
+    c2.L = L; c2.H = H; c2.W = W; c2.C = r.c2.C; c2.Wp = r.c2.Wp; c2.bias = r.c2.bias; c2.OH = H; c2.OW = W; c2.N = r.c2.N; c2.relu = 1;
+    return c2;
+}
+
+// Residual.forward (layers/Residual.py): THE place that decides how a block runs -- a pure function of the block, the call shape and the network's state.
+Net::BlockPlan Net::plan_block(const ResidualW& r, int L, int H, int W) const {
+    // A 256 -> 256 block on a small map in ONE launch (csrc/res_small_x3.hip / csrc/res_small.hip) instead of three: the call shape of the
+    // reference (one frame = 8 crops per call, lib/object_slam.py:1099).  Measured per block at 8 crops (tools/bench_res_block.py, us; per-layer
+    // launches -> one launch on the bf16 pipe): 32x32 47 -> 29.6, 16x16 26.6 -> 25.0; at 8x8 and 4x4 the three per-layer launches (13.5) stay
+    // faster -- a workgroup streams all 0.85 / 1.28 MB of the block's weights through ONE CU whatever its tile, 20-24 us at 35 bytes per clock.
+    //   SUO_RES_FUSED = 0: never; 1: the fp32-pipe kernel (bit-identical to the per-layer launches); 2 (default with SUO_WINO_BF16X3): the bf16x3 kernel
+    //   SUO_RES_FUSED_MAX_TILES: largest launch (4 x 8 pixel tiles) that takes it; beyond that the Winograd kernels' larger tiles win
     static const int mode = (int)SUO_TUNE("SUO_RES_FUSED", 2);
     static const long max_tiles = (long)SUO_TUNE("SUO_RES_FUSED_MAX_TILES", 768);
     static const int min_side = (int)SUO_TUNE("SUO_RES_FUSED_MIN_SIDE", 16);
-    if (probe_ || mode <= 0 || !r.rb_w[0] || H > 32 || W > 32) return 0;
-    const long t32 = (long)L * ((H + 3) / 4) * ((W + 7) / 8);
     // Half a round to three rounds of 4 x 8 pixel tiles (one workgroup per CU): the bf16x3 kernel, whatever the map (one frame at 32x32; batched frames at 8x8
     // and 4x4, where it replaces three launches of 17-47 us by one or two rounds of 30).  Fewer tiles than CUs on a map of >= 16 pixels a
     // side: the fp32 kernel's 4 x 4 tiles (16x16 at 8 crops: 128 workgroups x 23.4 us against 64 x 28).  Everything else -- few tiles on
@@ -626,32 +635,70 @@ int Net::residual_in_one_launch(const ResidualW& r, int L, int H, int W) const {
     // fp32 kernel's 128 tiles of 4 x 4 take 23.4 and the bf16x3 form 23.1 -- it takes over from 33 tiles (tools/bench_res_block.py; 8x8 at 8 crops = 16 tiles: 16.6
     // against 13.4 for the three per-layer launches, which stay)
     static const long f16_from = (long)SUO_TUNE("SUO_RES_FUSED_F16_FROM", 33);
-    const long x3_from = (pipe_ == 2 && r.rbh_w[0] && mode >= 2) ? std::min(f16_from, x3_from_env) : x3_from_env;
-    if (mode >= 2 && r.rbx_w[0] && t32 >= x3_from && t32 <= max_tiles) return 2;
-    if (H >= min_side && W >= min_side && (t32 < x3_from || (mode == 1 && t32 <= max_tiles))) return 1;
-    return 0;
+    static const int carry_next = (int)SUO_TUNE("SUO_FUSE_NEXT_CONV1", 1);           // 0: A/B
+    int one = 0;                                              // 1: csrc/res_small.hip; 2: csrc/res_small_x3.hip
+    if (mode > 0 && r.rb_w[0] && H <= 32 && W <= 32) {
+        const long t32 = (long)L * ((H + 3) / 4) * ((W + 7) / 8);
+        const long x3_from = (pipe_ == 2 && r.rbh_w[0] && mode >= 2) ? std::min(f16_from, x3_from_env) : x3_from_env;
+        if (mode >= 2 && r.rbx_w[0] && t32 >= x3_from && t32 <= max_tiles) one = 2;
+        else if (H >= min_side && W >= min_side && (t32 < x3_from || (mode == 1 && t32 <= max_tiles))) one = 1;
+    }
+    const ConvArgs c2 = conv2_args(r, L, H, W);
+    const long M = (long)L * H * W, tiles = (long)((W + 15) / 16) * ((H + 7) / 8) * L, fuse_tiles = wino_min_tiles();      // (tiles of 8 x 16 pixels)
+    // conv2 -> conv3 + skip can be one launch: the 128-channel tensor between them never leaves the CU
+    const bool tail_shape = !r.has_skip_conv && r.c3.N == 256 && r.c3.n_valid == 256 && r.c3.K1 == 128 && r.cin == 256;
+    BlockPlan p;
+    p.wino = r.c2.Wq && conv3x3_wino_pays(c2, pipe_ == 2 ? 32 : -1);       // 2.25x fewer MFMA MACs (csrc/conv_wino.hip)
+    if (probe_) p.route = BlockPlan::PER_LAYER;               // the calibration probe: every operand of the block's three sites in memory
+    else if (one) p.route = BlockPlan::ONE_LAUNCH;
+    else if (!p.wino && tail_shape && conv3x3_fusable(c2)) p.route = BlockPlan::DIRECT_FUSED;      // (csrc/conv.hip: FUSE)
+    else if (p.wino && fuse_tiles > 0 && tiles >= fuse_tiles && tail_shape) p.route = BlockPlan::WINO_FUSED;      // (933 vs 713 + 346 us at 64x64 / 128 crops, 257 vs 195 + 91 at 32x32)
+    const bool tail = p.route == BlockPlan::WINO_FUSED;
+    // one launch: two fp16 planes stream a third less weight per workgroup and take half the MFMAs; Winograd: both products as two fp16 terms (csrc/f16x2.h),
+    // else on the bf16 pipe with 3-way split operands, else fp32
+    if (p.route == BlockPlan::ONE_LAUNCH) p.form = one == 2 ? (pipe_ == 2 && r.rbh_w[0] ? 2 : 1) : 0;
+    else if (p.wino) p.form = pipe_ == 2 && r.c2.Wq16 && (!tail || r.c3x16) ? 2 : (r.c2.Wq3 && (!tail || r.c3x) ? 1 : 0);
+    p.form1 = gemm_form(r.c1, M); p.form3 = gemm_form(r.c3, M);
+    // the fused Winograd tail is the only epilogue of the per-layer kernels that can add an up-sampled tensor
+    p.takes_up = p.route == BlockPlan::ONE_LAUNCH || tail;
+    // The next block's conv1 on the fused fp16 tail's tile while it is in the CU: its 256-channel input is written once and not re-read by a GEMM launch.
+    // (Not with an up-sampled addend: that variant has no registers left -- measured no gain, tools/bench_f16x2.py; the eight-wave form of small launches
+    //  does not carry it.)  It can ride there when the separate launch would have been the fp16 GEMM on the same operands (256 -> 128 with a BatchNorm
+    // prologue, >= SUO_GEMM_X3_MIN_ROWS pixels, not a one-launch block): then the two are bit-identical (tests/test_gpu_f16x2.py)
+    p.can_carry_next_conv1 = carry_next && tail && p.form == 2 && !conv3x3_wino_f16x2_w8(tiles);
+    const bool from_tail = p.form1 == 2 && r.cin == 256 && r.c1.osc16 && r.c1.N == 128 && r.c1.n_valid == 128 && r.c1.K1 == 256 && r.c1.K2 == 0;
+    p.uses_producer_conv1 = p.route != BlockPlan::ONE_LAUNCH && (from_tail || (&r == &r1_ && stem_computes_r1_conv1()));
+    return p;
 }
 
-int Net::residual_one_launch(const ResidualW& r, const float* x, float* out, int L, int H, int W, hipStream_t s, const float* up, bool pool_in) {
-    const int kind = residual_in_one_launch(r, L, H, W);
+// the operands of a Winograd 3x3 (tail: and of its fused conv3) in the given form; returns the bytes per weight element the accounting uses
+static double wino_operands(ConvArgs& c, const ResidualW& r, int form, bool tail, unsigned* range_flag) {
+    if (form == 2) {
+        c.Wp = r.c2.Wq16; c.oscale = r.c2.osc16; c.range_flag = range_flag; c.xscale = r.c2.xs16;
+        if (tail) { c.W3p = r.c3x16; c.oscale3 = r.c3osc16; c.xscale3 = r.c3.xs16; }
+    } else if (form == 1) {
+        c.Wp = r.c2.Wq3;
+        if (tail) { c.W3p = r.c3x; c.w3_bf16x3 = 1; }
+    } else c.Wp = r.c2.Wq;
+    return weight_bytes(form);
+}
+static int launch_wino(const ConvArgs& c, int form, bool tail, hipStream_t s) {
+    if (tail) return form == 2 ? launch_conv3x3_wino_f16x2_fused(c, s) : form == 1 ? launch_conv3x3_wino_x3_fused(c, s) : launch_conv3x3_wino_fused(c, s);
+    return form == 2 ? launch_conv3x3_wino_f16x2(c, s) : form == 1 ? launch_conv3x3_wino_x3(c, s) : launch_conv3x3_wino(c, s);
+}
+
+int Net::residual_one_launch(const ResidualW& r, const BlockPlan& p, const float* x, float* out, int L, int H, int W, hipStream_t s, const float* up, bool pool_in) {
     ResBlockArgs a = {};
     a.x = x; a.L = L; a.H = H; a.W = W; a.pool_in = pool_in ? 1 : 0; a.pro_scale = r.pro_scale; a.pro_shift = r.pro_shift;
     a.b1 = r.c1.bias; a.b2 = r.c2.bias; a.b3 = r.c3.bias; a.up = up; a.out = out;
-    if (kind == 2 && pipe_ == 2 && r.rbh_w[0]) {                      // two fp16 planes: a third less weight traffic per workgroup, half the MFMAs
-        a.W1 = r.rbh_w[0]; a.W2 = r.rbh_w[1]; a.W3 = r.rbh_w[2];
+    float* const* w = p.form == 2 ? r.rbh_w : p.form == 1 ? r.rbx_w : r.rb_w;
+    a.W1 = w[0]; a.W2 = w[1]; a.W3 = w[2];
+    if (p.form == 2) {
         a.osc1 = r.rbh_osc[0]; a.osc2 = r.rbh_osc[1]; a.osc3 = r.rbh_osc[2]; a.range_flag = range_flag_;
         a.xs1 = r.c1.xs16; a.xs2 = r.c2.xs16; a.xs3 = r.c3.xs16;
-        acct(ACCT_BLOCK, block_bytes(a, 4));
-        SUO_LAUNCH(launch_res_block_f16x2(a, s));
-    } else if (kind == 2) {
-        a.W1 = r.rbx_w[0]; a.W2 = r.rbx_w[1]; a.W3 = r.rbx_w[2];
-        acct(ACCT_BLOCK, block_bytes(a, 6));
-        SUO_LAUNCH(launch_res_block_x3(a, s));
-    } else {
-        a.W1 = r.rb_w[0]; a.W2 = r.rb_w[1]; a.W3 = r.rb_w[2];
-        acct(ACCT_BLOCK, block_bytes(a, 4));
-        SUO_LAUNCH(launch_res_block(a, s));
     }
+    acct(ACCT_BLOCK, block_bytes(a, weight_bytes(p.form)));
+    SUO_LAUNCH(p.form == 2 ? launch_res_block_f16x2(a, s) : p.form == 1 ? launch_res_block_x3(a, s) : launch_res_block(a, s));
     return SUO_OK;
 }
 
@@ -661,27 +708,22 @@ int Net::maxpool(const float* in, float* out, int L, int H, int W, int C, hipStr
     return SUO_OK;
 }
 
-// A 1x1 convolution whose result is also wanted max-pooled (nn.MaxPool2d(2, 2)): pooled in the GEMM's epilogue when the launch
-// would use the persistent 128x128 kernel anyway (csrc/gemm_persist.hip: POOL), else GEMM + max-pool kernel.  g.out may be nullptr
+// A 1x1 convolution on the form the caller's plan gives (gemm_form), whose result may also be wanted max-pooled (nn.MaxPool2d(2, 2)): pooled in the GEMM's epilogue
+// when the launch would use the persistent 128x128 kernel anyway (csrc/gemm_persist.hip: POOL), else GEMM + max-pool kernel.  g.out may be nullptr
 // when only the pooled tensor is wanted.
-int Net::gemm_maybe_pooled(GemmArgs& g, int L, int H, int W, float* pool_out, hipStream_t s, const GemmW* gw) {
-    const float* Wx3 = gw ? gw->Wx3 : nullptr;
+int Net::gemm_maybe_pooled(GemmArgs& g, int L, int H, int W, float* pool_out, hipStream_t s, const GemmW& gw, int form) {
     static const int fuse_pool = (int)suo::env_switch("SUO_FUSE_POOL", 1);                    // 0: A/B
-    // large launches with a bf16x3 form of the weights: on the bf16 pipe (csrc/gemm_bf16x3.hip)
-    const long x3_min_rows = this->x3_min_rows();
-    if (Wx3 && g.M >= x3_min_rows) {
+    if (form) {
         GemmArgs gx = g;
         gx.pool_out = pool_out; gx.pool_H = H; gx.pool_W = W;                  // the pool in the epilogue (maps of 64-column multiples), `out` optional
-        const bool f16 = pipe_ == 2 && gw->W16;                              // the two-term fp16 form of the same kernel (csrc/f16x2.h)
-        if (f16) { gx.oscale = gw->osc16; gx.range_flag = range_flag_; gx.xscale = gw->xs16; }
-        auto launch = [&](const GemmArgs& a) { return f16 ? launch_gemm_f16x2_args(a, reinterpret_cast<const uint16_t*>(gw->W16), s) : launch_gemm_bf16x3_args(a, reinterpret_cast<const uint16_t*>(Wx3), s); };
-        if (gemm_bf16x3_takes(gx)) { acct(ACCT_GEMM, gemm_bytes(gx, f16 ? 4 : 6)); SUO_LAUNCH(launch(gx)); return SUO_OK; }
-        gx.pool_out = nullptr;                                                // else the pool as its own launch
-        if (g.out && gemm_bf16x3_takes(gx)) {
-            acct(ACCT_GEMM, gemm_bytes(gx, f16 ? 4 : 6));
+        if (form == 2) { gx.oscale = gw.osc16; gx.range_flag = range_flag_; gx.xscale = gw.xs16; }      // the two-term fp16 form of the same kernel (csrc/f16x2.h)
+        auto launch = [&](const GemmArgs& a) { return form == 2 ? launch_gemm_f16x2_args(a, reinterpret_cast<const uint16_t*>(gw.W16), s) : launch_gemm_bf16x3_args(a, reinterpret_cast<const uint16_t*>(gw.Wx3), s); };
+        const bool pool_in_gemm = gemm_bf16x3_takes(gx);
+        if (!pool_in_gemm) gx.pool_out = nullptr;                             // else the pool as its own launch
+        if (pool_in_gemm || (g.out && gemm_bf16x3_takes(gx))) {
+            acct(ACCT_GEMM, gemm_bytes(gx, weight_bytes(form)));
             SUO_LAUNCH(launch(gx));
-            if (pool_out) SUO_TRY(maxpool(g.out, pool_out, L, H, W, g.N, s));
-            return SUO_OK;
+            return !pool_in_gemm && pool_out ? maxpool(g.out, pool_out, L, H, W, g.N, s) : SUO_OK;
         }
     }
     if (!pool_out) { acct(ACCT_GEMM, gemm_bytes(g, 4)); SUO_LAUNCH(launch_gemm1x1(g, s)); return SUO_OK; }
@@ -695,27 +737,19 @@ int Net::gemm_maybe_pooled(GemmArgs& g, int L, int H, int W, float* pool_out, hi
     return maxpool(g.out, pool_out, L, H, W, g.N, s);
 }
 
-// The next block's conv1 can ride on this block's fused fp16 tail when the separate launch would have been the fp16 GEMM on the same operands
-// (256 -> 128 with a BatchNorm prologue, >= SUO_GEMM_X3_MIN_ROWS pixels, not a one-launch block): then the two are bit-identical (tests/test_gpu_f16x2.py)
-bool Net::next_conv1_fusable(const ResidualW& next, int L, int H, int W) const {
-    static const int on = (int)SUO_TUNE("SUO_FUSE_NEXT_CONV1", 1);                // 0: A/B
-    const long x3_min_rows = this->x3_min_rows();
-    return on && pipe_ == 2 && next.cin == 256 && next.c1.W16 && next.c1.osc16 && next.c1.N == 128 && next.c1.n_valid == 128 && next.c1.K1 == 256 && next.c1.K2 == 0 &&
-           (long)L * H * W >= x3_min_rows && !residual_in_one_launch(next, L, H, W) &&
-           !conv3x3_wino_f16x2_w8((long)((W + 15) / 16) * ((H + 7) / 8) * L);                     // (the eight-wave form of small launches does not carry it)
-}
-
+// Executes plan_block's plan; no decision of its own.  (The sequence of alloc calls per route is part of the behaviour: captured graphs hold the addresses.)
 int Net::residual(const ResidualW& r, const float* x, float* out, int L, int H, int W, hipStream_t s, const float* up, float* pool_out, const ResidualW* next) {
+    const BlockPlan p = plan_block(r, L, H, W);
     const int M = L * H * W;
-    if (residual_in_one_launch(r, L, H, W)) {
+    if (up && !p.takes_up) { suo_set_error("residual: an up-sampled addend needs a one-launch block or the fused Winograd tail"); return SUO_ERR_ARG; }
+    if (p.route == BlockPlan::ONE_LAUNCH) {
         if (!out) out = alloc((size_t)M * 256);
-        SUO_TRY(residual_one_launch(r, x, out, L, H, W, s, up, false));
-        if (pool_out) SUO_TRY(maxpool(out, pool_out, L, H, W, 256, s));
-        return SUO_OK;
+        SUO_TRY(residual_one_launch(r, p, x, out, L, H, W, s, up, false));
+        return pool_out ? maxpool(out, pool_out, L, H, W, 256, s) : SUO_OK;
     }
     float* mid1 = nullptr;
-    for (size_t i = 0; i < pre_.size(); ++i)
-        if (pre_[i].x == x && pre_[i].r == &r) {              // conv1 came with the producer block's tail (NEXT)
+    for (size_t i = 0; p.uses_producer_conv1 && i < pre_.size(); ++i)
+        if (pre_[i].x == x && pre_[i].r == &r) {              // conv1 came with the producer's launch (a fused tail's NEXT, the fused stem's)
             mid1 = pre_[i].mid1;
             pre_.erase(pre_.begin() + i);
             break;
@@ -725,61 +759,25 @@ int Net::residual(const ResidualW& r, const float* x, float* out, int L, int H, 
         GemmArgs g1 = {};
         g1.A1 = x; g1.lda1 = r.cin; g1.K1 = r.c1.K1; g1.pro_scale = r.pro_scale; g1.pro_shift = r.pro_shift;
         g1.Wp = r.c1.Wp; g1.bias = r.c1.bias; g1.out = mid1; g1.ldo = r.c1.N; g1.M = M; g1.N = r.c1.N; g1.n_valid = r.c1.n_valid; g1.relu = 1;
-        // large launches: on the bf16 pipe with 3-way split operands (464 vs 595 us at 256 crops / 64 x 64; below ~256 tiles the fp32 kernels' smaller tiles win)
-        SUO_TRY(gemm_maybe_pooled(g1, L, H, W, nullptr, s, &r.c1));
+        SUO_TRY(gemm_maybe_pooled(g1, L, H, W, nullptr, s, r.c1, p.form1));
     }
     float* mid2 = alloc((size_t)M * r.c2.N);
-    ConvArgs c2 = {};
-    c2.in = mid1; c2.L = L; c2.H = H; c2.W = W; c2.C = r.c2.C; c2.Wp = r.c2.Wp; c2.bias = r.c2.bias;
-    c2.out = mid2; c2.OH = H; c2.OW = W; c2.N = r.c2.N; c2.relu = 1;
-    const bool wino = r.c2.Wq && conv3x3_wino_pays(c2, pipe_ == 2 ? 32 : -1);       // 2.25x fewer MFMA MACs (csrc/conv_wino.hip)
-    if (!probe_ && !wino && !r.has_skip_conv && r.c3.N == 256 && r.c3.n_valid == 256 && r.c3.K1 == 128 && r.cin == 256 && conv3x3_fusable(c2)) {
-        // conv2 -> conv3 + skip in one launch: the 128-channel tensor between them never leaves the CU (csrc/conv.hip: FUSE)
+    ConvArgs c2 = conv2_args(r, L, H, W);
+    c2.in = mid1; c2.out = mid2;
+    const bool tail = p.route != BlockPlan::PER_LAYER;       // conv2 -> conv3 + skip in one launch
+    if (tail) {
         if (!out) out = alloc((size_t)M * 256);
-        c2.W3p = r.c3.Wp; c2.bias3 = r.c3.bias; c2.R = x; c2.out2 = out; c2.N2 = 256;
-        acct(ACCT_CONV3, conv_bytes(c2, 4, 9, true));
-        SUO_LAUNCH(launch_conv3x3_fused(c2, s));
-        if (pool_out) SUO_TRY(maxpool(out, pool_out, L, H, W, 256, s));
-        return SUO_OK;
+        c2.W3p = r.c3.Wp; c2.bias3 = r.c3.bias; c2.R = x; c2.out2 = out; c2.N2 = 256; c2.up = up;
     }
-    if (wino) {
-        c2.Wp = r.c2.Wq;
-        const long fuse_tiles = wino_min_tiles();
-        const long tiles = (long)((W + 15) / 16) * ((H + 7) / 8) * L;
-        if (!probe_ && fuse_tiles > 0 && tiles >= fuse_tiles && !r.has_skip_conv && r.c3.N == 256 && r.c3.n_valid == 256 && r.c3.K1 == 128 && r.cin == 256) {
-            // conv2 -> conv3 + skip in one launch (933 vs 713 + 346 us at 64x64 / 128 crops, 257 vs 195 + 91 at 32x32)
-            if (!out) out = alloc((size_t)M * 256);
-            c2.W3p = r.c3.Wp; c2.bias3 = r.c3.bias; c2.R = x; c2.out2 = out; c2.N2 = 256; c2.up = up;
-            if (pipe_ == 2 && r.c2.Wq16 && r.c3x16) {        // both products as two fp16 terms (csrc/f16x2.h)
-                c2.Wp = r.c2.Wq16; c2.W3p = r.c3x16; c2.oscale = r.c2.osc16; c2.oscale3 = r.c3osc16; c2.range_flag = range_flag_; c2.xscale = r.c2.xs16; c2.xscale3 = r.c3.xs16;
-                // the next block's conv1 on the tile while it is in the CU: its 256-channel input is written once and not re-read by a GEMM launch.
-                // (Not with an up-sampled addend: that variant has no registers left -- measured no gain, tools/bench_f16x2.py.)
-                if (next && !up && !pool_out && next_conv1_fusable(*next, L, H, W)) {
-                    float* nm = alloc((size_t)M * 128);
-                    c2.n_scale = next->pro_scale; c2.n_shift = next->pro_shift; c2.n_W1 = next->c1.W16; c2.n_osc1 = next->c1.osc16; c2.n_b1 = next->c1.bias; c2.n_out = nm; c2.n_xscale = next->c1.xs16;
-                    pre_.push_back({out, next, nm});
-                }
-                acct(ACCT_CONV3, conv_bytes(c2, 4, 16, true));
-                SUO_LAUNCH(launch_conv3x3_wino_f16x2_fused(c2, s));
-            } else if (r.c2.Wq3 && r.c3x) {                   // both products on the bf16 pipe, 3-way split operands
-                c2.Wp = r.c2.Wq3; c2.W3p = r.c3x; c2.w3_bf16x3 = 1;
-                acct(ACCT_CONV3, conv_bytes(c2, 6, 16, true));
-                SUO_LAUNCH(launch_conv3x3_wino_x3_fused(c2, s));
-            } else {
-                acct(ACCT_CONV3, conv_bytes(c2, 4, 16, true));
-                SUO_LAUNCH(launch_conv3x3_wino_fused(c2, s));
-            }
-            if (pool_out) SUO_TRY(maxpool(out, pool_out, L, H, W, 256, s));
-            return SUO_OK;
-        }
-        if (pipe_ == 2 && r.c2.Wq16) { c2.Wp = r.c2.Wq16; c2.oscale = r.c2.osc16; c2.range_flag = range_flag_; c2.xscale = r.c2.xs16; acct(ACCT_CONV3, conv_bytes(c2, 4, 16, false)); SUO_LAUNCH(launch_conv3x3_wino_f16x2(c2, s)); }
-        else if (r.c2.Wq3) { c2.Wp = r.c2.Wq3; acct(ACCT_CONV3, conv_bytes(c2, 6, 16, false)); SUO_LAUNCH(launch_conv3x3_wino_x3(c2, s)); }
-        else { acct(ACCT_CONV3, conv_bytes(c2, 4, 16, false)); SUO_LAUNCH(launch_conv3x3_wino(c2, s)); }
-    } else {
-        acct(ACCT_CONV3, conv_bytes(c2, 4, 9, false));
-        SUO_LAUNCH(launch_conv3x3(c2, s));
+    const double wb = p.wino ? wino_operands(c2, r, p.form, tail, range_flag_) : 4;
+    if (next && !up && !pool_out && p.can_carry_next_conv1 && plan_block(*next, L, H, W).uses_producer_conv1) {
+        float* nm = alloc((size_t)M * 128);
+        c2.n_scale = next->pro_scale; c2.n_shift = next->pro_shift; c2.n_W1 = next->c1.W16; c2.n_osc1 = next->c1.osc16; c2.n_b1 = next->c1.bias; c2.n_out = nm; c2.n_xscale = next->c1.xs16;
+        pre_.push_back({out, next, nm});
     }
-    if (up) { suo_set_error("residual: an up-sampled addend needs the fused Winograd tail"); return SUO_ERR_ARG; }
+    acct(ACCT_CONV3, conv_bytes(c2, wb, p.wino ? 16 : 9, tail));
+    SUO_LAUNCH(p.wino ? launch_wino(c2, p.form, tail, s) : tail ? launch_conv3x3_fused(c2, s) : launch_conv3x3(c2, s));
+    if (tail) return pool_out ? maxpool(out, pool_out, L, H, W, 256, s) : SUO_OK;
     GemmArgs g3 = {};
     g3.A1 = mid2; g3.lda1 = r.c2.N; g3.K1 = r.c3.K1;
     if (r.has_skip_conv) { g3.A2 = x; g3.lda2 = r.cin; g3.K2 = r.c3.K2; }
@@ -791,7 +789,7 @@ int Net::residual(const ResidualW& r, const float* x, float* out, int L, int H, 
         SUO_TRY(probe_site(r.c3.site, mid2, M, r.c2.N, r.c2.N, nullptr, nullptr, 0, s));
         if (r.has_skip_conv) SUO_TRY(probe_site(r.c3.site, x, M, r.cin, r.cin, nullptr, nullptr, 0, s));      // (conv4's segment of the same split operand)
     }
-    return gemm_maybe_pooled(g3, L, H, W, pool_out, s, &r.c3);
+    return gemm_maybe_pooled(g3, L, H, W, pool_out, s, r.c3, p.form3);
 }
 
 // Hourglass.forward (hg.py:37-58).  The up1 branch is independent of the low branch until the
@@ -823,7 +821,7 @@ int Net::hourglass(const HourglassW& h, const float* x, float* out, int L, int H
     // branch itself and writes `out` -- no up-sample kernel, no extra pass over the high-resolution tensor.  The block then has to
     // wait for the low branch; its predecessor still runs beside it on the side stream.
     static const int fuse_up = (int)suo::env_switch("SUO_FUSE_UPSAMPLE", 1);              // 0: A/B
-    const bool up_in_tail = fuse_up && (residual_tail_is_fused(h.up1[1], L, H, W) || residual_in_one_launch(h.up1[1], L, H, W));
+    const bool up_in_tail = fuse_up && plan_block(h.up1[1], L, H, W).takes_up;
     SUO_TRY(residual(h.up1[0], x, up_a, L, H, W, side, nullptr, nullptr, &h.up1[1]));
     if (!up_in_tail) SUO_TRY(residual(h.up1[1], up_a, up_b, L, H, W, side));
     SUO_HIP_LIVE(hipEventRecord(ev_join, side));
@@ -831,7 +829,8 @@ int Net::hourglass(const HourglassW& h, const float* x, float* out, int L, int H
     const float* pooled = x_pooled;                           // (the caller's producer kernel may have pooled x already)
     // max_pool2d(x) (hg.py:41) has ONE reader, the first low block: when that block runs in one launch it takes the pool while staging x
     static const int pool_in_block = (int)SUO_TUNE("SUO_RES_POOL_IN", 1);           // 0: A/B
-    const bool pool_by_block = !pooled && pool_in_block && residual_in_one_launch(h.low1[0], L, H / 2, W / 2) && (H % 2 == 0) && (W % 2 == 0);
+    const BlockPlan low1 = plan_block(h.low1[0], L, H / 2, W / 2);
+    const bool pool_by_block = !pooled && pool_in_block && low1.route == BlockPlan::ONE_LAUNCH && (H % 2 == 0) && (W % 2 == 0);
     if (!pooled && !pool_by_block) {
         float* p = alloc(n_lo);
         SUO_TRY(maxpool(x, p, L, H, W, C, s));
@@ -839,7 +838,7 @@ int Net::hourglass(const HourglassW& h, const float* x, float* out, int L, int H
     }
     float* lo_a = alloc(n_lo);
     float* lo_b = alloc(n_lo);
-    if (pool_by_block) SUO_TRY(residual_one_launch(h.low1[0], x, lo_a, L, H / 2, W / 2, s, nullptr, true));
+    if (pool_by_block) SUO_TRY(residual_one_launch(h.low1[0], low1, x, lo_a, L, H / 2, W / 2, s, nullptr, true));
     else SUO_TRY(residual(h.low1[0], pooled, lo_a, L, H / 2, W / 2, s, nullptr, nullptr, &h.low1[1]));
     // (lo_b has two readers -- the inner hourglass's up1[0] and, pooled, its low1[0]: the first one's conv1 rides along)
     SUO_TRY(residual(h.low1[1], lo_a, lo_b, L, H / 2, W / 2, s, nullptr, nullptr, h.n > 1 ? &h.inner->up1[0] : &h.low2[0]));
@@ -867,7 +866,7 @@ int Net::backbone(const float* in0, int in_c, float* logits, int L, hipStream_t 
     ev_next_ = 0;
     pre_.clear();
     float* stem = stem_slab_;
-    if (stem_done && stem_computes_r1_conv1()) pre_.push_back({stem, &r1_, stem_mid1_slab_});      // (the fused stem launch leaves r1's conv1 there)
+    if (stem_done && plan_block(r1_, L, 128, 128).uses_producer_conv1) pre_.push_back({stem, &r1_, stem_mid1_slab_});      // (the fused stem launch leaves r1's conv1 there)
     if (!stem_done) {                                          // (the fused stem of the prior-less pass has filled the slab already: csrc/stem_x3.hip)
         ConvArgs c = {};
         const ConvW& sw = in_c == IMG_C ? stem_img_ : stem_;
@@ -906,7 +905,7 @@ int Net::backbone(const float* in0, int in_c, float* logits, int L, hipStream_t 
         GemmArgs gl = {};
         gl.A1 = rb; gl.lda1 = 256; gl.K1 = 256; gl.Wp = lin_[i].Wp; gl.bias = lin_[i].bias; gl.out = ll; gl.ldo = 256;
         gl.M = M; gl.N = 256; gl.n_valid = 256; gl.relu = 1;
-        SUO_TRY(gemm_maybe_pooled(gl, L, 64, 64, nullptr, s, &lin_[i]));
+        SUO_TRY(gemm_maybe_pooled(gl, L, 64, 64, nullptr, s, lin_[i], gemm_form(lin_[i], M)));
         if (probe_) {
             SUO_TRY(probe_site(lin_[i].site, rb, M, 256, 256, nullptr, nullptr, 0, s));
             SUO_TRY(probe_site(head_[i].site, ll, M, 256, 256, nullptr, nullptr, 0, s));
@@ -922,7 +921,7 @@ int Net::backbone(const float* in0, int in_c, float* logits, int L, hipStream_t 
             gr.Wp = reinject_.Wp; gr.bias = reinject_.bias; gr.R = x; gr.ldr = 256; gr.out = xn; gr.ldo = 256;
             gr.M = M; gr.N = 256; gr.n_valid = 256;
             xp = alloc((size_t)L * 32 * 32 * 256);
-            SUO_TRY(gemm_maybe_pooled(gr, L, 64, 64, xp, s, &reinject_));
+            SUO_TRY(gemm_maybe_pooled(gr, L, 64, 64, xp, s, reinject_, gemm_form(reinject_, M)));
             x = xn;
         } else {
             gh.out = logits; gh.n_valid = NUM_KP; gh.nchw_hw = HEAT * HEAT;
@@ -1205,12 +1204,7 @@ int Net::prepare(int L, int with_priors, hipStream_t s) {
     const bool own = (s == nullptr);
     if (own) s = own_stream_;
     try {
-        ws_used_ = 0;                                             // the same persistent slabs as forward()
-        float* in0 = alloc((size_t)max_crops_ * CROP * CROP * IN_C);
-        float* logits = alloc((size_t)max_crops_ * NUM_KP * HEAT * HEAT);
-        stem_slab_ = alloc((size_t)max_crops_ * 128 * 128 * 64);          // the stem's output: persistent, the fused stem writes it OUTSIDE the captured graph
-        stem_mid1_slab_ = alloc((size_t)max_crops_ * 128 * 128 * 64);     // ... and r1's conv1 of it, when the stem launch computes that too
-        ws_mark_ = ws_used_;
+        auto [in0, logits] = layout_slabs();
         hipGraphExec_t exec = nullptr;
         SUO_TRY(ensure_graph(in0, with_priors ? IN_C : IMG_C, logits, L, s, &exec, !with_priors && fused_stem()));
     } catch (const std::exception& e) {
@@ -1226,12 +1220,7 @@ int Net::forward_staged(const float* in0_user, int L, float* logits_out, hipStre
     const bool own = (s == nullptr);
     if (own) { s = own_stream_; SUO_TRY(follow_null_stream()); }
     try {
-        ws_used_ = 0;
-        float* in0 = alloc((size_t)max_crops_ * CROP * CROP * IN_C);
-        float* logits = alloc((size_t)max_crops_ * NUM_KP * HEAT * HEAT);
-        stem_slab_ = alloc((size_t)max_crops_ * 128 * 128 * 64);          // the stem's output: persistent, the fused stem writes it OUTSIDE the captured graph
-        stem_mid1_slab_ = alloc((size_t)max_crops_ * 128 * 128 * 64);     // ... and r1's conv1 of it, when the stem launch computes that too
-        ws_mark_ = ws_used_;
+        auto [in0, logits] = layout_slabs();
         if (in0_user)
             SUO_HIP_CHECK(hipMemcpyAsync(in0, in0_user, (size_t)L * CROP * CROP * IN_C * sizeof(float), hipMemcpyDeviceToDevice, s));
         SUO_TRY(run_backbone(in0, IN_C, logits, L, s));
@@ -1256,13 +1245,7 @@ int Net::forward(const void* img, int fmt, int H, int W, const float* boxes, con
     const bool own = (s == nullptr);
     if (own) { s = own_stream_; SUO_TRY(follow_null_stream()); }   // the legacy NULL stream cannot be captured: run on an internal stream and block
     try {
-        // persistent slabs at the bottom of the workspace: staged input + logits
-        ws_used_ = 0;
-        float* in0 = alloc((size_t)max_crops_ * CROP * CROP * IN_C);
-        float* logits = alloc((size_t)max_crops_ * NUM_KP * HEAT * HEAT);
-        stem_slab_ = alloc((size_t)max_crops_ * 128 * 128 * 64);          // the stem's output: persistent, the fused stem writes it OUTSIDE the captured graph
-        stem_mid1_slab_ = alloc((size_t)max_crops_ * 128 * 128 * 64);     // ... and r1's conv1 of it, when the stem launch computes that too
-        ws_mark_ = ws_used_;
+        auto [in0, logits] = layout_slabs();
         const int in_c = (priors || prior_uv) ? IN_C : IMG_C;     // the slab is sized for IN_C; the prior-less layout uses a sixth of it
         if (in_c == IMG_C && fused_stem()) {
             // prior-less pass: RoIAlign + stem in one launch on the bf16 pipe (csrc/stem_x3.hip), ahead of the captured backbone (the frame and
