@@ -12,8 +12,9 @@
  * pointers; `stream` is a hipStream_t passed as void* (NULL = internal stream + blocking).
  * All work is stream-ordered; the library never reads or writes host memory behind *_dev names.
  *
- * Runtime switches.  The library reads NINE environment variables, all of them selections between forms whose results the test suite holds against each other
- * (csrc/tune.h: env_switch); nothing else in the environment changes what it does:
+ * Runtime switches.  The library reads NINE environment variables that select between forms whose results the test suite holds against each other
+ * (csrc/tune.h: env_switch), and one path -- SUO_RCCL_LIB, the RCCL library of suo_ba_comm_create_rccl when the process holds none yet; nothing else in the
+ * environment changes what it does:
  *     SUO_WINO_BF16X3=0      networks are built on the fp32 matrix pipe (SUO_PIPE_F32)                      read when a network is created
  *     SUO_F16X2=0            networks are built on three bf16 terms per operand (SUO_PIPE_BF16X3)             read when a network is created
  *     SUO_STEM_X3=0          prior-less pass: RoIAlign and the stem as two launches instead of the fused one  first use, per process
@@ -531,6 +532,44 @@ int suo_debug_ba_jacobians(suo_ba_ctx* ctx, int n_edge, double* jac_out, double*
  * linear_solver_cholmod.h) -- on a dense symmetric A [ns][ns] (HOST, row-major, lower triangle read; ns a multiple of 6, at most 96) and b [ns]: x_out [ns] solves
  * A x = b; *ok_out = 0 when a pivot was not positive (the LM kernels then reject the trial). */
 int suo_debug_cholesky_solve(const double* A, const double* b, int ns, double* x_out, int* ok_out);
+
+/* ---- the partitioned adjustment driven from C (csrc/ba_comm.hip, csrc/geom_api.hip: optimize_dist) ---------------------------------
+ * suo_ba_comm: the one collective the schedule above needs -- an in-place SUM all-reduce of n doubles on a device buffer, ordered on a stream.
+ *   RCCL backend: one rank per process and device.  suo_ba_comm_rccl_unique_id fills the 128 bytes of an ncclUniqueId on ONE rank; the caller carries them to
+ *     the others (any transport) and every rank calls suo_ba_comm_create_rccl on its current device.  ncclAllReduce(ncclDouble, ncclSum) on the driver's stream.
+ *     RCCL is resolved at first use with dlopen (RTLD_LOCAL): a copy the process already holds (e.g. PyTorch's), else the path in SUO_RCCL_LIB (a path that does
+ *     not load is an error, not a reason to look further), else librccl.so.1 on the loader path.  No RCCL: SUO_ERR_MISSING and a message, never an abort.
+ *   local backend: suo_ba_comm_create_local(world): `world` (1..16) ranks inside ONE process on ONE device and ONE stream.  The ranks' exchange buffers lie
+ *     `stride` doubles apart in one device block and the all-reduce is one launch of ba_local_allreduce_kernel: every element's addends summed in fp64 in ASCENDING
+ *     RANK ORDER, ((b0 + b1) + b2) + ..., written back to all `world` slots; no atomics, no second pass.  It runs the N-rank SCHEDULE on one GPU -- to test it and
+ *     to check a partitioning -- and is slower than suo_optimize by construction (world x the launches on one stream).
+ * suo_ba_comm_allreduce: buf_dev = this rank's buffer (local backend: rank 0's; rank r's is buf_dev + r * stride, stride >= n; RCCL ignores stride).
+ * suo_ba_comm_calls: all-reduces issued through the communicator so far. */
+typedef struct suo_ba_comm suo_ba_comm;
+int suo_ba_comm_rccl_unique_id(void* id128);
+int suo_ba_comm_create_rccl(const void* id128, int rank, int world, suo_ba_comm** out);
+int suo_ba_comm_create_local(int world, suo_ba_comm** out);
+void suo_ba_comm_destroy(suo_ba_comm* comm);
+int suo_ba_comm_rank(const suo_ba_comm* comm);
+int suo_ba_comm_world(const suo_ba_comm* comm);
+uint64_t suo_ba_comm_calls(const suo_ba_comm* comm);
+int suo_ba_comm_allreduce(suo_ba_comm* comm, double* buf_dev, size_t stride, size_t n, void* stream);
+/* Test entry: the local backend's kernel on a caller-owned block (slot r = block_dev + r * stride; the doubles between n and stride are not touched).
+ * 16-byte loads / stores when block_dev is 16-byte aligned and stride is even, scalar otherwise.  stream NULL: the null stream, blocking. */
+int suo_debug_ba_local_allreduce(double* block_dev, int world, size_t stride, size_t n, void* stream);
+/* optimize_distributed of suo_slam_amd/ba_dist.py as one C call.  Every rank passes the same FULL problem and gets the complete result back in it (cam_T, obj_T,
+ * inlier flags, chi2, stats).  Cameras are dealt round-robin (camera c to rank c % world; suo_ba_split), every rank keeps all objects; per LM iteration one
+ * all-reduce (linearisation totals), per LM trial two ([S | r | ok], three step scalars), one per classification, one for the result assembly.  Eager launches
+ * on one internal stream, the device-resident accept / reject schedule, a look at the control block once per suo_ba_units_per_look(world) units.
+ * With a local communicator the call runs all `world` ranks itself, phase by phase, and returns the one result; suo_optimize_partitioned(p, n) is that with a
+ * communicator of its own.  A rank without a camera (world > n_cam) takes part in every collective with zeros. */
+int suo_optimize_dist(suo_ba_problem* full, suo_ba_comm* comm);
+int suo_optimize_partitioned(suo_ba_problem* problem, int n_parts);
+/* Host only: rank `rank`'s share.  cams_out [<= n_cam]: its cameras, ascending (local camera index = position); edges_out [<= n_edge]: its edges in the
+ * caller's order (suo_slam_amd/ba_dist.py: split_problem). */
+int suo_ba_split(const suo_ba_problem* full, int rank, int world, int* cams_out, int* n_cams, int* edges_out, int* n_edges);
+/* units enqueued between two looks at the control block: 12 on one rank, 6 on several (a dead unit there costs three all-reduces) */
+int suo_ba_units_per_look(int world);
 
 /* ---- evaluation meter: ADD / ADD-S pose errors ------------------------------------
  * Replaces the distance part of EvalMeter.update (lib/utils/eval_meter.py:126-155,233-242):

@@ -124,6 +124,19 @@ SIGNATURES = {
     "suo_debug_ba_jacobians": (C.c_int, [VP, C.c_int, VP, VP]),
     "suo_debug_cholesky_solve": (C.c_int, [VP, VP, C.c_int, VP, VP]),
     "suo_debug_lm_routes": (C.c_int, [VP, C.c_int, VP, VP]),
+    "suo_ba_comm_rccl_unique_id": (C.c_int, [VP]),
+    "suo_ba_comm_create_rccl": (C.c_int, [VP, C.c_int, C.c_int, C.POINTER(VP)]),
+    "suo_ba_comm_create_local": (C.c_int, [C.c_int, C.POINTER(VP)]),
+    "suo_ba_comm_destroy": (None, [VP]),
+    "suo_ba_comm_rank": (C.c_int, [VP]),
+    "suo_ba_comm_world": (C.c_int, [VP]),
+    "suo_ba_comm_calls": (C.c_uint64, [VP]),
+    "suo_ba_comm_allreduce": (C.c_int, [VP, VP, C.c_size_t, C.c_size_t, VP]),
+    "suo_debug_ba_local_allreduce": (C.c_int, [VP, C.c_int, C.c_size_t, C.c_size_t, VP]),
+    "suo_optimize_dist": (C.c_int, [VP, VP]),
+    "suo_optimize_partitioned": (C.c_int, [VP, C.c_int]),
+    "suo_ba_split": (C.c_int, [VP, C.c_int, C.c_int, VP, VP, VP, VP]),
+    "suo_ba_units_per_look": (C.c_int, [C.c_int]),
     "suo_frame_geom_create": (C.c_int, [C.c_int, C.c_int, C.POINTER(VP)]),
     "suo_frame_geom_destroy": (None, [VP]),
     "suo_frame_geom_launch": (C.c_int, [VP, C.c_int, VP, VP, VP, VP, VP, VP, VP, VP, VP, VP]),

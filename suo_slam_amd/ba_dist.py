@@ -265,7 +265,7 @@ def optimize_distributed(full: _ba.Problem, phases_factory=HipPhases):
                 ph.begin_round(int(its), world)
                 # units between two looks at the control block: a dead unit (enqueued past the end of a round) costs ~50 us of empty launches on one rank, and three
                 # all-reduces more on several -- there the batches are half as long
-                batch = int(os.environ.get("SUO_BA_UNITS_PER_LOOK", "12" if world == 1 else "6"))
+                batch = int(os.environ.get("SUO_BA_UNITS_PER_LOOK", _lib.lib().suo_ba_units_per_look(world)))        # (12 at one rank, 6 at several: the C driver's constant)
                 budget, done = min(int(its), batch), int(its) <= 0
                 while not done:
                     for _ in range(budget):
@@ -342,3 +342,99 @@ def optimize_distributed(full: _ba.Problem, phases_factory=HipPhases):
         #  parks the buffers, csrc/geom_api.hip)
         if hasattr(ph, "close"):
             ph.close()
+
+
+# ---- the same adjustment as ONE C call (csrc/geom_api.hip: suo_optimize_dist): no interpreter and no torch.distributed between the launches ----------------
+
+
+class Comm:
+    """A suo_ba_comm (include/suo_hip.h): the in-place SUM all-reduce the C driver issues between its phases."""
+
+    def __init__(self, handle):
+        self.lib, self._h = _lib.lib(), handle
+
+    rank = property(lambda self: int(self.lib.suo_ba_comm_rank(self._h)))
+    world = property(lambda self: int(self.lib.suo_ba_comm_world(self._h)))
+    calls = property(lambda self: int(self.lib.suo_ba_comm_calls(self._h)))
+
+    def close(self):
+        if self._h is not None:
+            self.lib.suo_ba_comm_destroy(self._h)
+            self._h = None
+
+
+class LocalRanks(Comm):
+    """`world` (1..16) ranks inside this process, on one device and one stream: the N-rank SCHEDULE -- partition, per-rank camera elimination, reduce, redundant
+    solve, per-rank back-substitution, device-side accept / reject -- on one GPU.  For testing it and for checking a partitioning; world x the launches of one
+    rank on one stream, so slower than ba.optimize by construction."""
+
+    def __init__(self, world):
+        h = C.c_void_p()
+        _lib.check(_lib.lib().suo_ba_comm_create_local(int(world), C.byref(h)), "suo_ba_comm_create_local")
+        super().__init__(h)
+
+
+def _hand_over_torch_rccl():
+    """The process runs its collectives through ONE RCCL: torch's own copy (torch/lib/librccl.so), which `import torch` has mapped already -- the library finds a
+    loaded copy by its soname; SUO_RCCL_LIB names the same file for the case that it does not, unless the caller has set it."""
+    path = os.path.join(os.path.dirname(torch.__file__), "lib", "librccl.so")
+    if "SUO_RCCL_LIB" not in os.environ and os.path.exists(path):
+        os.environ["SUO_RCCL_LIB"] = path
+
+
+class RcclRanks(Comm):
+    """One RCCL rank per process of a torch.distributed group (default: the default group): rank 0 makes the unique id, its 128 bytes travel by dist.broadcast on
+    whatever backend the group has (gloo included), every rank joins on its current device."""
+
+    def __init__(self, group=None):
+        lib = _lib.lib()
+        _lib.require_gpu()
+        _hand_over_torch_rccl()
+        rank, world = dist.get_rank(group), dist.get_world_size(group)
+        ident = np.zeros(128, np.uint8)
+        if rank == 0:
+            _lib.check(lib.suo_ba_comm_rccl_unique_id(ident.ctypes.data), "suo_ba_comm_rccl_unique_id")
+        t = torch.from_numpy(ident)
+        on_device = dist.get_backend(group) == "nccl"
+        if on_device:
+            t = t.cuda()
+        src = 0 if group is None else dist.get_global_rank(group, 0)
+        dist.broadcast(t, src=src, group=group)
+        ident = np.ascontiguousarray(t.cpu().numpy())
+        h = C.c_void_p()
+        _lib.check(lib.suo_ba_comm_create_rccl(ident.ctypes.data, rank, world, C.byref(h)), "suo_ba_comm_create_rccl")
+        super().__init__(h)
+
+
+_COMMS = {}
+
+
+def group_comm(group=None):
+    """The RCCL communicator of a process group, made on first use and kept for the process (close_comms() before the group is destroyed)."""
+    key = id(group) if group is not None else None
+    if key not in _COMMS:
+        _COMMS[key] = RcclRanks(group)
+    return _COMMS[key]
+
+
+def close_comms():
+    for comm in _COMMS.values():
+        comm.close()
+    _COMMS.clear()
+
+
+def optimize_distributed_c(full: _ba.Problem, comm: Comm = None):
+    """optimize_distributed as one C call (suo_optimize_dist): every rank passes the same `full` problem and gets the complete result back in it.  comm=None: the
+    RCCL communicator of the default torch.distributed group; LocalRanks(n): n ranks on this one GPU."""
+    lib = _lib.lib()
+    _lib.require_gpu()
+    if comm is None:
+        if not (dist.is_available() and dist.is_initialized()):
+            raise _lib.SuoError("optimize_distributed_c: no communicator given and no torch.distributed process group initialised")
+        comm = group_comm()
+    s = _lib.BaProblem()
+    full._fill(s)
+    _lib.check(lib.suo_optimize_dist(C.byref(s), comm._h), "suo_optimize_dist")
+    full.stats[:] = list(s.stats)
+    full.chi2 = full.chi2[:len(full.edge_cam)]
+    return full
