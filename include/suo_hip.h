@@ -410,7 +410,12 @@ int suo_frame_geom_device_result(suo_frame_geom* g, suo_frame_geom_result* out);
  * (rows of objects that are not in the map: in_map 0, the rest ignored).  has_cov / kp_std2 / chi2_max as suo_slam_score; min_inliers = 4 (:975).
  * Outputs on the device: prior_uv_dev [n_b][41][2] float32 + prior_mask_dev [n_b][41] -- what suo_net_forward_prior_kp takes (rows of objects without a prior: zeros) --
  * and out_dev [SUO_SLAM_VOTE_OUT] doubles: T_GtoC [3][4] | best crop (-1: no hypothesis reached min_inliers -- the caller falls back to
- * __backup_estimate_camera_pose and issues pass B again) | number of hypotheses | best count | counts [16] (-1: not a hypothesis) | NaN flag. */
+ * __backup_estimate_camera_pose and issues pass B again) | number of hypotheses | best count | counts [16] (-1: not a hypothesis) | NaN flag.
+ * n_kp_dev is accepted for the chain's result block as it stands and NOT READ (it may be null): a crop's keypoints are those of its mask, in mask order.  The variances
+ * are clamped as np.maximum clamps them -- a NaN variance stays a NaN and sets the flag, as any NaN chi-square of a keypoint in front of the camera does.
+ * What "equal to the host route" means is tested directly (tests/test_gpu_slam_vote.py): T_GtoC and the priors are bit-identical to the documented arithmetic
+ * (csrc/slam_vote.hip's header; restated exactly in tests/slam_vote_ref.py), the counts are exact against the reference's rule.
+ * SUO_ERR_ARG (nothing launched): n_a or n_b outside 1..16, or a null pointer other than n_kp_dev / stream. */
 #define SUO_SLAM_VOTE_BLOCK 704
 #define SUO_SLAM_VOTE_OUT 32
 int suo_slam_vote(int n_a, const double* T_pnp_dev, const uint8_t* accepted_dev, const int* n_kp_dev, const float* uv_dev, const float* cov_dev,

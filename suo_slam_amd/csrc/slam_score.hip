@@ -48,7 +48,7 @@ __global__ __launch_bounds__(256) void slam_score_kernel(const double* __restric
             double chi2;
             if (row[SS_HAS_COV] != 0.0) {
                 const double* c = row + SS_COV + lane * 4;
-                const double a = fmax(c[0], 1e-4), d = fmax(c[3], 1e-4), bb = c[1], cc = c[2];
+                const double a = c[0] < 1e-4 ? 1e-4 : c[0], d = c[3] < 1e-4 ? 1e-4 : c[3], bb = c[1], cc = c[2];      // np.maximum: a NaN variance stays a NaN (fmax would drop it)
                 chi2 = ((d * rx * rx - (bb + cc) * rx * ry) + a * ry * ry) / (a * d - bb * cc);
             } else {
                 chi2 = (rx * rx + ry * ry) / kp_std2;

@@ -12,6 +12,10 @@
 // in ascending k whose first term is a plain product, fma(a3, b3, fma(a2, b2, fma(a1, b1, a0 b0))) (checked against numpy 2.2 / OpenBLAS on 300 random 4 x 4 pairs,
 // stacked products, 400 transposed matrix-vector products and n x 3 @ 3 x 3 products: bit for bit); the per-keypoint scoring expression is slam_score_kernel's
 // plain-sum one.  So the chain's votes, camera poses and priors equal the host route's (tests/test_gpu_slam_chain.py).
+// The diagonal of a covariance is clamped as np.maximum clamps it (:1054): a NaN variance stays a NaN, its chi-square is a NaN and the flag (out[31]) is raised, as
+// the reference's assert (:1056) fires.  n_kp (pass A's per-crop keypoint counts) is accepted with the chain's result block and not read: the masks say it.
+// Held to this description directly: tests/test_gpu_slam_vote.py compares every output with tests/slam_vote_ref.py -- the steps above in exact arithmetic -- bit
+// for bit, at the edges of the rule; tests/test_slam_vote_ref.py ties that restatement to oracle/slam_rules.py, to the reference's prior rule and to numpy's products.
 #include <math.h>
 
 #include "../../include/suo_hip.h"
@@ -27,7 +31,7 @@ static_assert(HB_SIZE == SUO_SLAM_VOTE_BLOCK, "include/suo_hip.h");
 
 struct SlamVoteArgs {
     int n_a, n_b;
-    const double* T_pnp; const uint8_t* accepted; const int* n_kp;                       // pass A's chain results (device)
+    const double* T_pnp; const uint8_t* accepted; const int* n_kp;                       // pass A's chain results (device); n_kp is not read (the masks say it)
     const float* uv; const float* cov; const uint8_t* mask; const float* kps_a;          // pass A's network outputs / masks / model keypoints
     const double* blk;                                                                   // the staged host block
     const float* kps_b; const uint8_t* kmask_b;
@@ -106,7 +110,8 @@ __global__ __launch_bounds__(1024) void slam_vote_kernel(const SlamVoteArgs a) {
                     double chi2;
                     if (a.has_cov) {
                         const double* c = row + SV_KP * 5 + lane * 4;
-                        const double aa = fmax(c[0], 1e-4), d = fmax(c[3], 1e-4), bb = c[1], cc = c[2];
+                        // np.maximum(v, 1e-4) (:1054): a NaN variance stays a NaN and reaches the flag (fmax would drop it)
+                        const double aa = c[0] < 1e-4 ? 1e-4 : c[0], d = c[3] < 1e-4 ? 1e-4 : c[3], bb = c[1], cc = c[2];
                         chi2 = ((d * rx * rx - (bb + cc) * rx * ry) + aa * ry * ry) / (aa * d - bb * cc);
                     } else {
                         chi2 = (rx * rx + ry * ry) / a.kp_std2;

@@ -134,6 +134,12 @@ def test_nan_in_the_information_matrix_is_reported():
     d["cov_pred"] = c
     with pytest.raises(AssertionError, match="NaN in information matrix"):
         SC.chi2_counts(Owner(), np.stack(Ts[:1]), [d], False, 0.005, CHI2_2DOF_95)
+    c = np.array(dets[0]["cov_pred"], dtype=np.float32)
+    c[0, 0, 0] = np.nan                                                  # a variance alone: np.maximum(nan, 1e-4) is nan (:1054-1056)
+    d = dict(d, cov_pred=c)
+    d.pop("_slot", None)
+    with pytest.raises(AssertionError, match="NaN in information matrix"):
+        SC.chi2_counts(Owner(), np.stack(Ts[:1]), [d], False, 0.005, CHI2_2DOF_95)
 
 
 def test_bad_slots_are_refused():
