@@ -459,8 +459,8 @@ int suo_optimize(suo_ba_problem* problem);
  *                                                                       (round 6; 60 cameras x 8 objects: 6.8 ms, 10.5 through the grid-barrier kernel of rounds 4-5)
  *   more than 16 free objects next to free cameras                      the same phases under the host-driven schedule (the reduced system then lives in HBM) */
 int suo_optimize_batch(suo_ba_problem* problems, int n_problems);
-/* Test entry: the kernel suo_optimize_batch runs each problem of this batch on, decided on the host exactly as the dispatcher decides (same thresholds, same
- * SUO_LM_CAM2); launches nothing and needs no device.  A batch runs on ONE kernel, except that a batch holding a PHASEWISE graph runs its other problems one by
+/* Test entry: the kernel suo_optimize_batch runs each problem of this batch on -- the plan the dispatcher itself executes (csrc/ba_api.hip: plan_ba_batch; same
+ * thresholds, same SUO_LM_CAM2), reported instead of run; launches nothing and needs no device.  A batch runs on ONE kernel, except that a batch holding a PHASEWISE graph runs its other problems one by
  * one, each on the route it takes alone.  route_out[i] is a SUO_LM_ROUTE_* code; lds_need_out (may be NULL) [i] is, on the LM / LM_BIG routes, the dynamic LDS
  * in bytes that a fully resident problem asks for BEFORE the 150 KiB cap (the kernel relocates arrays into LDS while they fit), -1 on the others. */
 #define SUO_LM_ROUTE_LM 0          /* lm_kernel, 256 threads (csrc/lm.hip): what no route below takes, < 512 edges */
@@ -538,7 +538,7 @@ int suo_debug_ba_jacobians(suo_ba_ctx* ctx, int n_edge, double* jac_out, double*
  * A x = b; *ok_out = 0 when a pivot was not positive (the LM kernels then reject the trial). */
 int suo_debug_cholesky_solve(const double* A, const double* b, int ns, double* x_out, int* ok_out);
 
-/* ---- the partitioned adjustment driven from C (csrc/ba_comm.hip, csrc/geom_api.hip: optimize_dist) ---------------------------------
+/* ---- the partitioned adjustment driven from C (csrc/ba_comm.hip, csrc/ba_drive.hip: optimize_dist) ---------------------------------
  * suo_ba_comm: the one collective the schedule above needs -- an in-place SUM all-reduce of n doubles on a device buffer, ordered on a stream.
  *   RCCL backend: one rank per process and device.  suo_ba_comm_rccl_unique_id fills the 128 bytes of an ncclUniqueId on ONE rank; the caller carries them to
  *     the others (any transport) and every rank calls suo_ba_comm_create_rccl on its current device.  ncclAllReduce(ncclDouble, ncclSum) on the driver's stream.

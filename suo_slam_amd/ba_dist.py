@@ -104,7 +104,7 @@ class HipPhases:
         decide [+ restore]; the phases that the control block does not call for return at once.  No host synchronisation."""
         s = self._stream()
         if world == 1 and not _collectives_forced() and os.environ.get("SUO_BA_FOLD_CTL", "1") not in ("", "0"):
-            # nothing is exchanged between the phases: the control steps ride in the tail kernels (csrc/geom_api.hip: suo_ba_lm_unit_one_rank_dev)
+            # nothing is exchanged between the phases: the control steps ride in the tail kernels (csrc/ba_ctx.hip: ba_unit_one_rank behind suo_ba_lm_unit_one_rank_dev)
             _lib.check(self.lib.suo_ba_lm_unit_one_rank_dev(self._h, int(robust_on), self._p(self.ctl), self._p(self.lin_loc), self._p(self.lin), self._p(self.sch),
                                                             self._p(self.red), s), "suo_ba_lm_unit_one_rank_dev")
             return
@@ -339,12 +339,12 @@ def optimize_distributed(full: _ba.Problem, phases_factory=HipPhases):
         return full
     finally:
         # (also on an exception between two phases: the context's kernels run on the CURRENT stream -- suo_ba_ctx_destroy drains the device before it
-        #  parks the buffers, csrc/geom_api.hip)
+        #  parks the buffers, csrc/ba_ctx.hip)
         if hasattr(ph, "close"):
             ph.close()
 
 
-# ---- the same adjustment as ONE C call (csrc/geom_api.hip: suo_optimize_dist): no interpreter and no torch.distributed between the launches ----------------
+# ---- the same adjustment as ONE C call (csrc/ba_drive.hip: suo_optimize_dist): no interpreter and no torch.distributed between the launches ----------------
 
 
 class Comm:

@@ -27,15 +27,10 @@
 
 #include "../../include/suo_hip.h"
 #include "lm_device.h"
+#include "lm_launch.h"
 #include "suo_internal.h"
 
 namespace suo {
-
-int pnp_get_iterations(double estimated_inliers);
-int launch_pnp_batch_counts(int n_obj, const int* offsets, const int* counts, const int* group_first, const double* xs, const double* ys, double threshold, uint64_t seed,
-                            const int* iter_tab, const int* iter_tab_off, int do_refine, double* T_out, int* status, int* best_out,
-                            int* iters_out, hipStream_t s, const uint64_t* seed_add = nullptr);
-int launch_lm_frame2(const void* problems_dev, int n_problems, int max_obj, int max_edges, hipStream_t s);
 
 constexpr int FG_MAX_OBJ = 16;          // objects per frame the one-wave-per-object LM kernel takes (csrc/lm_frame.hip: LF_MAX_OBJ)
 

@@ -23,6 +23,7 @@
 
 
 #include "lm_device.h"
+#include "lm_launch.h"
 
 namespace suo {
 
@@ -483,8 +484,6 @@ int launch_lm(const void* problems_dev, int n_problems, int lds_bytes, hipStream
     SUO_HIP_CHECK(hipGetLastError());
     return SUO_OK;
 }
-
-size_t lm_problem_struct_size() { return sizeof(LmProblem); }
 #endif  // SUO_LM_BIG
 
 }  // namespace suo

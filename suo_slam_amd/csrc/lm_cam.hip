@@ -12,6 +12,7 @@
 // Same rounds / robust-kernel schedule / lambda schedule / re-classification as csrc/lm.hip; only the summation order of
 // H, b and chi2 differs (rounding level).  Many problems run as independent one-wave workgroups.
 #include "lm_device.h"
+#include "lm_launch.h"
 
 namespace suo {
 

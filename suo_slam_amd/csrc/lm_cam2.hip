@@ -18,6 +18,7 @@
 #include <type_traits>
 
 #include "lm_device.h"
+#include "lm_launch.h"
 
 namespace suo {
 

@@ -16,6 +16,7 @@
 // fixed wave order and combined in workgroup order by a one-workgroup tail kernel (deterministic); only the reduced
 // (<= 96 x 96) system is factorised by a single workgroup.
 #include "lm_device.h"
+#include "lm_launch.h"
 
 namespace suo {
 

@@ -11,6 +11,7 @@
 //
 // Same arithmetic per edge / block entry as csrc/lm.hip; only the partition of the chi2 sums differs (rounding-level).
 #include "lm_device.h"
+#include "lm_launch.h"
 
 namespace suo {
 

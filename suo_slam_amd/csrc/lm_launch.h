@@ -1,0 +1,46 @@
+// Host launchers of the geometry kernels (csrc/pnp.hip, csrc/lm*.hip, csrc/lm_dist.hip), declared ONCE: the files that define them and the files that call them
+// (csrc/pnp_api.hip, csrc/ba_*.hip, csrc/frame_geom.hip) include this header, and default arguments live here only.
+#pragma once
+#include "suo_internal.h"
+
+namespace suo {
+// ---- PnP (csrc/pnp.hip; pnp_get_iterations: csrc/pnp_api.hip, on the host) ----
+int pnp_get_iterations(double estimated_inliers);
+int launch_pnp_replay(int n_obj, const int* offsets, const double* xs, const double* ys, double threshold, const int* iter_tab, const int* iter_tab_off,
+                      int do_refine, const int* draws, int n_draws, double* T_out, int* status, int* best_out, int* iters_out, int* win_out, hipStream_t s);
+int launch_pnp_batch(int n_obj, const int* offsets, const double* xs, const double* ys, double threshold, uint64_t seed,
+                     const int* iter_tab, const int* iter_tab_off, int do_refine, double* T_out, int* status, int* best_out,
+                     int* iters_out, hipStream_t s);
+int launch_pnp_batch_counts(int n_obj, const int* offsets, const int* counts, const int* group_first, const double* xs, const double* ys, double threshold, uint64_t seed,
+                            const int* iter_tab, const int* iter_tab_off, int do_refine, double* T_out, int* status, int* best_out,
+                            int* iters_out, hipStream_t s, const uint64_t* seed_add = nullptr);
+// ---- whole LM runs in one launch: problems_dev = n_problems LmProblem structs (csrc/lm_device.h) in device memory ----
+int launch_lm(const void* problems_dev, int n_problems, int lds_bytes, hipStream_t s);
+int launch_lm_big(const void* problems_dev, int n_problems, int lds_bytes, hipStream_t s);
+int lm_lds_bytes(int C, int O, int E, int NP, int n_free_obj_schur);
+size_t lm_lds_bytes_uncapped(int C, int O, int E, int NP, int n_free_obj_schur);
+int launch_lm_cam(const void* problems_dev, int n_problems, hipStream_t s);
+int launch_lm_cam2(const void* problems_dev, int n_problems, int max_edges, hipStream_t s);
+int lm_cam2_max_edges();
+int launch_lm_frame(const void* problems_dev, int n_problems, int max_obj, hipStream_t s);
+int launch_lm_frame2(const void* problems_dev, int n_problems, int max_obj, int max_edges, hipStream_t s);
+int lm_frame2_max_edges();
+int launch_lm_grid(const void* problem_dev, void* scratch_dev, int n_wgs, hipStream_t s);       // (csrc/lm_grid.hip: rounds 4-5's route for one large graph; tuning builds only)
+size_t lm_grid_scratch_bytes();
+// ---- the phases of one LM trial (csrc/lm_dist.hip); ctl: the control block of the device-resident schedule, fold_ctl: its step folded into the tail kernel ----
+size_t ba_scratch_doubles();
+int launch_ba_init(const void* P, hipStream_t s);
+int launch_ba_classify(const void* P, int keep_all, double* out, double* scratch, hipStream_t s);
+int launch_ba_linearize(const void* P, int robust_on, double* out, double* scratch, int rank, int world, hipStream_t s, const double* ctl = nullptr, double* copy_to = nullptr,
+                        int copy_n = 0, double* fold_ctl = nullptr);
+int launch_ba_schur(const void* P, double lambda, int ns, double* out, double* scratch, hipStream_t s, const double* ctl = nullptr);
+int launch_ba_solve_update(const void* P, double lambda, int ns, int robust_on, const double* HB, const double* St, int expect_ok, double* out,
+                           double* scratch, double* big, hipStream_t s, const double* ctl = nullptr, double* fold_ctl = nullptr);
+int launch_ba_ctl_begin(double* ctl, int its, int world, hipStream_t s);
+int launch_ba_ctl_lin(const void* P, double* ctl, const double* lin, double* scratch, hipStream_t s);
+int launch_ba_ctl_decide(const void* P, double* ctl, const double* red, hipStream_t s);
+int launch_ba_copy(const double* src, double* dst, int n, hipStream_t s);
+int launch_ba_restore(const void* P, hipStream_t s);
+int launch_ba_finalize(const void* P, hipStream_t s);
+int launch_debug_cholesky(const double* A, const double* b, int ns, double* x, int* ok, hipStream_t s);
+}  // namespace suo

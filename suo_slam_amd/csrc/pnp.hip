@@ -18,6 +18,7 @@
 // loop.  Refinement is a wave-parallel Levenberg-Marquardt (lanes over points, butterfly reduction
 // of the 6x6 normal equations, redundant per-lane Cholesky).  All arithmetic is fp64 with
 // contraction off so thresholds fall the same way as in the CPU restatement.
+#include "lm_launch.h"
 #include "suo_internal.h"
 #include "tune.h"
 
@@ -710,7 +711,7 @@ __global__ __launch_bounds__(64 * PNP_WAVES) void pnp_batch_kernel(const int* __
 
 int launch_pnp_batch_counts(int n_obj, const int* offsets, const int* counts, const int* group_first, const double* xs, const double* ys, double threshold, uint64_t seed,
                             const int* iter_tab, const int* iter_tab_off, int do_refine, double* T_out, int* status, int* best_out,
-                            int* iters_out, hipStream_t s, const uint64_t* seed_add = nullptr) {
+                            int* iters_out, hipStream_t s, const uint64_t* seed_add) {
     if (n_obj <= 0) return SUO_OK;
     static const int wide_upto = (int)SUO_TUNE("SUO_PNP_WIDE_UPTO", 32);      // objects per launch that still take 16 waves each (0: never)
     if (n_obj <= wide_upto)

@@ -1,0 +1,107 @@
+// Host-buffer entry points of the PnP kernels (what the reference's FFI would bind):
+//   suo_pnp / suo_pnp_batch / suo_pnp_replay  <- lambdatwist.pnp      (thirdparty/lambdatwist/pnp_python_binding.cpp:57-62)
+// They stage the caller's host arrays into the process arena (one H2D), launch, and copy results back (one D2H).
+#include <math.h>
+#include <string.h>
+
+#include <algorithm>
+
+#include "ba_stage.h"
+
+namespace suo {
+
+// PnpParams::get_iterations (thirdparty/lambdatwist/parameters.h:76-102), evaluated on the host so the
+// kernel's adaptive iteration count uses the same libm as the reference would.
+int pnp_get_iterations(double estimated_inliers) {
+    const double p_meets = 0.9, min_probability = 0.99999;
+    const unsigned max_iterations = 1000, min_iterations = 100;
+    double p_inlier = std::min(0.9, estimated_inliers * p_meets);
+    p_inlier = std::min(std::max(p_inlier, 1e-2), 1 - 1e-8);
+    if (p_inlier < 0.01) return (int)max_iterations;
+    const double p_failure = std::min(std::max(1.0 - min_probability, 1e-8), 0.01);
+    const double p_good = pow(p_inlier, 4);
+    const double iterations = ceil(log(p_failure) / log(1.0 - p_good)) + 50;
+    if (iterations < min_iterations) return (int)min_iterations;
+    if (iterations > max_iterations) return (int)max_iterations;
+    return (int)iterations;
+}
+
+}  // namespace suo
+
+using namespace suo;
+
+extern "C" {
+
+static int pnp_batch_impl(int n_obj, const int* n_pts, const double* xs, const double* ys, double threshold, uint64_t seed, const int* draws, int n_draws,
+                          int do_refine, double* T_out, int* status, int* best_inliers, int* iterations, int* winner) {
+    if (n_obj <= 0) return SUO_OK;
+    if (!n_pts || !xs || !ys || !T_out) { suo_set_error("suo_pnp_batch: null argument"); return SUO_ERR_ARG; }
+    if (draws && n_draws < pnp_get_iterations(0.0)) {
+        suo_set_error("suo_pnp_replay: %d draws per object, the RANSAC loop may run %d iterations", n_draws, pnp_get_iterations(0.0));
+        return SUO_ERR_ARG;
+    }
+    std::lock_guard<std::mutex> lock(g_arena.mu);
+    std::vector<int> offsets(n_obj + 1, 0), tab_off(n_obj, 0);
+    std::vector<int> tab;
+    for (int o = 0; o < n_obj; ++o) {
+        if (n_pts[o] < 0) { suo_set_error("suo_pnp_batch: negative point count"); return SUO_ERR_ARG; }
+        offsets[o + 1] = offsets[o] + n_pts[o];
+        tab_off[o] = (int)tab.size();
+        for (int b = 0; b <= n_pts[o]; ++b) tab.push_back(pnp_get_iterations(n_pts[o] > 0 ? b / (double)n_pts[o] : 0.0));
+    }
+    const int total = offsets[n_obj];
+    Layout L;
+    const size_t o_off = L.take(sizeof(int) * (n_obj + 1)), o_toff = L.take(sizeof(int) * n_obj), o_tab = L.take(sizeof(int) * tab.size());
+    const size_t o_xs = L.take(sizeof(double) * 3 * (size_t)total), o_ys = L.take(sizeof(double) * 2 * (size_t)total);
+    const size_t o_dr = L.take(draws ? sizeof(int) * 4 * (size_t)n_draws * n_obj : 0);
+    const size_t in_bytes = L.off;
+    const size_t o_T = L.take(sizeof(double) * 16 * (size_t)n_obj), o_st = L.take(sizeof(int) * n_obj), o_best = L.take(sizeof(int) * n_obj),
+                 o_it = L.take(sizeof(int) * n_obj), o_win = L.take(sizeof(int) * n_obj);
+    int rc = g_arena.ensure(L.off);
+    if (rc != SUO_OK) return rc;
+    char* h = g_arena.host;
+    char* d = g_arena.dev;
+    memcpy(h + o_off, offsets.data(), sizeof(int) * (n_obj + 1));
+    memcpy(h + o_toff, tab_off.data(), sizeof(int) * n_obj);
+    memcpy(h + o_tab, tab.data(), sizeof(int) * tab.size());
+    memcpy(h + o_xs, xs, sizeof(double) * 3 * (size_t)total);
+    memcpy(h + o_ys, ys, sizeof(double) * 2 * (size_t)total);
+    if (draws) memcpy(h + o_dr, draws, sizeof(int) * 4 * (size_t)n_draws * n_obj);
+    hipStream_t s = g_arena.stream;
+    SUO_HIP_CHECK(hipMemcpyAsync(d, h, in_bytes, hipMemcpyHostToDevice, s));
+    if (draws)
+        rc = launch_pnp_replay(n_obj, (const int*)(d + o_off), (const double*)(d + o_xs), (const double*)(d + o_ys), threshold, (const int*)(d + o_tab),
+                               (const int*)(d + o_toff), do_refine, (const int*)(d + o_dr), n_draws, (double*)(d + o_T), (int*)(d + o_st), (int*)(d + o_best),
+                               (int*)(d + o_it), (int*)(d + o_win), s);
+    else
+    rc = launch_pnp_batch(n_obj, (const int*)(d + o_off), (const double*)(d + o_xs), (const double*)(d + o_ys), threshold, seed,
+                          (const int*)(d + o_tab), (const int*)(d + o_toff), do_refine, (double*)(d + o_T), (int*)(d + o_st),
+                          (int*)(d + o_best), (int*)(d + o_it), s);
+    if (rc != SUO_OK) return rc;
+    SUO_HIP_CHECK(hipMemcpyAsync(h + o_T, d + o_T, L.off - o_T, hipMemcpyDeviceToHost, s));
+    SUO_HIP_CHECK(hipStreamSynchronize(s));
+    memcpy(T_out, h + o_T, sizeof(double) * 16 * (size_t)n_obj);
+    if (status) memcpy(status, h + o_st, sizeof(int) * n_obj);
+    if (best_inliers) memcpy(best_inliers, h + o_best, sizeof(int) * n_obj);
+    if (iterations) memcpy(iterations, h + o_it, sizeof(int) * n_obj);
+    if (winner && draws) memcpy(winner, h + o_win, sizeof(int) * n_obj);
+    return SUO_OK;
+}
+
+int suo_pnp_batch(int n_obj, const int* n_pts, const double* xs, const double* ys, double threshold, uint64_t seed,
+                  int do_refine, double* T_out, int* status, int* best_inliers, int* iterations) {
+    return pnp_batch_impl(n_obj, n_pts, xs, ys, threshold, seed, nullptr, 0, do_refine, T_out, status, best_inliers, iterations, nullptr);
+}
+
+int suo_pnp_replay(int n_obj, const int* n_pts, const double* xs, const double* ys, double threshold, const int* draws, int n_draws, int do_refine,
+                   double* T_out, int* status, int* best_inliers, int* iterations, int* winner) {
+    if (!draws) { suo_set_error("suo_pnp_replay: draws is NULL"); return SUO_ERR_ARG; }
+    return pnp_batch_impl(n_obj, n_pts, xs, ys, threshold, 0, draws, n_draws, do_refine, T_out, status, best_inliers, iterations, winner);
+}
+
+int suo_pnp(const double* xs, const double* ys, int n, double threshold, double* T_out) {
+    int st = 0;
+    return suo_pnp_batch(1, &n, xs, ys, threshold, 0, 1, T_out, &st, nullptr, nullptr);
+}
+
+}  // extern "C"

@@ -1,4 +1,4 @@
-"""Bundle-adjustment graphs placed on the dispatch boundaries of suo_optimize_batch (csrc/geom_api.hip), each with the kernel route the dispatcher
+"""Bundle-adjustment graphs placed on the dispatch boundaries of suo_optimize_batch (csrc/ba_api.hip), each with the kernel route the dispatcher
 must pick for every problem of it.  tests/test_lm_routes.py holds the table against suo_debug_lm_routes on the CPU; tests/test_gpu_lm_routes.py runs
 every case on the GPU against the C oracle.
 
@@ -196,7 +196,7 @@ def _c(name, routes, its=None, tracking=False):
 
 CASES: list = []
 
-# FRAME2's per-object cap: 32 edges per lane, 8 lanes up to 8 objects, 4 lanes with 9-16 (geom_api.hip: frame2_takes)
+# FRAME2's per-object cap: 32 edges per lane, 8 lanes up to 8 objects, 4 lanes with 9-16 (ba_api.hip: frame2_takes)
 _c("frame2_cap8_256", ["FRAME2"])(lambda r: [frame(r, [256, 60, 40])])
 _c("frame2_cap8_257", ["FRAME8"])(lambda r: [frame(r, [257, 60, 40])])
 _c("frame2_cap16_128", ["FRAME2"])(lambda r: [frame(r, [128] + [30] * 8)])

@@ -1,4 +1,4 @@
-"""The partition the C driver of the multi-rank bundle adjustment makes (csrc/geom_api.hip: suo_ba_split, behind suo_optimize_dist) is the one
+"""The partition the C driver of the multi-rank bundle adjustment makes (csrc/ba_drive.hip: suo_ba_split, behind suo_optimize_dist) is the one
 suo_slam_amd/ba_dist.py: split_problem makes: camera c to rank c % world, local camera indices in ascending global order, the edges of the rank's cameras in
 the caller's order.  Host only: no GPU."""
 import ctypes as C

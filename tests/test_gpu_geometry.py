@@ -281,7 +281,7 @@ def test_global_bundle_adjustment_matches_oracle(ba, n_cam, n_obj):
     """Global mode: first camera fixed, all other cameras and all objects free (object_slam.py:746-778).
     HIP eliminates cameras by Schur complement; the oracle solves the full dense system.  Below 512 edges one
     workgroup runs the whole adjustment (csrc/lm.hip); the larger graphs (612 - 5400 edges) take the phase kernels
-    of csrc/lm_dist.hip under the device-resident schedule, driven from C (geom_api.hip: optimize_phases_one_rank;
+    of csrc/lm_dist.hip under the device-resident schedule, driven from C (ba_drive.hip: optimize_phases_one_rank;
     rounds 4-5: the grid-barrier kernel of csrc/lm_grid.hip)."""
     rng = np.random.default_rng(n_cam * 7 + n_obj)
     P, obj_gt = _multi_view_scene(rng, n_cam, n_obj)
@@ -392,7 +392,7 @@ def test_device_resident_lm_schedule_equals_the_host_schedule(ba, monkeypatch, n
 @pytest.mark.parametrize("n_cam,n_obj", [(12, 6), (32, 16), (60, 8), (25, 13)])
 def test_the_one_c_call_runs_the_schedule_of_the_python_driver(ba, n_cam, n_obj):
     """suo_optimize on ONE large graph with free cameras and objects (what ObjectSLAM.optimize hands over for the global adjustment, lib/object_slam.py:746-778)
-    enqueues the phase kernels itself (csrc/geom_api.hip: optimize_phases_one_rank) -- the units, the looks at the control block and the robust rounds of
+    enqueues the phase kernels itself (csrc/ba_drive.hip: optimize_phases_one_rank) -- the units, the looks at the control block and the robust rounds of
     suo_slam_amd/ba_dist.py at one rank, without Python between the launches: poses, inlier flags, chi2 and the round / iteration / trial counters are
     bit-identical to the Python-driven run."""
     from suo_slam_amd import ba_dist
