@@ -262,13 +262,19 @@ __global__ __launch_bounds__(256) void decode_kernel(const float* __restrict__ l
     mx = wave_max(mx);
     raw = wave_sum(raw);
     if (argmax_idx) {                     // (uniform branch) smallest flat index holding the maximum: a wave-wide min over the lanes' own
-        int idx = HEAT * HEAT;
+        // torch.argmax counts NaN as the maximum (the first NaN wins); fmaxf above dropped them.  Key = index for a NaN, HEAT*HEAT + index for
+        // an element equal to mx: one of the two always exists (mx is attained unless every element is NaN), so the result is in range.
+        int idx = 2 * HEAT * HEAT;
 #pragma unroll
         for (int j = 15; j >= 0; --j)
 #pragma unroll
-            for (int t = 3; t >= 0; --t) idx = (v[j][t] == mx) ? (j * 64 + lane) * 4 + t : idx;
+            for (int t = 3; t >= 0; --t) {
+                const int e = (j * 64 + lane) * 4 + t;
+                idx = (v[j][t] == mx) ? min(idx, HEAT * HEAT + e) : idx;
+                idx = (v[j][t] != v[j][t]) ? e : idx;
+            }
         idx = -(int)wave_max((float)-idx);          // indices < 2^24 are exact in fp32
-        if (lane == 0) argmax_idx[map] = idx;
+        if (lane == 0) argmax_idx[map] = idx & (HEAT * HEAT - 1);
     }
     // row = e / 64 = j*4 + lane/16 ; col = (lane & 15)*4 + t
     const float colbase = (float)((lane & 15) * 4);
@@ -337,7 +343,10 @@ __global__ void classifier_kernel(const float* __restrict__ mean_logit, const fl
                                   const float* __restrict__ bc, float* __restrict__ kp_logit, float* __restrict__ kp_prob) {
     const int l = blockIdx.x, k = threadIdx.x;
     __shared__ float m[NUM_KP];
-    if (k < NUM_KP) m[k] = fmaxf(mean_logit[l * NUM_KP + k], 0.f);
+    if (k < NUM_KP) {                     // F.relu keeps a NaN (fmaxf would drop it): one NaN heat-map makes all 41 logits of its crop NaN
+        const float x = mean_logit[l * NUM_KP + k];
+        m[k] = x < 0.f ? 0.f : x;
+    }
     __syncthreads();
     if (k < NUM_KP) {
         float a = 0.f;
@@ -364,7 +373,8 @@ __global__ void kp_masks_kernel(const float* __restrict__ uv, const float* __res
     if (i >= n) return;
     const float u = uv[i * 2], v = uv[i * 2 + 1];
     bool m = (kp_prob[i] > 0.3f) && (model_mask ? model_mask[i] != 0 : true);
-    m = m && (fminf(u, v) > -bbox_thresh) && (fmaxf(u, v) < bbox_thresh);
+    // plain comparisons: a NaN component fails the gate, as np.min / np.max propagate it into a false comparison (fminf / fmaxf drop it)
+    m = m && (u > -bbox_thresh) && (v > -bbox_thresh) && (u < bbox_thresh) && (v < bbox_thresh);
     const float sx = sqrtf(cov[i * 4 + 0]), sy = sqrtf(cov[i * 4 + 3]);
     m = m && (sx < two_var) && (sy < two_var);
     out[i] = m ? 1 : 0;
