@@ -390,6 +390,7 @@ typedef struct suo_frame_geom_result {
     const int* pnp_status; const int* pnp_best_inliers; const int* pnp_iterations; const int* n_kp; const int* lm_stats;
     const uint8_t* accepted; const uint8_t* inlier;
     const float* uv; const float* cov; const uint8_t* mask;
+    const double* obj_cov;         /* [n_crops][36] after suo_frame_geom_covariances, NULL without it */
 } suo_frame_geom_result;
 int suo_frame_geom_create(int max_crops, int max_frames, suo_frame_geom** out);
 void suo_frame_geom_destroy(suo_frame_geom* g);
@@ -400,6 +401,12 @@ int suo_frame_geom_fetch(suo_frame_geom* g, suo_frame_geom_result* out);
 int suo_frame_geom_ready(suo_frame_geom* g);      /* 1 when the last launch has completed (or nothing is in flight), 0 otherwise; never blocks */
 /* The result block's DEVICE pointers (same fields): valid, stream-ordered, for work enqueued on the launch's stream behind it, until the context's next launch. */
 int suo_frame_geom_device_result(suo_frame_geom* g, suo_frame_geom_result* out);
+/* Optional, asynchronous, after suo_frame_geom_launch and on the SAME stream: the 6x6 covariance of every crop's refined pose (definition: suo_pose_covariances
+ * below; a single-view frame has no free camera, so every accepted crop is a block of its own) from the device-resident graph of the last launch, at the poses
+ * and inlier flags its LM left (do_lm = 0: at the PnP poses, every keypoint counted).  suo_frame_geom_fetch then waits for it too and obj_cov of both result
+ * calls points at [n_crops][36] row-major doubles: zeros for a crop that was not accepted, NaNs for an accepted crop without a counted keypoint or with a
+ * singular block.  Without this call obj_cov is NULL and nothing else differs. */
+int suo_frame_geom_covariances(suo_frame_geom* g, void* stream);
 
 /* ---- SLAM tracking between the two network passes of a view (round 6): camera-hypothesis vote + prior projection on the device -------------
  * Replaces, on the caller's stream and without a host round trip, ObjectSLAM.__estimate_camera_pose (lib/object_slam.py:975-1072) on the detections of the view's
@@ -474,6 +481,29 @@ int suo_optimize_batch(suo_ba_problem* problems, int n_problems);
 #define SUO_LM_ROUTE_PHASEWISE 8   /* the same phases under the host schedule: > 16 free objects next to free cameras */
 #define SUO_LM_ROUTE_GRID 9        /* lm_grid_kernel: tuning builds only (-DSUO_TUNING) */
 int suo_debug_lm_routes(const suo_ba_problem* problems, int n_problems, int* route_out, int* lds_need_out);
+
+/* ---- 6x6 pose covariances of the refined cameras and objects ----------------------------------------------------------------------
+ * The state is the one the suo_ba_problem holds, i.e. cam_T, obj_T and edge_inlier as suo_optimize leaves them.
+ *   Hessian.     H is the sum of J^T Omega J over edges whose edge_inlier is 1 and whose camera and object are not both fixed.  There is no Huber weight and no
+ *                lambda.  The columns of J are [omega, upsilon] of the left-multiplicative update exp(delta) * T, restricted to free vertices: the convention
+ *                suo_debug_ba_jacobians documents and csrc/lm_device.h implements.
+ *   Covariance.  Sigma = H^-1.  The result is the 6x6 diagonal block of Sigma for every camera and every object, as 36 row-major doubles per vertex:
+ *                - fixed vertex: 36 zeros;
+ *                - free vertex with no counted edge, or a system whose factorisation meets a non-positive pivot: 36 NaNs for every affected block, and `status`
+ *                  counts them.  Vertices in other connected blocks are unaffected.  The call never faults and never loops on a bad pivot.
+ *                  (Affected: without a free camera, or without a free object, every vertex is a block of its own; where free cameras meet free objects, a vertex
+ *                  without a counted edge is left out of the system, and a bad pivot of what remains marks every free vertex of that problem.)
+ *                - the chi2 scale is not applied: this is the covariance under the stated information matrices.
+ * Host buffers, blocking, staged through the arena of suo_optimize_batch; the problem is not modified (its, n_rounds, chi2_thr, huber_delta, stats are not read).
+ * cam_cov [n_cam][36], obj_cov [n_obj][36] (either may be NULL), status [2] = number of NaN camera blocks, NaN object blocks (may be NULL); the batch form takes
+ * one pointer per problem and status [n][2], and gives every problem the bits it gets alone.  Kernels (csrc/pose_cov.hip, fp64, fixed summation order):
+ *   no free camera (single-view frames, any number of objects)    one wave per problem, 8 / 4 lanes per object, passes of 16 objects
+ *   no free object (camera tracking, curr_only graphs)            the same over the cameras
+ *   free cameras next to <= 16 free objects                       one workgroup per problem: Schur complement onto the objects, the LM kernels' block-6 Cholesky once,
+ *                                                                  Sigma_OO = S^-1 in LDS, Sigma_cc = Hcc^-1 + Y Sigma_OO Y^T per camera
+ *   free cameras next to more than 16 free objects                SUO_ERR_ARG (the reduced system and its inverse no longer fit the LDS); nothing is launched */
+int suo_pose_covariances(const suo_ba_problem* problem, double* cam_cov /*[n_cam][36]*/, double* obj_cov /*[n_obj][36]*/, int* status /*[2]: NaN cam blocks, NaN obj blocks*/);
+int suo_pose_covariances_batch(const suo_ba_problem* problems, int n, double* const* cam_cov, double* const* obj_cov, int* status /*[n][2]*/);
 
 /* ---- phase-wise bundle adjustment for the multi-GPU global pose graph ------------------------
  * Cameras are partitioned across GPUs; each rank builds a context over ITS cameras' edges and ALL objects, and

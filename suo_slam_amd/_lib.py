@@ -137,6 +137,9 @@ SIGNATURES = {
     "suo_optimize_partitioned": (C.c_int, [VP, C.c_int]),
     "suo_ba_split": (C.c_int, [VP, C.c_int, C.c_int, VP, VP, VP, VP]),
     "suo_ba_units_per_look": (C.c_int, [C.c_int]),
+    "suo_pose_covariances": (C.c_int, [VP, VP, VP, VP]),
+    "suo_pose_covariances_batch": (C.c_int, [VP, C.c_int, VP, VP, VP]),
+    "suo_frame_geom_covariances": (C.c_int, [VP, VP]),
     "suo_frame_geom_create": (C.c_int, [C.c_int, C.c_int, C.POINTER(VP)]),
     "suo_frame_geom_destroy": (None, [VP]),
     "suo_frame_geom_launch": (C.c_int, [VP, C.c_int, VP, VP, VP, VP, VP, VP, VP, VP, VP, VP]),
@@ -174,7 +177,7 @@ class FrameGeomResult(C.Structure):
     """ctypes mirror of suo_frame_geom_result."""
     _fields_ = [("n_frames", C.c_int), ("n_crops", C.c_int), ("T_pnp", VP), ("T_opt", VP), ("chi2", VP), ("pnp_status", VP),
                 ("pnp_best_inliers", VP), ("pnp_iterations", VP), ("n_kp", VP), ("lm_stats", VP), ("accepted", VP), ("inlier", VP),
-                ("uv", VP), ("cov", VP), ("mask", VP)]
+                ("uv", VP), ("cov", VP), ("mask", VP), ("obj_cov", VP)]
 
 
 def register(extra):

@@ -73,3 +73,31 @@ def optimize(*args, **kw):
     p = Problem(*args, **kw)
     optimize_batch([p])
     return p.cam_T.reshape(-1, 3, 4), p.obj_T.reshape(-1, 3, 4), p.inlier, p.chi2, p.stats
+
+
+def pose_covariances_batch(problems):
+    """6x6 marginal covariances of every camera and object pose of each Problem at the state it holds (cam_T, obj_T, inlier): the diagonal blocks of the inverse
+    Gauss-Newton Hessian, rows and columns [omega, upsilon] of the left update exp(delta) T (include/suo_hip.h: suo_pose_covariances).  One call for the whole
+    list; per problem (cam_cov [C,6,6], obj_cov [O,6,6], status [2] = NaN camera blocks, NaN object blocks).  The problems are not modified."""
+    if not problems:
+        return []
+    lib = _lib.lib()
+    _lib.require_gpu()
+    n = len(problems)
+    arr = (_lib.BaProblem * n)()
+    out = []
+    cams, objs = (C.c_void_p * n)(), (C.c_void_p * n)()
+    status = np.zeros((n, 2), np.int32)
+    for i, (s, p) in enumerate(zip(arr, problems)):
+        p._fill(s)
+        cc, oc = np.zeros((len(p.cam_T), 6, 6)), np.zeros((len(p.obj_T), 6, 6))
+        cams[i], objs[i] = cc.ctypes.data, oc.ctypes.data
+        out.append((cc, oc, status[i]))
+    _lib.check(lib.suo_pose_covariances_batch(C.cast(arr, C.c_void_p), n, C.cast(cams, C.c_void_p), C.cast(objs, C.c_void_p), status.ctypes.data),
+               "suo_pose_covariances_batch")
+    return out
+
+
+def pose_covariances(*args, **kw):
+    """The arguments of optimize(); returns (cam_cov [C,6,6], obj_cov [O,6,6], status [2]) at the poses and inlier flags given."""
+    return pose_covariances_batch([Problem(*args, **kw)])[0]

@@ -101,11 +101,14 @@ static void lay_out(const suo_ba_problem* probs, int n_prob, char* base, Staged&
         put(S.Hcc_inv, 36 * C); put(S.Y, 36 * NP); put(S.yc, 6 * C); put(S.xc, 6 * C); put(S.xo, 6 * O); put(S.obj_slot, O);
         put(S.jac, 29 * E);
     }
+    st.cov_begin = L.off;
+    for (int i = 0; i < n_prob; ++i) { LmProblem& S = st.prep[i].S; put(S.cam_cov, 36 * (size_t)S.n_cam); put(S.obj_cov, 36 * (size_t)S.n_obj); put(S.cov_status, 2); }
+    st.cov_end = L.off;
     st.total = L.off;
 }
 
 // host prep + arena layout + H2D of one batch of problems
-int stage_problems(suo_ba_problem* probs, int n_prob, Arena& A, Staged& st, const char* who) {
+int stage_problems(const suo_ba_problem* probs, int n_prob, Arena& A, Staged& st, const char* who, const int* cov_form) {
     st.prep.assign(n_prob, Prep());
     for (int i = 0; i < n_prob; ++i) {
         int rc = prep_problem(probs[i], i, st.prep[i], who);
@@ -145,6 +148,7 @@ int stage_problems(suo_ba_problem* probs, int n_prob, Arena& A, Staged& st, cons
         memcpy(A.mirror(S.cam_obj_pair), P.cam_obj.data(), sizeof(int) * P.cam_obj.size());
         for (int k = 0; k < 8; ++k) S.its[k] = k < q.n_rounds ? q.its[k] : 0;
         S.n_rounds = q.n_rounds; S.init_with_outliers = q.init_with_outliers; S.chi2_thr = q.chi2_thr; S.huber_delta = q.huber_delta;
+        S.cov_form = cov_form ? cov_form[i] : 0;
         memcpy(A.host + st.o_structs + sizeof(LmProblem) * (size_t)i, &S, sizeof(LmProblem));
     }
     SUO_HIP_CHECK(hipMemcpyAsync(A.dev, A.host, st.in_end, hipMemcpyHostToDevice, A.stream));

@@ -52,6 +52,8 @@ struct FgArrays {                       // device pointers into the context's ar
     // read-back block
     double* T_pnp; double* T_opt; double* chi2; int* status; int* best; int* iters; int* counts_out; int* stats;
     uint8_t* accepted; uint8_t* inlier; float* uv_out; float* cov_out; uint8_t* mask_out;
+    // optional second read-back block (suo_frame_geom_covariances)
+    double* obj_cov;                    // [L][36]
 };
 
 // ---- compaction + normalisation + information (lib/object_slam.py:1118-1135, :34-36, :825-828) ----------------------------------
@@ -137,6 +139,7 @@ __global__ __launch_bounds__(64) void fg_build_kernel(FgArrays A, int n_rounds, 
         P.n_rounds = n_rounds; P.init_with_outliers = 0; P.chi2_thr = chi2_thr; P.huber_delta = huber_delta;
         P.level = A.level + e0;
         P.stats = A.stats + 4 * f;
+        P.obj_cov = A.obj_cov + 36 * (size_t)g0;                                     // (cov_form 0, no camera blocks, no status: csrc/pose_cov.hip)
         A.problems[f] = P;
         for (int t = 0; t < 4; ++t) A.stats[4 * f + t] = 0;
     }
@@ -149,11 +152,11 @@ using namespace suo;
 struct suo_frame_geom {
     int max_crops = 0, max_frames = 0;
     char* dev = nullptr; char* host = nullptr;          // one arena each; host pinned
-    size_t in_bytes = 0, out_off = 0, out_bytes = 0, total = 0;
+    size_t in_bytes = 0, out_off = 0, out_bytes = 0, cov_off = 0, cov_bytes = 0, total = 0;
     FgArrays A;                                         // device pointers
     FgArrays H;                                         // the same layout over the pinned host block (staged inputs + read-back block)
     hipEvent_t done = nullptr;
-    int n_frames = 0, L = 0, launched = 0;
+    int n_frames = 0, L = 0, launched = 0, cov_valid = 0, max_obj = 0;
 };
 
 namespace {
@@ -194,6 +197,10 @@ int suo_frame_geom_create(int max_crops, int max_frames, suo_frame_geom** out) {
     o[n++] = y.take(sizeof(int) * 4 * F);
     o[n++] = y.take(L); o[n++] = y.take(E); o[n++] = y.take(sizeof(float) * 2 * E); o[n++] = y.take(sizeof(float) * 4 * E); o[n++] = y.take(E);
     c->out_bytes = y.off - c->out_off;
+    // the covariances' own read-back block: copied only by suo_frame_geom_covariances
+    c->cov_off = y.off;
+    o[n++] = y.take(sizeof(double) * 36 * L);
+    c->cov_bytes = y.off - c->cov_off;
     c->total = y.off;
     if (hipMalloc((void**)&c->dev, c->total) != hipSuccess || hipHostMalloc((void**)&c->host, c->total, hipHostMallocDefault) != hipSuccess ||
         hipEventCreateWithFlags(&c->done, hipEventDisableTiming) != hipSuccess) {
@@ -217,6 +224,7 @@ int suo_frame_geom_create(int max_crops, int max_frames, suo_frame_geom** out) {
         A.stats = (int*)(base + o[k++]);
         A.accepted = (uint8_t*)(base + o[k++]); A.inlier = (uint8_t*)(base + o[k++]); A.uv_out = (float*)(base + o[k++]);
         A.cov_out = (float*)(base + o[k++]); A.mask_out = (uint8_t*)(base + o[k++]);
+        A.obj_cov = (double*)(base + o[k++]);
         return k;
     };
     const int used = bind(c->dev, c->A);
@@ -285,7 +293,23 @@ int suo_frame_geom_launch(suo_frame_geom* c, int n_frames, const int* frame_firs
     }
     SUO_HIP_CHECK(hipMemcpyAsync(c->host + c->out_off, c->dev + c->out_off, c->out_bytes, hipMemcpyDeviceToHost, s));
     SUO_HIP_CHECK(hipEventRecord(c->done, s));
-    c->n_frames = n_frames; c->L = L; c->launched = 1;
+    c->n_frames = n_frames; c->L = L; c->launched = 1; c->cov_valid = 0; c->max_obj = max_obj;
+    return SUO_OK;
+}
+
+// Behind the chain's LM, on the device-resident graph of the last launch (same stream as that launch): the block-diagonal kernel of csrc/pose_cov.hip, a wave per
+// frame, and the copy of its own read-back block.  Optional: without it suo_frame_geom_result.obj_cov is NULL and nothing else differs.
+int suo_frame_geom_covariances(suo_frame_geom* c, void* stream) {
+    if (!c) { suo_set_error("suo_frame_geom_covariances: null argument"); return SUO_ERR_ARG; }
+    if (!c->launched) { suo_set_error("suo_frame_geom_covariances: nothing launched"); return SUO_ERR_ARG; }
+    // (the graph's object -> pair table is the 0 .. 16 ramp the frame LM kernel reads: a do_lm = 0 launch may hold more crops per frame than it covers)
+    if (c->max_obj > FG_MAX_OBJ) { suo_set_error("suo_frame_geom_covariances: %d objects in one frame (the chain's graph takes %d)", c->max_obj, FG_MAX_OBJ); return SUO_ERR_ARG; }
+    hipStream_t s = (hipStream_t)stream;
+    int rc = launch_pose_cov_diag(c->A.problems, c->n_frames, s);
+    if (rc != SUO_OK) return rc;
+    SUO_HIP_CHECK(hipMemcpyAsync(c->host + c->cov_off, c->dev + c->cov_off, sizeof(double) * 36 * (size_t)c->L, hipMemcpyDeviceToHost, s));
+    SUO_HIP_CHECK(hipEventRecord(c->done, s));
+    c->cov_valid = 1;
     return SUO_OK;
 }
 
@@ -297,6 +321,7 @@ int suo_frame_geom_fetch(suo_frame_geom* c, suo_frame_geom_result* r) {
     r->T_pnp = c->H.T_pnp; r->T_opt = c->H.T_opt; r->chi2 = c->H.chi2; r->pnp_status = c->H.status; r->pnp_best_inliers = c->H.best;
     r->pnp_iterations = c->H.iters; r->n_kp = c->H.counts_out; r->lm_stats = c->H.stats; r->accepted = c->H.accepted; r->inlier = c->H.inlier;
     r->uv = c->H.uv_out; r->cov = c->H.cov_out; r->mask = c->H.mask_out;
+    r->obj_cov = c->cov_valid ? c->H.obj_cov : nullptr;
     return SUO_OK;
 }
 
@@ -309,6 +334,7 @@ int suo_frame_geom_device_result(suo_frame_geom* c, suo_frame_geom_result* r) {
     r->T_pnp = c->A.T_pnp; r->T_opt = c->A.T_opt; r->chi2 = c->A.chi2; r->pnp_status = c->A.status; r->pnp_best_inliers = c->A.best;
     r->pnp_iterations = c->A.iters; r->n_kp = c->A.counts_out; r->lm_stats = c->A.stats; r->accepted = c->A.accepted; r->inlier = c->A.inlier;
     r->uv = c->A.uv_out; r->cov = c->A.cov_out; r->mask = c->A.mask_out;
+    r->obj_cov = c->cov_valid ? c->A.obj_cov : nullptr;
     return SUO_OK;
 }
 

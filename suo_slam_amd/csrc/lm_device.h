@@ -276,6 +276,9 @@ struct LmProblem {
     // optional (nullptr = pair p's edges end at pair_start[p + 1]): explicit end of each pair's edge range, for problems built ON THE
     // DEVICE in fixed-stride slots (csrc/frame_geom.hip: 41 slots per object, the first n_keypoints of them used); lm_frame_kernel only
     const int* pair_end;
+    // optional outputs of csrc/pose_cov.hip (nullptr = not wanted): the 6x6 marginal covariance of every camera / object pose, row-major, and the number of
+    // NaN blocks [2] (cameras, objects); cov_form: which of its kernels takes the problem (0 block-diagonal over objects, 1 over cameras, 2 coupled)
+    double* cam_cov; double* obj_cov; int* cov_status; int cov_form;
 };
 DEV int pair_hi(const LmProblem& P, int p) { return P.pair_end ? P.pair_end[p] : P.pair_start[p + 1]; }
 
@@ -289,8 +292,8 @@ DEV int pair_hi(const LmProblem& P, int p) { return P.pair_end ? P.pair_end[p] :
 // bundle-adjustment trial.)  *ok is cleared on a non-positive / non-finite pivot; the factorisation then continues with a unit pivot
 // and the caller rejects the trial.  Call from ALL threads of the workgroup (>= 256); `rhs` holds the solution after the caller's
 // next barrier.
-DEV void wg_cholesky_solve(double* S, int sp, double* rhs, int ns_, int tid, int nthreads, int* ok) {
-    const int ns = __builtin_amdgcn_readfirstlane(ns_);
+// The factorisation alone (every thread of the workgroup; ends on a barrier): L in the lower triangle of S, 1 / L_rr right of the diagonal.
+DEV void wg_cholesky_factor(double* S, int sp, int ns, int tid, int nthreads, int* ok) {
     auto load_diag = [&](int k0, double (&L)[6][6]) {
 #pragma unroll
         for (int r = 0; r < 6; ++r)
@@ -381,10 +384,20 @@ DEV void wg_cholesky_solve(double* S, int sp, double* rhs, int ns_, int tid, int
         }
         __syncthreads();
     }
+}
+// L y = rhs, then L^T x = y, on a system wg_cholesky_factor left in S: ONE wave (all 64 lanes calling, tid = lane), rhs overwritten by the solution.  Waves may
+// solve different right-hand sides against the same factor at the same time (csrc/pose_cov.hip: the columns of the inverse).
+DEV void wave_cholesky_substitute(const double* S, int sp, double* rhs, int ns, int tid) {
+    auto load_diag = [&](int k0, double (&L)[6][6]) {
+#pragma unroll
+        for (int r = 0; r < 6; ++r)
+#pragma unroll
+            for (int c = 0; c <= r; ++c) L[r][c] = S[(k0 + r) * sp + k0 + c];
+    };
     // The substitutions by ONE wave (round 5): 2 ns / 6 block steps whose only parallel work is ns rows of six multiply-adds -- with the whole workgroup each step paid a
     // workgroup barrier and four redundant copies of the 6 x 6 solve (16 of the 56 us of a 96-row solve); a wave's LDS operations execute in order, so it needs none.
     // L y = rhs, block by block: every lane solves the 6 x 6 block redundantly, lane t then updates rows t, t + 64 below it
-    if (tid < 64) {
+    {
         for (int k0 = 0; k0 < ns; k0 += 6) {
             double L[6][6], y[6];
             load_diag(k0, L);
@@ -433,6 +446,11 @@ DEV void wg_cholesky_solve(double* S, int sp, double* rhs, int ns_, int tid, int
             __builtin_amdgcn_wave_barrier();
         }
     }
+}
+DEV void wg_cholesky_solve(double* S, int sp, double* rhs, int ns_, int tid, int nthreads, int* ok) {
+    const int ns = __builtin_amdgcn_readfirstlane(ns_);
+    wg_cholesky_factor(S, sp, ns, tid, nthreads, ok);
+    if (tid < 64) wave_cholesky_substitute(S, sp, rhs, ns, tid);
 }
 
 // The same solve for a kernel that does nothing else (csrc/lm_dist.hip: ba_solve_kernel -- the global adjustment's reduced system, up to 96 rows): Cholesky

@@ -1,0 +1,387 @@
+// 6x6 marginal covariances of the camera and object poses of a bundle-adjustment problem at the state it holds (include/suo_hip.h: suo_pose_covariances).
+//
+//   H      = sum of J^T Omega J over the edges whose edge_inlier is 1 and whose camera and object are not both fixed -- no Huber weight, no lambda; the columns of J are
+//            [omega, upsilon] of the left-multiplicative update exp(delta) T, restricted to the free vertices (the convention of suo_debug_ba_jacobians / lm_device.h)
+//   Sigma  = H^-1; the result is its 6x6 diagonal block per vertex, 36 row-major doubles: zeros for a fixed vertex, NaNs for a free vertex without a counted edge
+//            and for every block of a system whose factorisation meets a non-positive pivot.  The chi2 scale is not applied.
+//
+// Three forms, chosen per problem on the host (csrc/pose_cov_api.hip: plan_cov_batch -> LmProblem::cov_form):
+//   0  no free camera: H is block-diagonal over the objects.  One wave per problem in the lane layout of csrc/lm_frame2.hip -- G = 8 lanes own an object (G = 4 from
+//      9 objects on), lane (object, sub) walks the object's edges sub, sub + G, ...; the 21 packed entries of the block meet inside the group by log2(G) DPP steps;
+//      every group inverts its own block by Cholesky in registers.  Problems of more than 64 / G objects are walked in passes: nothing couples the objects.
+//   1  no free object (camera tracking): the same kernel over the cameras, with the camera's half of the Jacobian.
+//   2  free cameras next to at most 16 free objects: one 256-thread workgroup per problem.  The linearisation and the per-pair sums are lm_device.h's (edge_pass_partial,
+//      accumulate_pairs); S = Hoo - sum_c Hco^T Hcc^-1 Hco is factorised ONCE by the block-6 Cholesky of the LM kernels (wg_cholesky_factor), the ns columns of
+//      S^-1 = Sigma_OO are the substitutions against the identity, dealt to the four waves (wave_cholesky_substitute: no workgroup barrier between columns), and stay
+//      in LDS: a camera's block Hcc^-1 + Y Sigma_OO Y^T, Y = Hcc^-1 Hco over the objects it sees, needs the off-diagonal blocks between them.  A wave per camera
+//      forms Z = Y Sigma_OO (6 x ns) and Z Y^T in the LDS the factor no longer needs.  A free vertex without a counted edge gets no row in the system.
+// Vector stores only, no atomics; every sum runs in a fixed order, so two runs give the same bits, and a problem's result does not depend on the rest of the batch.
+#include <algorithm>
+
+#include "lm_device.h"
+#include "lm_launch.h"
+
+namespace suo {
+
+static_assert(LM_THREADS == 256, "pose_cov_coupled_kernel: four waves");
+
+template <int G>
+DEV double pc_gsum(double v) {                  // sum over the G lanes of a group, the same value in each of them (csrc/lm_frame2.hip: gsum)
+    v += dpp_get<0xB1>(v);                      // lane ^ 1
+    v += dpp_get<0x4E>(v);                      // lane ^ 2
+    if (G >= 8) v += dpp_get<0x141>(v);         // row_half_mirror: the other quad of the 8
+    return v;
+}
+
+// inverse of the symmetric positive definite 6x6 given by its packed upper triangle, packed the same way: Cholesky A = L L^T, M = L^-1, A^-1 = M^T M (exactly
+// symmetric).  Compile-time indices only: everything stays in registers.  false: a pivot was not positive (the result is then meaningless).
+DEV bool spd_inverse6_packed(const double (&h)[21], double (&inv)[21]) {
+    double A[6][6], L[6][6], M[6][6], dinv[6];
+    bool ok = true;
+    {
+        int u = 0;
+#pragma unroll
+        for (int r = 0; r < 6; ++r)
+#pragma unroll
+            for (int c = r; c < 6; ++c) { A[c][r] = h[u]; ++u; }
+    }
+#pragma unroll
+    for (int i = 0; i < 6; ++i) {
+#pragma unroll
+        for (int j = 0; j <= i; ++j) {
+            double s = A[i][j];
+#pragma unroll
+            for (int k = 0; k < j; ++k) s -= L[i][k] * L[j][k];
+            if (i == j) {
+                if (!(s > 0) || !isfinite(s)) ok = false;
+                const double sp = ok ? s : 1.0;
+                dinv[i] = rsqrt_nr(sp);
+                L[i][i] = sp * dinv[i];
+            } else {
+                L[i][j] = s * dinv[j];
+            }
+        }
+    }
+#pragma unroll
+    for (int j = 0; j < 6; ++j) {
+        M[j][j] = dinv[j];
+#pragma unroll
+        for (int i = j + 1; i < 6; ++i) {
+            double s = 0;
+#pragma unroll
+            for (int k = j; k < i; ++k) s += L[i][k] * M[k][j];
+            M[i][j] = -(s * dinv[i]);
+        }
+    }
+    {
+        int u = 0;
+#pragma unroll
+        for (int r = 0; r < 6; ++r)
+#pragma unroll
+            for (int c = r; c < 6; ++c) {
+                double s = 0;
+#pragma unroll
+                for (int k = c; k < 6; ++k) s += M[k][r] * M[k][c];
+                inv[u] = s;
+                ++u;
+            }
+    }
+    return ok;
+}
+
+// forms 0 / 1: the blocks of the vertices of one side (CAM: cameras, else objects), every vertex of the other side being fixed
+template <int G, bool CAM>
+DEV void pose_cov_diag_body(const LmProblem& P) {
+    constexpr int PER = 64 / G;
+    const int lane = threadIdx.x, slot = lane / G, sub = lane % G;
+    const int nv = CAM ? P.n_cam : P.n_obj;
+    const int* vptr = CAM ? P.cam_pair_ptr : P.obj_pair_ptr;
+    const int* vidx = CAM ? P.cam_pair_idx : P.obj_pair_idx;
+    const uint8_t* vfixed = CAM ? P.cam_fixed : P.obj_fixed;
+    double* out = CAM ? P.cam_cov : P.obj_cov;
+    const double nan = __longlong_as_double(0x7ff8000000000000ll);
+    int n_nan = 0;
+    for (int v0 = 0; v0 < nv; v0 += PER) {
+        const int v = v0 + slot;
+        const bool have = v < nv, fr = have && !vfixed[v];
+        double h[21], cnt = 0;
+#pragma unroll
+        for (int k = 0; k < 21; ++k) h[k] = 0;
+        if (fr) {
+            for (int a = vptr[v]; a < vptr[v + 1]; ++a) {
+                const int p = vidx[a];
+                double Tc[12], To[12];
+#pragma unroll
+                for (int i = 0; i < 12; ++i) { Tc[i] = P.cam_T[12 * (size_t)P.pair_cam[p] + i]; To[i] = P.obj_T[12 * (size_t)P.pair_obj[p] + i]; }
+                const int e1 = pair_hi(P, p);
+                for (int e = P.pair_start[p] + sub; e < e1; e += G) {
+                    if (!P.edge_inlier[e]) continue;
+                    const double* x = P.edge_p + 3 * (size_t)e;
+                    const double* k = P.edge_k + 4 * (size_t)e;
+                    const double* I = P.edge_info + 3 * (size_t)e;
+                    double pw[3], pc[3];
+#pragma unroll
+                    for (int r = 0; r < 3; ++r) pw[r] = To[4 * r] * x[0] + To[4 * r + 1] * x[1] + To[4 * r + 2] * x[2] + To[4 * r + 3];
+#pragma unroll
+                    for (int r = 0; r < 3; ++r) pc[r] = Tc[4 * r] * pw[0] + Tc[4 * r + 1] * pw[1] + Tc[4 * r + 2] * pw[2] + Tc[4 * r + 3];
+                    // d err / d p_c (2x3, two structural zeros), then the vertex's half of EdgeSE3ProjectFromObject::linearizeOplus: [-[q]x | I] behind it,
+                    // q = p_c for the camera, and behind R_c with q = p_w for the object
+                    const double iz = 1.0 / pc[2];
+                    const double pj00 = -(k[0] * iz), pj02 = k[0] * pc[0] * iz * iz, pj11 = -(k[1] * iz), pj12 = k[1] * pc[1] * iz * iz;
+                    double a0[3], a1[3];
+                    const double* q = CAM ? pc : pw;
+                    if (CAM) {
+                        a0[0] = pj00; a0[1] = 0; a0[2] = pj02;
+                        a1[0] = 0; a1[1] = pj11; a1[2] = pj12;
+                    } else {
+#pragma unroll
+                        for (int cc = 0; cc < 3; ++cc) { a0[cc] = pj00 * Tc[cc] + pj02 * Tc[8 + cc]; a1[cc] = pj11 * Tc[4 + cc] + pj12 * Tc[8 + cc]; }
+                    }
+                    const double J0[6] = {a0[2] * q[1] - a0[1] * q[2], a0[0] * q[2] - a0[2] * q[0], a0[1] * q[0] - a0[0] * q[1], a0[0], a0[1], a0[2]};
+                    const double J1[6] = {a1[2] * q[1] - a1[1] * q[2], a1[0] * q[2] - a1[2] * q[0], a1[1] * q[0] - a1[0] * q[1], a1[0], a1[1], a1[2]};
+                    double wj0[6], wj1[6];
+#pragma unroll
+                    for (int cc = 0; cc < 6; ++cc) { wj0[cc] = I[0] * J0[cc] + I[1] * J1[cc]; wj1[cc] = I[1] * J0[cc] + I[2] * J1[cc]; }
+                    int u = 0;
+#pragma unroll
+                    for (int r = 0; r < 6; ++r)
+#pragma unroll
+                        for (int cc = r; cc < 6; ++cc) { h[u] += J0[r] * wj0[cc] + J1[r] * wj1[cc]; ++u; }
+                    cnt += 1;
+                }
+            }
+        }
+#pragma unroll
+        for (int k = 0; k < 21; ++k) h[k] = pc_gsum<G>(h[k]);
+        cnt = pc_gsum<G>(cnt);
+        double inv[21];
+        const bool ok = spd_inverse6_packed(h, inv);          // every group its own block, in lock-step
+        const bool bad = fr && !(ok && cnt > 0);
+        if (have && sub == 0 && out) {
+            double* o = out + 36 * (size_t)v;
+            int u = 0;
+#pragma unroll
+            for (int r = 0; r < 6; ++r)
+#pragma unroll
+                for (int cc = r; cc < 6; ++cc) {
+                    const double val = !fr ? 0.0 : (bad ? nan : inv[u]);
+                    o[r * 6 + cc] = val; o[cc * 6 + r] = val;
+                    ++u;
+                }
+        }
+        n_nan += __popcll(__ballot(bad && sub == 0));
+    }
+    // the other side: fixed vertices only
+    double* other = CAM ? P.obj_cov : P.cam_cov;
+    const int n_other = CAM ? P.n_obj : P.n_cam;
+    if (other)
+        for (int i = lane; i < 36 * n_other; i += 64) other[i] = 0.0;
+    if (lane == 0 && P.cov_status) { P.cov_status[CAM ? 0 : 1] = n_nan; P.cov_status[CAM ? 1 : 0] = 0; }
+}
+
+// 8 lanes per vertex up to 8 vertices, 4 from 9 on (passes of 16): chosen per PROBLEM, so that its result does not depend on what else is in the launch
+__global__ __launch_bounds__(64) void pose_cov_diag_kernel(const LmProblem* __restrict__ problems) {
+    const LmProblem& P = problems[blockIdx.x];
+    if (P.cov_form == 0) {
+        if (P.n_obj <= 8) pose_cov_diag_body<8, false>(P);
+        else pose_cov_diag_body<4, false>(P);
+    } else if (P.cov_form == 1) {
+        if (P.n_cam <= 8) pose_cov_diag_body<8, true>(P);
+        else pose_cov_diag_body<4, true>(P);
+    }
+}
+
+// form 2.  Dynamic LDS (doubles): [16: ok, ns, the object of every slot | Sinv ns x ns | S ns x (ns + 1), later the waves' camera buffers 4 x (12 ns + 36)]
+constexpr int PC_HEAD = 16;
+static size_t pose_cov_lds_bytes(int max_free_obj) {
+    const size_t ns = 6 * (size_t)max_free_obj;
+    return sizeof(double) * (PC_HEAD + ns * ns + std::max(ns * (ns + 1), (size_t)(LM_THREADS / 64) * (12 * ns + 36)));
+}
+
+__global__ __launch_bounds__(LM_THREADS) void pose_cov_coupled_kernel(const LmProblem* __restrict__ problems) {
+    const LmProblem& P = problems[blockIdx.x];
+    if (P.cov_form != 2) return;
+    extern __shared__ __attribute__((aligned(16))) double pc_lds[];
+    int* sh = (int*)pc_lds;                     // [0] ok  [1] ns  [2 + s] the object in slot s
+    const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
+    const double nan = __longlong_as_double(0x7ff8000000000000ll);
+    // ---- the state as the LM kernels hold it; level 1 = not counted -------------------------------------------------------------
+    for (int c = tid; c < P.n_cam; c += LM_THREADS) pose_from_T(P.cam_T + 12 * c, P.cam[c]);
+    for (int o = tid; o < P.n_obj; o += LM_THREADS) pose_from_T(P.obj_T + 12 * o, P.obj[o]);
+    for (int e = tid; e < P.n_edge; e += LM_THREADS) P.level[e] = P.edge_inlier[e] ? 0 : 1;
+    if (tid == 0) sh[0] = 1;
+    __syncthreads();
+    (void)edge_pass_partial(P, 0, P.n_edge, false, true);      // Jacobians, weight 1
+    __syncthreads();
+    accumulate_pairs(P);                                        // per pair Hcc (21) Hoo (21) Hco (36), edge order
+    __syncthreads();
+    // ---- per vertex: its diagonal block (pairs in CSR order) and whether any counted edge reaches it (xc / xo [6 v]: scratch) ----
+    for (int idx = tid; idx < P.n_cam * 21; idx += LM_THREADS) {
+        const int c = idx / 21, k = idx - c * 21;
+        double s = 0;
+        if (!P.cam_fixed[c])
+            for (int a = P.cam_pair_ptr[c]; a < P.cam_pair_ptr[c + 1]; ++a) s += P.pair_part[90 * (size_t)P.cam_pair_idx[a] + k];
+        P.Hcc[36 * c + k] = s;
+    }
+    for (int idx = tid; idx < P.n_obj * 21; idx += LM_THREADS) {
+        const int o = idx / 21, k = idx - o * 21;
+        double s = 0;
+        if (!P.obj_fixed[o])
+            for (int a = P.obj_pair_ptr[o]; a < P.obj_pair_ptr[o + 1]; ++a) s += P.pair_part[90 * (size_t)P.obj_pair_idx[a] + 21 + k];
+        P.Hoo[36 * o + k] = s;
+    }
+    for (int v = tid; v < P.n_cam + P.n_obj; v += LM_THREADS) {
+        const bool is_cam = v < P.n_cam;
+        const int i = is_cam ? v : v - P.n_cam;
+        int n = 0;
+        if (!(is_cam ? P.cam_fixed[i] : P.obj_fixed[i])) {
+            const int* ptr = is_cam ? P.cam_pair_ptr : P.obj_pair_ptr;
+            const int* pidx = is_cam ? P.cam_pair_idx : P.obj_pair_idx;
+            for (int a = ptr[i]; a < ptr[i + 1]; ++a)
+                for (int e = P.pair_start[pidx[a]]; e < P.pair_start[pidx[a] + 1]; ++e) n += P.level[e] == 0 ? 1 : 0;
+        }
+        (is_cam ? P.xc : P.xo)[6 * i] = n > 0 ? 1.0 : 0.0;
+    }
+    __syncthreads();
+    auto cam_in = [&](int c) { return !P.cam_fixed[c] && P.xc[6 * c] > 0; };
+    if (tid == 0) {
+        int n = 0;
+        for (int o = 0; o < P.n_obj; ++o) {
+            const bool in = !P.obj_fixed[o] && P.xo[6 * o] > 0 && n < LM_MAX_SCHUR_OBJ;
+            P.obj_slot[o] = in ? n : -1;
+            if (in) { sh[2 + n] = o; ++n; }
+        }
+        sh[1] = 6 * n;
+    }
+    for (int c = tid; c < P.n_cam; c += LM_THREADS) {
+        if (!cam_in(c)) continue;
+        double A[36], Ai[36];
+        unpack_sym21(P.Hcc + 36 * c, A);
+        if (!spd_inverse6(A, Ai)) { sh[0] = 0; for (int i = 0; i < 36; ++i) Ai[i] = 0; }
+        for (int i = 0; i < 36; ++i) P.Hcc_inv[36 * c + i] = Ai[i];
+    }
+    __syncthreads();
+    const int ns = __builtin_amdgcn_readfirstlane(sh[1]), sp = ns + 1;
+    double* Sinv = pc_lds + PC_HEAD;
+    double* S = Sinv + ns * ns;
+    // ---- Y[p] = Hcc^-1 Hco[p];  S = blockdiag(Hoo) - sum_c Hco(c, o1)^T Y(c, o2), cameras in CSR order (csrc/lm.hip) --------------
+    for (int idx = tid; idx < P.n_pair * 36; idx += LM_THREADS) {
+        const int p = idx / 36, rc = idx - p * 36, r = rc / 6, cc = rc - r * 6;
+        const int c = P.pair_cam[p];
+        double s = 0;
+        if (cam_in(c) && P.obj_slot[P.pair_obj[p]] >= 0) {
+            const double* Hco = P.pair_part + 90 * (size_t)p + 42;
+            for (int k = 0; k < 6; ++k) s += P.Hcc_inv[36 * c + r * 6 + k] * Hco[k * 6 + cc];
+        }
+        P.Y[idx] = s;
+    }
+    for (int idx = tid; idx < ns * sp; idx += LM_THREADS) S[idx] = 0;
+    __syncthreads();
+    for (int idx = tid; idx < ns * ns; idx += LM_THREADS) {
+        const int row = idx / ns, col = idx - row * ns;
+        const int s1 = row / 6, i = row - s1 * 6, s2 = col / 6, j = col - s2 * 6;
+        const int o1 = sh[2 + s1], o2 = sh[2 + s2];
+        double acc = 0;
+        if (s1 == s2) {
+            const int rr = i < j ? i : j, c2 = i < j ? j : i;
+            acc = P.Hoo[36 * o1 + rr * 6 - rr * (rr - 1) / 2 + (c2 - rr)];
+        }
+        double sub = 0;
+        for (int a = P.obj_pair_ptr[o1]; a < P.obj_pair_ptr[o1 + 1]; ++a) {
+            const int p1 = P.obj_pair_idx[a], c = P.pair_cam[p1];
+            const int p2 = P.cam_obj_pair[(size_t)c * P.n_obj + o2];      // the same camera's pair with object o2
+            if (!cam_in(c) || p2 < 0) continue;
+            const double* H1 = P.pair_part + 90 * (size_t)p1 + 42;       // Hco(c, o1), row = camera dof
+            const double* Y2 = P.Y + 36 * (size_t)p2;
+            for (int k = 0; k < 6; ++k) sub += H1[k * 6 + i] * Y2[k * 6 + j];
+        }
+        S[row * sp + col] = acc - sub;
+    }
+    __syncthreads();
+    // ---- S = L L^T once; column c of Sigma_OO = S^-1 is the solve against e_c, one wave per column ----------------------------------
+    wg_cholesky_factor(S, sp, ns, tid, LM_THREADS, &sh[0]);
+    for (int col = wv; col < ns; col += LM_THREADS / 64) {
+        double* rhs = Sinv + col * ns;
+        for (int i = lane; i < ns; i += 64) rhs[i] = i == col ? 1.0 : 0.0;
+        __builtin_amdgcn_wave_barrier();
+        wave_cholesky_substitute(S, sp, rhs, ns, lane);
+    }
+    __syncthreads();
+    const bool ok = sh[0] != 0;
+    if (P.obj_cov)
+        for (int idx = tid; idx < P.n_obj * 36; idx += LM_THREADS) {
+            const int o = idx / 36, rc = idx - o * 36, r = rc / 6, cc = rc - r * 6;
+            const int s = P.obj_slot[o];
+            double val = 0.0;
+            if (!P.obj_fixed[o]) val = (s < 0 || !ok) ? nan : 0.5 * (Sinv[(6 * s + r) * ns + 6 * s + cc] + Sinv[(6 * s + cc) * ns + 6 * s + r]);
+            P.obj_cov[idx] = val;
+        }
+    // ---- cameras, a wave each: Hcc^-1 + Y Sigma_OO Y^T with Y (6 x ns, zero where the camera does not see the object), Z = Y Sigma_OO in the factor's LDS -----
+    if (P.cam_cov) {
+        double* Yd = S + wv * (12 * ns + 36);
+        double* Z = Yd + 6 * ns;
+        double* tmp = Z + 6 * ns;
+        for (int c = wv; c < P.n_cam; c += LM_THREADS / 64) {
+            double* oc = P.cam_cov + 36 * (size_t)c;
+            if (P.cam_fixed[c] || !cam_in(c) || !ok) {
+                if (lane < 36) oc[lane] = P.cam_fixed[c] ? 0.0 : nan;
+                continue;
+            }
+            for (int i = lane; i < 6 * ns; i += 64) Yd[i] = 0;
+            __builtin_amdgcn_wave_barrier();
+            for (int a = P.cam_pair_ptr[c]; a < P.cam_pair_ptr[c + 1]; ++a) {
+                const int p = P.cam_pair_idx[a], s = P.obj_slot[P.pair_obj[p]];
+                if (s >= 0 && lane < 36) Yd[(lane / 6) * ns + 6 * s + lane % 6] = P.Y[36 * (size_t)p + lane];
+            }
+            __builtin_amdgcn_wave_barrier();
+            for (int i = lane; i < 6 * ns; i += 64) {
+                const int r = i / ns, j = i - r * ns;
+                double acc = 0;
+                for (int k = 0; k < ns; ++k) acc += Yd[r * ns + k] * Sinv[k * ns + j];
+                Z[i] = acc;
+            }
+            __builtin_amdgcn_wave_barrier();
+            const int r = (lane % 36) / 6, c2 = lane % 6;
+            if (lane < 36) {
+                double acc = P.Hcc_inv[36 * c + lane];
+                for (int j = 0; j < ns; ++j) acc += Z[r * ns + j] * Yd[c2 * ns + j];
+                tmp[lane] = acc;
+            }
+            __builtin_amdgcn_wave_barrier();
+            if (lane < 36) oc[lane] = 0.5 * (tmp[lane] + tmp[c2 * 6 + r]);
+            __builtin_amdgcn_wave_barrier();
+        }
+    }
+    __syncthreads();
+    if (tid == 0 && P.cov_status) {
+        int nc = 0, no = 0;
+        if (P.cam_cov) for (int c = 0; c < P.n_cam; ++c) nc += isnan(P.cam_cov[36 * (size_t)c]) ? 1 : 0;
+        if (P.obj_cov) for (int o = 0; o < P.n_obj; ++o) no += isnan(P.obj_cov[36 * (size_t)o]) ? 1 : 0;
+        P.cov_status[0] = nc; P.cov_status[1] = no;
+    }
+}
+
+int launch_pose_cov_diag(const void* problems_dev, int n_problems, hipStream_t s) {
+    if (n_problems <= 0) return SUO_OK;
+    hipLaunchKernelGGL(pose_cov_diag_kernel, dim3(n_problems), dim3(64), 0, s, (const LmProblem*)problems_dev);
+    SUO_HIP_CHECK(hipGetLastError());
+    return SUO_OK;
+}
+
+int launch_pose_cov_coupled(const void* problems_dev, int n_problems, int max_free_obj, hipStream_t s) {
+    if (n_problems <= 0) return SUO_OK;
+    if (max_free_obj < 0 || max_free_obj > LM_MAX_SCHUR_OBJ) {
+        suo_set_error("pose covariances: %d free objects next to free cameras (the reduced system holds %d)", max_free_obj, LM_MAX_SCHUR_OBJ);
+        return SUO_ERR_ARG;
+    }
+    static bool attr_set = false;
+    if (!attr_set) {
+        SUO_HIP_CHECK(hipFuncSetAttribute((const void*)pose_cov_coupled_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)pose_cov_lds_bytes(LM_MAX_SCHUR_OBJ)));
+        attr_set = true;
+    }
+    hipLaunchKernelGGL(pose_cov_coupled_kernel, dim3(n_problems), dim3(LM_THREADS), pose_cov_lds_bytes(max_free_obj), s, (const LmProblem*)problems_dev);
+    SUO_HIP_CHECK(hipGetLastError());
+    return SUO_OK;
+}
+
+}  // namespace suo

@@ -78,6 +78,17 @@ class FrameGeometry:
         _lib.check(self._lib.suo_frame_geom_device_result(self._h, C.byref(r)), "suo_frame_geom_device_result")
         return r
 
+    def covariances(self, stream=None):
+        """6x6 covariance of every crop's refined pose from the device-resident graph of the last launch (suo_frame_geom_covariances: a wave per frame, enqueued
+        on `stream` -- the launch's stream -- behind the chain's LM), waited for and returned as [L,6,6] float64: zeros for crops that were not accepted.
+        fetch() afterwards carries the same array as "obj_cov"."""
+        if stream is None:
+            stream = _lib.current_stream_ptr()
+        _lib.check(self._lib.suo_frame_geom_covariances(self._h, C.c_void_p(int(stream))), "suo_frame_geom_covariances")
+        r = _lib.FrameGeomResult()
+        _lib.check(self._lib.suo_frame_geom_fetch(self._h, C.byref(r)), "suo_frame_geom_fetch")
+        return np.ctypeslib.as_array(C.cast(r.obj_cov, C.POINTER(C.c_double)), shape=(r.n_crops, 6, 6)).copy()
+
     def ready(self):
         return bool(self._lib.suo_frame_geom_ready(self._h))
 
@@ -92,7 +103,8 @@ class FrameGeometry:
         def arr(p, ctype, shape):
             a = np.ctypeslib.as_array(C.cast(p, C.POINTER(ctype)), shape=shape)
             return a.copy() if copy else a
-        return {"T_pnp": arr(r.T_pnp, C.c_double, (L, 4, 4)), "T_opt": arr(r.T_opt, C.c_double, (L, 3, 4)), "chi2": arr(r.chi2, C.c_double, (L, NUM_KP)),
+        extra = {"obj_cov": arr(r.obj_cov, C.c_double, (L, 6, 6))} if r.obj_cov else {}       # (only after covariances())
+        return {**extra, "T_pnp": arr(r.T_pnp, C.c_double, (L, 4, 4)), "T_opt": arr(r.T_opt, C.c_double, (L, 3, 4)), "chi2": arr(r.chi2, C.c_double, (L, NUM_KP)),
                 "pnp_status": arr(r.pnp_status, C.c_int, (L,)), "pnp_best_inliers": arr(r.pnp_best_inliers, C.c_int, (L,)),
                 "pnp_iterations": arr(r.pnp_iterations, C.c_int, (L,)), "n_kp": arr(r.n_kp, C.c_int, (L,)),
                 "lm_stats": arr(r.lm_stats, C.c_int, (F, 4)), "accepted": arr(r.accepted, C.c_uint8, (L,)).astype(bool),

@@ -1132,6 +1132,25 @@ class ObjectSLAM:
         self._cull_after_optimize(list(obj_index.keys()), curr_only, view_curr)
 
     @_on_stream
+    def pose_covariances(self, view_ids=None):
+        """6x6 marginal covariances of the current map: {"cams": {view_id: 6x6}, "objs": {obj_id: 6x6}} for every key of cam_poses (or those in view_ids) and
+        obj_poses, from the global graph of build_problem() at the stored poses and inlier flags (ba.pose_covariances: rows / columns [omega, upsilon] of the
+        left update; zeros for the gauge camera, NaNs for a vertex no counted measurement reaches).  Changes nothing in the map."""
+        nan = np.full((6, 6), np.nan)
+        cams = {v: nan.copy() for v in self.cam_poses if view_ids is None or v in view_ids}
+        objs = {o: nan.copy() for o in self.obj_poses}
+        built = self.build_problem(False)
+        if built is not None:
+            prob, (cam_index, obj_index, _, _, _) = built
+            cam_cov, obj_cov, _ = _ba.pose_covariances_batch([prob])[0]
+            for v, i in cam_index.items():
+                if v in cams:
+                    cams[v] = cam_cov[i].copy()
+            for o, j in obj_index.items():
+                objs[o] = obj_cov[j].copy()
+        return {"cams": cams, "objs": objs}
+
+    @_on_stream
     def optimize(self, curr_only=False):
         """object_slam.py:703-930 with the g2o graph replaced by one suo_optimize call."""
         built = self.build_problem(curr_only)
