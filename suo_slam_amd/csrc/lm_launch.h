@@ -6,6 +6,9 @@
 namespace suo {
 // ---- PnP (csrc/pnp.hip; pnp_get_iterations: csrc/pnp_api.hip, on the host) ----
 int pnp_get_iterations(double estimated_inliers);
+constexpr int PNP_MAX_PER_LANE = 16;                    // the refinement strides 64 lanes over an object's points, 16 per lane at the most
+constexpr int PNP_MAX_POINTS = 64 * PNP_MAX_PER_LANE;   // = 1024 points per object; the host entries refuse more (csrc/pnp_api.hip)
+// launch_pnp_replay takes launch_pnp_batch_counts' width rule: 16 waves per object for n_obj <= SUO_PNP_WIDE_UPTO (32), else 4
 int launch_pnp_replay(int n_obj, const int* offsets, const double* xs, const double* ys, double threshold, const int* iter_tab, const int* iter_tab_off,
                       int do_refine, const int* draws, int n_draws, double* T_out, int* status, int* best_out, int* iters_out, int* win_out, hipStream_t s);
 int launch_pnp_batch(int n_obj, const int* offsets, const double* xs, const double* ys, double threshold, uint64_t seed,

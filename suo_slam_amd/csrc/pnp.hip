@@ -402,7 +402,7 @@ DEV bool chol6(const double* A, const double* b, double* x) {
     return ok;
 }
 
-constexpr int PNP_MAX_PER_LANE = 16;   // n <= 1024 points per object
+// PNP_MAX_PER_LANE, PNP_MAX_POINTS (n <= 1024 points per object): csrc/lm_launch.h, shared with the host entries that refuse more
 
 // cost over the selected points; lanes stride over points; `sel` bit j = point lane + 64*j selected
 DEV double refine_cost(const double* xs, const double* ys, int n, unsigned sel, int lane, const double* q, const double* t) {
@@ -572,7 +572,7 @@ __global__ __launch_bounds__(64 * PNP_WAVES) void pnp_batch_kernel(const int* __
     unsigned best = 0;
     unsigned i_done = 0;
     int win_abs = -1;
-    const bool solvable = n >= 4 && n <= 64 * PNP_MAX_PER_LANE;
+    const bool solvable = n >= 4 && n <= PNP_MAX_POINTS;      // (the host entries refuse more; device-made counts keep this guard)
     const double thr2 = threshold * threshold;
     if (solvable) {
         unsigned iters = (unsigned)tab[0];
@@ -709,12 +709,17 @@ __global__ __launch_bounds__(64 * PNP_WAVES) void pnp_batch_kernel(const int* __
     }
 }
 
+// the width rule of every PnP launch, sampled or replayed: 16 waves per object while the launch is small enough that workgroups do not queue for CUs
+static bool pnp_wide(int n_obj) {
+    static const int wide_upto = (int)SUO_TUNE("SUO_PNP_WIDE_UPTO", 32);      // objects per launch that still take 16 waves each (0: never)
+    return n_obj <= wide_upto;
+}
+
 int launch_pnp_batch_counts(int n_obj, const int* offsets, const int* counts, const int* group_first, const double* xs, const double* ys, double threshold, uint64_t seed,
                             const int* iter_tab, const int* iter_tab_off, int do_refine, double* T_out, int* status, int* best_out,
                             int* iters_out, hipStream_t s, const uint64_t* seed_add) {
     if (n_obj <= 0) return SUO_OK;
-    static const int wide_upto = (int)SUO_TUNE("SUO_PNP_WIDE_UPTO", 32);      // objects per launch that still take 16 waves each (0: never)
-    if (n_obj <= wide_upto)
+    if (pnp_wide(n_obj))
         hipLaunchKernelGGL(pnp_batch_kernel<16>, dim3(n_obj), dim3(1024), 0, s, offsets, counts, group_first, xs, ys, threshold, seed, iter_tab, iter_tab_off,
                            do_refine, T_out, status, best_out, iters_out, (const int*)nullptr, 0, (int*)nullptr, seed_add);
     else
@@ -727,8 +732,12 @@ int launch_pnp_batch_counts(int n_obj, const int* offsets, const int* counts, co
 int launch_pnp_replay(int n_obj, const int* offsets, const double* xs, const double* ys, double threshold, const int* iter_tab, const int* iter_tab_off,
                       int do_refine, const int* draws, int n_draws, double* T_out, int* status, int* best_out, int* iters_out, int* win_out, hipStream_t s) {
     if (n_obj <= 0) return SUO_OK;
-    hipLaunchKernelGGL((pnp_batch_kernel<4, true>), dim3(n_obj), dim3(256), 0, s, offsets, (const int*)nullptr, (const int*)nullptr, xs, ys, threshold, (uint64_t)0, iter_tab,
-                       iter_tab_off, do_refine, T_out, status, best_out, iters_out, draws, n_draws, win_out);
+    if (pnp_wide(n_obj))
+        hipLaunchKernelGGL((pnp_batch_kernel<16, true>), dim3(n_obj), dim3(1024), 0, s, offsets, (const int*)nullptr, (const int*)nullptr, xs, ys, threshold, (uint64_t)0,
+                           iter_tab, iter_tab_off, do_refine, T_out, status, best_out, iters_out, draws, n_draws, win_out);
+    else
+        hipLaunchKernelGGL((pnp_batch_kernel<4, true>), dim3(n_obj), dim3(256), 0, s, offsets, (const int*)nullptr, (const int*)nullptr, xs, ys, threshold, (uint64_t)0,
+                           iter_tab, iter_tab_off, do_refine, T_out, status, best_out, iters_out, draws, n_draws, win_out);
     SUO_HIP_CHECK(hipGetLastError());
     return SUO_OK;
 }

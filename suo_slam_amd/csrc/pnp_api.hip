@@ -40,6 +40,24 @@ static int pnp_batch_impl(int n_obj, const int* n_pts, const double* xs, const d
         suo_set_error("suo_pnp_replay: %d draws per object, the RANSAC loop may run %d iterations", n_draws, pnp_get_iterations(0.0));
         return SUO_ERR_ARG;
     }
+    // limits and table indices are checked on the host before anything is staged: the whole call is refused, nothing is launched
+    for (int o = 0; o < n_obj; ++o) {
+        if (n_pts[o] < 0) { suo_set_error("suo_pnp_batch: negative point count"); return SUO_ERR_ARG; }
+        if (n_pts[o] > PNP_MAX_POINTS) {
+            suo_set_error("%s: object %d has %d points, the limit is %d per object", draws ? "suo_pnp_replay" : "suo_pnp_batch", o, n_pts[o], PNP_MAX_POINTS);
+            return SUO_ERR_ARG;
+        }
+    }
+    if (draws)
+        for (int o = 0; o < n_obj; ++o) {
+            const int* d = draws + 4 * (size_t)n_draws * o;
+            if (n_pts[o] < 4) continue;                               // not solvable: the kernel never reads this object's rows
+            for (size_t k = 0; k < 4 * (size_t)n_draws; ++k)        // (a repeated index within a row is a degenerate sample, not an error)
+                if (d[k] < 0 || d[k] >= n_pts[o]) {
+                    suo_set_error("suo_pnp_replay: object %d, row %d of the draw table holds index %d, the object has %d points", o, (int)(k / 4), d[k], n_pts[o]);
+                    return SUO_ERR_ARG;
+                }
+        }
     std::lock_guard<std::mutex> lock(g_arena.mu);
     std::vector<int> offsets(n_obj + 1, 0), tab_off(n_obj, 0);
     std::vector<int> tab;

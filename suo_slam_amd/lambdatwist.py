@@ -103,6 +103,27 @@ def pnp_replay(xs_in, ys_in, draws, threshold=0.001, refine=True):
     return T, {"best_inliers": int(best[0]), "iterations": int(its[0]), "winner": int(win[0]), "status": int(st[0])}
 
 
+def pnp_replay_batch(xs_list, ys_list, draws_list, threshold=0.001, refine=True):
+    """pnp_replay for several objects in ONE launch (16 waves per object up to 32 objects, 4 beyond: the width rule of pnp_batch).  draws_list[o]: int32
+    [n_draws, 4], the same n_draws >= 1000 for every object.  Returns (T[n_obj,4,4], info) with info = arrays best_inliers, iterations, winner, status."""
+    n_obj = len(xs_list)
+    assert n_obj > 0 and len(ys_list) == n_obj and len(draws_list) == n_obj
+    xs_l = [np.asarray(x, np.float64).reshape(-1, 3) for x in xs_list]
+    ys_l = [np.asarray(y, np.float64).reshape(-1, 2) for y in ys_list]
+    assert all(len(x) == len(y) for x, y in zip(xs_l, ys_l))
+    d = np.ascontiguousarray(np.stack([np.asarray(t, np.int32).reshape(-1, 4) for t in draws_list]))
+    lib = _lib.lib()
+    _lib.require_gpu()
+    n = np.array([len(x) for x in xs_l], np.int32)
+    xs = np.ascontiguousarray(np.concatenate(xs_l))
+    ys = np.ascontiguousarray(np.concatenate(ys_l))
+    T = np.zeros((n_obj, 4, 4))
+    st, best, its, win = (np.zeros(n_obj, np.int32) for _ in range(4))
+    _lib.check(lib.suo_pnp_replay(n_obj, n.ctypes.data, xs.ctypes.data, ys.ctypes.data, float(threshold), d.ctypes.data, int(d.shape[1]), int(refine),
+                                  T.ctypes.data, st.ctypes.data, best.ctypes.data, its.ctypes.data, win.ctypes.data), "suo_pnp_replay")
+    return T, {"best_inliers": best, "iterations": its, "winner": win, "status": st}
+
+
 def pnp(xs_in, ys_in, threshold=0.001):
     """Legacy signature of lambdatwist.pnp: returns a fresh 4x4 float64 array (identity = failure)."""
     xs = np.ascontiguousarray(xs_in, np.float64)
