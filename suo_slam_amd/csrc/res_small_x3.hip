@@ -8,13 +8,15 @@
 //
 // Workgroup = a 4 x 8 pixel tile of one crop, four waves (one per SIMD), 32 rows per MFMA:
 //   1. x tile + halo (60 rows, 64 staged): relu(bn(x)) split into three bf16 planes in LDS (A-operand order: row-major, 16-byte k granules);
-//   2. conv1 (256 -> 128): 64 rows x wave w's 32 channels, 16 k-steps x 12 MFMAs; relu(. + b1), zeros outside the map, split -> LDS planes;
+//   2. conv1 (256 -> 128): 64 rows x wave w's 32 channels, 16 k-steps x 12 MFMAs; relu(. + b1), zeros outside the map, split -> LDS planes
+//      (over the x tile, dead once every wave has left conv1: one barrier in front of the first store);
 //   3. conv2 (3x3): 32 rows, K = 9 taps x 128 channels = 72 k-steps x 6 MFMAs, the A rows of a tap picked per lane from the halo tile;
-//      relu(. + b2), split -> LDS planes (over the dead x tile);
-//   4. conv3 (128 -> 256): wave w's 64 channels, 8 k-steps x 12 MFMAs; patch -> + b3 + x [+ up] on 16-byte vectors.
+//      relu(. + b2), split -> LDS planes (in the x tile behind mid1);
+//   4. conv3 (128 -> 256): wave w's 64 channels, 8 k-steps x 12 MFMAs; patch (over the dead mid1) -> + b3 + x [+ up] on 16-byte vectors.
 // Weights: host-split planes in B-operand order ([k-step][32-channel tile][plane][lane][8 bf16], the layout of pack_gemm_weight_bf16x3),
 // each wave streams only its own channels' 16-byte fragments from L2 through a static register ring: 1.28 MB per workgroup.
-// LDS 153.6 KB, one workgroup per CU.  Accuracy: tests/test_gpu_res_block.py (fp64; never worse than 2x the fp32-pipe kernel of
+// LDS: everything lives inside the x tile -- 101 376 B with three planes (one workgroup per CU), 67 584 B with two (NP = 2: two workgroups per CU,
+// and one beside a Winograd workgroup of another stream).  Accuracy: tests/test_gpu_res_block.py (fp64; never worse than 2x the fp32-pipe kernel of
 // csrc/res_small.hip on the same inputs; per-element bound as tests/test_gpu_x3_accuracy.py).
 #include <string.h>
 
@@ -99,7 +101,7 @@ __device__ __forceinline__ bool r3_hyhx(int row, int& hy, int& hx) {
 // way into LDS, weight rows times 2^t_n, accumulators back to scale with a.osc1 / osc2 / osc3, a.range_flag raised beyond fp16's range) -- a third less weight
 // traffic per workgroup (0.85 MB instead of 1.28), which is what bounds this kernel
 template <bool POOL_IN, bool UP, int NP = 3>
-__global__ __launch_bounds__(256) void res_block_x3_kernel(const ResBlockArgs a) {
+__global__ __launch_bounds__(256, NP == 2 ? 2 : 1) void res_block_x3_kernel(const ResBlockArgs a) {
 #ifdef SUO_RS_PROF
     long long pt[10];
     R3_T(0);
@@ -108,11 +110,16 @@ __global__ __launch_bounds__(256) void res_block_x3_kernel(const ResBlockArgs a)
     constexpr int XPB = 528, XPL = 64 * XPB;                    // x tile: bytes per row (256 bf16 + 16), per plane (64 rows)
     constexpr int MPB = 272, MPL = 64 * MPB, M2PL = 32 * MPB;    // mid tiles: 128 bf16 + 16 per row; mid1 64 rows, mid2 32 rows per plane
     constexpr int PP = 260;                                     // output patch pitch (floats)
-    static_assert(NP * M2PL <= NP * XPL && T * PP * 4 <= NP * MPL, "mid2 re-uses the x tile, the output patch the mid1 tile");
+    // one LDS region, the x tile; mid1 over its head once conv1 has read it, mid2 behind mid1, the output patch over mid1 once conv2 has read it
+    constexpr int M1_AT = 0, M2_AT = NP * MPL, P3_AT = M1_AT;
+    static_assert(M2_AT + NP * M2PL <= NP * XPL, "mid1 and mid2 live inside the x tile");
+    static_assert(M1_AT + NP * MPL <= M2_AT, "conv2 reads mid1 while its epilogue writes mid2: disjoint");
+    static_assert(P3_AT + T * PP * 4 <= M2_AT, "conv3 reads mid2 while early waves write the output patch: disjoint");
+    static_assert(M2_AT % 16 == 0 && NP * XPL <= (NP == 2 ? 80 : 160) * 1024, "NP = 2: two workgroups per CU");
     __shared__ __attribute__((aligned(16))) unsigned char XA[NP * XPL];
-    __shared__ __attribute__((aligned(16))) unsigned char M1[NP * MPL];
-    unsigned char* M2 = XA;
-    float* P3 = reinterpret_cast<float*>(M1);
+    unsigned char* M1 = XA + M1_AT;
+    unsigned char* M2 = XA + M2_AT;
+    float* P3 = reinterpret_cast<float*>(XA + P3_AT);
     const int tid = threadIdx.x, lane = tid & 63;
     const int w = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int lr = lane & 31, lk = lane >> 5;
@@ -266,7 +273,8 @@ __global__ __launch_bounds__(256) void res_block_x3_kernel(const ResBlockArgs a)
     }
     R3_T(3);
 #pragma unroll
-    for (int g = 0; g < R2 - 2; ++g) load2(g, ring2[g]);        // conv2's first weights travel under the epilogue + barrier
+    for (int g = 0; g < R2 - 2; ++g) load2(g, ring2[g]);        // conv2's first weights travel under the epilogue + barriers
+    __syncthreads();                                            // mid1 goes over the x tile: every wave's last conv1 fragment is read
     {   // relu(acc + b1) -> M1 planes (zeros outside the map: Conv2d(padding=1) pads conv2's INPUT)
         const int ch = 32 * w + lr;
         // NP = 2: the accumulator carries 2^(t_n + s1); conv2's operand is 2^s2 relu(conv1 + b1) = relu(acc 2^-(t_n + s1) 2^s2 + 2^s2 b1): one fma
@@ -326,7 +334,7 @@ __global__ __launch_bounds__(256) void res_block_x3_kernel(const ResBlockArgs a)
     R3_T(5);
 #pragma unroll
     for (int g = 0; g < R3 - 1; ++g) load3(g, ring3[g]);
-    {   // relu(acc + b2) -> M2 planes (the x tile is dead: every wave is past conv1)
+    {   // relu(acc + b2) -> M2 planes (behind mid1, which slower waves still read)
         const int ch = 32 * w + lr;
         const float xs3 = NP == 2 ? s2_xscale(a.xs3) : 1.f;
         const float b2 = NP == 2 ? a.b2[ch] * xs3 : a.b2[ch];
