@@ -617,6 +617,23 @@ int suo_mesh_db_create(int n_models, const int* n_pts, const float* pts, void** 
 void suo_mesh_db_destroy(void* mesh_db);
 int suo_pose_errors(void* mesh_db, int n, const int* model_index, const float* T_pred, const float* T_gt, float* add, float* adds);
 
+/* ---- BOP-19 MSSD / MSPD pose errors --------------------------------------------------
+ * Replaces bop_toolkit_lib/pose_error.py:96-144 (mssd, mspd; misc.py:93-107 project_pts, misc.py:266-276 transform_pts_Rt) over the same mesh database.
+ * For every symmetry transformation s = [S_R|S_t] of the model:  R_s = R_gt S_R,  t_s = R_gt S_t + t_gt,
+ *   MSSD = min_s max_i |(R_est p_i + t_est) - (R_s p_i + t_s)|                 (mm)
+ *   MSPD = min_s max_i |pi(K, R_est, t_est, p_i) - pi(K, R_s, t_s, p_i)|       (px),  pi = (K X)_xy / (K X)_z, divided as given: a point behind the
+ *                                                                                camera keeps its finite value, as in the toolkit.
+ * All arithmetic is fp64 (the toolkit's; the recall compares these errors with thresholds) on the float32 points widened exactly.  max and min are exact and
+ * a (symmetry, point) value does not depend on the launch shape, so a pair in a batch has the bits it has alone.  One stated deviation: a pair that meets a
+ * non-finite projection or distance (z exactly 0, a NaN pose) reports +inf for that metric -- the toolkit's min() over NaNs depends on their order.
+ * suo_mesh_db_set_symmetries: symmetry transformations per model of an existing mesh database: n_sym[n_models] (each >= 1; the identity is one of them and
+ * is the caller's to list), sym [sum n_sym][12] row-major 3x4 [R|t], host doubles; replaces an earlier set.  Without this call every model has the identity alone.
+ * suo_pose_errors_bop: n (estimate, ground truth) pairs: model_index[n], T_est / T_gt [n][12] row-major 3x4 (doubles, mm), K [n][9] row-major (may be NULL
+ * when mspd is).  mssd[n] (mm), mspd[n] (px); either output may be NULL.  Host buffers, blocking.  n = 0 returns 0.
+ * SUO_ERR_ARG (nothing launched): a null database or required pointer, n < 0, a model index outside the database, n_sym[i] < 1. */
+int suo_mesh_db_set_symmetries(void* mesh_db, const int* n_sym, const double* sym);
+int suo_pose_errors_bop(void* mesh_db, int n, const int* model_index, const double* T_est, const double* T_gt, const double* K, double* mssd, double* mspd);
+
 /* ---- SLAM-mode hypothesis scoring ------------------------------------------
  * Replaces the per-pair numpy of ObjectSLAM.__estimate_camera_pose's hypothesis loop (lib/object_slam.py:1000-1066) and of
  * __maybe_reinit_objects' inlier counts (:619-690): count_k [ z_k > 0 and chi2_k <= chi2_max ] for n_pairs (pose, detection) pairs in one launch.

@@ -19,6 +19,7 @@
 
 #include "../../include/suo_hip.h"
 #include "suo_internal.h"
+#include "mesh_db.h"
 
 namespace suo {
 
@@ -26,18 +27,6 @@ constexpr int EV_BLOCK = 256;     // threads per block
 constexpr int EV_G = 4;           // gt points per thread (pair kernel)
 typedef float f32x2 __attribute__((ext_vector_type(2)));
 constexpr int EV_TILE = 1024;     // pred points staged in LDS per pass
-
-struct MeshDb {
-    int n_models = 0;
-    std::vector<int> off;         // [n_models + 1] point offsets
-    int max_pts = 0;
-    float* pts_dev = nullptr;     // [off.back()][3]
-    int* off_dev = nullptr;
-    // per-call scratch, grow-only
-    char* scratch_dev = nullptr; char* scratch_host = nullptr; size_t scratch_cap = 0;
-    hipStream_t stream = nullptr;
-    std::mutex mu;
-};
 
 struct EvalArgs {
     const float* pts; const int* off; const int* model;     // model[n]
@@ -146,7 +135,7 @@ __global__ __launch_bounds__(EV_BLOCK) void eval_finalize_kernel(EvalArgs a) {
     }
 }
 
-static int ensure_scratch(MeshDb* db, size_t bytes) {
+int ensure_scratch(MeshDb* db, size_t bytes) {
     if (bytes <= db->scratch_cap) return SUO_OK;
     size_t ncap = (std::max(bytes, db->scratch_cap * 2) + 4095) & ~(size_t)4095;
     if (db->scratch_dev) (void)hipFree(db->scratch_dev);
@@ -193,6 +182,8 @@ extern "C" void suo_mesh_db_destroy(void* h) {
     if (!db) return;
     if (db->pts_dev) (void)hipFree(db->pts_dev);
     if (db->off_dev) (void)hipFree(db->off_dev);
+    if (db->sym_dev) (void)hipFree(db->sym_dev);
+    if (db->sym_off_dev) (void)hipFree(db->sym_off_dev);
     if (db->scratch_dev) (void)hipFree(db->scratch_dev);
     if (db->scratch_host) (void)hipHostFree(db->scratch_host);
     if (db->stream) (void)hipStreamDestroy(db->stream);

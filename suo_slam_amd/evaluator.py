@@ -10,7 +10,8 @@ row N4) is handed off exactly as the reference does it: ``run`` returns the comm
 (``bop_eval_command``) and starts it when ``run_bop_eval=True`` and the toolkit is mounted; the CSV it consumes is pinned
 against the toolkit's own ``inout.load_bop_results`` (tests/golden/make_bop_results_golden.py).
 
-Everything numeric happens in ``ObjectSLAM`` (HIP network, PnP, bundle adjustment) and ``EvalMeter`` (HIP ADD-S).
+Everything numeric happens in ``ObjectSLAM`` (HIP network, PnP, bundle adjustment) and ``EvalMeter`` (HIP ADD-S).  ``bop19=True`` adds the
+renderer-free two thirds of the BOP-19 score (row N5): the poses of the CSV also go through ``bop_eval.Bop19Meter`` (HIP MSSD / MSPD, host matching).
 """
 from __future__ import annotations
 
@@ -19,7 +20,7 @@ from time import time
 
 import numpy as np
 
-from . import bop, detections
+from . import bop, bop_eval, detections
 from .eval_meter import EvalMeter
 from .geometry import invert_SE3
 from .object_slam import ObjectSLAM
@@ -61,13 +62,15 @@ def bop_eval_command(csv_path, outdir, targets_filename, repo_root="."):
 class Evaluator:
     def __init__(self, dataset, data_root, chkpt_path, nviews=1, no_network_cov=False, detection_type="saved", debug_gt_kp=False,
                  gt_cam_pose=False, no_prior_det=False, debug_saved_only=False, give_all_prior=False, out_dir=None, state_dict=None,
-                 do_add=None, seed=666, verbose=False, repo_root=".", run_bop_eval=False, frames_per_call=1):
+                 do_add=None, seed=666, verbose=False, repo_root=".", run_bop_eval=False, frames_per_call=1, bop19=False):
         """``dataset``: "ycbv" | "tless"; ``data_root``: the dataset directory of the BOP tree.  ``out_dir`` defaults to
         the checkpoint's directory like the reference.  ``do_add`` overrides the per-dataset default (the reference
         evaluates ADD only on YCB-V).  ``frames_per_call`` > 1 (single-view evaluation, nviews == 1, only): that many reference views go through
         ONE network call and ONE geometry launch (ObjectSLAM.process_views_single) -- the views of evaluate.py's loop are independent there
         (reset / process_view / collect_results per view, evaluate.py:338-395); results are the per-view loop's (geometry bit for bit on the same network
-        outputs; the shared network call agrees with per-view calls to the network's tolerance: ObjectSLAM.process_views_single)."""
+        outputs; the shared network call agrees with per-view calls to the network's tolerance: ObjectSLAM.process_views_single).
+        ``bop19``: also report the BOP-19 MSSD and MSPD average recalls of exactly the poses written to the CSV (``run()["bop19"]`` and two lines of
+        summary.txt); needs a dataset with a targets file (T-LESS) -- ValueError otherwise.  VSD stays the external hand-off."""
         cfg = _SETTINGS[dataset]
         self.frames_per_call = int(frames_per_call) if nviews == 1 else 1
         self.model_path = out_dir if out_dir is not None else os.path.dirname(chkpt_path or ".")
@@ -76,6 +79,12 @@ class Evaluator:
             detection_type = "gt"                                     # evaluate.py:378-379
         self.dataset = bop.BopDataset(data_root, cfg["split"], bop_dset=dataset, ignore_symmetry=True)
         self.mesh_db = bop.load_mesh_db(os.path.join(data_root, cfg["models"]))
+        self.bop_errors = None
+        if bop19:
+            if self.dataset.targets_filename is None:
+                raise ValueError(f"bop19=True needs a targets file and the {dataset!r} {cfg['split']!r} split has none "
+                                 "(the BOP-19 recall counts the targets of all_target_tless.json)")
+            self.bop_errors = bop_eval.BopErrors(self.mesh_db, bop_eval.load_models_info(os.path.join(data_root, cfg["models"])))
         self.debug_saved_only = debug_saved_only
         self.nviews, self.detection_type, self.debug_gt_kp, self.gt_cam_pose = nviews, detection_type, debug_gt_kp, gt_cam_pose
         self.verbose = verbose
@@ -161,6 +170,11 @@ class Evaluator:
         if self.saved_detections is not None and self.do_add:
             saved_meter = EvalMeter(self.mesh_db)
         csv_lines, num, num_cam_poses_found = [], 0, 0
+        bop19_meter = None
+        if self.bop_errors is not None and not self.debug_saved_only:
+            first_scene = ds.scene_ids()[0]
+            im_width = ds.read_img(first_scene, ds.view_ids(first_scene)[0]).shape[1]
+            bop19_meter = bop_eval.Bop19Meter.from_dataset_tree(self.bop_errors, ds.curr_root, ds.targets_filename, im_width)
         if not self.debug_saved_only:
             if self.do_add:
                 meter = EvalMeter(self.mesh_db)
@@ -246,6 +260,8 @@ class Evaluator:
                             meter.update([o], res["T_OtoC"][None, ...], ds.get_obj_pose(scene_id, view_id, o)[None, ...])
                         if ds.is_target(scene_id, view_id, o):
                             csv_lines.append(bop_csv_line(scene_id, view_id, o, res["score"], res["T_OtoC"]))
+                            if bop19_meter is not None:
+                                bop19_meter.add(scene_id, view_id, o, res["score"], res["T_OtoC"], ds.data[scene_id][view_id]["K"])
                     else:
                         self._log(f"NOTE: Could not obtain object pose for object {o}")
                         if meter is not None:                         # the reference updates unconditionally; without ADD there is no meter
@@ -262,6 +278,8 @@ class Evaluator:
             saved_meter.close()
         if not self.debug_saved_only:
             out["method"] = method
+            if bop19_meter is not None:
+                out["bop19"] = bop19_meter.result()
             out["summary_path"] = os.path.join(outdir, "summary.txt")
             with open(out["summary_path"], "w") as f:
                 if meter is not None:
@@ -270,6 +288,10 @@ class Evaluator:
                     for s in (f"NOTE: {100 * num_cam_poses_found / num:.1f}% of camera poses found!", self.object_slam.get_tracking_strtime(),
                               self.object_slam.get_global_opt_strtime(), f"Average keypoint stdev: {self.object_slam.avg_std_meter.average()}"):
                         f.write("\n" + s + "\n")
+                if bop19_meter is not None:
+                    for name in ("mssd", "mspd"):
+                        f.write(f"\nBOP-19 AR_{name.upper()}: {out['bop19'][name]['ar']:.4f} (recalls " +
+                                " ".join(f"{r:.4f}" for r in out["bop19"][name]["recalls"]) + f"; {out['bop19']['n_targets']} targets)\n")
             out["csv_path"] = os.path.join(outdir, method + ".csv")
             with open(out["csv_path"], "w") as f:
                 f.writelines(csv_lines)
