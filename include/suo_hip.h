@@ -23,7 +23,8 @@
  *     SUO_NET_SIDE_STREAMS=n the Hourglass up1 branches on n side streams (default 0)                          first use, per process
  *     SUO_SERIAL             (set) one stream, kernels back to back: per-kernel profiling                      per call
  *     SUO_LM_CAM2=0          camera tracking on lm_cam_kernel instead of lm_cam2_kernel                        first use, per process
- *     SUO_WINO_W8=0          small launches keep the four-wave Winograd kernels (see suo_conv3x3_wino_f16x2*)  per launch
+ *     SUO_WINO_W8=0          small launches keep the four-wave Winograd kernels (see suo_conv3x3_wino_f16x2*)  when a launch is issued: in a network,
+ *                            when the graph of a crop count is captured (suo_net_prepare / first call), not at its replays
  * The thresholds and A/B knobs behind the measurements of DESIGN.md / profiles/REJECTED.md (SUO_TUNE in csrc/tune.h: launch-size thresholds, tile choices, kernel
  * selections) are compiled to their defaults; only the variant builds of tools/build_variant.sh (-DSUO_TUNING) read them from the environment.  The host side above
  * the ABI has its own, in suo_slam_amd/: SUO_HIP_LIB (path of the library), SUO_BA_GRAPH / SUO_BA_HOST_SCHEDULE / SUO_FORCE_COLLECTIVES (ba_dist.py),

@@ -789,7 +789,8 @@ __global__ __launch_bounds__(W8 ? 512 : 256) __attribute__((amdgpu_waves_per_eu(
 }
 
 // Launches of at most one workgroup per CU (<= 256 tiles: a one-frame call, a SLAM pass) take the eight-wave form of the fp16 kernel (W8): there the
-// workgroup's latency IS the launch's duration.  SUO_WINO_W8=0 (supported switch, include/suo_hip.h; read per launch): the four-wave form everywhere (A/B);
+// workgroup's latency IS the launch's duration.  SUO_WINO_W8=0 (supported switch, include/suo_hip.h; read when a launch is issued -- a network's captured
+// graph keeps the form it was captured with, whatever the variable says at a replay): the four-wave form everywhere (A/B);
 // SUO_WINO_W8_TILES (tuning builds): largest such launch.
 bool conv3x3_wino_f16x2_w8(long tiles) {
     static const long upto = SUO_TUNE("SUO_WINO_W8_TILES", 256);

@@ -17,22 +17,21 @@ struct HostTensor {
     size_t numel = 0;
 };
 
-// Wx3: bf16x3 planes (N a multiple of 128, K segments multiples of 64; csrc/gemm_bf16x3.hip); W16 / osc16: the two fp16 planes and the per-column factors (csrc/f16x2.h)
+// one operator's weights in each matrix-pipe form: w[0] fp32 packing, w[1] three bf16 planes, w[2] two fp16 planes; osc: the fp16 form's per-column factors
+// (csrc/bf16x3.h, csrc/f16x2.h; a form the operator has no kernel for, or the network was not built for, stays null)
+struct PipeW { float* w[3] = {nullptr, nullptr, nullptr}; float* osc = nullptr; };
+// w[1]: N a multiple of 128, K segments multiples of 64 (csrc/gemm_bf16x3.hip)
 // site / xs16: the fp16 form's activation site of this convolution's input (Net::sites_ index, -1: none) and its factor 2^s in device memory
-struct GemmW { float* Wp = nullptr; float* bias = nullptr; int N = 0, n_valid = 0, K1 = 0, K2 = 0; float* Wx3 = nullptr; float* W16 = nullptr; float* osc16 = nullptr; int site = -1; const float* xs16 = nullptr; };
-// Wq: Winograd-packed (3x3, 128 -> 128 / 64 -> 64); Wq3: its bf16x3 planes (csrc/conv_wino_x3.hip); Wq16 / osc16: its fp16 planes and per-channel factors
-struct ConvW { float* Wp = nullptr; float* bias = nullptr; int N = 0, C = 0, KS = 0; float* Wq = nullptr; float* Wq3 = nullptr; float* Wq16 = nullptr; float* osc16 = nullptr; int site = -1; const float* xs16 = nullptr; };
+struct GemmW { PipeW w; float* bias = nullptr; int N = 0, n_valid = 0, K1 = 0, K2 = 0; int site = -1; const float* xs16 = nullptr; };
+// Wp: the direct kernels' packing; wino: Winograd-packed (3x3, 128 -> 128 / 64 -> 64; csrc/conv_wino.hip, csrc/conv_wino_x3.hip)
+struct ConvW { float* Wp = nullptr; float* bias = nullptr; int N = 0, C = 0, KS = 0; PipeW wino; int site = -1; const float* xs16 = nullptr; };
 struct ResidualW {
     float* pro_scale = nullptr; float* pro_shift = nullptr;
     GemmW c1; ConvW c2; GemmW c3;
     int cin = 0, cout = 0; bool has_skip_conv = false;
-    float* c3x = nullptr;                                // conv3 as bf16x3 planes for the fused Winograd tail on the bf16 pipe (256 <- 128 only)
-    float* c3x16 = nullptr; float* c3osc16 = nullptr;    // ... as two fp16 planes + per-column factors (csrc/f16x2.h)
-    // 256 -> 256 blocks: the whole block in one launch on small maps (csrc/res_small.hip fp32 pipe; csrc/res_small_x3.hip bf16 pipe)
-    float* rb_w[3] = {nullptr, nullptr, nullptr};        // pack_res16_gemm(W1 bn1-folded) | pack_res16_conv3x3(W2, bn2 scale) | pack_res16_gemm(W3)
-    float* rbx_w[3] = {nullptr, nullptr, nullptr};       // the same as bf16x3 planes (uint16)
-    float* rbh_w[3] = {nullptr, nullptr, nullptr};       // ... as two fp16 planes (csrc/f16x2.h)
-    float* rbh_osc[3] = {nullptr, nullptr, nullptr};     // and their per-channel factors [128], [128], [256]
+    PipeW tail;          // conv3 for the fused tail of the 3x3: w[0] is c3.w.w[0] (not a copy); w[1] / w[2] in the Winograd tail's layout (256 <- 128 only)
+    // 256 -> 256 blocks: the whole block in one launch on small maps (csrc/res_small.hip fp32 pipe; csrc/res_small_x3.hip bf16 / fp16 pipe)
+    PipeW block[3];      // pack_res16_gemm(W1 bn1-folded) | pack_res16_conv3x3(W2, bn2 scale) | pack_res16_gemm(W3), and their planes; factors [128], [128], [256]
 };
 struct HourglassW {
     int n = 0;
@@ -82,8 +81,13 @@ private:
     int commit_call(hipStream_t s);
     void leave_fp16_form();
     bool own_call_invalid();
+    // ---- weights (csrc/net_weights.hip)
+    void build_weights(int n, const char* const* names, const float* const* data, const int64_t* const* shapes, const int* ndims);
     float* upload(const std::vector<float>& v);
+    template <class Pack3, class Pack2>
+    void fill_pipes(PipeW& pw, const float* src, size_t numel, int ncol, Pack3 pack3, Pack2 pack2, bool with_bf16 = true);
     void make_gemm(const std::string& conv, const std::string& bn_after, const std::string& conv2, GemmW& g);
+    void pack_gemm(const std::vector<float>& full, const std::vector<float>& bias, int N, int K1, int K2, GemmW& g);
     void make_conv(const std::string& conv, const std::string& bn_after, int CK, ConvW& c, int c_used = 0);
     void make_residual(const std::string& p, ResidualW& r);
     void make_hourglass(const std::string& p, int n, HourglassW& h);
@@ -143,8 +147,7 @@ private:
     std::map<std::string, HostTensor> tensors_;
     std::vector<float*> owned_;
     ConvW stem_, stem_img_;      // all 44 input channels | the 3 image channels only (no priors: SLAM_C = 16)
-    float* stem_h2_w_ = nullptr; float* stem_h2_osc_ = nullptr;       // ... as two fp16 planes + per-channel factors (csrc/f16x2.h)
-    float* stem_x3_w_ = nullptr; float* stem_x3_bias_ = nullptr;      // the image-only stem as bf16x3 planes for the fused RoIAlign + stem launch (csrc/stem_x3.hip)
+    PipeW stem_x3_; float* stem_x3_bias_ = nullptr;                   // the image-only stem for the fused RoIAlign + stem launch (csrc/stem_x3.hip; no fp32 form: w[0] null)
     float* stem_slab_ = nullptr;                                      // [max_crops,128,128,64] persistent slab of the stem's output
     float* stem_mid1_slab_ = nullptr;                                 // ... and of r1's conv1 when the fused stem launch computes it (csrc/stem_x3.hip: NEXT)
     bool stem_computes_r1_conv1() const;

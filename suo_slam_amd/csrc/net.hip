@@ -1,8 +1,5 @@
-// Host-side runtime of the keypoint CNN: weight folding/packing, workspace, launch schedule,
-// multi-stream hourglass branches and hipGraph capture of the backbone.
-//
-// Mirrors PkpNet.forward (/root/reference/lib/models/pkpnet.py:80-119) over a state_dict with the
-// reference's key names (backbone.* / classifier.2.*), see suo_slam_amd/weights.py.
+// Host-side runtime of the keypoint CNN: workspace, launch schedule, multi-stream hourglass branches, hipGraph capture of the backbone and the fp16 form's
+// range guard.  Mirrors PkpNet.forward (lib/models/pkpnet.py:80-119) over the weights csrc/net_weights.hip builds.
 #include "net.h"
 #include "f16x2.h"
 
@@ -16,482 +13,10 @@
 
 namespace suo {
 
-static constexpr float BN_EPS = 1e-5f;
-
-// ------------------------------------------------------------------------------------------------
-// weight lookup helpers
-const HostTensor& Net::T(const std::string& name) const {
-    auto it = tensors_.find(name);
-    if (it == tensors_.end()) throw std::runtime_error("missing tensor: " + name);
-    return it->second;
-}
-
-// A checkpoint tensor must have exactly the shape the architecture (lib/models/hg.py:61-93, layers/Residual.py:7-18)
-// gives it: anything else would be read out of bounds or silently zero-padded.
-static void expect_shape(const Net& net, const std::string& name, std::initializer_list<int64_t> dims) {
-    const HostTensor& t = net.T(name);
-    if (t.shape.size() == dims.size() && std::equal(dims.begin(), dims.end(), t.shape.begin())) return;
-    std::string got, want;
-    for (int64_t d : t.shape) got += (got.empty() ? "" : ",") + std::to_string(d);
-    for (int64_t d : dims) want += (want.empty() ? "" : ",") + std::to_string(d);
-    throw std::runtime_error("tensor " + name + " has shape [" + got + "], expected [" + want + "]");
-}
-static void expect_bn(const Net& net, const std::string& p, int64_t c) {
-    for (const char* f : {".weight", ".bias", ".running_mean", ".running_var"}) expect_shape(net, p + f, {c});
-}
-static void expect_conv(const Net& net, const std::string& p, int64_t cout, int64_t cin, int64_t k) {
-    expect_shape(net, p + ".weight", {cout, cin, k, k});
-    expect_shape(net, p + ".bias", {cout});
-}
-
-// BN(eval) as y = x*scale + shift
-static void bn_affine(const Net& net, const std::string& p, std::vector<float>& scale, std::vector<float>& shift) {
-    const HostTensor& g = net.T(p + ".weight");
-    const HostTensor& b = net.T(p + ".bias");
-    const HostTensor& m = net.T(p + ".running_mean");
-    const HostTensor& v = net.T(p + ".running_var");
-    const size_t c = g.numel;
-    scale.resize(c);
-    shift.resize(c);
-    for (size_t i = 0; i < c; ++i) {
-        const float s = g.data[i] / sqrtf(v.data[i] + BN_EPS);
-        scale[i] = s;
-        shift[i] = b.data[i] - m.data[i] * s;
-    }
-}
-
-// Pack W[n][k] (n < N, k < K; zero beyond) into the MFMA B-operand layouts.  `out` holds 2*Np*Kp floats:
-//   [0, Np*Kp)        32x32x2 form  [Kp/8][Np/32][64][4]:  W[nb*32+(lane&31)][kb*8 +(lane>>5)*4+t]
-//   [Np*Kp, 2*Np*Kp)  16x16x4 form  [Kp/16][Np/16][64][4]: W[nb*16+(lane&15)][kg*16+(lane>>4)*4+t]   (small-map kernels)
-void pack_gemm_weight(const float* W, int N, int K, int ldw, int Np, int Kp, float* out) {
-    {
-        float* o16 = out + (size_t)Np * Kp;
-        const int NB16 = Np / 16;
-        for (int kg = 0; kg < Kp / 16; ++kg)
-            for (int nb = 0; nb < NB16; ++nb)
-                for (int lane = 0; lane < 64; ++lane)
-                    for (int t = 0; t < 4; ++t) {
-                        const int n = nb * 16 + (lane & 15), k = kg * 16 + (lane >> 4) * 4 + t;
-                        o16[(((size_t)kg * NB16 + nb) * 64 + lane) * 4 + t] = (n < N && k < K) ? W[(size_t)n * ldw + k] : 0.f;
-                    }
-    }
-    const int NB = Np / 32;
-    for (int kb = 0; kb < Kp / 8; ++kb)
-        for (int nb = 0; nb < NB; ++nb)
-            for (int lane = 0; lane < 64; ++lane)
-                for (int t = 0; t < 4; ++t) {
-                    const int n = nb * 32 + (lane & 31), k = kb * 8 + (lane >> 5) * 4 + t;
-                    out[(((size_t)kb * NB + nb) * 64 + lane) * 4 + t] = (n < N && k < K) ? W[(size_t)n * ldw + k] : 0.f;
-                }
-}
-
-// Conv weight W[n][c][ky][kx] -> GEMM weight with K' = [chunk][ky][kx][kk] (kk < CK), then packed.
-void pack_conv_weight(const float* W, int N, int C, int KS, int Np, int Cp, int CK, const float* out_scale, float* out) {
-    const int nch = Cp / CK, Kraw = nch * KS * KS * CK, Kp = (Kraw + 15) / 16 * 16;
-    std::vector<float> g((size_t)Np * Kp, 0.f);
-    if (CK == 4) {
-        // image-only stem (csrc/conv.hip, PAIR mode): dense K axis kk = tap * 3 + channel; MFMA k-step t of group kb multiplies
-        // kk = 8 kb + 2 t (lanes 0-31) and 8 kb + 2 t + 1 (lanes 32-63), which pack_gemm_weight reads from column kb*8 + half*4 + t
-        for (int n = 0; n < N; ++n)
-            for (int kk = 0; kk < KS * KS * 3; ++kk) {
-                const int tap = kk / 3, c = kk % 3;
-                if (c >= C) continue;
-                const int kb = kk / 8, r = kk % 8, t = r / 2, half = r % 2;
-                const float s = out_scale ? out_scale[n] : 1.f;
-                g[(size_t)n * Kp + kb * 8 + half * 4 + t] = W[(((size_t)n * C + c) * KS + tap / KS) * KS + tap % KS] * s;
-            }
-        pack_gemm_weight(g.data(), Np, Kp, Kp, Np, Kp, out);
-        return;
-    }
-    for (int n = 0; n < N; ++n)
-        for (int ch = 0; ch < nch; ++ch)
-            for (int ky = 0; ky < KS; ++ky)
-                for (int kx = 0; kx < KS; ++kx)
-                    for (int kk = 0; kk < CK; ++kk) {
-                        const int c = ch * CK + kk;
-                        if (c >= C) continue;
-                        const float s = out_scale ? out_scale[n] : 1.f;
-                        g[(size_t)n * Kp + ((ch * KS + ky) * KS + kx) * CK + kk] = W[(((size_t)n * C + c) * KS + ky) * KS + kx] * s;
-                    }
-    pack_gemm_weight(g.data(), Np, Kp, Kp, Np, Kp, out);
-}
-
-float* Net::upload(const std::vector<float>& v) {
-    float* d = nullptr;
-    if (hipMalloc(&d, v.size() * sizeof(float)) != hipSuccess) throw std::runtime_error("hipMalloc(weights) failed");
-    if (hipMemcpy(d, v.data(), v.size() * sizeof(float), hipMemcpyHostToDevice) != hipSuccess)
-        throw std::runtime_error("hipMemcpy(weights) failed");
-    owned_.push_back(d);
-    return d;
-}
-
-#ifndef SUO_WINO_BF16X3_DEFAULT
-#define SUO_WINO_BF16X3_DEFAULT 1
-#endif
-static int round_up(int v, int m) { return (v + m - 1) / m * m; }
-
-// SUO_WINO_BF16X3=0: the Residual blocks' 3x3 convolution + fused tail on the fp32 matrix pipe (csrc/conv_wino.hip) instead of the bf16 pipe
-// with 3-way split operands (csrc/conv_wino_x3.hip: same accuracy, ~1.2x faster)
-// (read when a network is built, not cached: one process can hold networks of both kinds)
-static bool wino_bf16x3() {
-    return env_switch("SUO_WINO_BF16X3", SUO_WINO_BF16X3_DEFAULT) != 0;
-}
-// SUO_F16X2=0: stay on the three-term bf16 form; default: the large launches run the two-term fp16 form (csrc/f16x2.h: half the MFMAs per product, range-guarded --
-// a call that leaves fp16's range is reported by Net::range_exceeded and the network falls back to the bf16 form, whose planes are packed as well)
-static bool pipe_f16x2() {
-    return wino_bf16x3() && env_switch("SUO_F16X2", 1) != 0;
-}
-
-// 1x1 conv W[N][K] with optional per-output scale (BN folded) -> device packed weight + bias
-void Net::make_gemm(const std::string& conv, const std::string& bn_after, const std::string& conv2, GemmW& g) {
-    const HostTensor& w = T(conv + ".weight");
-    const HostTensor& b = T(conv + ".bias");
-    const int N = (int)w.shape[0], K1 = (int)w.shape[1];
-    const int Np = round_up(N, 64), K1p = round_up(K1, 32);
-    int K2 = 0, K2p = 0;
-    if (!conv2.empty()) { K2 = (int)T(conv2 + ".weight").shape[1]; K2p = round_up(K2, 32); }
-    std::vector<float> scale, shift;
-    if (!bn_after.empty()) bn_affine(*this, bn_after, scale, shift);
-    const int Kp = K1p + K2p;
-    std::vector<float> full((size_t)Np * Kp, 0.f), bias(Np, 0.f);
-    for (int n = 0; n < N; ++n) {
-        const float s = scale.empty() ? 1.f : scale[n];
-        for (int k = 0; k < K1; ++k) full[(size_t)n * Kp + k] = w.data[(size_t)n * K1 + k] * s;
-        bias[n] = scale.empty() ? b.data[n] : b.data[n] * s + shift[n];
-    }
-    if (K2) {
-        const HostTensor& w2 = T(conv2 + ".weight");
-        const HostTensor& b2 = T(conv2 + ".bias");
-        for (int n = 0; n < N; ++n) {
-            for (int k = 0; k < K2; ++k) full[(size_t)n * Kp + K1p + k] = w2.data[(size_t)n * K2 + k];
-            bias[n] += b2.data[n];
-        }
-    }
-    std::vector<float> packed(2 * (size_t)Np * Kp);
-    pack_gemm_weight(full.data(), Np, Kp, Kp, Np, Kp, packed.data());
-    g.Wp = upload(packed);
-    g.bias = upload(bias);
-    g.N = Np; g.n_valid = N; g.K1 = K1p; g.K2 = K2p;
-    // (N = 64 -- conv1 of r1 / r4 -- stays on the persistent fp32-pipe kernel: these launches are HBM-streaming, 430 / 180 us there against 563 / 194
-    //  in the bf16x3 kernel's 64-column tiles at 256 crops)
-    if (N % 128 == 0 && Np == N && K1 == K1p && K2 == K2p && K1 % 64 == 0 && K2 % 64 == 0 && K1 <= 512 && wino_bf16x3()) {      // the same operator on the bf16 pipe at fp32 accuracy
-        std::vector<float> x3((size_t)3 * N * Kp / 2);                         // uint16 planes
-        pack_gemm_weight_bf16x3(full.data(), N, Kp, reinterpret_cast<uint16_t*>(x3.data()));
-        g.Wx3 = upload(x3);
-        if (pipe_f16x2()) {
-            std::vector<float> h2((size_t)N * Kp), osc(N);                    // uint16 planes: 2 * N * Kp
-            pack_gemm_weight_f16x2(full.data(), N, Kp, reinterpret_cast<uint16_t*>(h2.data()), osc.data());
-            g.W16 = upload(h2);
-            g.osc16 = upload(osc);
-        }
-    } else if (Np == 64 && N == 64 && K1 == 64 && K1p == K1 && K2 == 0 && pipe_f16x2()) {
-        // r1's conv1 (64 -> 64): fp16 planes for the stem launch that computes it on the tile (csrc/stem_x3.hip: NEXT)
-        std::vector<float> h2((size_t)Np * Kp), osc(Np);
-        pack_gemm_weight_f16x2(full.data(), Np, Kp, reinterpret_cast<uint16_t*>(h2.data()), osc.data());
-        g.W16 = upload(h2);
-        g.osc16 = upload(osc);
-    } else if (Np == 64 && K1 == 256 && K1p == K1 && K2 == 0 && pipe_f16x2()) {
-        // the output head (tmpOut: 256 -> 41, padded to 64 rows of zeros): fp16 planes for the lin + head launch (csrc/gemm_bf16x3.hip: gemm_chain_head_kernel)
-        std::vector<float> h2((size_t)Np * Kp), osc(Np);
-        pack_gemm_weight_f16x2(full.data(), Np, Kp, reinterpret_cast<uint16_t*>(h2.data()), osc.data());
-        g.W16 = upload(h2);
-        g.osc16 = upload(osc);
-    }
-}
-
-// c_used > 0: keep only the first c_used input channels of the filter (the others multiply structural zeros)
-void Net::make_conv(const std::string& conv, const std::string& bn_after, int CK, ConvW& c, int c_used) {
-    const HostTensor& w = T(conv + ".weight");
-    const HostTensor& b = T(conv + ".bias");
-    const int N = (int)w.shape[0], Cw = (int)w.shape[1], KS = (int)w.shape[2];
-    const int C = c_used > 0 ? c_used : Cw;
-    const int Np = round_up(N, 64), Cp = round_up(C, CK);
-    std::vector<float> scale, shift;
-    if (!bn_after.empty()) bn_affine(*this, bn_after, scale, shift);
-    std::vector<float> packed(2 * (size_t)Np * ((Cp * KS * KS + 15) / 16 * 16)), bias(Np, 0.f);
-    std::vector<float> sliced;
-    const float* wdata = w.data;
-    if (C != Cw) {
-        sliced.resize((size_t)N * C * KS * KS);
-        for (int n = 0; n < N; ++n)
-            memcpy(&sliced[(size_t)n * C * KS * KS], w.data + (size_t)n * Cw * KS * KS, (size_t)C * KS * KS * sizeof(float));
-        wdata = sliced.data();
-    }
-    pack_conv_weight(wdata, N, C, KS, Np, Cp, CK, scale.empty() ? nullptr : scale.data(), packed.data());
-    for (int n = 0; n < N; ++n) bias[n] = scale.empty() ? b.data[n] : b.data[n] * scale[n] + shift[n];
-    c.Wp = upload(packed);
-    c.bias = upload(bias);
-    c.N = Np; c.C = Cp; c.KS = KS;
-    if (KS == 3 && N == C && (N == 128 || N == 64) && c_used <= 0) {       // the Residual blocks' 128 -> 128 / 64 -> 64 convolutions: also in Winograd form
-        std::vector<float> wq((size_t)16 * N * C);
-        pack_wino_weight(w.data, N, C, N, C, scale.empty() ? nullptr : scale.data(), wq.data());
-        c.Wq = upload(wq);
-        if (wino_bf16x3()) {                                  // the same on the bf16 pipe at fp32 accuracy (csrc/conv_wino_x3.hip; 128 -> 128 and 64 -> 64)
-            std::vector<float> wq3((size_t)3 * 16 * N * C / 2);                  // uint16 planes
-            pack_wino_weight_bf16x3(w.data, N, C, N, C, scale.empty() ? nullptr : scale.data(), reinterpret_cast<uint16_t*>(wq3.data()));
-            c.Wq3 = upload(wq3);
-            if (pipe_f16x2()) {
-                std::vector<float> wq16((size_t)16 * N * C), osc(N);             // uint16 planes: 2 * 16 * N * C
-                pack_wino_weight_f16x2(w.data, N, C, N, C, scale.empty() ? nullptr : scale.data(), reinterpret_cast<uint16_t*>(wq16.data()), osc.data());
-                c.Wq16 = upload(wq16);
-                c.osc16 = upload(osc);
-            }
-        }
-    }
-}
-
-void Net::make_residual(const std::string& p, ResidualW& r) {
-    {   // Residual(cin, cout): bn[cin] conv1[cout/2,cin,1] bn1 conv2[cout/2,cout/2,3] bn2 conv3[cout,cout/2,1] (+conv4[cout,cin,1] iff cin != cout)
-        const int64_t cin = (int64_t)T(p + ".bn.weight").numel, cout = T(p + ".conv3.weight").shape.empty() ? 0 : T(p + ".conv3.weight").shape[0];
-        const int64_t h = cout / 2;
-        expect_bn(*this, p + ".bn", cin);
-        expect_conv(*this, p + ".conv1", h, cin, 1);
-        expect_bn(*this, p + ".bn1", h);
-        expect_conv(*this, p + ".conv2", h, h, 3);
-        expect_bn(*this, p + ".bn2", h);
-        expect_conv(*this, p + ".conv3", cout, h, 1);
-        if (tensors_.count(p + ".conv4.weight")) expect_conv(*this, p + ".conv4", cout, cin, 1);
-        else if (cin != cout) throw std::runtime_error("residual " + p + ": " + std::to_string(cin) + " -> " + std::to_string(cout) + " channels needs conv4");
-    }
-    std::vector<float> sc, sh;
-    bn_affine(*this, p + ".bn", sc, sh);
-    r.cin = (int)sc.size();
-    r.pro_scale = upload(sc);
-    r.pro_shift = upload(sh);
-    make_gemm(p + ".conv1", p + ".bn1", "", r.c1);
-    make_conv(p + ".conv2", p + ".bn2", 32, r.c2);
-    r.has_skip_conv = tensors_.count(p + ".conv4.weight") > 0;
-    // conv3 (+ conv4 on the raw input as a second K segment: out = W3*mid + W4*x + b3 + b4)
-    make_gemm(p + ".conv3", "", r.has_skip_conv ? p + ".conv4" : "", r.c3);
-    r.cout = r.c3.n_valid;
-    if (r.cin == 256 && r.cout == 256 && !r.has_skip_conv) {
-        // the block in one launch (small maps): bn1 folded into W1's rows and bn2 into W2's exactly as make_gemm / make_conv fold them
-        // (float products w * s), so the fp32 form is bit-identical to the per-layer launches
-        const HostTensor& w1 = T(p + ".conv1.weight");
-        const HostTensor& w2 = T(p + ".conv2.weight");
-        const HostTensor& w3 = T(p + ".conv3.weight");
-        std::vector<float> s1, t1, s2, t2;
-        bn_affine(*this, p + ".bn1", s1, t1);
-        bn_affine(*this, p + ".bn2", s2, t2);
-        std::vector<float> w1f((size_t)128 * 256);
-        for (int n = 0; n < 128; ++n)
-            for (int k = 0; k < 256; ++k) w1f[(size_t)n * 256 + k] = w1.data[(size_t)n * 256 + k] * s1[n];
-        std::vector<float> p1((size_t)128 * 256), p2((size_t)128 * 128 * 9), p3((size_t)256 * 128);
-        pack_res16_gemm(w1f.data(), 128, 256, p1.data());
-        pack_res16_conv3x3(w2.data, 128, 128, s2.data(), p2.data());
-        pack_res16_gemm(w3.data, 256, 128, p3.data());
-        r.rb_w[0] = upload(p1); r.rb_w[1] = upload(p2); r.rb_w[2] = upload(p3);
-        if (wino_bf16x3()) {
-            std::vector<float> x1((size_t)3 * 128 * 256 / 2), x2((size_t)3 * 128 * 128 * 9 / 2), x3((size_t)3 * 256 * 128 / 2);      // uint16 planes
-            pack_gemm_weight_bf16x3(w1f.data(), 128, 256, reinterpret_cast<uint16_t*>(x1.data()));
-            pack_res_conv3x3_bf16x3(w2.data, s2.data(), reinterpret_cast<uint16_t*>(x2.data()));
-            pack_gemm_weight_bf16x3(w3.data, 256, 128, reinterpret_cast<uint16_t*>(x3.data()));
-            r.rbx_w[0] = upload(x1); r.rbx_w[1] = upload(x2); r.rbx_w[2] = upload(x3);
-            if (pipe_f16x2()) {
-                std::vector<float> h1((size_t)128 * 256), h2((size_t)128 * 128 * 9), h3((size_t)256 * 128), o1(128), o2(128), o3(256);      // uint16 planes: 2 per entry
-                pack_gemm_weight_f16x2(w1f.data(), 128, 256, reinterpret_cast<uint16_t*>(h1.data()), o1.data());
-                pack_res_conv3x3_f16x2(w2.data, s2.data(), reinterpret_cast<uint16_t*>(h2.data()), o2.data());
-                pack_gemm_weight_f16x2(w3.data, 256, 128, reinterpret_cast<uint16_t*>(h3.data()), o3.data());
-                r.rbh_w[0] = upload(h1); r.rbh_w[1] = upload(h2); r.rbh_w[2] = upload(h3);
-                r.rbh_osc[0] = upload(o1); r.rbh_osc[1] = upload(o2); r.rbh_osc[2] = upload(o3);
-            }
-        }
-    }
-    if (r.c2.Wq3 && !r.has_skip_conv) {
-        const HostTensor& w3 = T(p + ".conv3.weight");
-        if (w3.shape[0] == 256 && w3.shape[1] == 128) {
-            std::vector<float> x3((size_t)3 * 256 * 128 / 2);
-            pack_tail_weight_bf16x3(w3.data, 256, 128, reinterpret_cast<uint16_t*>(x3.data()));
-            r.c3x = upload(x3);
-            if (r.c2.Wq16) {
-                std::vector<float> h2((size_t)256 * 128), osc(256);
-                pack_tail_weight_f16x2(w3.data, 256, 128, reinterpret_cast<uint16_t*>(h2.data()), osc.data());
-                r.c3x16 = upload(h2);
-                r.c3osc16 = upload(osc);
-            }
-        }
-    }
-    register_residual_sites(p, r);
-}
-
-// ------------------------------------------------------------------------------------------------
-// fp16 activation sites (csrc/f16x2.h): one per convolution with fp16 planes, whichever kernel computes it.  Its factor 2^s lives at site_xs_[i], which every
-// fp16 launch splitting that operand reads; the per-channel factors 2^-(t_n + s) of the convolution's epilogues are kept at s = S2_XSHIFT on the host as well,
-// so a new s rewrites them in place (no pointer changes: captured graphs stay valid).
-int Net::add_site(const std::string& name, int ksize) {
-    if ((int)sites_.size() >= kMaxSites) throw std::runtime_error("too many fp16 activation sites");
-    Site st;
-    st.name = name; st.ksize = ksize; st.shift = S2_XSHIFT;
-    sites_.push_back(st);
-    return (int)sites_.size() - 1;
-}
-void Net::site_osc(int site, float* dev, int n) {
-    if (!dev) return;
-    std::vector<float> h(n);
-    if (hipMemcpy(h.data(), dev, (size_t)n * sizeof(float), hipMemcpyDeviceToHost) != hipSuccess) throw std::runtime_error("hipMemcpy(factors) failed");
-    sites_[site].osc.emplace_back(dev, std::move(h));
-}
-void Net::register_gemm_site(const std::string& p, GemmW& g) {
-    if (!g.W16) return;
-    g.site = add_site(p, 1);
-    g.xs16 = site_xs_ + g.site;
-    site_osc(g.site, g.osc16, g.N);
-}
-void Net::register_residual_sites(const std::string& p, ResidualW& r) {
-    if (r.c1.W16 || r.rbh_w[0]) {                           // relu(bn(x)): the GEMM's prologue, the one-launch block's staging, the stem's / a fused tail's NEXT
-        r.c1.site = add_site(p + ".conv1", 1);
-        r.c1.xs16 = site_xs_ + r.c1.site;
-        site_osc(r.c1.site, r.c1.osc16, r.c1.N);
-        site_osc(r.c1.site, r.rbh_osc[0], 128);
-    }
-    if (r.c2.Wq16 || r.rbh_w[1]) {                          // conv1's output: the Winograd staging, the one-launch block's conv1 epilogue
-        r.c2.site = add_site(p + ".conv2", 3);
-        r.c2.xs16 = site_xs_ + r.c2.site;
-        site_osc(r.c2.site, r.c2.osc16, r.c2.N);
-        site_osc(r.c2.site, r.rbh_osc[1], 128);
-    }
-    if (r.c3.W16 || r.c3x16 || r.rbh_w[2]) {                // conv2's output (+ the block input of a skip conv4): the GEMM, the fused tail, the one-launch block
-        r.c3.site = add_site(p + ".conv3", 1);
-        r.c3.xs16 = site_xs_ + r.c3.site;
-        site_osc(r.c3.site, r.c3.osc16, r.c3.N);
-        site_osc(r.c3.site, r.c3osc16, 256);
-        site_osc(r.c3.site, r.rbh_osc[2], 256);
-    }
-}
-
-void Net::make_hourglass(const std::string& p, int n, HourglassW& h) {
-    h.n = n;
-    auto check256 = [&](const ResidualW& r, const std::string& name) {
-        if (r.cin != 256 || r.cout != 256) throw std::runtime_error("residual " + name + " must be 256 -> 256 channels");
-    };
-    for (int j = 0; j < 2; ++j) {
-        make_residual(p + ".up1_." + std::to_string(j), h.up1[j]);
-        make_residual(p + ".low1_." + std::to_string(j), h.low1[j]);
-        make_residual(p + ".low3_." + std::to_string(j), h.low3[j]);
-        check256(h.up1[j], p + ".up1_"); check256(h.low1[j], p + ".low1_"); check256(h.low3[j], p + ".low3_");
-    }
-    if (n > 1) {
-        h.inner.reset(new HourglassW());
-        make_hourglass(p + ".low2", n - 1, *h.inner);
-    } else {
-        for (int j = 0; j < 2; ++j) make_residual(p + ".low2_." + std::to_string(j), h.low2[j]);
-    }
-}
-
 // ------------------------------------------------------------------------------------------------
 Net::Net(int n, const char* const* names, const float* const* data, const int64_t* const* shapes, const int* ndims, int max_crops)
     : max_crops_(max_crops) {
-    for (int i = 0; i < n; ++i) {
-        HostTensor t;
-        t.data = data[i];
-        t.numel = 1;
-        for (int d = 0; d < ndims[i]; ++d) { t.shape.push_back(shapes[i][d]); t.numel *= (size_t)shapes[i][d]; }
-        tensors_[names[i]] = t;
-    }
-    const std::string b = "backbone";
-    auto expect_io = [&](const std::string& p, int cin, int cout) {
-        expect_shape(*this, p + ".bn.weight", {cin});
-        expect_shape(*this, p + ".conv3.bias", {cout});
-    };
-    expect_conv(*this, b + ".conv1_", 64, 3 + NUM_KP, 7);
-    expect_bn(*this, b + ".bn1", 64);
-    expect_io(b + ".r1", 64, 128);
-    expect_io(b + ".r4", 128, 128);
-    expect_io(b + ".r5", 128, 256);
-    for (int i = 0; i < 2; ++i) {
-        const std::string si = std::to_string(i);
-        expect_conv(*this, b + ".lin_." + si + ".0", 256, 256, 1);
-        expect_bn(*this, b + ".lin_." + si + ".1", 256);
-        expect_conv(*this, b + ".tmpOut." + si, NUM_KP, 256, 1);
-    }
-    expect_conv(*this, b + ".ll_.0", 256, 256, 1);
-    expect_conv(*this, b + ".tmpOut_.0", 256, NUM_KP, 1);
-    expect_shape(*this, "classifier.2.weight", {NUM_KP, NUM_KP});
-    expect_shape(*this, "classifier.2.bias", {NUM_KP});
-    site_xs_ = upload(std::vector<float>(kMaxSites, S2_XSCALE));
-    probe_max_ = reinterpret_cast<unsigned*>(upload(std::vector<float>(kMaxSites, 0.f)));
-    make_conv(b + ".conv1_", b + ".bn1", 16, stem_);
-    // Without priors (every single-view pass and the first SLAM pass, lib/object_slam.py:1094-1097) the 41 prior
-    // channels are zeros: multiply only the 3 image channels.  Same taps, same order, so the result is bit-identical
-    // to feeding zero priors through the full filter; 13 % of the network's MACs (41/44 of the stem) are never issued.
-    make_conv(b + ".conv1_", b + ".bn1", IMG_C, stem_img_, 3);
-    if (wino_bf16x3()) {                                      // ... and for the fused RoIAlign + stem launch on the bf16 pipe (csrc/stem_x3.hip)
-        const HostTensor& w = T(b + ".conv1_.weight");
-        const HostTensor& bb = T(b + ".conv1_.bias");
-        std::vector<float> sc, sh;
-        bn_affine(*this, b + ".bn1", sc, sh);
-        std::vector<float> wx((size_t)14 * 2 * 3 * 64 * 8 / 2), bias(64);        // uint16 planes
-        pack_stem_weight_bf16x3(w.data, (int)w.shape[1], sc.data(), reinterpret_cast<uint16_t*>(wx.data()));
-        for (int n = 0; n < 64; ++n) bias[n] = bb.data[n] * sc[n] + sh[n];
-        stem_x3_w_ = upload(wx);
-        stem_x3_bias_ = upload(bias);
-        if (pipe_f16x2()) {
-            std::vector<float> wh((size_t)14 * 2 * 2 * 64 * 8 / 2), osc(64);    // uint16 planes
-            pack_stem_weight_f16x2(w.data, (int)w.shape[1], sc.data(), reinterpret_cast<uint16_t*>(wh.data()), osc.data());
-            stem_h2_w_ = upload(wh);
-            stem_h2_osc_ = upload(osc);
-        }
-    }
-    make_residual(b + ".r1", r1_);
-    make_residual(b + ".r4", r4_);
-    make_residual(b + ".r5", r5_);
-    for (int i = 0; i < 2; ++i) {
-        make_hourglass(b + ".hourglass." + std::to_string(i), 4, hg_[i]);
-        for (int j = 0; j < 2; ++j) make_residual(b + ".Residual." + std::to_string(i * 2 + j), post_[i][j]);
-        make_gemm(b + ".lin_." + std::to_string(i) + ".0", b + ".lin_." + std::to_string(i) + ".1", "", lin_[i]);
-        make_gemm(b + ".tmpOut." + std::to_string(i), "", "", head_[i]);
-        register_gemm_site(b + ".lin_." + std::to_string(i) + ".0", lin_[i]);
-        register_gemm_site(b + ".tmpOut." + std::to_string(i), head_[i]);
-    }
-    // inter-stack re-injection (hg.py:112-117): x + ll_(ll) + tmpOut_(tmpOut(ll)).  tmpOut and tmpOut_ are both plain 1x1
-    // convolutions with nothing between them, so the sum is ONE 256 -> 256 GEMM on ll with
-    //     W' = W_ll + W_tmpOut_ W_tmpOut ,   b' = b_ll + b_tmpOut_ + W_tmpOut_ b_tmpOut      (folded here in fp64, rounded once)
-    // + the residual x: the 41-channel stack-0 heat-maps -- which nothing else reads (only the last stack is returned,
-    // pkpnet.py:103-105) -- are never materialised and the 64 extra K columns of the dual-operand form are not multiplied.
-    {
-        const HostTensor& wl = T(b + ".ll_.0.weight");   const HostTensor& bl = T(b + ".ll_.0.bias");
-        const HostTensor& wt_ = T(b + ".tmpOut_.0.weight"); const HostTensor& bt_ = T(b + ".tmpOut_.0.bias");
-        const HostTensor& wh = T(b + ".tmpOut.0.weight");  const HostTensor& bh = T(b + ".tmpOut.0.bias");
-        const int N = (int)wl.shape[0], K = (int)wl.shape[1], J = (int)wh.shape[0];      // 256, 256, 41
-        if ((int)wt_.shape[0] != N || (int)wt_.shape[1] != J || (int)wh.shape[1] != K) throw std::runtime_error("re-injection convolutions have unexpected shapes");
-        std::vector<float> full((size_t)N * K), bias(N);
-        for (int n = 0; n < N; ++n) {
-            double bb = (double)bl.data[n] + (double)bt_.data[n];
-            for (int j = 0; j < J; ++j) bb += (double)wt_.data[(size_t)n * J + j] * (double)bh.data[j];
-            bias[n] = (float)bb;
-            for (int k = 0; k < K; ++k) {
-                double v = wl.data[(size_t)n * K + k];
-                for (int j = 0; j < J; ++j) v += (double)wt_.data[(size_t)n * J + j] * (double)wh.data[(size_t)j * K + k];
-                full[(size_t)n * K + k] = (float)v;
-            }
-        }
-        std::vector<float> packed(2 * (size_t)N * K);
-        pack_gemm_weight(full.data(), N, K, K, N, K, packed.data());
-        reinject_.Wp = upload(packed);
-        reinject_.bias = upload(bias);
-        reinject_.N = N; reinject_.n_valid = N; reinject_.K1 = K; reinject_.K2 = 0;
-        if (N % 128 == 0 && K % 64 == 0 && K <= 512 && wino_bf16x3()) {
-            std::vector<float> x3((size_t)3 * N * K / 2);                     // uint16 planes
-            pack_gemm_weight_bf16x3(full.data(), N, K, reinterpret_cast<uint16_t*>(x3.data()));
-            reinject_.Wx3 = upload(x3);
-            if (pipe_f16x2()) {
-                std::vector<float> h2((size_t)N * K), osc(N);
-                pack_gemm_weight_f16x2(full.data(), N, K, reinterpret_cast<uint16_t*>(h2.data()), osc.data());
-                reinject_.W16 = upload(h2);
-                reinject_.osc16 = upload(osc);
-            }
-        }
-        register_gemm_site(b + ".ll_.0", reinject_);          // (ll_ + tmpOut_ tmpOut folded: one operand, ll)
-    }
-    {
-        const HostTensor& w = T("classifier.2.weight");
-        const HostTensor& bb = T("classifier.2.bias");
-        cls_w_ = upload(std::vector<float>(w.data, w.data + w.numel));
-        cls_b_ = upload(std::vector<float>(bb.data, bb.data + bb.numel));
-    }
-    tensors_.clear();   // host pointers are not retained past construction
-    pipe_built_ = pipe_f16x2() ? 2 : (wino_bf16x3() ? 1 : 0);
-    pipe_ = pipe_built_;
+    build_weights(n, names, data, shapes, ndims);
     // the range guard's words: host memory mapped into the device's address space -- the kernels store to the live flag (rarely: only beyond fp16's range), each
     // forward's commit launch moves it into the call's slot, the host reads plain words after whatever synchronisation its results needed anyway
     const size_t guard_bytes = (size_t)(kSlotWord + kCallRing) * sizeof(unsigned);
@@ -603,7 +128,7 @@ long Net::x3_min_rows() const {
 // a 1x1 convolution of M rows as a launch of its own: large launches with a bf16x3 form of the weights run on the bf16 pipe (csrc/gemm_bf16x3.hip; 464 vs 595 us at
 // 256 crops / 64 x 64; below ~256 tiles the fp32 kernels' smaller tiles win), as two fp16 terms where the network is on that form (csrc/f16x2.h)
 int Net::gemm_form(const GemmW& gw, long M) const {
-    return !gw.Wx3 || M < x3_min_rows() ? 0 : (pipe_ == 2 && gw.W16 ? 2 : 1);
+    return !gw.w.w[1] || M < x3_min_rows() ? 0 : (pipe_ == 2 && gw.w.w[2] ? 2 : 1);
 }
 
 // conv2 of a block at L x H x W, on the direct kernel's operands: what the kernels' shape predicates look at; residual() adds the tensors
@@ -637,10 +162,10 @@ Net::BlockPlan Net::plan_block(const ResidualW& r, int L, int H, int W) const {
     static const long f16_from = (long)SUO_TUNE("SUO_RES_FUSED_F16_FROM", 33);
     static const int carry_next = (int)SUO_TUNE("SUO_FUSE_NEXT_CONV1", 1);           // 0: A/B
     int one = 0;                                              // 1: csrc/res_small.hip; 2: csrc/res_small_x3.hip
-    if (mode > 0 && r.rb_w[0] && H <= 32 && W <= 32) {
+    if (mode > 0 && r.block[0].w[0] && H <= 32 && W <= 32) {
         const long t32 = (long)L * ((H + 3) / 4) * ((W + 7) / 8);
-        const long x3_from = (pipe_ == 2 && r.rbh_w[0] && mode >= 2) ? std::min(f16_from, x3_from_env) : x3_from_env;
-        if (mode >= 2 && r.rbx_w[0] && t32 >= x3_from && t32 <= max_tiles) one = 2;
+        const long x3_from = (pipe_ == 2 && r.block[0].w[2] && mode >= 2) ? std::min(f16_from, x3_from_env) : x3_from_env;
+        if (mode >= 2 && r.block[0].w[1] && t32 >= x3_from && t32 <= max_tiles) one = 2;
         else if (H >= min_side && W >= min_side && (t32 < x3_from || (mode == 1 && t32 <= max_tiles))) one = 1;
     }
     const ConvArgs c2 = conv2_args(r, L, H, W);
@@ -648,7 +173,7 @@ Net::BlockPlan Net::plan_block(const ResidualW& r, int L, int H, int W) const {
     // conv2 -> conv3 + skip can be one launch: the 128-channel tensor between them never leaves the CU
     const bool tail_shape = !r.has_skip_conv && r.c3.N == 256 && r.c3.n_valid == 256 && r.c3.K1 == 128 && r.cin == 256;
     BlockPlan p;
-    p.wino = r.c2.Wq && conv3x3_wino_pays(c2, pipe_ == 2 ? 32 : -1);       // 2.25x fewer MFMA MACs (csrc/conv_wino.hip)
+    p.wino = r.c2.wino.w[0] && conv3x3_wino_pays(c2, pipe_ == 2 ? 32 : -1);       // 2.25x fewer MFMA MACs (csrc/conv_wino.hip)
     if (probe_) p.route = BlockPlan::PER_LAYER;               // the calibration probe: every operand of the block's three sites in memory
     else if (one) p.route = BlockPlan::ONE_LAUNCH;
     else if (!p.wino && tail_shape && conv3x3_fusable(c2)) p.route = BlockPlan::DIRECT_FUSED;      // (csrc/conv.hip: FUSE)
@@ -656,8 +181,8 @@ Net::BlockPlan Net::plan_block(const ResidualW& r, int L, int H, int W) const {
     const bool tail = p.route == BlockPlan::WINO_FUSED;
     // one launch: two fp16 planes stream a third less weight per workgroup and take half the MFMAs; Winograd: both products as two fp16 terms (csrc/f16x2.h),
     // else on the bf16 pipe with 3-way split operands, else fp32
-    if (p.route == BlockPlan::ONE_LAUNCH) p.form = one == 2 ? (pipe_ == 2 && r.rbh_w[0] ? 2 : 1) : 0;
-    else if (p.wino) p.form = pipe_ == 2 && r.c2.Wq16 && (!tail || r.c3x16) ? 2 : (r.c2.Wq3 && (!tail || r.c3x) ? 1 : 0);
+    if (p.route == BlockPlan::ONE_LAUNCH) p.form = one == 2 ? (pipe_ == 2 && r.block[0].w[2] ? 2 : 1) : 0;
+    else if (p.wino) p.form = pipe_ == 2 && r.c2.wino.w[2] && (!tail || r.tail.w[2]) ? 2 : (r.c2.wino.w[1] && (!tail || r.tail.w[1]) ? 1 : 0);
     p.form1 = gemm_form(r.c1, M); p.form3 = gemm_form(r.c3, M);
     // the fused Winograd tail is the only epilogue of the per-layer kernels that can add an up-sampled tensor
     p.takes_up = p.route == BlockPlan::ONE_LAUNCH || tail;
@@ -666,39 +191,39 @@ Net::BlockPlan Net::plan_block(const ResidualW& r, int L, int H, int W) const {
     //  does not carry it.)  It can ride there when the separate launch would have been the fp16 GEMM on the same operands (256 -> 128 with a BatchNorm
     // prologue, >= SUO_GEMM_X3_MIN_ROWS pixels, not a one-launch block): then the two are bit-identical (tests/test_gpu_f16x2.py)
     p.can_carry_next_conv1 = carry_next && tail && p.form == 2 && !conv3x3_wino_f16x2_w8(tiles);
-    const bool from_tail = p.form1 == 2 && r.cin == 256 && r.c1.osc16 && r.c1.N == 128 && r.c1.n_valid == 128 && r.c1.K1 == 256 && r.c1.K2 == 0;
+    const bool from_tail = p.form1 == 2 && r.cin == 256 && r.c1.w.osc && r.c1.N == 128 && r.c1.n_valid == 128 && r.c1.K1 == 256 && r.c1.K2 == 0;
     p.uses_producer_conv1 = p.route != BlockPlan::ONE_LAUNCH && (from_tail || (&r == &r1_ && stem_computes_r1_conv1()));
     return p;
 }
 
 // the operands of a Winograd 3x3 (tail: and of its fused conv3) in the given form; returns the bytes per weight element the accounting uses
 static double wino_operands(ConvArgs& c, const ResidualW& r, int form, bool tail, unsigned* range_flag) {
+    c.Wp = r.c2.wino.w[form];
+    if (tail) { c.W3p = r.tail.w[form]; c.w3_bf16x3 = form == 1; }
     if (form == 2) {
-        c.Wp = r.c2.Wq16; c.oscale = r.c2.osc16; c.range_flag = range_flag; c.xscale = r.c2.xs16;
-        if (tail) { c.W3p = r.c3x16; c.oscale3 = r.c3osc16; c.xscale3 = r.c3.xs16; }
-    } else if (form == 1) {
-        c.Wp = r.c2.Wq3;
-        if (tail) { c.W3p = r.c3x; c.w3_bf16x3 = 1; }
-    } else c.Wp = r.c2.Wq;
+        c.oscale = r.c2.wino.osc; c.range_flag = range_flag; c.xscale = r.c2.xs16;
+        if (tail) { c.oscale3 = r.tail.osc; c.xscale3 = r.c3.xs16; }
+    }
     return weight_bytes(form);
 }
 static int launch_wino(const ConvArgs& c, int form, bool tail, hipStream_t s) {
-    if (tail) return form == 2 ? launch_conv3x3_wino_f16x2_fused(c, s) : form == 1 ? launch_conv3x3_wino_x3_fused(c, s) : launch_conv3x3_wino_fused(c, s);
-    return form == 2 ? launch_conv3x3_wino_f16x2(c, s) : form == 1 ? launch_conv3x3_wino_x3(c, s) : launch_conv3x3_wino(c, s);
+    static int (*const launch[2][3])(const ConvArgs&, hipStream_t) = {{launch_conv3x3_wino, launch_conv3x3_wino_x3, launch_conv3x3_wino_f16x2},
+                                                                     {launch_conv3x3_wino_fused, launch_conv3x3_wino_x3_fused, launch_conv3x3_wino_f16x2_fused}};
+    return launch[tail][form](c, s);
 }
 
 int Net::residual_one_launch(const ResidualW& r, const BlockPlan& p, const float* x, float* out, int L, int H, int W, hipStream_t s, const float* up, bool pool_in) {
     ResBlockArgs a = {};
     a.x = x; a.L = L; a.H = H; a.W = W; a.pool_in = pool_in ? 1 : 0; a.pro_scale = r.pro_scale; a.pro_shift = r.pro_shift;
     a.b1 = r.c1.bias; a.b2 = r.c2.bias; a.b3 = r.c3.bias; a.up = up; a.out = out;
-    float* const* w = p.form == 2 ? r.rbh_w : p.form == 1 ? r.rbx_w : r.rb_w;
-    a.W1 = w[0]; a.W2 = w[1]; a.W3 = w[2];
+    a.W1 = r.block[0].w[p.form]; a.W2 = r.block[1].w[p.form]; a.W3 = r.block[2].w[p.form];
     if (p.form == 2) {
-        a.osc1 = r.rbh_osc[0]; a.osc2 = r.rbh_osc[1]; a.osc3 = r.rbh_osc[2]; a.range_flag = range_flag_;
+        a.osc1 = r.block[0].osc; a.osc2 = r.block[1].osc; a.osc3 = r.block[2].osc; a.range_flag = range_flag_;
         a.xs1 = r.c1.xs16; a.xs2 = r.c2.xs16; a.xs3 = r.c3.xs16;
     }
     acct(ACCT_BLOCK, block_bytes(a, weight_bytes(p.form)));
-    SUO_LAUNCH(p.form == 2 ? launch_res_block_f16x2(a, s) : p.form == 1 ? launch_res_block_x3(a, s) : launch_res_block(a, s));
+    static int (*const launch[3])(const ResBlockArgs&, hipStream_t) = {launch_res_block, launch_res_block_x3, launch_res_block_f16x2};
+    SUO_LAUNCH(launch[p.form](a, s));
     return SUO_OK;
 }
 
@@ -716,8 +241,8 @@ int Net::gemm_maybe_pooled(GemmArgs& g, int L, int H, int W, float* pool_out, hi
     if (form) {
         GemmArgs gx = g;
         gx.pool_out = pool_out; gx.pool_H = H; gx.pool_W = W;                  // the pool in the epilogue (maps of 64-column multiples), `out` optional
-        if (form == 2) { gx.oscale = gw.osc16; gx.range_flag = range_flag_; gx.xscale = gw.xs16; }      // the two-term fp16 form of the same kernel (csrc/f16x2.h)
-        auto launch = [&](const GemmArgs& a) { return form == 2 ? launch_gemm_f16x2_args(a, reinterpret_cast<const uint16_t*>(gw.W16), s) : launch_gemm_bf16x3_args(a, reinterpret_cast<const uint16_t*>(gw.Wx3), s); };
+        if (form == 2) { gx.oscale = gw.w.osc; gx.range_flag = range_flag_; gx.xscale = gw.xs16; }      // the two-term fp16 form of the same kernel (csrc/f16x2.h)
+        auto launch = [&](const GemmArgs& a) { return (form == 2 ? launch_gemm_f16x2_args : launch_gemm_bf16x3_args)(a, reinterpret_cast<const uint16_t*>(gw.w.w[form]), s); };
         const bool pool_in_gemm = gemm_bf16x3_takes(gx);
         if (!pool_in_gemm) gx.pool_out = nullptr;                             // else the pool as its own launch
         if (pool_in_gemm || (g.out && gemm_bf16x3_takes(gx))) {
@@ -758,7 +283,7 @@ int Net::residual(const ResidualW& r, const float* x, float* out, int L, int H, 
         mid1 = alloc((size_t)M * r.c1.N);
         GemmArgs g1 = {};
         g1.A1 = x; g1.lda1 = r.cin; g1.K1 = r.c1.K1; g1.pro_scale = r.pro_scale; g1.pro_shift = r.pro_shift;
-        g1.Wp = r.c1.Wp; g1.bias = r.c1.bias; g1.out = mid1; g1.ldo = r.c1.N; g1.M = M; g1.N = r.c1.N; g1.n_valid = r.c1.n_valid; g1.relu = 1;
+        g1.Wp = r.c1.w.w[0]; g1.bias = r.c1.bias; g1.out = mid1; g1.ldo = r.c1.N; g1.M = M; g1.N = r.c1.N; g1.n_valid = r.c1.n_valid; g1.relu = 1;
         SUO_TRY(gemm_maybe_pooled(g1, L, H, W, nullptr, s, r.c1, p.form1));
     }
     float* mid2 = alloc((size_t)M * r.c2.N);
@@ -767,12 +292,12 @@ int Net::residual(const ResidualW& r, const float* x, float* out, int L, int H, 
     const bool tail = p.route != BlockPlan::PER_LAYER;       // conv2 -> conv3 + skip in one launch
     if (tail) {
         if (!out) out = alloc((size_t)M * 256);
-        c2.W3p = r.c3.Wp; c2.bias3 = r.c3.bias; c2.R = x; c2.out2 = out; c2.N2 = 256; c2.up = up;
+        c2.W3p = r.c3.w.w[0]; c2.bias3 = r.c3.bias; c2.R = x; c2.out2 = out; c2.N2 = 256; c2.up = up;
     }
     const double wb = p.wino ? wino_operands(c2, r, p.form, tail, range_flag_) : 4;
     if (next && !up && !pool_out && p.can_carry_next_conv1 && plan_block(*next, L, H, W).uses_producer_conv1) {
         float* nm = alloc((size_t)M * 128);
-        c2.n_scale = next->pro_scale; c2.n_shift = next->pro_shift; c2.n_W1 = next->c1.W16; c2.n_osc1 = next->c1.osc16; c2.n_b1 = next->c1.bias; c2.n_out = nm; c2.n_xscale = next->c1.xs16;
+        c2.n_scale = next->pro_scale; c2.n_shift = next->pro_shift; c2.n_W1 = next->c1.w.w[2]; c2.n_osc1 = next->c1.w.osc; c2.n_b1 = next->c1.bias; c2.n_out = nm; c2.n_xscale = next->c1.xs16;
         pre_.push_back({out, next, nm});
     }
     acct(ACCT_CONV3, conv_bytes(c2, wb, p.wino ? 16 : 9, tail));
@@ -782,7 +307,7 @@ int Net::residual(const ResidualW& r, const float* x, float* out, int L, int H, 
     g3.A1 = mid2; g3.lda1 = r.c2.N; g3.K1 = r.c3.K1;
     if (r.has_skip_conv) { g3.A2 = x; g3.lda2 = r.cin; g3.K2 = r.c3.K2; }
     else { g3.R = x; g3.ldr = r.cin; }
-    g3.Wp = r.c3.Wp; g3.bias = r.c3.bias; g3.out = out; g3.ldo = r.cout; g3.M = M; g3.N = r.c3.N; g3.n_valid = r.c3.n_valid;
+    g3.Wp = r.c3.w.w[0]; g3.bias = r.c3.bias; g3.out = out; g3.ldo = r.cout; g3.M = M; g3.N = r.c3.N; g3.n_valid = r.c3.n_valid;
     if (probe_) {                                             // the calibration probe: every operand of the block's three sites is in memory here
         SUO_TRY(probe_site(r.c1.site, x, M, r.cin, r.cin, r.pro_scale, r.pro_shift, 1, s));
         SUO_TRY(probe_site(r.c2.site, mid1, M, r.c1.N, r.c1.N, nullptr, nullptr, 0, s));
@@ -894,16 +419,16 @@ int Net::backbone(const float* in0, int in_c, float* logits, int L, hipStream_t 
         // the last stack's lin -> head pair: `ll` has one reader, so it never leaves the CU (one launch, 1.2 GB of traffic instead of 3.3 at 256 crops)
         static const int chain_head = (int)SUO_TUNE("SUO_CHAIN_HEAD", 1);            // 0: A/B
         const long chain_min_rows = x3_min_rows();
-        if (i == 1 && chain_head && pipe_ == 2 && lin_[i].W16 && head_[i].W16 && lin_[i].N == 256 && lin_[i].K1 == 256 && M >= chain_min_rows &&
+        if (i == 1 && chain_head && pipe_ == 2 && lin_[i].w.w[2] && head_[i].w.w[2] && lin_[i].N == 256 && lin_[i].K1 == 256 && M >= chain_min_rows &&
             gemm_chain_head_takes(M, 256, NUM_KP, HEAT * HEAT)) {
             acct(ACCT_GEMM, 4.0 * M * 256 + 4.0 * M * NUM_KP + 4.0 * (256.0 * 256 + 64.0 * 256));
-            SUO_LAUNCH(launch_gemm_chain_head(rb, 256, M, reinterpret_cast<const uint16_t*>(lin_[i].W16), lin_[i].osc16, lin_[i].bias, reinterpret_cast<const uint16_t*>(head_[i].W16),
-                                              head_[i].osc16, head_[i].bias, logits, NUM_KP, HEAT * HEAT, range_flag_, s, lin_[i].xs16, head_[i].xs16));
+            SUO_LAUNCH(launch_gemm_chain_head(rb, 256, M, reinterpret_cast<const uint16_t*>(lin_[i].w.w[2]), lin_[i].w.osc, lin_[i].bias, reinterpret_cast<const uint16_t*>(head_[i].w.w[2]),
+                                              head_[i].w.osc, head_[i].bias, logits, NUM_KP, HEAT * HEAT, range_flag_, s, lin_[i].xs16, head_[i].xs16));
             continue;
         }
         float* ll = alloc((size_t)M * 256);
         GemmArgs gl = {};
-        gl.A1 = rb; gl.lda1 = 256; gl.K1 = 256; gl.Wp = lin_[i].Wp; gl.bias = lin_[i].bias; gl.out = ll; gl.ldo = 256;
+        gl.A1 = rb; gl.lda1 = 256; gl.K1 = 256; gl.Wp = lin_[i].w.w[0]; gl.bias = lin_[i].bias; gl.out = ll; gl.ldo = 256;
         gl.M = M; gl.N = 256; gl.n_valid = 256; gl.relu = 1;
         SUO_TRY(gemm_maybe_pooled(gl, L, 64, 64, nullptr, s, lin_[i], gemm_form(lin_[i], M)));
         if (probe_) {
@@ -912,13 +437,13 @@ int Net::backbone(const float* in0, int in_c, float* logits, int L, hipStream_t 
             if (i == 0) SUO_TRY(probe_site(reinject_.site, ll, M, 256, 256, nullptr, nullptr, 0, s));
         }
         GemmArgs gh = {};
-        gh.A1 = ll; gh.lda1 = 256; gh.K1 = 256; gh.Wp = head_[i].Wp; gh.bias = head_[i].bias; gh.M = M; gh.N = 64;
+        gh.A1 = ll; gh.lda1 = 256; gh.K1 = 256; gh.Wp = head_[i].w.w[0]; gh.bias = head_[i].bias; gh.M = M; gh.N = 64;
         if (i == 0) {
             // x <- x + ll_(ll) + tmpOut_(tmpOut(ll)) as one folded GEMM + residual (see the constructor)
             float* xn = alloc((size_t)M * 256);
             GemmArgs gr = {};
             gr.A1 = ll; gr.lda1 = 256; gr.K1 = 256;
-            gr.Wp = reinject_.Wp; gr.bias = reinject_.bias; gr.R = x; gr.ldr = 256; gr.out = xn; gr.ldo = 256;
+            gr.Wp = reinject_.w.w[0]; gr.bias = reinject_.bias; gr.R = x; gr.ldr = 256; gr.out = xn; gr.ldo = 256;
             gr.M = M; gr.N = 256; gr.n_valid = 256;
             xp = alloc((size_t)L * 32 * 32 * 256);
             SUO_TRY(gemm_maybe_pooled(gr, L, 64, 64, xp, s, reinject_, gemm_form(reinject_, M)));
@@ -1189,11 +714,11 @@ int Net::schedule_bytes(int L, int n_frames, int H, int W, int with_priors, doub
 // backbone without launching the stem
 bool Net::stem_computes_r1_conv1() const {
     static const int on = (int)SUO_TUNE("SUO_STEM_NEXT", 1);              // 0: A/B
-    return on && fused_stem() && pipe_ == 2 && stem_h2_w_ && r1_.c1.W16 && r1_.c1.osc16 && r1_.cin == 64 && r1_.c1.N == 64 && r1_.c1.K1 == 64 && r1_.c1.K2 == 0;
+    return on && fused_stem() && pipe_ == 2 && stem_x3_.w[2] && r1_.c1.w.w[2] && r1_.c1.w.osc && r1_.cin == 64 && r1_.c1.N == 64 && r1_.c1.K1 == 64 && r1_.c1.K2 == 0;
 }
 bool Net::fused_stem() const {
     static const int on = (int)suo::env_switch("SUO_STEM_X3", 1);
-    return on != 0 && stem_x3_w_ != nullptr;
+    return on != 0 && stem_x3_.w[1] != nullptr;
 }
 
 // Capture the backbone graph for L crops ahead of time (nothing runs): a stream of frames with a varying number of
@@ -1250,14 +775,11 @@ int Net::forward(const void* img, int fmt, int H, int W, const float* boxes, con
         if (in_c == IMG_C && fused_stem()) {
             // prior-less pass: RoIAlign + stem in one launch on the bf16 pipe (csrc/stem_x3.hip), ahead of the captured backbone (the frame and
             // the boxes are the caller's buffers: their addresses change from call to call, a captured launch could not take them)
-            if (stem_computes_r1_conv1()) {
-                // r1's conv1 on the tile while the stem has it (the stem's output is read by r1's skip convolution only)
-                const StemNext nx = {r1_.pro_scale, r1_.pro_shift, reinterpret_cast<const uint16_t*>(r1_.c1.W16), r1_.c1.osc16, r1_.c1.bias, stem_mid1_slab_, r1_.c1.xs16};
-                SUO_LAUNCH(launch_stem_x3(img, fmt, H, W, boxes, box_img, L, reinterpret_cast<const uint16_t*>(stem_h2_w_), stem_x3_bias_, stem_slab_, s, stem_h2_osc_, range_flag_, &nx));
-            } else if (pipe_ == 2 && stem_h2_w_)
-                SUO_LAUNCH(launch_stem_x3(img, fmt, H, W, boxes, box_img, L, reinterpret_cast<const uint16_t*>(stem_h2_w_), stem_x3_bias_, stem_slab_, s, stem_h2_osc_, range_flag_));
-            else
-            SUO_LAUNCH(launch_stem_x3(img, fmt, H, W, boxes, box_img, L, reinterpret_cast<const uint16_t*>(stem_x3_w_), stem_x3_bias_, stem_slab_, s));
+            // fp16 form: also r1's conv1 on the tile while the stem has it, where the plan takes it (the stem's output is then read by r1's skip convolution only)
+            const bool f16 = pipe_ == 2 && stem_x3_.w[2];
+            const StemNext nx = {r1_.pro_scale, r1_.pro_shift, reinterpret_cast<const uint16_t*>(r1_.c1.w.w[2]), r1_.c1.w.osc, r1_.c1.bias, stem_mid1_slab_, r1_.c1.xs16};
+            SUO_LAUNCH(launch_stem_x3(img, fmt, H, W, boxes, box_img, L, reinterpret_cast<const uint16_t*>(stem_x3_.w[f16 ? 2 : 1]), stem_x3_bias_, stem_slab_, s,
+                                      f16 ? stem_x3_.osc : nullptr, f16 ? range_flag_ : nullptr, stem_computes_r1_conv1() ? &nx : nullptr));
             SUO_TRY(run_backbone(in0, in_c, logits, L, s, true));
         } else {
             SUO_LAUNCH(launch_roi_align_concat(img, fmt, H, W, boxes, box_img, L, in_c, priors, prior_uv, prior_mask, in0, s));

@@ -18,7 +18,7 @@ def ops():
 
 
 def _block_weights(rng):
-    """A Residual block with its BatchNorms (eval mode, eps 1e-5) folded the way csrc/net.hip folds them: bn -> prologue scale / shift,
+    """A Residual block with its BatchNorms (eval mode, eps 1e-5) folded the way csrc/net_weights.hip folds them: bn -> prologue scale / shift,
     bn1 / bn2 into the preceding convolution's rows (float32 products) and bias."""
     def bn(c):
         g, b = rng.uniform(0.5, 1.5, c).astype(np.float32), (rng.standard_normal(c) * 0.1).astype(np.float32)
