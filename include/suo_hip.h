@@ -635,6 +635,52 @@ int suo_pose_errors(void* mesh_db, int n, const int* model_index, const float* T
 int suo_mesh_db_set_symmetries(void* mesh_db, const int* n_sym, const double* sym);
 int suo_pose_errors_bop(void* mesh_db, int n, const int* model_index, const double* T_est, const double* T_gt, const double* K, double* mssd, double* mspd);
 
+/* ---- BOP-19 VSD: depth rasteriser and error ------------------------------------------
+ * The third term of the BOP-19 score over the same mesh database.  Opt-in: nothing above changes when these are not called.
+ *
+ * suo_mesh_db_set_faces: triangles per model, n_faces[n_models] (0 allowed: that model cannot be rendered), faces [sum n_faces][3] vertex indices into the
+ * model's own point list, host ints; replaces an earlier set.  SUO_ERR_ARG, nothing uploaded: a null pointer, a negative count, an index outside [0, n_pts[i]).
+ *
+ * suo_render_depth: n depth images [n][height][width] (host floats, eye-space Z in the mesh's unit, 0.0f where nothing is drawn) of model_index[i] under the
+ * pose T[i] (row-major 3x4 [R|t], doubles) and the camera K[i] (row-major 3x3; only fx = K[0], fy = K[4], cx = K[2], cy = K[5] are used, as in the toolkit's
+ * Renderer.render_object).  It restates what bop_toolkit's Python renderer draws into its depth image (renderer_py.py:124-143, 185-226, 428-457, 524-556)
+ * under OpenGL's rasterisation rules; no GL exists to pin it, so these rules ARE the specification (tests/vsd_ref.py restates them in fp64 numpy):
+ *   camera space   X = R p + t in fp64 on the float32 points widened exactly, each row ((r0 x + r1 y) + r2 z) + t;  u = fx (X / Z) + cx,  v = fy (Y / Z) + cy.
+ *   sample point   of pixel (x, y): (x + 0.5, y + 0.5).  This half pixel is the Python renderer's (its projection maps u to window x with x0 = y0 = 0 and GL
+ *                  samples pixel centres; the y_down matrix plus the row flip after glReadPixels gives the same for rows) and is kept on purpose, although
+ *                  the error below has none.
+ *   coverage       fp64 edge functions on (u, v): E_PQ(p) = (Qx - Px)(py - Py) - (Qy - Py)(px - Px) for the edges 1->2, 2->0, 0->1, multiplied by the sign s of
+ *                  the doubled area E_01(2) so that both windings are drawn (no face culling).  A sample is covered when all three are > 0, or == 0 on an edge
+ *                  that is a left edge (inward normal s (-(Qy - Py), Qx - Px) has x > 0) or a top edge (x == 0 and y > 0; rows grow downwards).
+ *                  Zero-area triangles are skipped.
+ *   depth          eye-space Z, perspective-correct: 1 / z = ((w0 / Z0 + w1 / Z1) + w2 / Z2) / |area2| with the weights w_i = s E_i above (1 / Z_i rounded
+ *                  once each); z is rounded once to float32.
+ *   z-buffer       the nearest fragment wins (depth test "less"); the result does not depend on the order of the triangles or of the renders in a call.
+ *   deviation      a triangle with any vertex at Z <= 0 is skipped whole (GL would clip it at a near plane placed at the nearest bounding-box corner, which
+ *                  means nothing once that corner is behind the camera).
+ * SUO_ERR_ARG before anything is launched: a null pointer, non-finite T or K, width or height < 1, a model index outside the database, a model without
+ * faces, more than 65535 renders in a call.  n = 0 returns 0.  Blocking.
+ *
+ * suo_vsd_from_depth: the toolkit's pose_error.vsd (pose_error.py:40-93, cost 'step'; misc.py:130-163; visibility.py:9-75, mode 'bop19') operation for
+ * operation on n pairs of rendered depth images depth_est / depth_gt [n][height][width] against the test depth image image_index[i] of depth_test
+ * [n_images][height][width] (mm, host floats):  pre_X = (x - cx) / fx, pre_Y = (y - cy) / fy in fp64 (no half pixel: the toolkit has none),
+ * dist = sqrt(((pre_X d)^2 + (pre_Y d)^2) + d^2) in fp64; the visibility differences in float32 on the distances rounded to float32, compared with
+ * float32(delta); visib_gt = (diff_gt <= delta or dist_test == 0) and dist_gt > 0; visib_est = (the same for est) or (visib_gt and dist_est > 0);
+ * cost_t = count over the intersection of |dist_gt - dist_est| (divided by diameter[i] when normalized_by_diameter) >= taus[t];
+ * errors[i][t] = (cost_t + union - intersection) / union, or 1.0 when union == 0.  counts (may be NULL) [n][2 + n_taus]: union, intersection, cost per tau.
+ * The counters are integers: they do not depend on the launch shape.  1 <= n_taus <= 16.
+ * suo_pose_errors_vsd: the same on poses: renders T_est[i] and T_gt[i] of model_index[i] under K[i] on the device (each distinct (model, pose, fx, fy, cx, cy)
+ * of the call once -- the ground truths repeat) and feeds the error kernel without the depth images leaving device memory.
+ * SUO_ERR_ARG (nothing launched) as for suo_render_depth, and for an image index outside [0, n_images), n_taus outside 1..16, a non-finite delta. */
+int suo_mesh_db_set_faces(void* mesh_db, const int* n_faces, const int* faces);
+int suo_render_depth(void* mesh_db, int n, const int* model_index, const double* T, const double* K, int width, int height, float* depth_out);
+int suo_vsd_from_depth(int n, int width, int height, const float* depth_est, const float* depth_gt, int n_images, const float* depth_test, const int* image_index,
+                       const double* K, double delta, int n_taus, const double* taus, int normalized_by_diameter, const double* diameter, double* errors,
+                       long long* counts);
+int suo_pose_errors_vsd(void* mesh_db, int n, const int* model_index, const double* T_est, const double* T_gt, const double* K, int width, int height,
+                        int n_images, const float* depth_test, const int* image_index, double delta, int n_taus, const double* taus, int normalized_by_diameter,
+                        const double* diameter, double* errors, long long* counts);
+
 /* ---- SLAM-mode hypothesis scoring ------------------------------------------
  * Replaces the per-pair numpy of ObjectSLAM.__estimate_camera_pose's hypothesis loop (lib/object_slam.py:1000-1066) and of
  * __maybe_reinit_objects' inlier counts (:619-690): count_k [ z_k > 0 and chi2_k <= chi2_max ] for n_pairs (pose, detection) pairs in one launch.

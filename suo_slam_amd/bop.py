@@ -61,16 +61,101 @@ def load_ply_points(path):
         return np.stack([rec[a].astype(np.float64) for a in ("x", "y", "z")], axis=1)
 
 
-def load_mesh_db(model_dir):
+def load_ply_mesh(path):
+    """``(points float32 [P,3], faces int32 [F,3])`` of a PLY file, ascii or binary little endian, with the face property ``list uchar int`` or
+    ``list uchar uint`` named vertex_indices / vertex_index; triangles only.  Stands in for the ``pts`` and ``faces`` of bop_toolkit's ``inout.load_ply``
+    (inout.py:333-515) where the VSD renderer needs the triangles; other vertex and face properties are skipped."""
+    with open(path, "rb") as f:
+        assert f.readline().strip() == b"ply", f"{path}: not a PLY file"
+        fmt, counts, props, section = None, {}, {"vertex": [], "face": []}, None
+        while True:
+            line = f.readline()
+            assert line, f"{path}: unterminated PLY header"
+            tok = line.decode("ascii", "replace").split()
+            if not tok:
+                continue
+            if tok[0] == "format":
+                fmt = tok[1]
+            elif tok[0] == "element":
+                section = tok[1]
+                counts[section] = int(tok[2])
+                props.setdefault(section, [])
+            elif tok[0] == "property" and section is not None:
+                if tok[1] == "list":
+                    props[section].append((tok[4], _PLY_TYPES[tok[2]], _PLY_TYPES[tok[3]]))
+                else:
+                    props[section].append((tok[2], _PLY_TYPES[tok[1]], None))
+            elif tok[0] == "end_header":
+                break
+        assert fmt in ("ascii", "binary_little_endian"), f"{path}: PLY format {fmt!r} is not read here"
+        assert list(counts)[:2] == ["vertex", "face"][:len(counts)] or "face" not in counts, f"{path}: vertex and face elements must come first, in this order"
+        n_vert, n_face = counts.get("vertex", 0), counts.get("face", 0)
+        vprops, fprops = props["vertex"], props["face"]
+        assert all(p[2] is None for p in vprops), f"{path}: list property on vertices"
+        names = [p[0] for p in vprops]
+        ix = [names.index(a) for a in ("x", "y", "z")]
+        lists = [k for k, p in enumerate(fprops) if p[2] is not None and p[0] in ("vertex_indices", "vertex_index")]
+        assert n_face == 0 or len(lists) == 1, f"{path}: the faces need one vertex_indices list"
+        if n_face:
+            assert fprops[lists[0]][1] == "B" and fprops[lists[0]][2] in ("i", "I"), f"{path}: face property must be list uchar int|uint"
+        faces = np.zeros((n_face, 3), np.int64)                     # int64 until checked: a uint index may not fit int32
+        if fmt == "ascii":
+            rows = np.array([f.readline().split() for _ in range(n_vert)], dtype=np.float64).reshape(n_vert, len(vprops))
+            pts = rows[:, ix]
+            for k in range(n_face):
+                tok, at = f.readline().split(), 0
+                for name, _, item in fprops:                      # a scalar takes one token, a list its count and that many
+                    if item is None:
+                        at += 1
+                        continue
+                    cnt = int(tok[at])
+                    if name in ("vertex_indices", "vertex_index"):
+                        if cnt != 3:
+                            raise ValueError(f"{path}: only triangular faces are supported")
+                        faces[k] = [int(v) for v in tok[at + 1:at + 4]]
+                    at += 1 + cnt
+        else:
+            dt = np.dtype([(n, "<" + c) for n, c, _ in vprops])
+            rec = np.frombuffer(f.read(dt.itemsize * n_vert), dtype=dt, count=n_vert)
+            pts = np.stack([rec[a].astype(np.float64) for a in ("x", "y", "z")], axis=1)
+            if n_face and len(fprops) == 1:                       # the usual file: count byte + three indices per face
+                ft = np.dtype([("n", "u1"), ("v", {"i": "<i4", "I": "<u4"}[fprops[0][2]], (3,))])
+                rec = np.frombuffer(f.read(ft.itemsize * n_face), dtype=ft, count=n_face)
+                if not (rec["n"] == 3).all():
+                    raise ValueError(f"{path}: only triangular faces are supported")
+                faces = rec["v"].astype(np.int64)
+            else:
+                for k in range(n_face):
+                    for name, c, item in fprops:
+                        if item is None:
+                            f.read(struct.calcsize("<" + c))
+                            continue
+                        cnt = struct.unpack("<" + c, f.read(struct.calcsize("<" + c)))[0]
+                        vals = struct.unpack("<" + item * cnt, f.read(struct.calcsize("<" + item) * cnt))
+                        if name in ("vertex_indices", "vertex_index"):
+                            if cnt != 3:
+                                raise ValueError(f"{path}: only triangular faces are supported")
+                            faces[k] = vals
+        if n_face and (faces.min() < 0 or faces.max() > np.iinfo(np.int32).max):
+            raise ValueError(f"{path}: vertex index {int(faces.max() if faces.min() >= 0 else faces.min())} outside int32")
+        return pts.astype(np.float32), np.ascontiguousarray(faces, np.int32)
+
+
+def load_mesh_db(model_dir, faces=False):
     """``{obj_id: {"is_symmetric", "continuous_sym", "diameter", "points"}}`` from ``models_info.json`` +
     ``obj_%06d.ply`` (mesh_database.py:17-45).  ``points`` is a float32 numpy array [P,3] in mm; ``EvalMeter`` uploads
-    it to the GPU once (the reference keeps a CUDA tensor here)."""
+    it to the GPU once (the reference keeps a CUDA tensor here).  ``faces=True`` adds ``"faces"``, int32 [F,3] vertex
+    indices, for the VSD renderer (bop_eval.BopErrors); the other entries are the same either way."""
     with open(os.path.join(model_dir, "models_info.json"), "r") as f:
         model_info = json.load(f)
     mesh_db = {}
     for key, info in model_info.items():
         obj_id = int(key)
-        pts = load_ply_points(os.path.join(model_dir, f"obj_{obj_id:06d}.ply")).astype(np.float32)
+        path = os.path.join(model_dir, f"obj_{obj_id:06d}.ply")
+        if faces:
+            pts, tris = load_ply_mesh(path)                           # one parse: the same float32 points as below
+        else:
+            pts = load_ply_points(path).astype(np.float32)
         cont = info.get("symmetries_continuous", [])
         mesh_db[obj_id] = {
             "is_symmetric": len(info.get("symmetries_discrete", [])) > 0 or len(cont) > 0,
@@ -78,6 +163,8 @@ def load_mesh_db(model_dir):
             "diameter": info["diameter"],
             "points": pts,
         }
+        if faces:
+            mesh_db[obj_id]["faces"] = tris
     return mesh_db
 
 
@@ -226,6 +313,15 @@ class BopDataset:
         img = np.asarray(Image.open(path).convert("RGB"), np.uint8)
         assert img.size > 0, f"Empty image {path}"
         return np.ascontiguousarray(img[:, :, ::-1])
+
+    def read_depth(self, scene_id, view_id):
+        """float32 [H,W] depth in mm: the 16-bit PNG under ``depth/%06d.png`` times the frame's ``depth_scale``, both as float32
+        (inout.load_depth and eval_calc_errors.py:239-242: an in-place float32 product)."""
+        from PIL import Image
+        path = os.path.join(self.curr_root, f"{scene_id:06d}", "depth", f"{view_id:06d}.png")
+        raw = np.asarray(Image.open(path))
+        assert raw.ndim == 2 and raw.size > 0, f"{path}: not a single-channel depth image"
+        return raw.astype(np.float32) * np.float32(self.data[scene_id][view_id]["depth_scale"])
 
     def get_raw(self, scene_id, view_id, obj_ids):
         """The sample dictionary of bop.py:469-723 at test time (torch tensors, same keys, dtypes and shapes), minus

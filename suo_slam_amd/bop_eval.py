@@ -1,4 +1,4 @@
-"""BOP-19 MSSD / MSPD average recall: the renderer-free two of the three terms of the BOP-19 score.
+"""BOP-19 average recall: MSSD / MSPD, the renderer-free two of the three terms of the BOP-19 score, and, opt-in, VSD (row N6).
 
 Host mirror of what the reference's vendored bop_toolkit does between a results CSV and the two recall tables
 (``scripts/eval_bop19.py`` driving ``eval_calc_errors.py`` and ``eval_calc_scores.py``) for the error types ``mssd`` and ``mspd``:
@@ -13,7 +13,16 @@ Host mirror of what the reference's vendored bop_toolkit does between a results 
                                                     pose_matching.match_poses / match_poses_scene, score.calc_localization_scores
 
 The max-over-points inside min-over-symmetries runs on the GPU in fp64; sorting, greedy matching and counting are a few thousand scalars and stay on the
-host exactly as in the toolkit.  VSD, the third term, needs a renderer and depth images and stays the external hand-off of row N4.
+host exactly as in the toolkit.  VSD, the third term, needs a renderer and depth images and stays the external hand-off of row N4 unless opted in, below.
+
+Opt-in since row N6, with nothing above changed when it is not asked for: a mesh database with ``"faces"`` (bop.load_mesh_db(..., faces=True)) and a
+``depth_loader`` give the third term without an external tool:
+
+    BopErrors.render_depth(obj_ids, T, K, hw)       Renderer.render_object(...)["depth"]       -> HIP, csrc/raster.hip (suo_render_depth)
+    BopErrors.vsd(obj_ids, T_est, T_gt, K, depth_images, image_index, delta, taus, normalized)
+                                                    pose_error.vsd (cost 'step', mode 'bop19')  -> HIP, csrc/eval_vsd.hip (suo_pose_errors_vsd)
+    overlapping_sphere_projections(radius, p1, p2)  misc.overlapping_sphere_projections (the gate of eval_calc_errors.py:295-312)
+    Bop19Meter(..., depth_loader=..., vsd_delta=15) adds "vsd" (one recall per tau and threshold, eval_bop19.py:178-225) and "ar", the mean of the three.
 """
 from __future__ import annotations
 
@@ -28,6 +37,9 @@ from . import _lib
 
 MSSD_THRESHOLDS = np.arange(0.05, 0.51, 0.05)          # eval_bop19.py:44, fractions of the object diameter
 MSPD_THRESHOLDS = np.arange(5, 51, 5)                  # eval_bop19.py:49, pixels at an image width of 640
+VSD_TAUS = VSD_THRESHOLDS = np.arange(0.05, 0.51, 0.05)  # eval_bop19.py:37,39: misalignment tolerances (fractions of the diameter) and thresholds of correctness
+VSD_DELTAS = {"hb": 15, "icbin": 15, "icmi": 15, "itodd": 5, "lm": 15, "lmo": 15, "ruapc": 15, "tless": 15, "tudl": 15, "tyol": 15, "ycbv": 15}   # eval_bop19.py:24-36, mm
+VSD_PAIRS_PER_CALL = 32                                # pairs of one device call: two 640 x 480 renders each stay on the device, 2.4 MB a pair
 
 
 # ---- symmetries ------------------------------------------------------------------------------------------
@@ -109,6 +121,14 @@ class BopErrors:
         n_sym = np.array([self.syms[o].shape[0] for o in ids], np.int32)
         allsym = np.ascontiguousarray(np.concatenate([self.syms[o].reshape(-1, 12) for o in ids], 0))
         _lib.check(self.lib.suo_mesh_db_set_symmetries(self._h, n_sym.ctypes.data, allsym.ctypes.data), "suo_mesh_db_set_symmetries")
+        self.has_faces = any("faces" in mesh_db[o] for o in ids)
+        if self.has_faces:                                          # the triangles of the VSD renderer; a model without them cannot be rendered
+            tris = [np.ascontiguousarray(mesh_db[o].get("faces", np.zeros((0, 3))), np.int32).reshape(-1, 3) for o in ids]
+            n_faces = np.array([t.shape[0] for t in tris], np.int32)
+            allf = np.ascontiguousarray(np.concatenate(tris, 0))
+            if allf.size == 0:
+                allf = np.zeros((1, 3), np.int32)
+            _lib.check(self.lib.suo_mesh_db_set_faces(self._h, n_faces.ctypes.data, allf.ctypes.data), "suo_mesh_db_set_faces")
 
     def close(self):
         if getattr(self, "_h", None) is not None:
@@ -133,6 +153,58 @@ class BopErrors:
         _lib.check(self.lib.suo_pose_errors_bop(self._h, n, idx.ctypes.data, Te.ctypes.data, Tg.ctypes.data, Kn.ctypes.data, mssd.ctypes.data, mspd.ctypes.data),
                    "suo_pose_errors_bop")
         return mssd, mspd
+
+    def render_depth(self, obj_ids, T, K, hw):
+        """float32 [n,H,W] depth images (mm, 0 where nothing is drawn) of the objects under poses [n,3|4,4] and K [n,3,3] or one [3,3]; ``hw`` = (H, W).
+        The rules are those of include/suo_hip.h (suo_render_depth)."""
+        n, (H, W) = len(obj_ids), hw
+        out = np.zeros((n, int(H), int(W)), np.float32)
+        idx = np.array([self._index[int(o)] for o in obj_ids], np.int32)
+        Tn = _pack34(T, n) if n else np.zeros((0, 12))
+        Kn = np.ascontiguousarray(np.broadcast_to(np.asarray(K, np.float64).reshape(-1, 3, 3), (n, 3, 3))).reshape(n, 9)
+        _lib.check(self.lib.suo_render_depth(self._h, n, idx.ctypes.data, Tn.ctypes.data, Kn.ctypes.data, int(W), int(H), out.ctypes.data), "suo_render_depth")
+        return out
+
+    def vsd(self, obj_ids, T_est, T_gt, K, depth_images, image_index, delta=15, taus=VSD_TAUS, normalized=True, return_counts=False):
+        """VSD errors [n, len(taus)] of n (object, estimated pose, ground-truth pose, camera matrix, test depth image) items: ``depth_images`` a sequence of
+        float32 [H,W] in mm, ``image_index[n]`` into it.  Both poses are rendered on the device; a call takes VSD_PAIRS_PER_CALL pairs with the images they
+        name.  ``return_counts``: also int64 [n, 2 + len(taus)] union, intersection and cost per tau."""
+        n = len(obj_ids)
+        taus = np.ascontiguousarray(taus, np.float64)
+        errors, counts = np.ones((n, len(taus)), np.float64), np.zeros((n, 2 + len(taus)), np.int64)
+        if n:
+            idx = np.array([self._index[int(o)] for o in obj_ids], np.int32)
+            Te, Tg = _pack34(T_est, n), _pack34(T_gt, n)
+            Kn = np.ascontiguousarray(np.broadcast_to(np.asarray(K, np.float64).reshape(-1, 3, 3), (n, 3, 3))).reshape(n, 9)
+            diam = np.array([float(self.models_info[int(o)]["diameter"]) for o in obj_ids], np.float64)
+            image_index = [int(i) for i in image_index]
+            H, W = np.asarray(depth_images[image_index[0]]).shape
+        for b in range(0, n, VSD_PAIRS_PER_CALL):
+            sl = slice(b, min(n, b + VSD_PAIRS_PER_CALL))
+            used = sorted(set(image_index[sl]))
+            test = np.ascontiguousarray(np.stack([np.asarray(depth_images[i], np.float32) for i in used]))
+            assert test.shape[1:] == (H, W), "the depth images of a call must have one size"
+            ii = np.array([used.index(i) for i in image_index[sl]], np.int32)
+            m = sl.stop - sl.start
+            e, c = np.zeros((m, len(taus)), np.float64), np.zeros((m, 2 + len(taus)), np.int64)
+            i_, te, tg, kk, dd = (np.ascontiguousarray(a[sl]) for a in (idx, Te, Tg, Kn, diam))
+            _lib.check(self.lib.suo_pose_errors_vsd(self._h, m, i_.ctypes.data, te.ctypes.data, tg.ctypes.data, kk.ctypes.data, int(W), int(H), len(used),
+                                                    test.ctypes.data, ii.ctypes.data, float(delta), len(taus), taus.ctypes.data, int(bool(normalized)),
+                                                    dd.ctypes.data, e.ctypes.data, c.ctypes.data), "suo_pose_errors_vsd")
+            errors[sl], counts[sl] = e, c
+        return (errors, counts) if return_counts else errors
+
+
+def overlapping_sphere_projections(radius, p1, p2):
+    """misc.overlapping_sphere_projections (misc.py:309-331): do the projections of two spheres of one radius about p1 and p2 overlap (approximated)."""
+    p1, p2 = np.asarray(p1, np.float64).reshape(3), np.asarray(p2, np.float64).reshape(3)
+    if p1[2] == 0 or p2[2] == 0:
+        return False
+    proj1 = (p1 / p1[2])[:2]
+    proj2 = (p2 / p2[2])[:2]
+    proj_dist = np.linalg.norm(proj1 - proj2)
+    proj_dist_thresh = radius * (1.0 / p1[2] + 1.0 / p2[2])
+    return bool(proj_dist < proj_dist_thresh)
 
 
 def kernel_partition(n, max_points, max_syms):
@@ -199,8 +271,11 @@ class Bop19Meter:
     ``targets``: the list of the targets file (``{"scene_id", "im_id", "obj_id", "inst_count"}``); ``scene_gt`` / ``scene_gt_info``:
     ``{scene_id: {im_id: [ground truths of scene_gt.json / scene_gt_info.json, unfiltered]}}``; ``im_width``: width of the split's images in pixels."""
 
-    def __init__(self, errors, targets, scene_gt, scene_gt_info, im_width):
+    def __init__(self, errors, targets, scene_gt, scene_gt_info, im_width, depth_loader=None, vsd_delta=15):
+        """``depth_loader(scene_id, im_id)`` -> float32 [H,W] depth in mm (BopDataset.read_depth): with it ``result()`` also carries VSD (``errors`` then
+        needs ``.vsd``, a BopErrors over a mesh database with faces) and the mean of the three terms; without it nothing changes."""
         self.errors = errors
+        self.depth_loader, self.vsd_delta = depth_loader, vsd_delta
         self.im_width = float(im_width)
         self.scene_gt, self.scene_gt_info = scene_gt, scene_gt_info
         self.targets = {}                                         # scene -> image -> obj -> inst_count, in the file's order
@@ -210,7 +285,7 @@ class Bop19Meter:
         self.n_estimates = 0                                      # the estimates that were scored (top inst_count of a target), after result()
 
     @classmethod
-    def from_dataset_tree(cls, errors, split_dir, targets_filename, im_width):
+    def from_dataset_tree(cls, errors, split_dir, targets_filename, im_width, depth_loader=None, vsd_delta=15):
         """Targets file + the ``scene_gt.json`` / ``scene_gt_info.json`` of every scene it names, read unfiltered."""
         with open(targets_filename, "r") as f:
             targets = json.load(f)
@@ -219,7 +294,7 @@ class Bop19Meter:
             for name, dst in (("scene_gt.json", scene_gt), ("scene_gt_info.json", scene_gt_info)):
                 with open(os.path.join(split_dir, f"{s:06d}", name), "r") as f:
                     dst[s] = {int(k): v for k, v in json.load(f).items()}
-        return cls(errors, targets, scene_gt, scene_gt_info, im_width)
+        return cls(errors, targets, scene_gt, scene_gt_info, im_width, depth_loader=depth_loader, vsd_delta=vsd_delta)
 
     def add(self, scene_id, im_id, obj_id, score, T_est, K):
         """One line of the results file: pose [3|4,4] object to camera in mm, the image's camera matrix."""
@@ -251,6 +326,39 @@ class Bop19Meter:
                                             np.stack([p[5] for p in pairs]))
             for (row, gt_id, _, _, _, _, overlap), e3, e2 in zip(pairs, mssd.tolist(), mspd.tolist()):
                 row["errors"][gt_id] = (e3 if overlap else float("inf"), e2)
+        return table
+
+    def vsd_table(self, taus=VSD_TAUS):
+        """eval_calc_errors.py:196-325 for the error type ``vsd``: the table of error_table with ``errors: {gt_id: [e per tau]}`` (already normalised by the
+        diameter inside the error).  A pair whose sphere projections do not overlap gets 1.0 for every tau without a device call (:295-312)."""
+        table, pairs, images, slot = {}, [], [], {}
+        for s, ims in self.targets.items():
+            for im, objs in ims.items():
+                for o, inst_count in objs.items():
+                    radius = 0.5 * self.errors.models_info[o]["diameter"]
+                    for est_id, est in top_estimates(self.ests.get((s, im, o), []), inst_count):
+                        row = {"est_id": est_id, "score": est["score"], "errors": {}}
+                        table.setdefault(s, {}).setdefault(im, {}).setdefault(o, []).append(row)
+                        for gt_id, gt in enumerate(self.scene_gt[s][im]):
+                            if gt["obj_id"] != o:
+                                continue
+                            Tg = np.hstack((np.reshape(gt["cam_R_m2c"], (3, 3)), np.reshape(gt["cam_t_m2c"], (3, 1)))).astype(np.float64)
+                            if not overlapping_sphere_projections(radius, est["T"][:, 3], Tg[:, 3]):
+                                row["errors"][gt_id] = [1.0] * len(taus)
+                                continue
+                            if (s, im) not in slot:
+                                slot[(s, im)] = len(images)
+                                images.append((s, im))
+                            pairs.append((row, gt_id, o, est["T"], Tg, est["K"], slot[(s, im)]))
+        # device calls over runs of pairs that share few images: the pairs come image by image, so a run of VSD_PAIRS_PER_CALL names a handful
+        for b in range(0, len(pairs), VSD_PAIRS_PER_CALL):
+            run = pairs[b:b + VSD_PAIRS_PER_CALL]
+            used = sorted({p[6] for p in run})
+            depth = [np.asarray(self.depth_loader(*images[i]), np.float32) for i in used]
+            errs = self.errors.vsd([p[2] for p in run], np.stack([p[3] for p in run]), np.stack([p[4] for p in run]), np.stack([p[5] for p in run]),
+                                   depth, [used.index(p[6]) for p in run], delta=self.vsd_delta, taus=taus, normalized=True)
+            for (row, gt_id, *_), e in zip(run, np.asarray(errs).tolist()):
+                row["errors"][gt_id] = e
         return table
 
     def normalised(self, table):
@@ -285,7 +393,9 @@ class Bop19Meter:
         return out, n_targets
 
     def result(self):
-        """``{"mssd": {"recalls": [10], "ar"}, "mspd": {...}, "n_targets", "n_estimates", "max_sym_disc_step"}``; ``ar`` is the mean of the ten recalls."""
+        """``{"mssd": {"recalls": [10], "ar"}, "mspd": {...}, "n_targets", "n_estimates", "max_sym_disc_step"}``; ``ar`` is the mean of the ten recalls.
+        With a depth loader also ``"vsd": {"recalls": [[10] per tau], "ar"}`` (100 recalls: the errors of each tau matched at each of the ten thresholds;
+        ``ar`` their mean) and ``"ar"``, the mean of the three terms."""
         table = self.normalised(self.error_table())
         out = {}
         for name, which, ths in (("mssd", 0, MSSD_THRESHOLDS), ("mspd", 1, MSPD_THRESHOLDS)):
@@ -294,4 +404,9 @@ class Bop19Meter:
             out["n_targets"] = int(n_targets)
         out["n_estimates"] = int(self.n_estimates)
         out["max_sym_disc_step"] = self.errors.max_sym_disc_step
+        if self.depth_loader is not None:
+            vtable = self.vsd_table(VSD_TAUS)                      # VSD errors are not normalised again (eval_calc_scores.py:246-258 touches mssd / mspd only)
+            rec = [self.recalls(vtable, t, VSD_THRESHOLDS)[0] for t in range(len(VSD_TAUS))]
+            out["vsd"] = {"recalls": rec, "ar": float(np.mean(rec))}
+            out["ar"] = float(np.mean([out["vsd"]["ar"], out["mssd"]["ar"], out["mspd"]["ar"]]))      # eval_bop19.py:240-241
         return out

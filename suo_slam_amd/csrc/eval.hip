@@ -184,6 +184,12 @@ extern "C" void suo_mesh_db_destroy(void* h) {
     if (db->off_dev) (void)hipFree(db->off_dev);
     if (db->sym_dev) (void)hipFree(db->sym_dev);
     if (db->sym_off_dev) (void)hipFree(db->sym_off_dev);
+    if (db->faces_dev) (void)hipFree(db->faces_dev);
+    if (db->face_off_dev) (void)hipFree(db->face_off_dev);
+    if (db->ras_dev) (void)hipFree(db->ras_dev);
+    if (db->ras_host) (void)hipHostFree(db->ras_host);
+    if (db->img_dev) (void)hipFree(db->img_dev);
+    if (db->test_dev) (void)hipFree(db->test_dev);
     if (db->scratch_dev) (void)hipFree(db->scratch_dev);
     if (db->scratch_host) (void)hipHostFree(db->scratch_host);
     if (db->stream) (void)hipStreamDestroy(db->stream);

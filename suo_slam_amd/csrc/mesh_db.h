@@ -18,12 +18,26 @@ struct MeshDb {
     std::vector<int> sym_off;     // [n_models + 1]
     double* sym_dev = nullptr;    // [sym_off.back()][12] row-major 3x4 [R|t]
     int* sym_off_dev = nullptr;
+    // triangles (csrc/raster.hip): absent until suo_mesh_db_set_faces; a model with no faces cannot be rendered
+    std::vector<int> face_off;    // [n_models + 1], empty until set
+    int* faces_dev = nullptr;     // [face_off.back()][3] vertex indices into the model's own points
+    int* face_off_dev = nullptr;
     // per-call scratch, grow-only
     char* scratch_dev = nullptr; char* scratch_host = nullptr; size_t scratch_cap = 0;
+    // the rasteriser's own, grow-only: staged poses + triangle records, and the rendered depth images (they stay on the device for csrc/eval_vsd.hip)
+    char* ras_dev = nullptr; char* ras_host = nullptr; size_t ras_cap = 0;
+    char* img_dev = nullptr; size_t img_cap = 0;
+    char* test_dev = nullptr; size_t test_cap = 0;      // the test depth images of a VSD call (csrc/eval_vsd.hip): device only, the host never reads them back
     hipStream_t stream = nullptr;
     std::mutex mu;
 };
 
 int ensure_scratch(MeshDb* db, size_t bytes);     // csrc/eval.hip
+
+// csrc/raster.hip.  check_render_args: the argument rules of suo_render_depth (SUO_ERR_ARG with the message set, nothing launched).
+// render_depth_locked: enqueue n renders on db->stream (caller holds db->mu and has checked the arguments); on return *img_dev is [n][height][width]
+// float32 depth and *rbox_dev [n][4] the renders' clipped pixel boxes (x0, y0, x1, y1; x0 > x1: nothing drawn), both valid until the next render.
+int check_render_args(const char* who, MeshDb* db, int n, const int* model_index, const double* T, const double* K, int width, int height);
+int render_depth_locked(MeshDb* db, int n, const int* model_index, const double* T, const double* K, int width, int height, float** img_dev, int** rbox_dev);
 
 }  // namespace suo

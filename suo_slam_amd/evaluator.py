@@ -62,7 +62,7 @@ def bop_eval_command(csv_path, outdir, targets_filename, repo_root="."):
 class Evaluator:
     def __init__(self, dataset, data_root, chkpt_path, nviews=1, no_network_cov=False, detection_type="saved", debug_gt_kp=False,
                  gt_cam_pose=False, no_prior_det=False, debug_saved_only=False, give_all_prior=False, out_dir=None, state_dict=None,
-                 do_add=None, seed=666, verbose=False, repo_root=".", run_bop_eval=False, frames_per_call=1, bop19=False):
+                 do_add=None, seed=666, verbose=False, repo_root=".", run_bop_eval=False, frames_per_call=1, bop19=False, bop19_vsd=False):
         """``dataset``: "ycbv" | "tless"; ``data_root``: the dataset directory of the BOP tree.  ``out_dir`` defaults to
         the checkpoint's directory like the reference.  ``do_add`` overrides the per-dataset default (the reference
         evaluates ADD only on YCB-V).  ``frames_per_call`` > 1 (single-view evaluation, nviews == 1, only): that many reference views go through
@@ -70,7 +70,9 @@ class Evaluator:
         (reset / process_view / collect_results per view, evaluate.py:338-395); results are the per-view loop's (geometry bit for bit on the same network
         outputs; the shared network call agrees with per-view calls to the network's tolerance: ObjectSLAM.process_views_single).
         ``bop19``: also report the BOP-19 MSSD and MSPD average recalls of exactly the poses written to the CSV (``run()["bop19"]`` and two lines of
-        summary.txt); needs a dataset with a targets file (T-LESS) -- ValueError otherwise.  VSD stays the external hand-off."""
+        summary.txt); needs a dataset with a targets file (T-LESS) -- ValueError otherwise.  VSD stays the external hand-off unless
+        ``bop19_vsd`` (with ``bop19``) is set: the third term is then rendered and scored on the device too (``run()["bop19"]["vsd"]`` and ``["ar"]``, the
+        ``AR_VSD`` and ``AR`` lines of summary.txt); needs the ``depth/`` folder of every scene of the split -- ValueError otherwise."""
         cfg = _SETTINGS[dataset]
         self.frames_per_call = int(frames_per_call) if nviews == 1 else 1
         self.model_path = out_dir if out_dir is not None else os.path.dirname(chkpt_path or ".")
@@ -78,13 +80,23 @@ class Evaluator:
         if debug_gt_kp:
             detection_type = "gt"                                     # evaluate.py:378-379
         self.dataset = bop.BopDataset(data_root, cfg["split"], bop_dset=dataset, ignore_symmetry=True)
-        self.mesh_db = bop.load_mesh_db(os.path.join(data_root, cfg["models"]))
+        mesh = bop.load_mesh_db(os.path.join(data_root, cfg["models"]), faces=bool(bop19 and bop19_vsd))
+        # what every other consumer saw before: no "faces"
+        self.mesh_db = {o: {k: v for k, v in m.items() if k != "faces"} for o, m in mesh.items()} if bop19 and bop19_vsd else mesh
         self.bop_errors = None
         if bop19:
             if self.dataset.targets_filename is None:
                 raise ValueError(f"bop19=True needs a targets file and the {dataset!r} {cfg['split']!r} split has none "
                                  "(the BOP-19 recall counts the targets of all_target_tless.json)")
-            self.bop_errors = bop_eval.BopErrors(self.mesh_db, bop_eval.load_models_info(os.path.join(data_root, cfg["models"])))
+            if bop19_vsd:
+                missing = [s for s in self.dataset.scene_ids() if not os.path.isdir(os.path.join(self.dataset.curr_root, f"{s:06d}", "depth"))]
+                if missing:
+                    raise ValueError(f"bop19_vsd=True needs the depth images of the {cfg['split']!r} split and scenes {missing} have no depth/ folder")
+            self.bop_errors = bop_eval.BopErrors(mesh, bop_eval.load_models_info(os.path.join(data_root, cfg["models"])))
+        elif bop19_vsd:
+            raise ValueError("bop19_vsd=True is the third term of bop19=True: set both")
+        self.bop19_vsd = bool(bop19 and bop19_vsd)
+        self._vsd_delta = bop_eval.VSD_DELTAS[dataset]
         self.debug_saved_only = debug_saved_only
         self.nviews, self.detection_type, self.debug_gt_kp, self.gt_cam_pose = nviews, detection_type, debug_gt_kp, gt_cam_pose
         self.verbose = verbose
@@ -174,7 +186,11 @@ class Evaluator:
         if self.bop_errors is not None and not self.debug_saved_only:
             first_scene = ds.scene_ids()[0]
             im_width = ds.read_img(first_scene, ds.view_ids(first_scene)[0]).shape[1]
-            bop19_meter = bop_eval.Bop19Meter.from_dataset_tree(self.bop_errors, ds.curr_root, ds.targets_filename, im_width)
+            if self.bop19_vsd:
+                bop19_meter = bop_eval.Bop19Meter.from_dataset_tree(self.bop_errors, ds.curr_root, ds.targets_filename, im_width, depth_loader=ds.read_depth,
+                                                                    vsd_delta=self._vsd_delta)
+            else:
+                bop19_meter = bop_eval.Bop19Meter.from_dataset_tree(self.bop_errors, ds.curr_root, ds.targets_filename, im_width)
         if not self.debug_saved_only:
             if self.do_add:
                 meter = EvalMeter(self.mesh_db)
@@ -292,6 +308,10 @@ class Evaluator:
                     for name in ("mssd", "mspd"):
                         f.write(f"\nBOP-19 AR_{name.upper()}: {out['bop19'][name]['ar']:.4f} (recalls " +
                                 " ".join(f"{r:.4f}" for r in out["bop19"][name]["recalls"]) + f"; {out['bop19']['n_targets']} targets)\n")
+                    if "vsd" in out["bop19"]:
+                        f.write(f"\nBOP-19 AR_VSD: {out['bop19']['vsd']['ar']:.4f} (recalls per tau: " +
+                                " ".join(f"{np.mean(r):.4f}" for r in out["bop19"]["vsd"]["recalls"]) + f"; delta {self._vsd_delta} mm)\n")
+                        f.write(f"\nBOP-19 AR: {out['bop19']['ar']:.4f}\n")
             out["csv_path"] = os.path.join(outdir, method + ".csv")
             with open(out["csv_path"], "w") as f:
                 f.writelines(csv_lines)
