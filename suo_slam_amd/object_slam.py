@@ -11,14 +11,14 @@ for the hot path: same public methods, argument order and state dictionaries (``
 
 What differs is where the work runs: the network, the keypoint masks, PnP for all objects of the frame
 and every LM round execute in libsuo_hip.so (HIP, gfx950); this file only keeps the reference's
-bookkeeping (thresholds, acceptance / removal / re-initialisation rules).  There is no CPU fallback.
+bookkeeping: the map state, the rules (thresholds, acceptance / removal / re-initialisation) and the host route
+of a pass (_run_kp_model), which restates the reference's data flow.  The routes that keep a view's keypoints on
+the device between the network and the poses are the base class, view_chain.DeviceRoutes.  There is no CPU fallback.
 """
 from __future__ import annotations
 
 from collections import defaultdict
 from time import time
-
-import os
 
 import numpy as np
 
@@ -26,9 +26,8 @@ from . import ba as _ba
 from . import lambdatwist as _lt
 from . import slam_score as _sc
 from .geometry import fix_K_for_bbox_ndc, fix_K_for_bbox_ndc_many, invert_SE3, normalize_uv, to4x4
+from .view_chain import CHI2_2DOF_95, DeviceRoutes, _on_stream, prior_arrays
 from .weights import NUM_KP
-
-CHI2_2DOF_95 = 5.991
 
 
 class AverageMeter:
@@ -173,24 +172,7 @@ class _EdgeRefs:
                 yield (v, o, k)
 
 
-def _on_stream(fn):
-    """Run a method's device work on the object's own (non-NULL) stream.  torch's default stream is the legacy NULL stream, on which libsuo_hip's network
-    entries BLOCK (include/suo_hip.h: "NULL = internal stream + blocking"): measured 13.3 ms of host time per 128-crop call that an asynchronous call returns
-    from in 0.3 ms.  Everything a method enqueues -- uploads, network, masks, geometry chain, read-backs -- goes to the one stream, so it stays ordered."""
-    import functools
-
-    @functools.wraps(fn)
-    def wrapped(self, *a, **kw):
-        st = getattr(self, "_gpu_stream", None)
-        if st is None:
-            return fn(self, *a, **kw)
-        import torch
-        with torch.cuda.stream(st):
-            return fn(self, *a, **kw)
-    return wrapped
-
-
-class ObjectSLAM:
+class ObjectSLAM(DeviceRoutes):
     def __init__(self, chkpt_path, mesh_db, no_network_cov=False, no_prior_det=False, pred_res=(256, 256),
                  debug_gt_kp=False, sfm_mode=False, single_view_mode=False, viz_cov=False, do_viz_extra=False,
                  global_opt_every=10, kp_var_thresh=0.2, bbox_thresh=0.9, bbox_inflate=0.0, manual_kp_std=0.005,
@@ -217,7 +199,8 @@ class ObjectSLAM:
         # single-view frames: masks -> compaction -> PnP -> acceptance -> graph -> LM as ONE device chain behind the network
         # (suo_slam_amd/frame_geom.py); False = the host route that restates the reference's data flow (three read-backs, Python lists)
         self.device_chain = bool(device_chain)
-        self._fg = None
+        super().__init__()                     # what this object keeps on the GPU between views (view_chain.DeviceRoutes)
+        self._score_store = None               # the scene's detections on the device, made by slam_score.chi2_counts at its first call; cleared with the map
         self._rng = np.random.default_rng(seed)
         self._pnp_seed = int(seed)
         self.reset()
@@ -263,9 +246,8 @@ class ObjectSLAM:
         self.obj_num_det_kps = defaultdict(int)
         self.remove_penalty = defaultdict(int)
         self.needs_opt = False
-        st = getattr(self, "_score_store", None)             # the scene's detections on the device (suo_slam_amd/slam_score.py)
-        if st is not None:
-            st.clear()
+        if self._score_store is not None:
+            self._score_store.clear()
 
     def num_views_processed(self):
         return len(self.cam_poses)
@@ -390,210 +372,6 @@ class ObjectSLAM:
             self.opt_time_meter.update(time() - t0)
             self.needs_opt = False
 
-    # ---------------------------------------------------------------------------------------------
-    def _process_view_single_device(self, view_id, img, K, obj_ids, bboxes, model_kps, model_kps_masks):
-        """A single-view frame (evaluate.py --nviews 1: __process_objects(False, ...) :464-593, __run_kp_model :1077-1167, then
-        optimize() :703-930 with the camera fixed at identity) with everything between the network and the poses on the device
-        (csrc/frame_geom.hip): one launch chain, one read-back.  Leaves the same state behind as the host route."""
-        import torch
-        from .frame_geom import FrameGeometry, kbbox_terms
-        from .pkpnet import keypoint_masks
-        L = len(obj_ids)
-        K_bbox = fix_K_for_bbox_ndc_many(K, bboxes).astype(np.float32)                                   # float32 container (:1082)
-        kinv, camk = kbbox_terms(K_bbox)
-        min_depth = np.array([0.5 * self.mesh_db[o]["diameter"] for o in obj_ids], dtype=np.float64)
-        if self._fg is None or self._fg.max_crops < L:
-            self._fg = FrameGeometry(max(16, L), 1)
-        its = (10, 10, 40, 40) if self.sfm_mode else (10, 10, 10, 10)                                    # (:843-846)
-        for _attempt in range(2):
-            pred = self.model(np.ascontiguousarray(img), [torch.as_tensor(np.asarray(bboxes, np.float32))], None, check=False)
-            vt = 1e30 if self.no_network_cov else self.kp_var_thresh
-            masks_dev = keypoint_masks(pred["uv"], pred["cov"], pred["kp_mask"], model_kps_masks, self.bbox_thresh, vt)
-            kps_dev = torch.as_tensor(np.ascontiguousarray(model_kps, dtype=np.float32)).to(pred["uv"].device)
-            self._fg.launch([0, L], pred["uv"], pred["cov"], masks_dev, kps_dev, kinv, camk, min_depth, seed=self._pnp_seed,
-                            use_cov=not self.no_network_cov, do_lm=True, its=its)
-            r = self._fg.fetch(copy=True)
-            if not self.model.call_range_exceeded(pred.call):  # (fp16 form only: an activation of this call left its range -> the network is on bf16x3 now, once more)
-                break
-            self.fp16_range_reissues += 1
-        self._pnp_seed += int(np.count_nonzero(r["n_kp"] >= 4))
-        self._ingest_single_view(view_id, obj_ids, bboxes, model_kps, model_kps_masks, K_bbox, r, 0, 0)
-
-    def _ingest_single_view(self, view_id, obj_ids, bboxes, model_kps, model_kps_masks, K_bbox, r, lo, frame):
-        """State of a single-view frame from the device chain's read-back (crops [lo, lo + L) of launch result r, frame index `frame`)."""
-        detection = {}
-        for k, obj_id in enumerate(obj_ids):
-            c = lo + k
-            m = r["mask"][c]
-            n = int(r["n_kp"][c])
-            cov_pred = None if self.no_network_cov else r["cov"][c][m]
-            pose = r["T_pnp"][c].copy() if r["accepted"][c] else None
-            if cov_pred is not None and cov_pred.size > 0:
-                std = np.sqrt(cov_pred[..., [0, 1], [0, 1]])
-                self.avg_std_meter.update(std.mean(), std.size)
-            self.obj_num_dets[obj_id] += 1
-            self.obj_num_det_kps[obj_id] += n
-            assert obj_id not in self.obj_poses and obj_id not in detection, f"Object {obj_id} is in detections twice! obj_id must be an instance label."
-            detection[obj_id] = {"bbox": bboxes[k], "model_kp_mask": model_kps_masks[k], "prior_uv": None, "pose": pose,
-                                 "inliers": r["inlier"][c, :n].copy(), "kp_mask": m, "model_kp": model_kps[k][m].astype(np.float64), "uv_gt": None,
-                                 "uv_pred": r["uv"][c][m].astype(np.float64), "cov_pred": cov_pred, "K": K_bbox[k].astype(np.float64),
-                                 "score": 0.0 if n == 0 else 1.0}
-            if pose is not None:
-                self.obj_poses[obj_id] = r["T_opt"][c].copy()
-        self.detections[view_id] = detection
-        self.cam_poses[view_id] = np.eye(4)[:3, :]
-        self.view_ids.append(view_id)
-        self.last_lm_stats = r["lm_stats"][frame].copy()
-        t0 = time()
-        self._cull_after_optimize([o for k, o in enumerate(obj_ids) if r["accepted"][lo + k]], False, view_id)
-        self.opt_time_meter.update(time() - t0)
-
-    def single_views_take_the_device_chain(self, views):
-        """True when process_views_single can run `views` as ONE device call (else it processes them one by one)."""
-        if not (self.single_view_mode and self.device_chain and self.model is not None and not self.debug_gt_kp and len(views) > 1):
-            return False
-        shape = np.asarray(views[0][1]).shape
-        if sum(len(v[3]) for v in views) > self.model.max_crops:      # more crops than the network was built for: view by view (ObjectSLAM(max_crops=...) lifts it)
-            return False
-        return all(0 < len(v[3]) <= 16 and np.asarray(v[1]).shape == shape and np.asarray(v[1]).dtype == np.uint8 for v in views)
-
-    @_on_stream
-    def process_views_single(self, views):
-        """Single-view evaluation (evaluate.py --nviews 1: reset / process_view / collect_results per reference view, evaluate.py:338-395) of SEVERAL
-        independent views in one device call: `views` = [(view_id, img, K, obj_ids, bboxes, model_kps, model_kps_masks, kp_masks), ...].
-        Returns [collect_results() of view 0, of view 1, ...] -- what the per-view loop returns: everything downstream of the network is bit for bit
-        the per-view loop's on the same network outputs (one geometry launch; the PnP sampler's keys continue from frame to frame as the per-view
-        loop advances its seed, csrc/pnp.hip); the shared network call picks its kernels by launch size, so its keypoints agree with the
-        per-view calls' to the network's tolerance (1e-5 of the reference either way).  tests/test_gpu_evaluator.py holds both.
-        = submit_views_single + collect_views_single; a caller with more batches to come submits the next one BEFORE collecting this one
-        (Evaluator.run does), so that the host's share of a batch -- bookkeeping of the results, preparation of the next -- runs under the device's.
-        Refuses to run with batches of an earlier submit_views_single still in flight: collect_views_single hands back the OLDEST batch, which would be zipped
-        against these views."""
-        if self.views_in_flight():
-            raise RuntimeError("process_views_single: %d batch(es) submitted earlier are still in flight -- collect_views_single() / drain_views_single() them first"
-                               % self.views_in_flight())
-        if not self.single_views_take_the_device_chain(views):
-            self.drain_views_single()
-            out = []
-            for v in views:
-                self.reset()
-                self.process_view(*v[:8])
-                out.append(self.collect_results(no_viz=True))
-            return out
-        self.submit_views_single(views)
-        return self.collect_views_single()
-
-    def views_in_flight(self):
-        return len(getattr(self, "_tickets", ()))
-
-    @_on_stream
-    def drain_views_single(self):
-        """Collect (and drop) whatever submit_views_single left in flight."""
-        while self.views_in_flight():
-            self.collect_views_single()
-
-    def _enqueue_views(self, prep, ff):
-        """Network + masks + geometry chain of one prepared batch on the current stream; nothing here waits for the device."""
-        import torch
-        from .frame_geom import FrameGeometry, kbbox_terms
-        from .pkpnet import keypoint_masks
-        Ltot, B = ff[-1], len(prep)
-        ring = getattr(self, "_fg_ring", None)
-        if ring is None:
-            ring = self._fg_ring = {"ctx": [None, None], "next": 0}
-        k = ring["next"]
-        ring["next"] = (k + 1) % 2
-        fg = ring["ctx"][k]
-        if fg is None or fg.max_crops < Ltot or fg.max_frames < B:
-            fg = ring["ctx"][k] = FrameGeometry(max(256, Ltot), max(32, B))
-        if getattr(self, "_seed_run", None) is None:
-            self._seed_run = torch.zeros(1, dtype=torch.int64, device=self.model.device)      # the sampler's running key, device-resident
-            self._seed_base = self._pnp_seed
-        K_all = np.concatenate([p[7] for p in prep])
-        kinv, camk = kbbox_terms(K_all)
-        min_depth = np.array([0.5 * self.mesh_db[o]["diameter"] for p in prep for o in p[3]], dtype=np.float64)
-        mm_all = np.concatenate([p[6] for p in prep]).astype(np.uint8)
-        kps_all = np.ascontiguousarray(np.concatenate([p[5] for p in prep]), dtype=np.float32)
-        pred = self.model.forward_frames([np.ascontiguousarray(p[1]) for p in prep], [np.asarray(p[4], np.float32) for p in prep], check=False,
-                                         extra=[mm_all, kps_all])
-        mm_dev, kps_dev = pred["extra"]
-        vt = 1e30 if self.no_network_cov else self.kp_var_thresh
-        masks_dev = keypoint_masks(pred["uv"], pred["cov"], pred["kp_mask"], mm_dev, self.bbox_thresh, vt)
-        its = (10, 10, 40, 40) if self.sfm_mode else (10, 10, 10, 10)
-        fg.launch(ff, pred["uv"], pred["cov"], masks_dev, kps_dev, kinv, camk, min_depth, seed=self._seed_base, seed_dev=self._seed_run,
-                  use_cov=not self.no_network_cov, do_lm=True, its=its)
-        return fg, pred, self.model.last_call()           # (the network call whose validity decides the batch's: PkpNet.call_range_exceeded)
-
-    @_on_stream
-    def submit_views_single(self, views):
-        """First half of process_views_single: prepare the batch and enqueue its device work.  Up to two batches may be in flight."""
-        import torch
-        assert self.single_views_take_the_device_chain(views), "submit_views_single: this batch does not take the device chain (process_views_single decides)"
-        assert self.views_in_flight() < 2, "two batches are already in flight: collect one first"
-        if not self.views_in_flight():
-            # nothing in flight: the host's seed is complete -- (re)base the device-resident key on it (another route may have advanced it meanwhile)
-            if getattr(self, "_seed_run", None) is not None and getattr(self, "_seed_expect", 0) + self._seed_base != self._pnp_seed:
-                self._seed_run.zero_()
-                self._seed_base, self._seed_expect = self._pnp_seed, 0
-            elif getattr(self, "_seed_run", None) is None:
-                self._seed_expect = 0
-        prep, ff = [], [0]
-        for view_id, img, K, obj_ids, bboxes, model_kps, model_kps_masks, _ in views:
-            obj_ids = np.asarray(obj_ids)
-            bboxes = np.array(bboxes, dtype=np.float64)
-            bboxes[:, [0, 1]] *= 1.0 - self.bbox_inflate                                               # (process_view, :368-369)
-            bboxes[:, [2, 3]] *= 1.0 + self.bbox_inflate
-            K_bbox = fix_K_for_bbox_ndc_many(K, bboxes).astype(np.float32)
-            prep.append((view_id, img, K, obj_ids, bboxes, np.asarray(model_kps), np.asarray(model_kps_masks, dtype=bool), K_bbox))
-            ff.append(ff[-1] + len(obj_ids))
-        assert ff[-1] <= self.model.max_crops, f"{ff[-1]} crops in one call, the network was built for {self.model.max_crops} (ObjectSLAM(max_crops=...))"
-        fg, pred, call = self._enqueue_views(prep, ff)
-        if not hasattr(self, "_tickets"):
-            self._tickets = []
-        self._tickets.append({"prep": prep, "ff": ff, "fg": fg, "pred": pred, "call": call, "t0": time()})
-
-    @_on_stream
-    def collect_views_single(self):
-        """Second half: wait for the OLDEST batch in flight, install its state view by view and return [collect_results() per view]."""
-        tk = self._tickets[0]
-        r = tk["fg"].fetch(copy=True)
-        if self.model.call_range_exceeded(tk["call"]):
-            # fp16 form only: this batch's own call left the range (a batch still in flight behind it cannot mark it) -- its results are invalid, and so are those
-            # of every batch enqueued after it: their PnP keys continue from its counts on the running key.  The network is on bf16x3 now: re-issue them all in
-            # order from the host's seed, which only ever counted valid batches.  Batches collected before it were valid and stay.
-            redo = self._tickets
-            self._tickets = []
-            self.fp16_range_reissues += len(redo)
-            import torch
-            torch.cuda.synchronize()                          # (the batches behind it drain before their contexts and the key are reused)
-            self._seed_run.zero_()
-            self._seed_base, self._seed_expect = self._pnp_seed, 0
-            for t in redo:
-                fg, pred, call = self._enqueue_views(t["prep"], t["ff"])
-                self._tickets.append({"prep": t["prep"], "ff": t["ff"], "fg": fg, "pred": pred, "call": call, "t0": t["t0"]})
-            tk = self._tickets[0]
-            r = tk["fg"].fetch(copy=True)
-        self._tickets.pop(0)
-        prep, ff = tk["prep"], tk["ff"]
-        n_solv = int(np.count_nonzero(r["n_kp"] >= 4))
-        self._pnp_seed += n_solv
-        self._seed_expect += n_solv
-        now = time()
-        per_view = (now - max(tk["t0"], getattr(self, "_last_collect", 0.0))) / len(prep)              # batches overlap: the time this batch added to the stream of results
-        self._last_collect = now
-        out = []
-        for f, (view_id, img, K, obj_ids, bboxes, model_kps, model_kps_masks, K_bbox) in enumerate(prep):
-            self.reset()
-            self.cam_K[view_id] = K
-            self.images[view_id] = img
-            self.all_time_num_views += 1
-            self._ingest_single_view(view_id, obj_ids, bboxes, model_kps, model_kps_masks, K_bbox, r, ff[f], f)
-            if self.all_time_num_views > 5:
-                self.track_time_meter.update(per_view)
-            self.needs_opt = False
-            out.append(self.collect_results(no_viz=True))
-        return out
-
     def _cull_after_optimize(self, graph_objs, curr_only, view_curr):
         """object_slam.py:904-930: objects whose centre fell behind 0.5 diameter in the current view, then objects with too few inliers."""
         if not curr_only:
@@ -675,17 +453,6 @@ class ObjectSLAM:
                 self.obj_poses[obj_id] = invert_SE3(to4x4(self.cam_poses[view_id])) @ detection[obj_id]["pose"]
 
     # ---------------------------------------------------------------------------------------------
-    def _frame_on_device(self, img):
-        """The frame of the current view on the device: uploaded once (pinned staging + copy kernel, pkpnet.PkpNet._to_device) and handed to
-        BOTH network passes of a SLAM view (the reference uploads the full frame per pass, lib/object_slam.py:1092-1098)."""
-        import torch
-        key = (id(img), getattr(img, "shape", None))
-        if getattr(self, "_frame_key", None) != key or self._frame_dev is None:
-            host = np.ascontiguousarray(img)
-            self._frame_dev = self.model._to_device(torch.from_numpy(host)) if isinstance(host, np.ndarray) and host.dtype == np.uint8 else host
-            self._frame_key = key
-        return self._frame_dev
-
     def _run_kp_model(self, view_id, img, K, obj_ids, bboxes, model_kps, model_kps_masks, kp_masks_gt=None, uv_gt=None, prior_dets=None):
         """object_slam.py:1077-1167.  Network + masks on the GPU, then ONE batched PnP launch for all
         objects of the frame (the reference loops lambdatwist.pnp per object)."""
@@ -697,15 +464,7 @@ class ObjectSLAM:
         if not self.debug_gt_kp or self.run_network_in_debug:
             import torch
             from .pkpnet import keypoint_masks
-            prior_uv = prior_mask = None
-            if prior_dets:
-                # the reference stamps the heat-maps on the host (make_prior_kp_input) and uploads [L,41,256,256];
-                # here the projected keypoints go to the device and the stamps are rendered while the crop is staged
-                prior_uv = np.zeros((L, NUM_KP, 2), dtype=np.float32)
-                prior_mask = np.zeros((L, NUM_KP), dtype=np.uint8)
-                for k, obj_id in enumerate(obj_ids):
-                    if obj_id in prior_dets:
-                        prior_uv[k], prior_mask[k] = prior_dets[obj_id]
+            prior_uv, prior_mask = prior_arrays(obj_ids, prior_dets) if prior_dets else (None, None)
             if self.no_network_cov:
                 bt, vt = self.bbox_thresh, 1e30
             else:
@@ -762,216 +521,6 @@ class ObjectSLAM:
                         "uv_pred": uv_pred, "cov_pred": cov_pred, "K": K_kp,
                         "score": 0.0 if inliers.size == 0 else float(inliers.astype(np.float32).mean())})
         return ret
-
-    def _run_kp_model_chain(self, img, K_bbox, obj_ids, bboxes, model_kps, model_kps_masks, kp_masks_gt, uv_gt, prior_dets):
-        """__run_kp_model (object_slam.py:1077-1167) of a SLAM pass with everything between the network and the PnP poses on the device: network -> masks ->
-        compaction -> normalisation -> batched PnP -> acceptance as ONE stream-ordered chain (suo_frame_geom_launch with do_lm = 0: the camera hypotheses of
-        :975-1072 continue on the host) and ONE read-back, where the host route makes three read-backs, compacts in Python and ships the points back for the PnP
-        launch.  Same kernels on the same numbers: PnP poses and statuses are those of the host route bit for bit (tests/test_gpu_frame_geom.py)."""
-        import torch
-        from .frame_geom import FrameGeometry, kbbox_terms
-        from .pkpnet import keypoint_masks
-        L = len(obj_ids)
-        prior_uv = prior_mask = None
-        if prior_dets:
-            prior_uv = np.zeros((L, NUM_KP, 2), dtype=np.float32)
-            prior_mask = np.zeros((L, NUM_KP), dtype=np.uint8)
-            for k, obj_id in enumerate(obj_ids):
-                if obj_id in prior_dets:
-                    prior_uv[k], prior_mask[k] = prior_dets[obj_id]
-        kinv, camk = kbbox_terms(K_bbox)
-        min_depth = np.array([0.5 * self.mesh_db[o]["diameter"] for o in obj_ids], dtype=np.float64)
-        if self._fg is None or self._fg.max_crops < L:
-            self._fg = FrameGeometry(max(16, L), 1)
-        vt = 1e30 if self.no_network_cov else self.kp_var_thresh
-        gt_uv = gt_mask = None
-        if self.debug_gt_kp:                                  # (debug_gt_on_device: the same draws, in the same order, as the host route's :1129-1131)
-            gt_mask = np.ascontiguousarray(kp_masks_gt, dtype=np.uint8)
-            gt_uv = np.zeros((L, NUM_KP, 2), dtype=np.float32)
-            for k in range(L):
-                m = gt_mask[k].astype(bool)
-                u = uv_gt[k][m].astype(np.float64)
-                gt_uv[k][m] = (u + self._rng.normal(scale=0.01, size=u.shape)).astype(np.float32)
-        # every small host array of the pass in ONE pinned block and ONE stream-ordered copy kernel, enqueued BEFORE the network: a pageable .to(device) per array
-        # blocks the host until it has run -- in front of the network that is tens of microseconds each on the critical path, behind it a wait for the network
-        host_arrays = [np.ascontiguousarray(model_kps, dtype=np.float32), np.ascontiguousarray(bboxes, dtype=np.float32),
-                       gt_mask if gt_uv is not None else np.ascontiguousarray(model_kps_masks, dtype=np.uint8)]
-        if gt_uv is not None:
-            host_arrays.append(gt_uv)
-        if prior_uv is not None:
-            host_arrays += [prior_uv, prior_mask]
-        for _attempt in range(2):
-            frame = self._frame_on_device(img)
-            st = self.model.stage_block(host_arrays)
-            kps_dev, bx_dev, mm_dev = st[0], st[1], st[2]
-            puv_dev, pmk_dev = (st[-2], st[-1]) if prior_uv is not None else (None, None)
-            pred = self.model(frame, [bx_dev], None, prior_uv=puv_dev, prior_mask=pmk_dev, check=False)
-            if gt_uv is not None:
-                uv_dev, masks_dev = st[3], mm_dev
-            else:
-                uv_dev, masks_dev = pred["uv"], keypoint_masks(pred["uv"], pred["cov"], pred["kp_mask"], mm_dev, self.bbox_thresh, vt)
-            self._fg.launch([0, L], uv_dev, pred["cov"], masks_dev, kps_dev, kinv, camk, min_depth, seed=self._pnp_seed,
-                            use_cov=not self.no_network_cov, do_lm=False)
-            r = self._fg.fetch(copy=True)
-            if not self.model.call_range_exceeded(pred.call):  # (fp16 form only: the fetch synchronised; on True the network is on bf16x3 now, once more)
-                break
-            self.fp16_range_reissues += 1
-        self._pnp_seed += int(np.count_nonzero(r["n_kp"] >= 4))
-        return self._kp_det_from_chain(r, obj_ids, model_kps, K_bbox, uv_gt)
-
-    def _kp_det_from_chain(self, r, obj_ids, model_kps, K_bbox, uv_gt):
-        """What __run_kp_model returns per object (:1150-1165), from a chain read-back."""
-        ret = []
-        for k, obj_id in enumerate(obj_ids):
-            m = r["mask"][k]
-            n = int(r["n_kp"][k])
-            self.obj_num_dets[obj_id] += 1
-            self.obj_num_det_kps[obj_id] += n
-            ret.append({"pose": r["T_pnp"][k].copy() if r["accepted"][k] else None, "inliers": np.ones(n, dtype=bool), "kp_mask": m,
-                        "model_kp": model_kps[k][m].astype(np.float64), "uv_gt": uv_gt, "uv_pred": r["uv"][k][m].astype(np.float64),
-                        "cov_pred": None if self.no_network_cov else r["cov"][k][m], "K": K_bbox[k].astype(np.float64), "score": 0.0 if n == 0 else 1.0})
-        return ret
-
-    def _slam_view_takes_the_vote_chain(self, view_id, cam_pose, n_non_sym, n_sym):
-        """Both passes of a SLAM view as ONE device chain (pass A -> PnP -> hypothesis vote -> prior projection -> pass B): a tracking view of a running map with
-        objects of both kinds, on the routes that keep their keypoints on the device.  SUO_SLAM_VOTE_CHAIN=0: the host votes between the passes (A/B)."""
-        return (self.device_chain and self.model is not None and (not self.debug_gt_kp or self.debug_gt_on_device) and not self.single_view_mode and cam_pose is None
-                and not self.no_prior_det and 0 < n_non_sym <= 16 and 0 < n_sym <= 16 and self.num_views_processed() > 0 and view_id not in self.cam_poses
-                and os.environ.get("SUO_SLAM_VOTE_CHAIN", "1") not in ("", "0"))
-
-    def _process_view_slam_chain(self, view_id, img, K, A, B):
-        """A SLAM view's two network passes with NOTHING on the host between them (round 6; lib/object_slam.py:464-593 twice, :975-1072 between): pass A (the
-        non-symmetric objects) -> masks -> compaction -> PnP -> acceptance (csrc/frame_geom.hip) -> camera-hypothesis vote + projection of the symmetric objects' prior
-        keypoints (csrc/slam_vote.hip) -> pass B with device-rendered priors -> its PnP, enqueued back to back; the host reads pass A's block and the vote while pass B
-        runs and does pass A's bookkeeping under it.  A / B = (obj_ids, bboxes, model_kps, model_kps_masks, kp_masks, uv_gt) of the two passes.  Leaves the state the
-        two _process_objects calls leave; when no hypothesis reaches four inliers (:1067) it returns False with pass A installed, and the caller continues as the
-        reference does (__backup_estimate_camera_pose, then pass B again with that pose)."""
-        import ctypes as C
-        import torch
-        from . import _lib
-        from .frame_geom import FrameGeometry, kbbox_terms
-        from .pkpnet import keypoint_masks
-        lib = _lib.lib()
-        ids_a, bb_a, kps_a, mm_a, gtm_a, gtu_a = A
-        ids_b, bb_b, kps_b, mm_b, gtm_b, gtu_b = B
-        La, Lb = len(ids_a), len(ids_b)
-        if self._fg is None or self._fg.max_crops < max(La, Lb):
-            self._fg = FrameGeometry(max(16, La, Lb), 1)
-        if getattr(self, "_fg2", None) is None or self._fg2.max_crops < max(La, Lb):
-            self._fg2 = FrameGeometry(max(16, La, Lb), 1)
-        vt = 1e30 if self.no_network_cov else self.kp_var_thresh
-        debug = self.debug_gt_kp
-        P = lambda t: C.c_void_p(t.data_ptr())  # noqa: E731
-
-        def gt_arrays(L, gtm, gtu):                           # (debug_gt_on_device: the host route's draws, in its order -- pass A's objects, then pass B's)
-            mask = np.ascontiguousarray(gtm, dtype=np.uint8)
-            uv = np.zeros((L, NUM_KP, 2), dtype=np.float32)
-            for k in range(L):
-                m = mask[k].astype(bool)
-                u = gtu[k][m].astype(np.float64)
-                uv[k][m] = (u + self._rng.normal(scale=0.01, size=u.shape)).astype(np.float32)
-            return mask, uv
-        # pass A's host arrays now; pass B's and the vote's block are prepared AFTER pass A is enqueued, under its GPU time
-        Kb_a = fix_K_for_bbox_ndc_many(K, bb_a).astype(np.float32)            # float32 container (:1082)
-        kinv_a, camk_a = kbbox_terms(Kb_a)
-        md_a = np.array([0.5 * self.mesh_db[o]["diameter"] for o in ids_a], dtype=np.float64)
-        host_a = [np.ascontiguousarray(kps_a, dtype=np.float32), np.ascontiguousarray(bb_a, dtype=np.float32), np.ascontiguousarray(mm_a, dtype=np.uint8)]
-        if debug:
-            host_a += list(gt_arrays(La, gtm_a, gtu_a))
-        rng_after_a = self._rng.bit_generator.state if debug else None      # (a pass B that has to be issued again draws its noise again: from here)
-        host_b = None
-        for _attempt in range(2):
-            frame = self._frame_on_device(img)
-            sa = self.model.stage_block(host_a)
-            dev = sa[0].device
-            seed_run = torch.zeros(1, dtype=torch.int64, device=dev)
-            # ---- pass A
-            pa = self.model(frame, [sa[1]], None, check=False, out_slot="slam A")
-            uv_a, mk_a = (sa[4], sa[3]) if debug else (pa["uv"], keypoint_masks(pa["uv"], pa["cov"], pa["kp_mask"], sa[2], self.bbox_thresh, vt))
-            self._fg.launch([0, La], uv_a, pa["cov"], mk_a, sa[0], kinv_a, camk_a, md_a, seed=self._pnp_seed, use_cov=not self.no_network_cov, do_lm=False,
-                            seed_dev=seed_run)
-            ra_dev = self._fg.device_result()
-            if host_b is None:
-                Kb_b = fix_K_for_bbox_ndc_many(K, bb_b).astype(np.float32)
-                kinv_b, camk_b = kbbox_terms(Kb_b)
-                md_b = np.array([0.5 * self.mesh_db[o]["diameter"] for o in ids_b], dtype=np.float64)
-                # the vote's host block (include/suo_hip.h: SUO_SLAM_VOTE_BLOCK): map poses and intrinsics of both passes' objects
-                blk = np.zeros(704)
-                for k, o in enumerate(ids_a):
-                    if o in self.obj_poses:
-                        blk[k] = 1.0
-                        blk[16 + 12 * k:28 + 12 * k] = np.asarray(self.obj_poses[o], dtype=np.float64)[:3, :4].reshape(-1)
-                    blk[208 + 9 * k:217 + 9 * k] = Kb_a[k].astype(np.float64).reshape(-1)
-                for k, o in enumerate(ids_b):
-                    if o in self.obj_poses:
-                        blk[352 + k] = 1.0
-                        blk[368 + 12 * k:380 + 12 * k] = np.asarray(self.obj_poses[o], dtype=np.float64)[:3, :4].reshape(-1)
-                    blk[560 + 9 * k:569 + 9 * k] = fix_K_for_bbox_ndc(K, bb_b[k]).reshape(-1)       # (double, as the reference projects with it: :505)
-                host_b = [np.ascontiguousarray(kps_b, dtype=np.float32), np.ascontiguousarray(bb_b, dtype=np.float32), np.ascontiguousarray(mm_b, dtype=np.uint8), blk]
-                if debug:
-                    host_b += list(gt_arrays(Lb, gtm_b, gtu_b))
-            sb = self.model.stage_block(host_b)
-            puv = torch.empty((Lb, NUM_KP, 2), dtype=torch.float32, device=dev)
-            pmk = torch.empty((Lb, NUM_KP), dtype=torch.uint8, device=dev)
-            vout = torch.empty(32, dtype=torch.float64, device=dev)
-            # ---- vote + priors, on the stream, behind pass A's PnP
-            _lib.check(lib.suo_slam_vote(La, ra_dev.T_pnp, ra_dev.accepted, ra_dev.n_kp, P(uv_a), P(pa["cov"]), P(mk_a), P(sa[0]), P(sb[3]), Lb, P(sb[0]), P(sb[2]),
-                                         int(not self.no_network_cov), float(self.manual_kp_std) ** 2, CHI2_2DOF_95, 4, P(puv), P(pmk), P(vout),
-                                         C.c_void_p(_lib.current_stream_ptr())), "suo_slam_vote")
-            if getattr(self, "_vote_pin", None) is None:
-                self._vote_pin = (torch.empty(32, dtype=torch.float64).pin_memory(), torch.empty((16, NUM_KP, 2), dtype=torch.float32).pin_memory(),
-                                  torch.empty((16, NUM_KP), dtype=torch.uint8).pin_memory(), torch.cuda.Event())
-            v_pin, puv_pin, pmk_pin, v_ev = self._vote_pin
-            v_pin.copy_(vout, non_blocking=True)
-            puv_pin[:Lb].copy_(puv, non_blocking=True)
-            pmk_pin[:Lb].copy_(pmk, non_blocking=True)
-            v_ev.record()
-            # ---- pass B: priors rendered on the device from what the vote kernel wrote; nothing above has waited
-            pb = self.model(frame, [sb[1]], None, prior_uv=puv, prior_mask=pmk, check=False, out_slot="slam B")
-            uv_b, mk_b = (sb[5], sb[4]) if debug else (pb["uv"], keypoint_masks(pb["uv"], pb["cov"], pb["kp_mask"], sb[2], self.bbox_thresh, vt))
-            self._fg2.launch([0, Lb], uv_b, pb["cov"], mk_b, sb[0], kinv_b, camk_b, md_b, seed=self._pnp_seed, use_cov=not self.no_network_cov, do_lm=False,
-                             seed_dev=seed_run)
-            # ---- the host, under pass B: pass A's block and the vote
-            ra = self._fg.fetch(copy=False)                   # (views into the pinned block: everything the state keeps is copied out per object below)
-            v_ev.synchronize()
-            vote = v_pin.numpy().copy()
-            prior_uv_h, prior_mask_h = puv_pin[:Lb].numpy().copy(), pmk_pin[:Lb].numpy().copy()
-            if not self.model.call_range_exceeded(pa.call):   # (pass A's own call: pass B, still running, cannot mark it)
-                break
-            # (fp16 form only) pass A left the range: its results -- and the priors pass B is running on -- are invalid.  Let pass B drain, then both again on bf16x3
-            self._fg2.fetch(copy=False)
-            self.fp16_range_reissues += 2
-        assert vote[31] == 0.0, "NaN in information matrix"
-        n_solv_a = int(np.count_nonzero(ra["n_kp"] >= 4))
-        best = int(vote[12])
-        hyp_ids = [o for k, o in enumerate(ids_a) if vote[15 + k] >= 0]
-        # ---- pass A into the state, with the device's vote -- while pass B runs
-        self._pnp_seed += n_solv_a
-        det_a = self._kp_det_from_chain(ra, ids_a, kps_a, Kb_a, gtu_a)
-        cam = None
-        if best >= 0:
-            cam = np.eye(4)
-            cam[:3, :4] = vote[:12].reshape(3, 4)
-        self.last_cam_hypotheses = ({"obj_ids": hyp_ids, "counts": [int(vote[15 + k]) for k in range(La) if vote[15 + k] >= 0], "best_num_inliers": int(vote[14])}
-                                    if hyp_ids else None)
-        self._install_kp_detections(view_id, ids_a, bb_a, mm_a, det_a, None, cam_vote=cam)
-        rb = self._fg2.fetch(copy=False)
-        b_invalid = self.model.call_range_exceeded(pb.call)   # (fp16 form only: pass B left the range, pass A did not -- its results stand)
-        if b_invalid:
-            self.fp16_range_reissues += 1
-        if cam is None or b_invalid:
-            # no hypothesis reached four inliers: the reference falls back to the bbox-centroid pose and THEN runs pass B -- with priors this chain did not have.
-            # Pass B's speculative results are dropped (its PnP consumed sampler keys past the host's seed, which never counted them) and the caller issues the
-            # pass again, one at a time; the noise draws of its ground-truth keypoints are taken back so that it draws them again.
-            if rng_after_a is not None:
-                self._rng.bit_generator.state = rng_after_a
-            return False
-        # ---- pass B into the state
-        self._pnp_seed += int(np.count_nonzero(rb["n_kp"] >= 4))
-        det_b = self._kp_det_from_chain(rb, ids_b, kps_b, Kb_b, gtu_b)
-        prior_det_uv = {o: prior_uv_h[k] for k, o in enumerate(ids_b) if prior_mask_h[k].any()}
-        self._install_kp_detections(view_id, ids_b, bb_b, mm_b, det_b, prior_det_uv)
-        return True
 
     # ---------------------------------------------------------------------------------------------
     def _estimate_camera_pose(self, view_id, min_num_inliers=4):
