@@ -506,6 +506,32 @@ int suo_debug_lm_routes(const suo_ba_problem* problems, int n_problems, int* rou
 int suo_pose_covariances(const suo_ba_problem* problem, double* cam_cov /*[n_cam][36]*/, double* obj_cov /*[n_obj][36]*/, int* status /*[2]: NaN cam blocks, NaN obj blocks*/);
 int suo_pose_covariances_batch(const suo_ba_problem* problems, int n, double* const* cam_cov, double* const* obj_cov, int* status /*[n][2]*/);
 
+/* ---- cross blocks and relative-pose covariances of vertex pairs ---------------------------------------------------------------------
+ * The marginal blocks above are expressed relative to whichever camera is fixed (the gauge).  The pose of an object in a camera's frame, and of one object
+ * relative to another, do not depend on that choice, and neither do their covariances; they need the off-diagonal blocks of Sigma.
+ *   Vertices.    One index codes a vertex: camera c is c, object o is n_cam + o.
+ *   Perturbation. The library's: left update exp(delta) * T, delta = [omega, upsilon].  Ad(T) = [[R, 0], [[t]x R, R]].
+ *   Pairs.       (camera c, object o), in either order:  T_OtoC = T_c * T_o,      delta_rel = delta_c + Ad(T_c) delta_o,
+ *                                                         rel = Sigma_cc + A Sigma_oo A^T + Sigma_co A^T + A Sigma_oc,   A = Ad(T_c)
+ *                (object a, object b):                    T_AtoB = T_b^-1 * T_a,   delta_rel = B (delta_a - delta_b),
+ *                                                         rel = B (Sigma_aa + Sigma_bb - Sigma_ab - Sigma_ba) B^T,       B = Ad(T_b^-1)
+ *                (camera, camera): SUO_ERR_ARG, nothing is launched.
+ *   cross [n_pair][36]  Sigma_ab: rows are vertex a, columns are vertex b, row-major.  (a, a) is the marginal block.
+ *   rel   [n_pair][36]  as above, exactly symmetric.  Either may be NULL.
+ *   - A fixed vertex contributes zeros: a pair with the gauge camera reduces to A Sigma_oo A^T, a pair with a fixed object to Sigma_cc, two fixed objects to 36 zeros.
+ *   - Both blocks of a pair are 36 NaNs if a vertex of the pair is NaN in the marginal call; status[2] counts those pairs.
+ *   - An index outside [0, n_cam + n_obj), a (camera, camera) pair or n_pair < 0: SUO_ERR_ARG.  Duplicate pairs are allowed.  n_pair == 0 is suo_pose_covariances.
+ *   - cam_cov / obj_cov / status[0..1] are those of suo_pose_covariances, bit for bit; more than 16 free objects next to free cameras: SUO_ERR_ARG, as there.
+ * Buffers, blocking and arena as suo_pose_covariances.  Kernels (csrc/pose_cov.hip, fp64, fixed summation order, two calls give the same bits, a problem's pairs
+ * do not depend on the rest of the batch): without a free camera or without a free object every cross block between two vertices is zero; in the coupled form the
+ * camera waves write Sigma_co = -(Y Sigma_OO)[:, o] -- dense over the objects, also where the camera does not see the object -- and Sigma_ab comes from Sigma_OO;
+ * one small kernel behind them propagates.  The batch form takes one pointer (and one n_pair) per problem and status [n][3]. */
+int suo_pose_covariances_pairs(const suo_ba_problem* problem, int n_pair, const int32_t* pair_a, const int32_t* pair_b, double* cam_cov /*[n_cam][36]*/,
+                               double* obj_cov /*[n_obj][36]*/, double* cross /*[n_pair][36]*/, double* rel /*[n_pair][36]*/,
+                               int* status /*[3]: NaN cam blocks, NaN obj blocks, NaN pairs*/);
+int suo_pose_covariances_pairs_batch(const suo_ba_problem* problems, int n, const int* n_pair, const int32_t* const* pair_a, const int32_t* const* pair_b,
+                                     double* const* cam_cov, double* const* obj_cov, double* const* cross, double* const* rel, int* status /*[n][3]*/);
+
 /* ---- phase-wise bundle adjustment for the multi-GPU global pose graph ------------------------
  * Cameras are partitioned across GPUs; each rank builds a context over ITS cameras' edges and ALL objects, and
  * a host driver (suo_slam_amd/ba_dist.py) runs g2o's LM schedule with two all-reduces per trial (RCCL):

@@ -101,3 +101,41 @@ def pose_covariances_batch(problems):
 def pose_covariances(*args, **kw):
     """The arguments of optimize(); returns (cam_cov [C,6,6], obj_cov [O,6,6], status [2]) at the poses and inlier flags given."""
     return pose_covariances_batch([Problem(*args, **kw)])[0]
+
+
+def pose_covariances_pairs_batch(problems, pairs):
+    """pose_covariances_batch plus, per problem, the cross block and the relative-pose covariance of the vertex pairs in pairs[i] ([P,2] ints; camera c is c,
+    object o is n_cam + o; (camera, object) in either order or (object, object)): cross [P,6,6] = Sigma_ab, rows vertex a; rel [P,6,6] = the covariance of
+    T_OtoC = T_c T_o, or of T_AtoB = T_b^-1 T_a (include/suo_hip.h: suo_pose_covariances_pairs).  Per problem (cam_cov, obj_cov, cross, rel, status [3] = NaN
+    camera blocks, NaN object blocks, NaN pairs).  One call for the whole list; the problems are not modified."""
+    if not problems:
+        return []
+    if len(pairs) != len(problems):
+        raise ValueError("pose_covariances_pairs_batch: one pair list per problem")
+    lib = _lib.lib()
+    _lib.require_gpu()
+    n = len(problems)
+    arr = (_lib.BaProblem * n)()
+    out, keep = [], []
+    ptrs = [(C.c_void_p * n)() for _ in range(6)]           # pair_a, pair_b, cam_cov, obj_cov, cross, rel
+    n_pair = np.zeros(n, np.int32)
+    status = np.zeros((n, 3), np.int32)
+    for i, (s, p, pr) in enumerate(zip(arr, problems, pairs)):
+        p._fill(s)
+        pr = np.asarray(pr, np.int32).reshape(-1, 2)
+        a, b = np.ascontiguousarray(pr[:, 0]), np.ascontiguousarray(pr[:, 1])
+        P = len(pr)
+        bufs = (a, b, np.zeros((len(p.cam_T), 6, 6)), np.zeros((len(p.obj_T), 6, 6)), np.zeros((P, 6, 6)), np.zeros((P, 6, 6)))
+        for col, buf in zip(ptrs, bufs):
+            col[i] = buf.ctypes.data
+        n_pair[i] = P
+        keep.append((a, b))
+        out.append(bufs[2:] + (status[i],))
+    _lib.check(lib.suo_pose_covariances_pairs_batch(C.cast(arr, C.c_void_p), n, n_pair.ctypes.data, *[C.cast(c, C.c_void_p) for c in ptrs], status.ctypes.data),
+               "suo_pose_covariances_pairs_batch")
+    return out
+
+
+def pose_covariances_pairs(*args, pairs, **kw):
+    """The arguments of optimize() plus pairs [P,2]; returns (cam_cov [C,6,6], obj_cov [O,6,6], cross [P,6,6], rel [P,6,6], status [3])."""
+    return pose_covariances_pairs_batch([Problem(*args, **kw)], [pairs])[0]

@@ -35,13 +35,14 @@ struct Prep {
 struct Staged {
     std::vector<Prep> prep;
     size_t o_structs = 0, in_end = 0, out_end = 0, total = 0;      // arena: [LmProblem structs | inputs | in_end: outputs | out_end: scratch | total]
-    size_t cov_begin = 0, cov_end = 0;                             // inside the scratch: every problem's cam_cov / obj_cov / cov_status (csrc/pose_cov_api.hip reads them back)
+    size_t cov_begin = 0, cov_end = 0;                             // inside the scratch: every problem's cam_cov / obj_cov / cov_status / cov_cross / cov_rel (csrc/pose_cov_api.hip reads them back)
 };
 
 // `who`: the entry the caller called, for the error texts.  prep_problem is the host half of stage_problems (validation, stable sort by pair, pair CSR).
 int prep_problem(const suo_ba_problem& q, int index, Prep& P, const char* who);
-// cov_form (optional, [n_prob]): LmProblem::cov_form of every problem (csrc/pose_cov_api.hip: plan_cov_batch)
-int stage_problems(const suo_ba_problem* probs, int n_prob, Arena& A, Staged& st, const char* who, const int* cov_form = nullptr);
+// cov_form (optional, [n_prob]): LmProblem::cov_form of every problem (csrc/pose_cov_api.hip: plan_cov_batch); pairs (optional): its vertex pairs
+struct CovPairs { const int* n; const int32_t* const* a; const int32_t* const* b; };      // per problem: the count and the two index lists
+int stage_problems(const suo_ba_problem* probs, int n_prob, Arena& A, Staged& st, const char* who, const int* cov_form = nullptr, const CovPairs* pairs = nullptr);
 int fetch_results(suo_ba_problem* probs, int n_prob, Arena& A, Staged& st);
 
 }  // namespace suo

@@ -74,7 +74,7 @@ int prep_problem(const suo_ba_problem& q, int index, Prep& P, const char* who) {
 
 // The arena layout of a batch, every array on a 16-byte boundary: the structs, then every problem's inputs (one H2D up to in_end), then the outputs that are not
 // inputs too (one D2H up to out_end), then device-only scratch.  Each Prep::S gets its sizes and its addresses, counted from `base`.
-static void lay_out(const suo_ba_problem* probs, int n_prob, char* base, Staged& st) {
+static void lay_out(const suo_ba_problem* probs, int n_prob, const CovPairs* pairs, char* base, Staged& st) {
     Layout L;
     auto put = [&](auto*& p, size_t n) { p = (std::remove_reference_t<decltype(p)>)((uintptr_t)base + L.take(sizeof(*p) * n)); };
     st.o_structs = L.take(sizeof(LmProblem) * (size_t)n_prob);
@@ -88,6 +88,8 @@ static void lay_out(const suo_ba_problem* probs, int n_prob, char* base, Staged&
         put(S.pair_cam, NP); put(S.pair_obj, NP); put(S.pair_start, NP + 1);
         put(S.cam_pair_ptr, C + 1); put(S.cam_pair_idx, NP); put(S.obj_pair_ptr, O + 1); put(S.obj_pair_idx, NP);
         put(S.cam_obj_pair, C * O);
+        S.n_cpair = pairs ? pairs->n[i] : 0;
+        put(S.cpair_a, (size_t)S.n_cpair); put(S.cpair_b, (size_t)S.n_cpair);
     }
     st.in_end = L.off;
     for (int i = 0; i < n_prob; ++i) { LmProblem& S = st.prep[i].S; put(S.edge_chi2, S.n_edge); put(S.stats, 4); }
@@ -102,22 +104,23 @@ static void lay_out(const suo_ba_problem* probs, int n_prob, char* base, Staged&
         put(S.jac, 29 * E);
     }
     st.cov_begin = L.off;
-    for (int i = 0; i < n_prob; ++i) { LmProblem& S = st.prep[i].S; put(S.cam_cov, 36 * (size_t)S.n_cam); put(S.obj_cov, 36 * (size_t)S.n_obj); put(S.cov_status, 2); }
+    for (int i = 0; i < n_prob; ++i) { LmProblem& S = st.prep[i].S; put(S.cam_cov, 36 * (size_t)S.n_cam); put(S.obj_cov, 36 * (size_t)S.n_obj); put(S.cov_status, 3);
+                                       put(S.cov_cross, 36 * (size_t)S.n_cpair); put(S.cov_rel, 36 * (size_t)S.n_cpair); }
     st.cov_end = L.off;
     st.total = L.off;
 }
 
 // host prep + arena layout + H2D of one batch of problems
-int stage_problems(const suo_ba_problem* probs, int n_prob, Arena& A, Staged& st, const char* who, const int* cov_form) {
+int stage_problems(const suo_ba_problem* probs, int n_prob, Arena& A, Staged& st, const char* who, const int* cov_form, const CovPairs* pairs) {
     st.prep.assign(n_prob, Prep());
     for (int i = 0; i < n_prob; ++i) {
         int rc = prep_problem(probs[i], i, st.prep[i], who);
         if (rc != SUO_OK) return rc;
     }
-    lay_out(probs, n_prob, nullptr, st);          // sizes first: the arena may move when it grows
+    lay_out(probs, n_prob, pairs, nullptr, st);          // sizes first: the arena may move when it grows
     int rc = A.ensure(st.total);
     if (rc != SUO_OK) return rc;
-    lay_out(probs, n_prob, A.dev, st);
+    lay_out(probs, n_prob, pairs, A.dev, st);
     for (int i = 0; i < n_prob; ++i) {
         const suo_ba_problem& q = probs[i];
         Prep& P = st.prep[i];
@@ -149,6 +152,10 @@ int stage_problems(const suo_ba_problem* probs, int n_prob, Arena& A, Staged& st
         for (int k = 0; k < 8; ++k) S.its[k] = k < q.n_rounds ? q.its[k] : 0;
         S.n_rounds = q.n_rounds; S.init_with_outliers = q.init_with_outliers; S.chi2_thr = q.chi2_thr; S.huber_delta = q.huber_delta;
         S.cov_form = cov_form ? cov_form[i] : 0;
+        if (S.n_cpair > 0) {
+            memcpy(A.mirror(S.cpair_a), pairs->a[i], sizeof(int) * S.n_cpair);
+            memcpy(A.mirror(S.cpair_b), pairs->b[i], sizeof(int) * S.n_cpair);
+        }
         memcpy(A.host + st.o_structs + sizeof(LmProblem) * (size_t)i, &S, sizeof(LmProblem));
     }
     SUO_HIP_CHECK(hipMemcpyAsync(A.dev, A.host, st.in_end, hipMemcpyHostToDevice, A.stream));

@@ -279,6 +279,9 @@ struct LmProblem {
     // optional outputs of csrc/pose_cov.hip (nullptr = not wanted): the 6x6 marginal covariance of every camera / object pose, row-major, and the number of
     // NaN blocks [2] (cameras, objects); cov_form: which of its kernels takes the problem (0 block-diagonal over objects, 1 over cameras, 2 coupled)
     double* cam_cov; double* obj_cov; int* cov_status; int cov_form;
+    // optional pairs of suo_pose_covariances_pairs (n_cpair = 0: none): vertices coded camera c = c, object o = n_cam + o; per pair the cross block Sigma_ab
+    // (rows a, columns b) and the covariance of the relative pose, 36 row-major doubles each; cov_status then has a third entry, the pairs with NaN blocks
+    int n_cpair; const int* cpair_a; const int* cpair_b; double* cov_cross; double* cov_rel;
 };
 DEV int pair_hi(const LmProblem& P, int p) { return P.pair_end ? P.pair_end[p] : P.pair_start[p + 1]; }
 

@@ -47,6 +47,8 @@ int launch_ba_restore(const void* P, hipStream_t s);
 int launch_ba_finalize(const void* P, hipStream_t s);
 // ---- 6x6 marginal pose covariances at the state of the problems (csrc/pose_cov.hip); each kernel takes the problems whose LmProblem::cov_form names it ----
 int launch_pose_cov_diag(const void* problems_dev, int n_problems, hipStream_t s);                        // cov_form 0 / 1: one wave per problem
-int launch_pose_cov_coupled(const void* problems_dev, int n_problems, int max_free_obj, hipStream_t s);   // cov_form 2: one workgroup per problem, <= 16 free objects
+// cov_form 2: one workgroup per problem, <= 16 free objects; pairs: the instantiation that also writes the cross blocks of LmProblem::cpair_a / cpair_b
+int launch_pose_cov_coupled(const void* problems_dev, int n_problems, int max_free_obj, hipStream_t s, bool pairs = false);
+int launch_pose_cov_pairs(const void* problems_dev, int n_problems, int max_pairs, hipStream_t s);        // every form, behind the two: cross / rel of the pairs
 int launch_debug_cholesky(const double* A, const double* b, int ns, double* x, int* ok, hipStream_t s);
 }  // namespace suo

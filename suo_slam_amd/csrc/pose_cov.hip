@@ -15,6 +15,13 @@
 //      S^-1 = Sigma_OO are the substitutions against the identity, dealt to the four waves (wave_cholesky_substitute: no workgroup barrier between columns), and stay
 //      in LDS: a camera's block Hcc^-1 + Y Sigma_OO Y^T, Y = Hcc^-1 Hco over the objects it sees, needs the off-diagonal blocks between them.  A wave per camera
 //      forms Z = Y Sigma_OO (6 x ns) and Z Y^T in the LDS the factor no longer needs.  A free vertex without a counted edge gets no row in the system.
+// Pairs (suo_pose_covariances_pairs): the cross block Sigma_ab and the covariance of the relative pose of requested vertex pairs (camera, object) / (object, object).
+//   Forms 0 and 1 couple nothing, so every cross block between two different vertices is zero.  In form 2 the PAIRS instantiation of the coupled kernel writes, for
+//   the requested pairs whose two vertices are in the system, Sigma_co = -Z[:, slot(o)] from the camera wave that holds Z (dense over the objects: also where the
+//   camera does not see the object) and Sigma_ab from Sinv; the marginal entries keep the <false> instantiation, which compiles the pair work out.
+//   pose_cov_pairs_kernel runs behind both kernels, a workgroup per 64 pairs of a problem and a thread per (pair, entry): it fills the blocks that are zeros (a fixed vertex,
+//   forms 0 / 1), NaNs (a vertex whose marginal block is NaN) or the marginal block itself (a == b), and propagates  Sigma_cc + A Sigma_oo A^T + Sigma_co A^T +
+//   A Sigma_oc, A = Ad(T_c),  or  B (Sigma_aa + Sigma_bb - Sigma_ab - Sigma_ba) B^T, B = Ad(T_b^-1)  (include/suo_hip.h).
 // Vector stores only, no atomics; every sum runs in a fixed order, so two runs give the same bits, and a problem's result does not depend on the rest of the batch.
 #include <algorithm>
 
@@ -198,6 +205,7 @@ static size_t pose_cov_lds_bytes(int max_free_obj) {
     return sizeof(double) * (PC_HEAD + ns * ns + std::max(ns * (ns + 1), (size_t)(LM_THREADS / 64) * (12 * ns + 36)));
 }
 
+template <bool PAIRS>
 __global__ __launch_bounds__(LM_THREADS) void pose_cov_coupled_kernel(const LmProblem* __restrict__ problems) {
     const LmProblem& P = problems[blockIdx.x];
     if (P.cov_form != 2) return;
@@ -316,6 +324,19 @@ __global__ __launch_bounds__(LM_THREADS) void pose_cov_coupled_kernel(const LmPr
             if (!P.obj_fixed[o]) val = (s < 0 || !ok) ? nan : 0.5 * (Sinv[(6 * s + r) * ns + 6 * s + cc] + Sinv[(6 * s + cc) * ns + 6 * s + r]);
             P.obj_cov[idx] = val;
         }
+    if constexpr (PAIRS) {
+        // Sigma_ab of the requested (object, object) pairs whose two objects are in the system, symmetrised like the marginal blocks: (a, b) is the transpose
+        // of (b, a) to the bit, and (a, a) is the marginal block
+        if (ok)
+            for (int idx = tid; idx < P.n_cpair * 36; idx += LM_THREADS) {
+                const int q = idx / 36, rc = idx - q * 36, r = rc / 6, cc = rc - r * 6;
+                const int a = P.cpair_a[q] - P.n_cam, b = P.cpair_b[q] - P.n_cam;
+                if (a < 0 || b < 0) continue;
+                const int sa = P.obj_slot[a], sb = P.obj_slot[b];
+                if (sa < 0 || sb < 0) continue;
+                P.cov_cross[idx] = 0.5 * (Sinv[(6 * sa + r) * ns + 6 * sb + cc] + Sinv[(6 * sb + cc) * ns + 6 * sa + r]);
+            }
+    }
     // ---- cameras, a wave each: Hcc^-1 + Y Sigma_OO Y^T with Y (6 x ns, zero where the camera does not see the object), Z = Y Sigma_OO in the factor's LDS -----
     if (P.cam_cov) {
         double* Yd = S + wv * (12 * ns + 36);
@@ -342,6 +363,25 @@ __global__ __launch_bounds__(LM_THREADS) void pose_cov_coupled_kernel(const LmPr
             }
             __builtin_amdgcn_wave_barrier();
             const int r = (lane % 36) / 6, c2 = lane % 6;
+            if constexpr (PAIRS) {
+                // Sigma_co = -Z[:, slot(o)] of the requested pairs of this camera, while Z is in LDS; rows are the pair's first vertex.  The list is searched 64
+                // pairs at a time, a lane each; the wave then writes the blocks of the hits one after the other
+                for (int q0 = 0; q0 < P.n_cpair; q0 += 64) {
+                    int s = -1;
+                    bool cam_first = false;
+                    if (q0 + lane < P.n_cpair) {
+                        const int a = P.cpair_a[q0 + lane], b = P.cpair_b[q0 + lane];
+                        cam_first = a == c && b >= P.n_cam;
+                        if (cam_first || (b == c && a >= P.n_cam)) s = P.obj_slot[(cam_first ? b : a) - P.n_cam];
+                    }
+                    for (unsigned long long hits = __ballot(s >= 0); hits; hits &= hits - 1) {
+                        const int l = __ffsll(hits) - 1;
+                        const int sl = __shfl(s, l, 64);
+                        const bool first = __shfl((int)cam_first, l, 64) != 0;
+                        if (lane < 36) P.cov_cross[36 * (size_t)(q0 + l) + (first ? r * 6 + c2 : c2 * 6 + r)] = -Z[r * ns + 6 * sl + c2];
+                    }
+                }
+            }
             if (lane < 36) {
                 double acc = P.Hcc_inv[36 * c + lane];
                 for (int j = 0; j < ns; ++j) acc += Z[r * ns + j] * Yd[c2 * ns + j];
@@ -361,6 +401,103 @@ __global__ __launch_bounds__(LM_THREADS) void pose_cov_coupled_kernel(const LmPr
     }
 }
 
+// row r of Ad(T) = [[R, 0], [[t]x R, R]] of the pose T (row-major 3x4), or of Ad(T^-1) (R^T, -R^T t)
+DEV void pc_ad_row(const double* T, bool inverse, int r, double (&row)[6]) {
+    double R[9], t[3];
+#pragma unroll
+    for (int i = 0; i < 3; ++i) {
+#pragma unroll
+        for (int j = 0; j < 3; ++j) R[3 * i + j] = inverse ? T[4 * j + i] : T[4 * i + j];
+    }
+#pragma unroll
+    for (int i = 0; i < 3; ++i) t[i] = inverse ? -(T[i] * T[3] + T[4 + i] * T[7] + T[8 + i] * T[11]) : T[4 * i + 3];
+    const int i = r % 3, i1 = (i + 1) % 3, i2 = (i + 2) % 3;
+#pragma unroll
+    for (int j = 0; j < 3; ++j) {
+        const double tx = t[i1] * R[3 * i2 + j] - t[i2] * R[3 * i1 + j];     // ([t]x R)[i][j]
+        row[j] = r < 3 ? R[3 * i + j] : tx;
+        row[3 + j] = r < 3 ? 0.0 : R[3 * i + j];
+    }
+}
+
+// entry (r, c) of  Scc + A Soo A^T + Sco A^T + A Sco^T  (S1 = Scc, S2 = Soo, X = Sigma_co or, x_transposed, Sigma_oc)  or, obj_obj, of
+// A (Saa + Sbb - Sab - Sab^T) A^T  (S1 = Saa, S2 = Sbb, X = Sigma_ab); Ar / Ac: rows r and c of A; X == nullptr: a cross block of zeros
+DEV double pc_rel_entry(bool obj_obj, const double* S1, const double* S2, const double* X, bool x_transposed, const double (&Ar)[6], const double (&Ac)[6], int r, int c) {
+    auto x = [&](int i, int j) { return !X ? 0.0 : (x_transposed ? X[6 * j + i] : X[6 * i + j]); };
+    double acc = obj_obj ? 0.0 : S1[6 * r + c];
+    for (int k = 0; k < 6; ++k) {
+        double row = 0;
+        for (int l = 0; l < 6; ++l) {
+            const double d = obj_obj ? ((S1[6 * k + l] + S2[6 * k + l]) - x(k, l)) - x(l, k) : S2[6 * k + l];
+            row += d * Ac[l];
+        }
+        acc += Ar[k] * row;
+    }
+    if (!obj_obj) {
+        double w1 = 0, w2 = 0;
+        for (int k = 0; k < 6; ++k) { w1 += x(r, k) * Ac[k]; w2 += Ar[k] * x(c, k); }
+        acc += w1;
+        acc += w2;
+    }
+    return acc;
+}
+
+// Behind the two kernels above, every form: cross and rel of the problem's requested pairs (the block comment on top), PC_PAIRS_PER_WG pairs per workgroup
+// (blockIdx.y); the first workgroup of a problem also counts status[2] = pairs with NaN blocks (integer sums: no order to fix)
+constexpr int PC_PAIRS_PER_WG = 64;
+__global__ __launch_bounds__(LM_THREADS) void pose_cov_pairs_kernel(const LmProblem* __restrict__ problems) {
+    const LmProblem& P = problems[blockIdx.x];
+    const int tid = threadIdx.x;
+    const double nan = __longlong_as_double(0x7ff8000000000000ll);
+    auto block_of = [&](int v) { return v < P.n_cam ? P.cam_cov + 36 * (size_t)v : P.obj_cov + 36 * (size_t)(v - P.n_cam); };
+    if (blockIdx.y == 0) {
+        __shared__ int wave_nan[LM_THREADS / 64];
+        int n = 0;
+        for (int q = tid; q < P.n_cpair; q += LM_THREADS) n += (isnan(block_of(P.cpair_a[q])[0]) || isnan(block_of(P.cpair_b[q])[0])) ? 1 : 0;
+#pragma unroll
+        for (int m = 32; m > 0; m >>= 1) n += __shfl_xor(n, m, 64);
+        if ((tid & 63) == 0) wave_nan[tid >> 6] = n;
+        __syncthreads();
+        if (tid == 0 && P.cov_status) {
+            int total = 0;
+            for (int w = 0; w < LM_THREADS / 64; ++w) total += wave_nan[w];
+            P.cov_status[2] = total;
+        }
+    }
+    const int q_lo = blockIdx.y * PC_PAIRS_PER_WG, q_hi = min(P.n_cpair, q_lo + PC_PAIRS_PER_WG);
+    for (int idx = 36 * q_lo + tid; idx < 36 * q_hi; idx += LM_THREADS) {
+        const int q = idx / 36, rc = idx - q * 36, r = rc / 6, c = rc - r * 6;
+        const int a = P.cpair_a[q], b = P.cpair_b[q];
+        const bool a_cam = a < P.n_cam, b_cam = b < P.n_cam;
+        const double* Sa = block_of(a);
+        const double* Sb = block_of(b);
+        const bool a_fixed = a_cam ? P.cam_fixed[a] : P.obj_fixed[a - P.n_cam], b_fixed = b_cam ? P.cam_fixed[b] : P.obj_fixed[b - P.n_cam];
+        double* cross = P.cov_cross + 36 * (size_t)q;
+        if (isnan(Sa[0]) || isnan(Sb[0])) { cross[rc] = nan; P.cov_rel[idx] = nan; continue; }
+        // Sigma_ab: the marginal block (a == b), zeros (a fixed vertex; forms 0 / 1 couple nothing), or what the coupled kernel wrote -- that block is only read
+        // here: the other threads of the pair read it too
+        const bool same = a == b, zero = !same && (a_fixed || b_fixed || P.cov_form != 2);
+        const double* X = same ? Sa : (zero ? nullptr : cross);
+        if (same) cross[rc] = Sa[rc];
+        if (zero) cross[rc] = 0.0;
+        double Ar[6], Ac[6], m_rc, m_cr;
+        if (!a_cam && !b_cam) {
+            const double* Tb = P.obj_T + 12 * (size_t)(b - P.n_cam);
+            pc_ad_row(Tb, true, r, Ar);
+            pc_ad_row(Tb, true, c, Ac);
+            m_rc = pc_rel_entry(true, Sa, Sb, X, false, Ar, Ac, r, c);
+            m_cr = pc_rel_entry(true, Sa, Sb, X, false, Ac, Ar, c, r);
+        } else {
+            const double* Tc = P.cam_T + 12 * (size_t)(a_cam ? a : b);
+            pc_ad_row(Tc, false, r, Ar);
+            pc_ad_row(Tc, false, c, Ac);
+            m_rc = pc_rel_entry(false, a_cam ? Sa : Sb, a_cam ? Sb : Sa, X, !a_cam, Ar, Ac, r, c);
+            m_cr = pc_rel_entry(false, a_cam ? Sa : Sb, a_cam ? Sb : Sa, X, !a_cam, Ac, Ar, c, r);
+        }
+        P.cov_rel[idx] = 0.5 * (m_rc + m_cr);
+    }
+}
+
 int launch_pose_cov_diag(const void* problems_dev, int n_problems, hipStream_t s) {
     if (n_problems <= 0) return SUO_OK;
     hipLaunchKernelGGL(pose_cov_diag_kernel, dim3(n_problems), dim3(64), 0, s, (const LmProblem*)problems_dev);
@@ -368,7 +505,8 @@ int launch_pose_cov_diag(const void* problems_dev, int n_problems, hipStream_t s
     return SUO_OK;
 }
 
-int launch_pose_cov_coupled(const void* problems_dev, int n_problems, int max_free_obj, hipStream_t s) {
+template <bool PAIRS>
+static int launch_pose_cov_coupled_as(const void* problems_dev, int n_problems, int max_free_obj, hipStream_t s) {
     if (n_problems <= 0) return SUO_OK;
     if (max_free_obj < 0 || max_free_obj > LM_MAX_SCHUR_OBJ) {
         suo_set_error("pose covariances: %d free objects next to free cameras (the reduced system holds %d)", max_free_obj, LM_MAX_SCHUR_OBJ);
@@ -376,10 +514,22 @@ int launch_pose_cov_coupled(const void* problems_dev, int n_problems, int max_fr
     }
     static bool attr_set = false;
     if (!attr_set) {
-        SUO_HIP_CHECK(hipFuncSetAttribute((const void*)pose_cov_coupled_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)pose_cov_lds_bytes(LM_MAX_SCHUR_OBJ)));
+        SUO_HIP_CHECK(hipFuncSetAttribute((const void*)pose_cov_coupled_kernel<PAIRS>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)pose_cov_lds_bytes(LM_MAX_SCHUR_OBJ)));
         attr_set = true;
     }
-    hipLaunchKernelGGL(pose_cov_coupled_kernel, dim3(n_problems), dim3(LM_THREADS), pose_cov_lds_bytes(max_free_obj), s, (const LmProblem*)problems_dev);
+    hipLaunchKernelGGL(pose_cov_coupled_kernel<PAIRS>, dim3(n_problems), dim3(LM_THREADS), pose_cov_lds_bytes(max_free_obj), s, (const LmProblem*)problems_dev);
+    SUO_HIP_CHECK(hipGetLastError());
+    return SUO_OK;
+}
+
+int launch_pose_cov_coupled(const void* problems_dev, int n_problems, int max_free_obj, hipStream_t s, bool pairs) {
+    return pairs ? launch_pose_cov_coupled_as<true>(problems_dev, n_problems, max_free_obj, s) : launch_pose_cov_coupled_as<false>(problems_dev, n_problems, max_free_obj, s);
+}
+
+int launch_pose_cov_pairs(const void* problems_dev, int n_problems, int max_pairs, hipStream_t s) {
+    if (n_problems <= 0) return SUO_OK;
+    const int ny = std::max(1, (max_pairs + PC_PAIRS_PER_WG - 1) / PC_PAIRS_PER_WG);
+    hipLaunchKernelGGL(pose_cov_pairs_kernel, dim3(n_problems, ny), dim3(LM_THREADS), 0, s, (const LmProblem*)problems_dev);
     SUO_HIP_CHECK(hipGetLastError());
     return SUO_OK;
 }

@@ -1,4 +1,4 @@
-// Host-buffer entry points of the pose covariances (include/suo_hip.h: suo_pose_covariances / suo_pose_covariances_batch): staged through the arena of
+// Host-buffer entry points of the pose covariances (include/suo_hip.h: suo_pose_covariances / suo_pose_covariances_pairs and their batch forms): staged through the arena of
 // suo_optimize_batch (csrc/ba_stage.hip), one H2D, the kernels of csrc/pose_cov.hip, one D2H of the blocks.  The caller's problem is read only.
 #include <string.h>
 
@@ -39,36 +39,70 @@ static int plan_cov_batch(const suo_ba_problem* probs, int n_prob, CovPlan& plan
     return SUO_OK;
 }
 
+// The shared body of the entries.  pairs == nullptr: the marginal entry -- the coupled kernel without the pair work, no pair kernel, status [n][2].
+// With pairs: the PAIRS instantiation, the pair kernel behind both, status [n][3]; cross / rel (one pointer per problem) and their members may be null.
+static int cov_batch(const suo_ba_problem* probs, int n_prob, double* const* cam_cov, double* const* obj_cov, int* status, const CovPairs* pairs, double* const* cross,
+                     double* const* rel, const char* who) {
+    CovPlan plan;
+    int rc = plan_cov_batch(probs, n_prob, plan);
+    if (rc != SUO_OK) return rc;
+    for (int i = 0; pairs && i < n_prob; ++i) {
+        const int n = pairs->n[i], nc = probs[i].n_cam, nv = probs[i].n_cam + probs[i].n_obj;
+        if (n < 0 || (n > 0 && (!pairs->a[i] || !pairs->b[i]))) { suo_set_error("%s: problem %d: n_pair = %d or null pair lists", who, i, n); return SUO_ERR_ARG; }
+        for (int q = 0; q < n; ++q) {
+            const int a = pairs->a[i][q], b = pairs->b[i][q];
+            if (a < 0 || a >= nv || b < 0 || b >= nv) { suo_set_error("%s: problem %d: pair %d = (%d, %d) names a vertex outside [0, %d)", who, i, q, a, b, nv); return SUO_ERR_ARG; }
+            if (a < nc && b < nc) { suo_set_error("%s: problem %d: pair %d = (%d, %d) is (camera, camera); pairs are (camera, object) or (object, object)", who, i, q, a, b); return SUO_ERR_ARG; }
+        }
+    }
+    std::lock_guard<std::mutex> lock(g_arena.mu);
+    Staged st;
+    rc = stage_problems(probs, n_prob, g_arena, st, who, plan.form.data(), pairs);
+    if (rc != SUO_OK) return rc;
+    const void* P = g_arena.dev + st.o_structs;
+    hipStream_t s = g_arena.stream;
+    if (plan.diag) { rc = launch_pose_cov_diag(P, n_prob, s); if (rc != SUO_OK) return rc; }
+    if (plan.coupled) { rc = launch_pose_cov_coupled(P, n_prob, plan.max_free_obj, s, pairs != nullptr); if (rc != SUO_OK) return rc; }
+    if (pairs) { rc = launch_pose_cov_pairs(P, n_prob, *std::max_element(pairs->n, pairs->n + n_prob), s); if (rc != SUO_OK) return rc; }
+    SUO_HIP_CHECK(hipMemcpyAsync(g_arena.host + st.cov_begin, g_arena.dev + st.cov_begin, st.cov_end - st.cov_begin, hipMemcpyDeviceToHost, s));
+    SUO_HIP_CHECK(hipStreamSynchronize(s));
+    const int ns = pairs ? 3 : 2;
+    for (int i = 0; i < n_prob; ++i) {
+        const LmProblem& S = st.prep[i].S;
+        if (cam_cov && cam_cov[i]) memcpy(cam_cov[i], g_arena.mirror(S.cam_cov), sizeof(double) * 36 * (size_t)S.n_cam);
+        if (obj_cov && obj_cov[i]) memcpy(obj_cov[i], g_arena.mirror(S.obj_cov), sizeof(double) * 36 * (size_t)S.n_obj);
+        if (cross && cross[i]) memcpy(cross[i], g_arena.mirror(S.cov_cross), sizeof(double) * 36 * (size_t)S.n_cpair);
+        if (rel && rel[i]) memcpy(rel[i], g_arena.mirror(S.cov_rel), sizeof(double) * 36 * (size_t)S.n_cpair);
+        if (status) memcpy(status + ns * i, g_arena.mirror(S.cov_status), sizeof(int) * ns);
+    }
+    return SUO_OK;
+}
+
 extern "C" {
 
 int suo_pose_covariances_batch(const suo_ba_problem* probs, int n_prob, double* const* cam_cov, double* const* obj_cov, int* status) {
     if (n_prob <= 0) return SUO_OK;
     if (!probs || !cam_cov || !obj_cov) { suo_set_error("suo_pose_covariances_batch: null argument"); return SUO_ERR_ARG; }
-    CovPlan plan;
-    int rc = plan_cov_batch(probs, n_prob, plan);
-    if (rc != SUO_OK) return rc;
-    std::lock_guard<std::mutex> lock(g_arena.mu);
-    Staged st;
-    rc = stage_problems(probs, n_prob, g_arena, st, "suo_pose_covariances", plan.form.data());
-    if (rc != SUO_OK) return rc;
-    const void* P = g_arena.dev + st.o_structs;
-    hipStream_t s = g_arena.stream;
-    if (plan.diag) { rc = launch_pose_cov_diag(P, n_prob, s); if (rc != SUO_OK) return rc; }
-    if (plan.coupled) { rc = launch_pose_cov_coupled(P, n_prob, plan.max_free_obj, s); if (rc != SUO_OK) return rc; }
-    SUO_HIP_CHECK(hipMemcpyAsync(g_arena.host + st.cov_begin, g_arena.dev + st.cov_begin, st.cov_end - st.cov_begin, hipMemcpyDeviceToHost, s));
-    SUO_HIP_CHECK(hipStreamSynchronize(s));
-    for (int i = 0; i < n_prob; ++i) {
-        const LmProblem& S = st.prep[i].S;
-        if (cam_cov[i]) memcpy(cam_cov[i], g_arena.mirror(S.cam_cov), sizeof(double) * 36 * (size_t)S.n_cam);
-        if (obj_cov[i]) memcpy(obj_cov[i], g_arena.mirror(S.obj_cov), sizeof(double) * 36 * (size_t)S.n_obj);
-        if (status) memcpy(status + 2 * i, g_arena.mirror(S.cov_status), sizeof(int) * 2);
-    }
-    return SUO_OK;
+    return cov_batch(probs, n_prob, cam_cov, obj_cov, status, nullptr, nullptr, nullptr, "suo_pose_covariances");
 }
 
 int suo_pose_covariances(const suo_ba_problem* problem, double* cam_cov, double* obj_cov, int* status) {
     if (!problem) { suo_set_error("suo_pose_covariances: null argument"); return SUO_ERR_ARG; }
     return suo_pose_covariances_batch(problem, 1, &cam_cov, &obj_cov, status);
+}
+
+int suo_pose_covariances_pairs_batch(const suo_ba_problem* probs, int n_prob, const int* n_pair, const int32_t* const* pair_a, const int32_t* const* pair_b,
+                                     double* const* cam_cov, double* const* obj_cov, double* const* cross, double* const* rel, int* status) {
+    if (n_prob <= 0) return SUO_OK;
+    if (!probs || !n_pair || !pair_a || !pair_b) { suo_set_error("suo_pose_covariances_pairs_batch: null argument"); return SUO_ERR_ARG; }
+    const CovPairs pairs{n_pair, pair_a, pair_b};
+    return cov_batch(probs, n_prob, cam_cov, obj_cov, status, &pairs, cross, rel, "suo_pose_covariances_pairs");
+}
+
+int suo_pose_covariances_pairs(const suo_ba_problem* problem, int n_pair, const int32_t* pair_a, const int32_t* pair_b, double* cam_cov, double* obj_cov, double* cross,
+                               double* rel, int* status) {
+    if (!problem) { suo_set_error("suo_pose_covariances_pairs: null argument"); return SUO_ERR_ARG; }
+    return suo_pose_covariances_pairs_batch(problem, 1, &n_pair, &pair_a, &pair_b, &cam_cov, &obj_cov, &cross, &rel, status);
 }
 
 }  // extern "C"

@@ -81,7 +81,8 @@ class FrameGeometry:
     def covariances(self, stream=None):
         """6x6 covariance of every crop's refined pose from the device-resident graph of the last launch (suo_frame_geom_covariances: a wave per frame, enqueued
         on `stream` -- the launch's stream -- behind the chain's LM), waited for and returned as [L,6,6] float64: zeros for crops that were not accepted.
-        fetch() afterwards carries the same array as "obj_cov"."""
+        fetch() afterwards carries the same array as "obj_cov".  The frame's camera is fixed at the identity, so an object's block IS the covariance of its pose
+        relative to the camera (Ad(I) = I, no camera or cross term): nothing more is needed for the relative covariance of suo_pose_covariances_pairs."""
         if stream is None:
             stream = _lib.current_stream_ptr()
         _lib.check(self._lib.suo_frame_geom_covariances(self._h, C.c_void_p(int(stream))), "suo_frame_geom_covariances")

@@ -270,8 +270,9 @@ class ObjectSLAM(DeviceRoutes):
         return f"TIMING: Global opt time: {1000 * (t1 - t0)} ms ({1000 * avg} avg) ({'inf' if avg < 1e-12 else 1 / avg} Hz)"
 
     # ---------------------------------------------------------------------------------------------
-    def collect_results(self, last_only=False, no_viz=True, final=False):
-        """object_slam.py:175-225: T_OtoC = T_GtoC @ T_OtoG per view; score = 1 + total inliers."""
+    def collect_results(self, last_only=False, no_viz=True, final=False, covariances=False):
+        """object_slam.py:175-225: T_OtoC = T_GtoC @ T_OtoG per view; score = 1 + total inliers.  covariances=True: every pose entry also carries "cov_OtoC", the
+        6x6 covariance of that T_OtoC (pose_covariances(relative=True)), None where T_OtoC is None."""
         if self.slam_mode and self.needs_opt and final:
             t0 = time()
             self.optimize()
@@ -279,7 +280,9 @@ class ObjectSLAM(DeviceRoutes):
         results = {}
         n_inl = {}                     # per object, the same for every view: counted once (the reference recounts per view, :199-214)
         assert len(self.view_ids) == len(self.cam_poses)
-        for view_id in ([self.view_ids[-1]] if last_only else self.view_ids):
+        views = [self.view_ids[-1]] if last_only else self.view_ids
+        rel = self.pose_covariances(view_ids=views, relative=True)["rel"] if covariances else None
+        for view_id in views:
             T_GtoC = to4x4(self.cam_poses[view_id])
             detection = self.detections[view_id]
             results[view_id] = {"poses": {}}
@@ -290,6 +293,8 @@ class ObjectSLAM(DeviceRoutes):
                 if obj_id not in n_inl:
                     n_inl[obj_id] = self.obj_num_inliers(obj_id)
                 results[view_id]["poses"][obj_id] = {"T_OtoC": T_OtoC, "score": 1 + n_inl[obj_id]}
+                if covariances:
+                    results[view_id]["poses"][obj_id]["cov_OtoC"] = None if T_OtoC is None else rel[(view_id, obj_id)]
         return results
 
     # ---------------------------------------------------------------------------------------------
@@ -681,23 +686,36 @@ class ObjectSLAM(DeviceRoutes):
         self._cull_after_optimize(list(obj_index.keys()), curr_only, view_curr)
 
     @_on_stream
-    def pose_covariances(self, view_ids=None):
+    def pose_covariances(self, view_ids=None, relative=False):
         """6x6 marginal covariances of the current map: {"cams": {view_id: 6x6}, "objs": {obj_id: 6x6}} for every key of cam_poses (or those in view_ids) and
         obj_poses, from the global graph of build_problem() at the stored poses and inlier flags (ba.pose_covariances: rows / columns [omega, upsilon] of the
-        left update; zeros for the gauge camera, NaNs for a vertex no counted measurement reaches).  Changes nothing in the map."""
+        left update; zeros for the gauge camera, NaNs for a vertex no counted measurement reaches).  These blocks are relative to the gauge camera.
+        relative=True adds "rel": {(view_id, obj_id): 6x6} for every selected view and every object of the map: the covariance of the T_OtoC = T_GtoC T_OtoG that
+        collect_results reports, which does not depend on the gauge (ba.pose_covariances_pairs, the same single device call).  Changes nothing in the map."""
         nan = np.full((6, 6), np.nan)
         cams = {v: nan.copy() for v in self.cam_poses if view_ids is None or v in view_ids}
         objs = {o: nan.copy() for o in self.obj_poses}
         built = self.build_problem(False)
         if built is not None:
             prob, (cam_index, obj_index, _, _, _) = built
-            cam_cov, obj_cov, _ = _ba.pose_covariances_batch([prob])[0]
+            if relative:
+                keys = [(v, o) for v in cams if v in cam_index for o in obj_index]
+                pairs = np.array([(cam_index[v], len(cam_index) + obj_index[o]) for v, o in keys], np.int32).reshape(-1, 2)
+                cam_cov, obj_cov, _, rel_cov, _ = _ba.pose_covariances_pairs_batch([prob], [pairs])[0]
+            else:
+                cam_cov, obj_cov, _ = _ba.pose_covariances_batch([prob])[0]
             for v, i in cam_index.items():
                 if v in cams:
                     cams[v] = cam_cov[i].copy()
             for o, j in obj_index.items():
                 objs[o] = obj_cov[j].copy()
-        return {"cams": cams, "objs": objs}
+        out = {"cams": cams, "objs": objs}
+        if relative:
+            out["rel"] = {(v, o): nan.copy() for v in cams for o in objs}
+            if built is not None:
+                for k, S6 in zip(keys, rel_cov):
+                    out["rel"][k] = S6.copy()
+        return out
 
     @_on_stream
     def optimize(self, curr_only=False):
