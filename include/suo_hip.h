@@ -661,6 +661,44 @@ int suo_pose_errors(void* mesh_db, int n, const int* model_index, const float* T
 int suo_mesh_db_set_symmetries(void* mesh_db, const int* n_sym, const double* sym);
 int suo_pose_errors_bop(void* mesh_db, int n, const int* model_index, const double* T_est, const double* T_gt, const double* K, double* mssd, double* mspd);
 
+/* ---- consistency of the reported uncertainties: pose NEES and keypoint chi2 ------------------------------------------------------
+ * Compares a reported covariance with ground truth: the normalised estimation error squared of a pose under its 6x6 covariance (suo_pose_covariances,
+ * suo_pose_covariances_pairs' `rel`) and the chi2 of a keypoint's reprojection error under the network's 2x2 covariance.  fp64, no contraction, fixed summation
+ * order: two calls give the same bits and a pair in a batch has the bits it has alone.
+ *
+ * suo_pose_nees: n (estimate, ground truth, covariance) triples over the mesh database and its symmetry sets (suo_mesh_db_set_symmetries).
+ *   Symmetry.    s* = the symmetry that attains the MSSD minimum min_s max_i |T_est p_i - T_gt S_s p_i| (the per-symmetry maxima of suo_pose_errors_bop's own
+ *                kernel).  On equal maxima the LOWEST index wins.  sym_index[i] = s*, an index into the model's set.
+ *   Reference.   T_ref = T_gt S_s*:  R_ref = R_gt S_R,  t_ref = R_gt S_t + t_gt, as above.
+ *   Error.       xi = log(T_est T_ref^-1) = [omega, upsilon]: the inverse of the library's update T <- exp([omega, upsilon]) T (csrc/lm_device.h, g2o's
+ *                SE3Quat::exp), the perturbation the covariances above are defined for -- not a free choice.  omega = 2 atan2(|v|, w) v / |v| from the unit
+ *                quaternion (w >= 0, v) of R_est R_ref^T; upsilon = V^-1 t, V = I + b Om + c Om^2 of the exponential.  Series for atan2(|v|, w) / |v| below
+ *                |v|^2 < 1e-8 and for the V^-1 coefficient below theta^2 < 0.09, closed forms above.  Covered: 0 <= theta <= 3.0 rad to a few ulp of
+ *                (1 + |xi|); beyond 3.0 only finiteness and |omega| <= pi are promised.
+ *   NEES.        xi^T Sigma^-1 xi through the Cholesky factor of Sigma (cov [n][36] row-major, rows and columns [omega, upsilon]; the lower triangle is read).
+ *                The chi2 scale is STILL NOT applied: this is the NEES under the stated covariance.
+ *   NaN rules.   nees[i] is NaN for a block with a non-finite entry (all 36 are looked at), for a pivot that is not positive (this includes the 36 zeros of a
+ *                fixed vertex), and for a pair whose MSSD meets a non-finite distance (a NaN or overflowing pose): that pair also gets sym_index -1 and NaN xi
+ *                and T_ref.  status[0] counts the NaN results.  The call never faults and never loops on a bad block; the other pairs of the batch are unaffected.
+ *   Units.       Poses, symmetry translations, mesh points and the upsilon rows and columns of cov share ONE length unit (mm throughout this project's evaluation;
+ *                the rotation rows are radians).
+ *   Outputs.     nees [n]; xi [n][6], sym_index [n], T_ref [n][12] row-major 3x4, status [1]: each may be NULL.
+ *
+ * suo_keypoint_nees: ragged over n_det detections like suo_pnp_batch: n_pts[n_det] keypoints each (0 is fine), model_kp / uv / cov concatenated in that order
+ * (cov row-major 2x2), K [n_det][9] row-major (the K_bbox of the crop the uv live in), T_ref [n_det][12] (e.g. suo_pose_nees' T_ref).  Per keypoint:
+ *   e    = uv - pi(K, T_ref x),  pi = (K X)_xy / (K X)_z divided as given: a point behind the camera keeps its finite value;
+ *   chi2 = e^T C^-1 e by the closed 2x2 inverse; NaN when det C <= 0, when a diagonal entry is not positive, or when an input (or the result) is not finite.
+ *   chi2 [sum n_pts]; err [sum n_pts][2] (= e) may be NULL.  The mesh database lends its scratch and stream only.
+ * Host buffers, blocking, staged through the database's grow-only scratch.  n = 0 / n_det = 0 return 0.  SUO_ERR_ARG with a message and nothing launched: a null
+ * database, a null required pointer, n < 0 / n_det < 0, a model index outside the database, a negative n_pts.  Kernels: csrc/eval_nees.hip (one pair per 8-lane
+ * group; one thread per keypoint). */
+int suo_pose_nees(void* mesh_db, int n, const int* model_index, const double* T_est /*[n][12]*/, const double* T_gt /*[n][12]*/,
+                  const double* cov /*[n][36] row-major, [omega, upsilon]*/, double* nees /*[n]*/, double* xi /*[n][6] or NULL*/,
+                  int* sym_index /*[n] or NULL*/, double* T_ref /*[n][12] or NULL*/, int* status /*[1] or NULL*/);
+int suo_keypoint_nees(void* mesh_db /*scratch + stream only*/, int n_det, const int* n_pts, const double* model_kp /*[sum][3]*/,
+                      const double* uv /*[sum][2]*/, const double* cov /*[sum][4]*/, const double* K /*[n_det][9]*/,
+                      const double* T_ref /*[n_det][12]*/, double* chi2 /*[sum]*/, double* err /*[sum][2] or NULL*/);
+
 /* ---- BOP-19 VSD: depth rasteriser and error ------------------------------------------
  * The third term of the BOP-19 score over the same mesh database.  Opt-in: nothing above changes when these are not called.
  *

@@ -154,6 +154,8 @@ SIGNATURES = {
     "suo_pose_errors": (C.c_int, [VP, C.c_int, VP, VP, VP, VP, VP]),
     "suo_mesh_db_set_symmetries": (C.c_int, [VP, VP, VP]),
     "suo_pose_errors_bop": (C.c_int, [VP, C.c_int, VP, VP, VP, VP, VP, VP]),
+    "suo_pose_nees": (C.c_int, [VP, C.c_int, VP, VP, VP, VP, VP, VP, VP, VP, VP]),
+    "suo_keypoint_nees": (C.c_int, [VP, C.c_int, VP, VP, VP, VP, VP, VP, VP, VP]),
     "suo_mesh_db_set_faces": (C.c_int, [VP, VP, VP]),
     "suo_render_depth": (C.c_int, [VP, C.c_int, VP, VP, VP, C.c_int, C.c_int, VP]),
     "suo_vsd_from_depth": (C.c_int, [C.c_int, C.c_int, C.c_int, VP, VP, C.c_int, VP, VP, VP, C.c_double, C.c_int, VP, C.c_int, VP, VP, VP]),

@@ -18,6 +18,7 @@ host exactly as in the toolkit.  VSD, the third term, needs a renderer and depth
 Opt-in since row N6, with nothing above changed when it is not asked for: a mesh database with ``"faces"`` (bop.load_mesh_db(..., faces=True)) and a
 ``depth_loader`` give the third term without an external tool:
 
+    BopErrors.pose_nees / .keypoint_nees            consistency figures of reported covariances (consistency.py) -> HIP, csrc/eval_nees.hip
     BopErrors.render_depth(obj_ids, T, K, hw)       Renderer.render_object(...)["depth"]       -> HIP, csrc/raster.hip (suo_render_depth)
     BopErrors.vsd(obj_ids, T_est, T_gt, K, depth_images, image_index, delta, taus, normalized)
                                                     pose_error.vsd (cost 'step', mode 'bop19')  -> HIP, csrc/eval_vsd.hip (suo_pose_errors_vsd)
@@ -153,6 +154,17 @@ class BopErrors:
         _lib.check(self.lib.suo_pose_errors_bop(self._h, n, idx.ctypes.data, Te.ctypes.data, Tg.ctypes.data, Kn.ctypes.data, mssd.ctypes.data, mspd.ctypes.data),
                    "suo_pose_errors_bop")
         return mssd, mspd
+
+    def pose_nees(self, obj_ids, T_est, T_gt, cov):
+        """NEES of n (object, estimated pose, ground-truth pose, 6x6 covariance) items against T_ref = T_gt S of the MSSD-minimising symmetry:
+        ``{"nees", "xi", "sym_index", "T_ref", "n_nan"}`` (consistency.pose_nees; include/suo_hip.h: suo_pose_nees)."""
+        from . import consistency
+        return consistency.pose_nees(self, obj_ids, T_est, T_gt, cov)
+
+    def keypoint_nees(self, dets, T_ref):
+        """chi2 of the keypoints of ObjectSLAM detection dicts at the poses T_ref: ``{"chi2", "err", "n_skipped"}`` (consistency.keypoint_nees)."""
+        from . import consistency
+        return consistency.keypoint_nees(self, dets, T_ref)
 
     def render_depth(self, obj_ids, T, K, hw):
         """float32 [n,H,W] depth images (mm, 0 where nothing is drawn) of the objects under poses [n,3|4,4] and K [n,3,3] or one [3,3]; ``hw`` = (H, W).

@@ -37,18 +37,6 @@ constexpr int BE_TILE = BE_BLOCK * BE_NP;        // points per workgroup
 constexpr int BE_SCH = 64;                       // most symmetries per workgroup
 constexpr int BE_WG_TARGET = 1024;               // workgroups wanted where the problem allows: 256 CUs x 4
 
-struct BopArgs {
-    const float* pts; const int* off;            // mesh database
-    const double* sym; const int* soff;          // its symmetry sets [soff[m] .. soff[m + 1])[12]
-    const int* model;                            // [n]
-    const double* Te; const double* Tg;          // [n][12] row-major 3x4
-    const double* K;                             // [n][9]
-    unsigned long long* smax;                    // [n][stride][2] bit patterns of max_i d^2: 3-D, 2-D
-    unsigned* flags;                             // [n] bit 0: a non-finite 3-D distance, bit 1: a non-finite 2-D distance
-    double* out;                                 // [n][2] min_s max_i d^2
-    int stride, chunk;
-};
-
 // (a0 b0 + a1 b1) + a2 b2, the order of a 3-term numpy dot
 __device__ __forceinline__ double dot3(double a0, double b0, double a1, double b1, double a2, double b2) { return (a0 * b0 + a1 * b1) + a2 * b2; }
 
@@ -195,14 +183,12 @@ extern "C" int suo_mesh_db_set_symmetries(void* h, const int* n_sym, const doubl
     return set_symmetries_locked(db, n_sym, sym);
 }
 
-extern "C" int suo_pose_errors_bop(void* h, int n, const int* model_index, const double* T_est, const double* T_gt, const double* K, double* mssd, double* mspd) {
-    MeshDb* db = (MeshDb*)h;
-    if (!db || n < 0 || (n > 0 && (!model_index || !T_est || !T_gt || (mspd && !K)))) { suo_set_error("suo_pose_errors_bop: bad argument"); return SUO_ERR_ARG; }
-    if (n == 0) return SUO_OK;
-    for (int i = 0; i < n; ++i)
-        if (model_index[i] < 0 || model_index[i] >= db->n_models) { suo_set_error("suo_pose_errors_bop: model_index[%d]=%d out of range", i, model_index[i]); return SUO_ERR_ARG; }
-    if (!mssd && !mspd) return SUO_OK;
-    std::lock_guard<std::mutex> lk(db->mu);
+namespace suo {
+
+// What suo_pose_errors_bop and suo_pose_nees (csrc/eval_nees_api.hip) share: the scratch layout, the staging of a call's pairs and the launch of
+// bop_errors_kernel.  `extra` bytes behind the block of maxima (256-aligned, L->o_extra) are the caller's.  Caller holds db->mu and has checked the arguments.
+int bop_maxima_enqueue_locked(MeshDb* db, const char* who, int n, const int* model_index, const double* T_est, const double* T_gt, const double* K, size_t extra,
+                              BopLayout* L) {
     int rc;
     if (!db->sym_dev && (rc = set_symmetries_locked(db, nullptr, nullptr))) return rc;
     int pmax = 0, smax = 0;
@@ -214,7 +200,9 @@ extern "C" int suo_pose_errors_bop(void* h, int n, const int* model_index, const
     // staged block: Te[n][12] | Tg[n][12] | K[n][9] | model[n]   then device-only: out[n][2] | flags[n] | smax[n][stride][2]
     const size_t o_te = 0, o_tg = (size_t)n * 96, o_k = o_tg + (size_t)n * 96, o_model = o_k + (size_t)n * 72, staged = (o_model + (size_t)n * 4 + 15) & ~(size_t)15;
     const size_t o_out = staged, o_flags = o_out + (size_t)n * 16, o_smax = (o_flags + (size_t)n * 4 + 255) & ~(size_t)255;
-    const size_t total = o_smax + (size_t)n * smax * 16;
+    const size_t end = o_smax + (size_t)n * smax * 16;
+    const size_t o_extra = extra ? (end + 255) & ~(size_t)255 : end;
+    const size_t total = o_extra + extra;
     if ((rc = ensure_scratch(db, total))) return rc;
     memcpy(db->scratch_host + o_te, T_est, (size_t)n * 96);
     memcpy(db->scratch_host + o_tg, T_gt, (size_t)n * 96);
@@ -223,7 +211,7 @@ extern "C" int suo_pose_errors_bop(void* h, int n, const int* model_index, const
     else for (int i = 0; i < n; ++i) for (int e = 0; e < 9; ++e) Kh[(size_t)i * 9 + e] = e % 4 == 0 ? 1.0 : 0.0;      // MSPD not asked for: any camera does
     memcpy(db->scratch_host + o_model, model_index, (size_t)n * 4);
     SUO_HIP_CHECK(hipMemcpyAsync(db->scratch_dev, db->scratch_host, staged, hipMemcpyHostToDevice, db->stream));
-    SUO_HIP_CHECK(hipMemsetAsync(db->scratch_dev + o_flags, 0, total - o_flags, db->stream));                           // +0.0: the identity of max over d^2 >= 0
+    SUO_HIP_CHECK(hipMemsetAsync(db->scratch_dev + o_flags, 0, end - o_flags, db->stream));                             // +0.0: the identity of max over d^2 >= 0
     BopArgs a;
     a.pts = db->pts_dev; a.off = db->off_dev; a.sym = db->sym_dev; a.soff = db->sym_off_dev;
     a.Te = (const double*)(db->scratch_dev + o_te); a.Tg = (const double*)(db->scratch_dev + o_tg); a.K = (const double*)(db->scratch_dev + o_k);
@@ -236,9 +224,28 @@ extern "C" int suo_pose_errors_bop(void* h, int n, const int* model_index, const
     const int want = (int)std::max<long long>(1, (BE_WG_TARGET + wgs - 1) / wgs);
     a.chunk = std::min(smax, std::max(4, std::min(BE_SCH, (smax + want - 1) / want)));
     const int chunks = (smax + a.chunk - 1) / a.chunk;
-    if (ptiles > 65535 || chunks > 65535) { suo_set_error("suo_pose_errors_bop: %d points x %d symmetries exceed the grid", pmax, smax); return SUO_ERR_ARG; }
+    if (ptiles > 65535 || chunks > 65535) { suo_set_error("%s: %d points x %d symmetries exceed the grid", who, pmax, smax); return SUO_ERR_ARG; }
     hipLaunchKernelGGL(bop_errors_kernel, dim3(n, ptiles, chunks), dim3(BE_BLOCK), 0, db->stream, a);
-    hipLaunchKernelGGL(bop_errors_min_kernel, dim3(n), dim3(BE_BLOCK), 0, db->stream, a);
+    SUO_HIP_CHECK(hipGetLastError());
+    L->args = a; L->o_out = o_out; L->o_flags = o_flags; L->o_extra = o_extra;
+    return SUO_OK;
+}
+
+}  // namespace suo
+
+extern "C" int suo_pose_errors_bop(void* h, int n, const int* model_index, const double* T_est, const double* T_gt, const double* K, double* mssd, double* mspd) {
+    MeshDb* db = (MeshDb*)h;
+    if (!db || n < 0 || (n > 0 && (!model_index || !T_est || !T_gt || (mspd && !K)))) { suo_set_error("suo_pose_errors_bop: bad argument"); return SUO_ERR_ARG; }
+    if (n == 0) return SUO_OK;
+    for (int i = 0; i < n; ++i)
+        if (model_index[i] < 0 || model_index[i] >= db->n_models) { suo_set_error("suo_pose_errors_bop: model_index[%d]=%d out of range", i, model_index[i]); return SUO_ERR_ARG; }
+    if (!mssd && !mspd) return SUO_OK;
+    std::lock_guard<std::mutex> lk(db->mu);
+    int rc;
+    BopLayout L;
+    if ((rc = bop_maxima_enqueue_locked(db, "suo_pose_errors_bop", n, model_index, T_est, T_gt, K, 0, &L))) return rc;
+    const size_t o_out = L.o_out, o_flags = L.o_flags;
+    hipLaunchKernelGGL(bop_errors_min_kernel, dim3(n), dim3(BE_BLOCK), 0, db->stream, L.args);
     SUO_HIP_CHECK(hipGetLastError());
     SUO_HIP_CHECK(hipMemcpyAsync(db->scratch_host + o_out, db->scratch_dev + o_out, o_flags + (size_t)n * 4 - o_out, hipMemcpyDeviceToHost, db->stream));
     SUO_HIP_CHECK(hipStreamSynchronize(db->stream));

@@ -34,6 +34,28 @@ struct MeshDb {
 
 int ensure_scratch(MeshDb* db, size_t bytes);     // csrc/eval.hip
 
+// csrc/eval_bop.hip.  The arguments of bop_errors_kernel / bop_errors_min_kernel.
+struct BopArgs {
+    const float* pts; const int* off;            // mesh database
+    const double* sym; const int* soff;          // its symmetry sets [soff[m] .. soff[m + 1])[12]
+    const int* model;                            // [n]
+    const double* Te; const double* Tg;          // [n][12] row-major 3x4
+    const double* K;                             // [n][9]
+    unsigned long long* smax;                    // [n][stride][2] bit patterns of max_i d^2: 3-D, 2-D
+    unsigned* flags;                             // [n] bit 0: a non-finite 3-D distance, bit 1: a non-finite 2-D distance
+    double* out;                                 // [n][2] min_s max_i d^2
+    int stride, chunk;
+};
+
+// bop_maxima_enqueue_locked: what suo_pose_errors_bop and suo_pose_nees (csrc/eval_nees_api.hip) share -- stage n pairs into the database's scratch and enqueue
+// bop_errors_kernel on db->stream.  On return L->args.smax is the [n][stride][2] block of merged squared maxima per symmetry (bit patterns; 3-D, 2-D) and
+// L->args.flags the sticky non-finite flags, both complete once the stream reaches what the caller enqueues next; o_out / o_flags are scratch offsets, and
+// `extra` bytes at o_extra (256-aligned, behind everything the kernels touch) are the caller's.  K may be NULL (the 2-D half is then not meaningful).
+// Caller holds db->mu and has checked the arguments.
+struct BopLayout { BopArgs args; size_t o_out, o_flags, o_extra; };
+int bop_maxima_enqueue_locked(MeshDb* db, const char* who, int n, const int* model_index, const double* T_est, const double* T_gt, const double* K, size_t extra,
+                              BopLayout* L);
+
 // csrc/raster.hip.  check_render_args: the argument rules of suo_render_depth (SUO_ERR_ARG with the message set, nothing launched).
 // render_depth_locked: enqueue n renders on db->stream (caller holds db->mu and has checked the arguments); on return *img_dev is [n][height][width]
 // float32 depth and *rbox_dev [n][4] the renders' clipped pixel boxes (x0, y0, x1, y1; x0 > x1: nothing drawn), both valid until the next render.

@@ -21,6 +21,7 @@ from time import time
 import numpy as np
 
 from . import bop, bop_eval, detections
+from . import consistency as _consistency
 from .eval_meter import EvalMeter
 from .geometry import invert_SE3
 from .object_slam import ObjectSLAM
@@ -62,7 +63,8 @@ def bop_eval_command(csv_path, outdir, targets_filename, repo_root="."):
 class Evaluator:
     def __init__(self, dataset, data_root, chkpt_path, nviews=1, no_network_cov=False, detection_type="saved", debug_gt_kp=False,
                  gt_cam_pose=False, no_prior_det=False, debug_saved_only=False, give_all_prior=False, out_dir=None, state_dict=None,
-                 do_add=None, seed=666, verbose=False, repo_root=".", run_bop_eval=False, frames_per_call=1, bop19=False, bop19_vsd=False):
+                 do_add=None, seed=666, verbose=False, repo_root=".", run_bop_eval=False, frames_per_call=1, bop19=False, bop19_vsd=False,
+                 consistency=False):
         """``dataset``: "ycbv" | "tless"; ``data_root``: the dataset directory of the BOP tree.  ``out_dir`` defaults to
         the checkpoint's directory like the reference.  ``do_add`` overrides the per-dataset default (the reference
         evaluates ADD only on YCB-V).  ``frames_per_call`` > 1 (single-view evaluation, nviews == 1, only): that many reference views go through
@@ -72,7 +74,11 @@ class Evaluator:
         ``bop19``: also report the BOP-19 MSSD and MSPD average recalls of exactly the poses written to the CSV (``run()["bop19"]`` and two lines of
         summary.txt); needs a dataset with a targets file (T-LESS) -- ValueError otherwise.  VSD stays the external hand-off unless
         ``bop19_vsd`` (with ``bop19``) is set: the third term is then rendered and scored on the device too (``run()["bop19"]["vsd"]`` and ``["ar"]``, the
-        ``AR_VSD`` and ``AR`` lines of summary.txt); needs the ``depth/`` folder of every scene of the split -- ValueError otherwise."""
+        ``AR_VSD`` and ``AR`` lines of summary.txt); needs the ``depth/`` folder of every scene of the split -- ValueError otherwise.
+        ``consistency``: also compare the reported uncertainties with the ground truth (consistency.ConsistencyMeter): the NEES of every pose that reaches the
+        ADD meter under its ``cov_OtoC`` and the chi2 of that view's keypoints under the network's covariances at the symmetry-resolved ground truth
+        (``run()["consistency"]`` and three lines of summary.txt).  The CSV does not change.  With ``frames_per_call`` > 1 it raises ValueError: the batched route
+        carries no ``cov_OtoC``."""
         cfg = _SETTINGS[dataset]
         self.frames_per_call = int(frames_per_call) if nviews == 1 else 1
         self.model_path = out_dir if out_dir is not None else os.path.dirname(chkpt_path or ".")
@@ -95,7 +101,13 @@ class Evaluator:
             self.bop_errors = bop_eval.BopErrors(mesh, bop_eval.load_models_info(os.path.join(data_root, cfg["models"])))
         elif bop19_vsd:
             raise ValueError("bop19_vsd=True is the third term of bop19=True: set both")
-        self.bop19_vsd = bool(bop19 and bop19_vsd)
+        self.bop19, self.bop19_vsd = bool(bop19), bool(bop19 and bop19_vsd)
+        self.consistency = bool(consistency)
+        if self.consistency:
+            if self.frames_per_call > 1:
+                raise ValueError("consistency=True needs frames_per_call == 1: the batched single-view route carries no cov_OtoC")
+            if self.bop_errors is None:
+                self.bop_errors = bop_eval.BopErrors(mesh, bop_eval.load_models_info(os.path.join(data_root, cfg["models"])))
         self._vsd_delta = bop_eval.VSD_DELTAS[dataset]
         self.debug_saved_only = debug_saved_only
         self.nviews, self.detection_type, self.debug_gt_kp, self.gt_cam_pose = nviews, detection_type, debug_gt_kp, gt_cam_pose
@@ -162,7 +174,12 @@ class Evaluator:
             a = self._view_args(scene_id, view_id, views_to_proc[0])
             if a is not None:
                 self.object_slam.process_view(*a[0], **a[1])
-        return self.object_slam.collect_results(last_only=self.nviews < 0, no_viz=True)
+        if not self.consistency:
+            return self.object_slam.collect_results(last_only=self.nviews < 0, no_viz=True)
+        results = self.object_slam.collect_results(last_only=self.nviews < 0, no_viz=True, covariances=True)
+        # the reference view's detections, read before the next reset() drops them
+        self._view_dets = dict(self.object_slam.detections.get(views_to_proc[0], {}))
+        return results
 
     @staticmethod
     def _to4(T):
@@ -183,7 +200,8 @@ class Evaluator:
             saved_meter = EvalMeter(self.mesh_db)
         csv_lines, num, num_cam_poses_found = [], 0, 0
         bop19_meter = None
-        if self.bop_errors is not None and not self.debug_saved_only:
+        cmeter = _consistency.ConsistencyMeter(self.bop_errors) if self.consistency and not self.debug_saved_only else None
+        if self.bop19 and not self.debug_saved_only:
             first_scene = ds.scene_ids()[0]
             im_width = ds.read_img(first_scene, ds.view_ids(first_scene)[0]).shape[1]
             if self.bop19_vsd:
@@ -202,6 +220,7 @@ class Evaluator:
             if not self.debug_saved_only and self.nviews < 0:
                 self.object_slam.reset()
             scene_results = []
+            view_dets = {}                                            # consistency: view -> that view's detections
             batched = not self.debug_saved_only and self.frames_per_call > 1 and not self.debug_gt_kp and not self.gt_cam_pose
             pending = []                                              # (view_id, gt_obj_ids, process_view arguments) waiting for their shared call
 
@@ -249,6 +268,8 @@ class Evaluator:
                     if len(results) == 0:
                         continue
                     scene_results.append((view_id, results[view_id]["poses"] if self.nviews > 0 else None, gt_obj_ids))
+                    if cmeter is not None:
+                        view_dets[view_id] = self._view_dets
                 if saved_meter is not None:
                     for o in gt_obj_ids:
                         idx = self.saved_detections_map.get(scene_id, {}).get(view_id, {}).get(o)
@@ -259,7 +280,7 @@ class Evaluator:
             flush(last=True)
             if self.debug_saved_only:
                 continue
-            final = self.object_slam.collect_results(no_viz=True, final=True) if self.nviews < 0 else None
+            final = self.object_slam.collect_results(no_viz=True, final=True, covariances=cmeter is not None) if self.nviews < 0 else None
             for view_id, pred_poses, gt_obj_ids in scene_results:
                 num += 1
                 if self.nviews < 0:
@@ -269,11 +290,14 @@ class Evaluator:
                         continue
                     num_cam_poses_found += 1
                     pred_poses = final[view_id]["poses"]
+                c_items = []                                          # consistency: (object, T_est, T_gt, cov) of the poses that reach the ADD meter
                 for o in gt_obj_ids:
                     res = pred_poses.get(o)
                     if res is not None and res["T_OtoC"] is not None:
                         if meter is not None:
                             meter.update([o], res["T_OtoC"][None, ...], ds.get_obj_pose(scene_id, view_id, o)[None, ...])
+                        if cmeter is not None:
+                            c_items.append((o, res["T_OtoC"], self._to4(ds.get_obj_pose(scene_id, view_id, o)), res["cov_OtoC"]))
                         if ds.is_target(scene_id, view_id, o):
                             csv_lines.append(bop_csv_line(scene_id, view_id, o, res["score"], res["T_OtoC"]))
                             if bop19_meter is not None:
@@ -282,6 +306,13 @@ class Evaluator:
                         self._log(f"NOTE: Could not obtain object pose for object {o}")
                         if meter is not None:                         # the reference updates unconditionally; without ADD there is no meter
                             meter.update_no_det([o])
+                if c_items:
+                    c_res = cmeter.add_poses([c[0] for c in c_items], np.stack([self._to4(c[1]) for c in c_items]), np.stack([c[2] for c in c_items]),
+                                             np.stack([np.asarray(c[3], np.float64).reshape(6, 6) for c in c_items]))
+                    dets = view_dets.get(view_id, {})
+                    with_det = [i for i, c in enumerate(c_items) if c[0] in dets]
+                    if with_det:
+                        cmeter.add_keypoints([dets[c_items[i][0]] for i in with_det], c_res["T_ref"][with_det])
         out = {"method": None, "csv_path": None, "summary_path": None, "result": None, "saved_result": None, "num_views": num,
                "num_cam_poses_found": num_cam_poses_found,
                # a silent demotion of the network to the bf16x3 form must show in the reported numbers: calls re-issued, and the form it ended on
@@ -296,6 +327,8 @@ class Evaluator:
             out["method"] = method
             if bop19_meter is not None:
                 out["bop19"] = bop19_meter.result()
+            if cmeter is not None:
+                out["consistency"] = cmeter.result()
             out["summary_path"] = os.path.join(outdir, "summary.txt")
             with open(out["summary_path"], "w") as f:
                 if meter is not None:
@@ -312,6 +345,16 @@ class Evaluator:
                         f.write(f"\nBOP-19 AR_VSD: {out['bop19']['vsd']['ar']:.4f} (recalls per tau: " +
                                 " ".join(f"{np.mean(r):.4f}" for r in out["bop19"]["vsd"]["recalls"]) + f"; delta {self._vsd_delta} mm)\n")
                         f.write(f"\nBOP-19 AR: {out['bop19']['ar']:.4f}\n")
+                if cmeter is not None:
+                    cp, ck = out["consistency"]["pose"], out["consistency"]["keypoint"]
+                    f.write(f"\nConsistency, poses: mean NEES {cp['mean_nees']:.4f} (6 if consistent), {100 * cp['frac_95']:.2f}% <= {_consistency.CHI2_6_95}, "
+                            f"{100 * cp['frac_99']:.2f}% <= {_consistency.CHI2_6_99}; {cp['n']} poses, {cp['n_nan']} NaN, "
+                            f"{cp['n_skipped_continuous']} of continuous-symmetry models left out\n")
+                    f.write("\nConsistency, poses per object (mean NEES, n): " +
+                            " ".join(f"{o}: {v['mean_nees']:.3f} ({v['n']})" for o, v in cp["per_object"].items()) + "\n")
+                    f.write(f"\nConsistency, keypoints: mean chi2 {ck['mean_chi2']:.4f} (2 if consistent), {100 * ck['frac_95']:.2f}% <= {_consistency.CHI2_2_95}, "
+                            f"{100 * ck['frac_99']:.2f}% <= {_consistency.CHI2_2_99}; {ck['n']} keypoints, {ck['n_nan']} NaN, "
+                            f"{ck['n_skipped']} detections without a covariance\n")
             out["csv_path"] = os.path.join(outdir, method + ".csv")
             with open(out["csv_path"], "w") as f:
                 f.writelines(csv_lines)
