@@ -464,7 +464,7 @@ int suo_optimize(suo_ba_problem* problem);
  *   frame-sized graphs (the per-view refinements)                       one 256-thread workgroup per problem (csrc/lm.hip)
  *   ONE graph of >= 512 edges with free cameras and free objects        the phase kernels of the multi-GPU adjustment below on one rank under the device-resident
  *   (ObjectSLAM.optimize's global adjustment, lib/object_slam.py:746)   schedule, driven from C: ~12 launches per LM trial, the host reads 16 doubles once per <= 12 trials
- *                                                                       (round 6; 60 cameras x 8 objects: 6.8 ms, 10.5 through the grid-barrier kernel of rounds 4-5)
+ *                                                                       (round 6; 60 cameras x 8 objects: 6.8 ms)
  *   more than 16 free objects next to free cameras                      the same phases under the host-driven schedule (the reduced system then lives in HBM) */
 int suo_optimize_batch(suo_ba_problem* problems, int n_problems);
 /* Test entry: the kernel suo_optimize_batch runs each problem of this batch on -- the plan the dispatcher itself executes (csrc/ba_api.hip: plan_ba_batch; same
@@ -480,7 +480,6 @@ int suo_optimize_batch(suo_ba_problem* problems, int n_problems);
 #define SUO_LM_ROUTE_CAM 6         /* lm_cam_kernel: one free camera, every object fixed, otherwise */
 #define SUO_LM_ROUTE_PHASES 7      /* csrc/lm_dist.hip phases, device-resident schedule: ONE graph of >= 512 edges, free cameras and free objects */
 #define SUO_LM_ROUTE_PHASEWISE 8   /* the same phases under the host schedule: > 16 free objects next to free cameras */
-#define SUO_LM_ROUTE_GRID 9        /* lm_grid_kernel: tuning builds only (-DSUO_TUNING) */
 int suo_debug_lm_routes(const suo_ba_problem* problems, int n_problems, int* route_out, int* lds_need_out);
 
 /* ---- 6x6 pose covariances of the refined cameras and objects ----------------------------------------------------------------------

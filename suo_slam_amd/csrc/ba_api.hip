@@ -63,12 +63,10 @@ static BaPlan plan_ba_batch(const suo_ba_problem* probs, int n_prob) {
     }
     auto all = [&](int r) { plan.route.assign(n_prob, r); return plan; };
     // ONE large graph with free cameras and free objects (the global SLAM adjustment): the phase kernels of csrc/lm_dist.hip under the device-resident LM schedule,
-    // driven from C (round 6).  Measured at 60 cameras x 8 objects: 106 us per LM trial against 129 for lm_grid_kernel's grid barriers; the Python-driven form of
+    // driven from C (round 6).  Measured at 60 cameras x 8 objects: 106 us per LM trial (129 for the grid-barrier kernel rounds 4-5 ran instead, since removed); the Python-driven form of
     // this very schedule (suo_slam_amd/ba_dist.py, one rank) was already the faster route and ObjectSLAM.optimize could not reach it through one C call.
-    // SUO_LM_PHASES (tuning builds, which also link csrc/lm_grid.hip): 0 = lm_grid_kernel as in rounds 4-5.
-    static const int phases = (int)SUO_TUNE("SUO_LM_PHASES", 1);
     static const int big_from = (int)SUO_TUNE("SUO_LM_BIG_EDGES", 512);       // (640 edges: 9.5 vs 12.2 ms, 1000: 10.9 vs 16.0, 350: 8.6 vs 6.1)
-    if (phases && n_prob == 1 && plan.max_edges >= big_from && plan.sum[0].nfo > 0 && plan.sum[0].nfc > 0) return all(SUO_LM_ROUTE_PHASES);
+    if (n_prob == 1 && plan.max_edges >= big_from && plan.sum[0].nfo > 0 && plan.sum[0].nfc > 0) return all(SUO_LM_ROUTE_PHASES);
     // camera tracking (ObjectSLAM.optimize(curr_only=True)): one free camera, every object fixed -> one wave per problem; the camera alone in its graph
     // (what curr_only=True builds): registers / LDS only (csrc/lm_cam2.hip)
     static const int cam_kernel = (int)SUO_TUNE("SUO_LM_CAM", 1);                    // 0: general kernel (A/B)
@@ -78,12 +76,7 @@ static BaPlan plan_ba_batch(const suo_ba_problem* probs, int n_prob) {
     // (csrc/lm_frame2.hip); otherwise one wave per object (csrc/lm_frame.hip, launch_lm_frame's two builds)
     if (frame_kernel > 0 && frame_only) return all(all_frame2 ? SUO_LM_ROUTE_FRAME2 : (plan.frame_max_obj <= 8 ? SUO_LM_ROUTE_FRAME8 : SUO_LM_ROUTE_FRAME16));
     // frame-sized graphs: one 256-thread workgroup each (csrc/lm.hip); large graphs that the phase route above does not take (several in one call, or no free
-    // object / no free camera): the 1024-thread single-workgroup build (csrc/lm_big.hip).  Tuning builds with SUO_LM_PHASES=0: ONE large graph spread over up
-    // to 32 workgroups with grid barriers (csrc/lm_grid.hip), rounds 4-5's route.
-#ifdef SUO_TUNING
-    static const int grid_wgs = (int)SUO_TUNE("SUO_LM_GRID_WGS", 32);          // 0: never use the grid kernel
-    if (plan.max_edges >= big_from && n_prob == 1 && grid_wgs > 0) return all(SUO_LM_ROUTE_GRID);
-#endif
+    // object / no free camera): the 1024-thread single-workgroup build (csrc/lm_big.hip).
     return all(plan.max_edges >= big_from ? SUO_LM_ROUTE_LM_BIG : SUO_LM_ROUTE_LM);
 }
 
@@ -119,16 +112,6 @@ int suo_optimize_batch(suo_ba_problem* probs, int n_prob) {
     case SUO_LM_ROUTE_FRAME2: rc = launch_lm_frame2(P, n_prob, plan.frame_max_obj, plan.max_edges, s); break;
     case SUO_LM_ROUTE_FRAME8:
     case SUO_LM_ROUTE_FRAME16: rc = launch_lm_frame(P, n_prob, plan.frame_max_obj, s); break;
-#ifdef SUO_TUNING
-    case SUO_LM_ROUTE_GRID: {
-        static void* grid_scratch = nullptr;
-        if (!grid_scratch) SUO_HIP_CHECK(hipMalloc(&grid_scratch, lm_grid_scratch_bytes()));
-        SUO_HIP_CHECK(hipMemsetAsync(grid_scratch, 0, 64, s));
-        static const int grid_wgs = (int)SUO_TUNE("SUO_LM_GRID_WGS", 32);
-        rc = launch_lm_grid(P, grid_scratch, std::max(1, std::min(grid_wgs, (plan.max_edges + 255) / 256)), s);
-        break;
-    }
-#endif
     case SUO_LM_ROUTE_LM_BIG: rc = launch_lm_big(P, n_prob, lds_need, s); break;
     default: rc = launch_lm(P, n_prob, lds_need, s); break;
     }

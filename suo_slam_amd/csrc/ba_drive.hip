@@ -7,6 +7,7 @@
 
 #include "ba_comm.h"
 #include "ba_stage.h"
+#include "lm_schedule.h"
 #include "tune.h"
 
 using namespace suo;
@@ -53,12 +54,12 @@ int suo::optimize_phasewise(suo_ba_problem* q) {
     if (q->init_with_outliers) { rc = suo_ba_classify(c, 1, &good); if (rc) return rc; }
     else { rc = suo_ba_classify(c, 0, &good); if (rc) return rc; num_good = (int)(good + 0.5); }
     bool robust_on = true;
-    const int drop = std::max(1, q->n_rounds / 2);
-    static const int diag21[6] = {0, 6, 11, 15, 18, 20};
+    const int drop = lm_drop_round(q->n_rounds);
     for (int rnd = 0; rnd < q->n_rounds; ++rnd) {
-        if (q->n_edge < 4 || num_good < 4) break;
+        if (lm_round_exit(q->n_edge, num_good)) break;
         ++rounds;
         double lam = -1, ni = 2;
+        // (unlike every other form of the schedule this loop does not ask whether any edge is active before it iterates: kept as it was)
         for (int it = 0; it < q->its[rnd]; ++it) {
             rc = suo_ba_linearize(c, robust_on, lin.data()); if (rc) return rc;
             double current_chi = lin[0];
@@ -67,31 +68,26 @@ int suo::optimize_phasewise(suo_ba_problem* q) {
                 double maxd = lin[1 + 27 * (size_t)O];
                 for (int o = 0; o < O; ++o)
                     if (!q->obj_fixed[o]) for (int d = 0; d < 6; ++d) maxd = std::max(maxd, fabs(HB[27 * o + diag21[d]]));
-                lam = 1e-5 * maxd; ni = 2;
+                lam = lm_lambda_init(maxd); ni = 2;
             }
-            double rho = 0; int qmax = 0; bool lam_finite = true;
+            LmTrials tr;
             do {
                 rc = suo_ba_schur(c, lam, sch.data()); if (rc) return rc;
-                double temp_chi = 1.7976931348623157e308, scale = 0;
+                double temp_chi = LM_CHI2_FAILED, scale = 0;
                 if (sch[(size_t)ns * ns + ns] > 0.5) {
                     memcpy(tot.data(), HB, 27 * (size_t)O * sizeof(double));
                     memcpy(tot.data() + 27 * (size_t)O, sch.data(), ((size_t)ns * ns + ns) * sizeof(double));
                     rc = suo_ba_solve_update(c, lam, robust_on, tot.data(), red); if (rc) return rc;
                     if (red[3] > 0.5) { temp_chi = red[0]; scale = red[1] + red[2]; }
                 }
-                rho = (current_chi - temp_chi) / (scale + 1e-3);
-                if (rho > 0 && std::isfinite(temp_chi)) {
-                    const double alpha = std::min(1.0 - pow(2 * rho - 1, 3.0), 2.0 / 3.0);
-                    lam *= std::max(1.0 / 3.0, alpha); ni = 2; current_chi = temp_chi;
-                } else {
-                    lam *= ni; ni *= 2;
+                if (!tr.verdict<true>(lam, ni, current_chi, temp_chi, scale)) {
                     rc = suo_ba_restore(c); if (rc) return rc;
-                    if (!std::isfinite(lam)) { lam_finite = false; break; }
+                    if (!tr.lam_finite) break;
                 }
-                ++qmax; ++lm_trials;
-            } while (rho < 0 && qmax < 10);
+                tr.count(); ++lm_trials;
+            } while (tr.another());
             ++lm_its;
-            if (qmax == 10 || rho == 0 || !lam_finite) break;
+            if (tr.terminate()) break;
         }
         rc = suo_ba_classify(c, 0, &good); if (rc) return rc;
         num_good = (int)(good + 0.5);
@@ -117,9 +113,9 @@ static int lm_rounds(const suo_ba_problem* q, int batch, const double* h_ctl, in
     if (q->init_with_outliers) { rc = classify(1, &tmp); if (rc) return rc; }
     else { rc = classify(0, &num_good); if (rc) return rc; }
     int robust_on = 1;
-    const int drop = std::max(1, q->n_rounds / 2);
+    const int drop = lm_drop_round(q->n_rounds);
     for (int rnd = 0; rnd < q->n_rounds; ++rnd) {
-        if (q->n_edge < 4 || num_good < 4) break;
+        if (lm_round_exit(q->n_edge, num_good)) break;
         ++rounds;
         const int its = q->its[rnd];
         rc = begin(its); if (rc) return rc;

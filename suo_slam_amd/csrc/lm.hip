@@ -159,13 +159,15 @@ __global__ __launch_bounds__(LM_THREADS) void lm_kernel(const LmProblem* __restr
         if (tid == 0) sh_good = (int)g;
     }
     __syncthreads();
+    // The rounds are written out here over the steps of csrc/lm_schedule.h instead of going through lm_run_rounds: with the phases as callables the
+    // 1024-thread build of this kernel (csrc/lm_big.hip) spilled 32 bytes per lane more.
     int num_good = sh_good;
     bool robust_on = true;
     int rounds = 0, lm_its = 0, lm_trials = 0;
-    const int drop = (P.n_rounds / 2) > 1 ? (P.n_rounds / 2) : 1;
+    const int drop = lm_drop_round(P.n_rounds);
 
     for (int round = 0; round < P.n_rounds; ++round) {
-        if (P.n_edge < 4 || num_good < 4) break;
+        if (lm_round_exit(P.n_edge, num_good)) break;
         ++rounds;
         // any active edge at all?  (g2o: 0 vertices to optimise -> optimize() returns without iterating)
         double nact = 0;
@@ -224,21 +226,17 @@ __global__ __launch_bounds__(LM_THREADS) void lm_kernel(const LmProblem* __restr
             __syncthreads();
             if (it == 0) {      // computeLambdaInit: tau * max |diag|
                 double md = 0;
-                const int diag21[6] = {0, 6, 11, 15, 18, 20};
                 for (int idx = tid; idx < (P.n_cam + P.n_obj) * 6; idx += LM_THREADS) {
                     const int v = idx / 6, d = idx - v * 6;
                     if (v < P.n_cam) { if (!P.cam_fixed[v]) md = fmax(md, fabs(P.Hcc[36 * v + diag21[d]])); }
                     else { const int o = v - P.n_cam; if (!P.obj_fixed[o]) md = fmax(md, fabs(P.Hoo[36 * o + diag21[d]])); }
                 }
-                md = block_max(md, red);
-                lambda = 1e-5 * md;
+                lambda = lm_lambda_init(block_max(md, red));
                 ni = 2;
             }
             LMPROF(3);
             // ---- trials ----------------------------------------------------------------------
-            double rho = 0;
-            int qmax = 0;
-            bool lam_finite = true;
+            LmTrials tr;
             do {
                 // push()
                 for (int c = tid; c < P.n_cam; c += LM_THREADS) P.cam_bak[c] = P.cam[c];
@@ -379,7 +377,7 @@ __global__ __launch_bounds__(LM_THREADS) void lm_kernel(const LmProblem* __restr
                 LMPROF(9);
                 double tempChi = active_errors_and_chi2(P, robust_on, false, red);
                 LMPROF(10);
-                if (!ok2) tempChi = 1.7976931348623157e308;
+                if (!ok2) tempChi = LM_CHI2_FAILED;
                 // computeScale: sum x (lambda x + b)
                 double sc = 0;
                 if (ok2) {
@@ -389,27 +387,18 @@ __global__ __launch_bounds__(LM_THREADS) void lm_kernel(const LmProblem* __restr
                         if (!P.obj_fixed[idx / 6]) sc += P.xo[idx] * (lambda * P.xo[idx] + P.bo[idx]);
                 }
                 sc = block_sum(sc, red);
-                rho = (currentChi - tempChi) / (sc + 1e-3);
-                if (rho > 0 && isfinite(tempChi)) {
-                    double alpha = 1. - pow(2 * rho - 1, 3.0);
-                    alpha = fmin(alpha, 2. / 3.);
-                    lambda *= fmax(1. / 3., alpha);
-                    ni = 2;
-                    currentChi = tempChi;
-                } else {
-                    lambda *= ni;
-                    ni *= 2;
+                if (!tr.verdict<true>(lambda, ni, currentChi, tempChi, sc)) {
                     __syncthreads();
                     for (int c = tid; c < P.n_cam; c += LM_THREADS) P.cam[c] = P.cam_bak[c];     // pop()
                     for (int o = tid; o < P.n_obj; o += LM_THREADS) P.obj[o] = P.obj_bak[o];
                     __syncthreads();
-                    if (!isfinite(lambda)) { lam_finite = false; break; }
+                    if (!tr.lam_finite) break;
                 }
-                ++qmax;
+                tr.count();
                 ++lm_trials;
-            } while (rho < 0 && qmax < 10);
+            } while (tr.another());
             ++lm_its;
-            if (qmax == 10 || rho == 0 || !lam_finite) break;      // Terminate
+            if (tr.terminate()) break;
         }
         // ---- re-classification (object_slam.py:877-896), chi2 at the accepted state -----------
         __syncthreads();
@@ -438,9 +427,7 @@ __global__ __launch_bounds__(LM_THREADS) void lm_kernel(const LmProblem* __restr
 #endif
 }
 
-#ifdef SUO_LM_BIG
-// the 1024-thread build of this file (csrc/lm_big.hip): only the kernel and its launcher
-int launch_lm_big(const void* problems_dev, int n_problems, int lds_bytes, hipStream_t s) {
+static int launch_lm_kernel(const void* problems_dev, int n_problems, int lds_bytes, hipStream_t s) {
     if (n_problems <= 0) return SUO_OK;
     if (lds_bytes <= 0 || lds_bytes > LM_LDS_BYTES) lds_bytes = LM_LDS_BYTES;
     static bool attr_set = false;
@@ -452,6 +439,10 @@ int launch_lm_big(const void* problems_dev, int n_problems, int lds_bytes, hipSt
     SUO_HIP_CHECK(hipGetLastError());
     return SUO_OK;
 }
+
+#ifdef SUO_LM_BIG
+// the 1024-thread build of this file (csrc/lm_big.hip): only the kernel and its launcher
+int launch_lm_big(const void* problems_dev, int n_problems, int lds_bytes, hipStream_t s) { return launch_lm_kernel(problems_dev, n_problems, lds_bytes, s); }
 #else
 // Dynamic LDS a problem of this size wants (everything resident), capped at LM_LDS_BYTES.  Small problems ask
 // for little, so their workgroup can share a CU with the CNN's workgroups instead of waiting for an empty one.
@@ -472,18 +463,7 @@ int lm_lds_bytes(int C, int O, int E, int NP, int n_free_obj_schur) {
     return (int)(b > (size_t)LM_LDS_BYTES ? (size_t)LM_LDS_BYTES : b);
 }
 
-int launch_lm(const void* problems_dev, int n_problems, int lds_bytes, hipStream_t s) {
-    if (n_problems <= 0) return SUO_OK;
-    if (lds_bytes <= 0 || lds_bytes > LM_LDS_BYTES) lds_bytes = LM_LDS_BYTES;
-    static bool attr_set = false;
-    if (!attr_set) {
-        SUO_HIP_CHECK(hipFuncSetAttribute((const void*)lm_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, LM_LDS_BYTES));
-        attr_set = true;
-    }
-    hipLaunchKernelGGL(lm_kernel, dim3(n_problems), dim3(LM_THREADS), lds_bytes, s, (const LmProblem*)problems_dev, lds_bytes);
-    SUO_HIP_CHECK(hipGetLastError());
-    return SUO_OK;
-}
+int launch_lm(const void* problems_dev, int n_problems, int lds_bytes, hipStream_t s) { return launch_lm_kernel(problems_dev, n_problems, lds_bytes, s); }
 #endif  // SUO_LM_BIG
 
 }  // namespace suo

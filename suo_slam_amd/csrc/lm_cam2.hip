@@ -96,35 +96,24 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(1, 1))) void
                 cs += robust_on ? huber_rho(c2, P.huber_delta, wgt) : c2;
                 const double i0 = wgt * E[9], i1 = wgt * E[10], i2 = wgt * E[11];
                 const double g0 = -(E[9] * er[0] + E[10] * er[1]) * wgt, g1 = -(E[10] * er[0] + E[11] * er[1]) * wgt;
-                double wj0[6], wj1[6];
-#pragma unroll
-                for (int cc = 0; cc < 6; ++cc) { wj0[cc] = i0 * J[cc] + i1 * J[6 + cc]; wj1[cc] = i1 * J[cc] + i2 * J[6 + cc]; }
-                int u = 0;
-#pragma unroll
-                for (int r = 0; r < 6; ++r)
-#pragma unroll
-                    for (int cc = r; cc < 6; ++cc) { h[u] = fma(J[6 + r], wj1[cc], fma(J[r], wj0[cc], h[u])); ++u; }
-#pragma unroll
-                for (int r = 0; r < 6; ++r) h[21 + r] = fma(J[6 + r], g1, fma(J[r], g0, h[21 + r]));
+                accumulate_jtwj<true>(J, i0, i1, i2, g0, g1, h);
             }
         }
         return cs;
     };
 
-    int num_good = P.init_with_outliers ? ne : (int)classify();
-    bool robust_on = true;
-    int rounds = 0, lm_its = 0, lm_trials = 0;
-    const int drop = (P.n_rounds / 2) > 1 ? (P.n_rounds / 2) : 1;
-
-    for (int round = 0; round < P.n_rounds; ++round) {
-        if (ne < 4 || num_good < 4) break;
-        ++rounds;
-        double nact = 0;
-        for (int j = 0; j < epl; ++j) if (lane + 64 * j < ne && !((lvl >> j) & 1u)) nact += 1;
-        const int iterations = wsum(nact) > 0 ? P.its[round] : 0;
-        double lambda = -1, ni = 2;
-        double h[27], currentChi = 0;
-        for (int it = 0; it < iterations; ++it) {
+    double h[27], h2[27], chi_h = 0, chi_h2 = 0;     // the system and its chi2 at the standing pose / at the trial pose
+    Pose trial;
+    const LmCounters n = lm_run_rounds<false>(
+        P,
+        [&]() -> int { return P.init_with_outliers ? ne : (int)classify(); },
+        [&]() -> bool {
+            double nact = 0;
+            for (int j = 0; j < epl; ++j) if (lane + 64 * j < ne && !((lvl >> j) & 1u)) nact += 1;
+            return wsum(nact) > 0;
+        },
+        // only the first iteration linearises: an accepted trial's edge pass has accumulated the next iteration's system (csrc/lm_frame2.hip)
+        [&](bool robust_on, int it, double& max_diag) -> double {
             if (it == 0) {
                 double Rc[9];
                 q_to_R(pose.q, Rc);
@@ -133,66 +122,36 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(1, 1))) void
                 const double c = edge_pass(Rc, pose.t, robust_on, h);
 #pragma unroll
                 for (int k = 0; k < 27; ++k) h[k] = wsum(h[k]);
-                currentChi = wsum(c);
-                const int diag21[6] = {0, 6, 11, 15, 18, 20};           // computeLambdaInit: tau * max |diag H|
-                double md = 0;
-#pragma unroll
-                for (int d = 0; d < 6; ++d) md = fmax(md, fabs(h[diag21[d]]));
-                lambda = 1e-5 * md;
-                ni = 2;
+                chi_h = wsum(c);
+                max_diag = sym21_max_abs_diag(h);
             }
-            double rho = 0;
-            int qmax = 0;
-            bool lam_finite = true;
-            do {
-                double A[36], b6[6], x[6] = {0, 0, 0, 0, 0, 0};
-                {
-                    int u = 0;
+            return chi_h;
+        },
+        [&](double lambda, bool robust_on) -> LmTrial {
+            double A[36], b6[6], x[6] = {0, 0, 0, 0, 0, 0};
+            sym21_to_system(h, lambda, A, b6);
+            const bool ok2 = spd_solve6(A, b6, x);                       // every lane, identically
+            trial = pose;
+            double sc = 0;
+            if (ok2) {
+                pose_oplus(trial, x);
+                for (int d = 0; d < 6; ++d) sc += x[d] * (lambda * x[d] + h[21 + d]);      // computeScale: sum x (lambda x + b)
+            }
+            double Rt[9];
+            q_to_R(trial.q, Rt);
 #pragma unroll
-                    for (int r = 0; r < 6; ++r)
+            for (int k = 0; k < 27; ++k) h2[k] = 0;
+            chi_h2 = wsum(edge_pass(Rt, trial.t, robust_on, h2));
+            return {chi_h2, sc, ok2};
+        },
+        [&]() {
+            pose = trial;                                                // update(x) is kept ...
+            chi_h = chi_h2;
 #pragma unroll
-                        for (int c = r; c < 6; ++c) { A[r * 6 + c] = h[u]; A[c * 6 + r] = h[u]; ++u; }
-#pragma unroll
-                    for (int d = 0; d < 6; ++d) { A[d * 7] += lambda; b6[d] = h[21 + d]; }
-                }
-                const bool ok2 = spd_solve6(A, b6, x);                   // every lane, identically
-                Pose trial = pose;
-                double sc = 0;
-                if (ok2) {
-                    pose_oplus(trial, x);
-                    for (int d = 0; d < 6; ++d) sc += x[d] * (lambda * x[d] + h[21 + d]);      // computeScale: sum x (lambda x + b)
-                }
-                double Rt[9], h2[27];
-                q_to_R(trial.q, Rt);
-#pragma unroll
-                for (int k = 0; k < 27; ++k) h2[k] = 0;
-                double tempChi = wsum(edge_pass(Rt, trial.t, robust_on, h2));
-                if (!ok2) tempChi = 1.7976931348623157e308;
-                rho = (currentChi - tempChi) / (sc + 1e-3);
-                if (rho > 0 && isfinite(tempChi)) {
-                    const double r21 = 2 * rho - 1;
-                    double alpha = 1. - r21 * r21 * r21;
-                    alpha = fmin(alpha, 2. / 3.);
-                    lambda *= fmax(1. / 3., alpha);
-                    ni = 2;
-                    currentChi = tempChi;
-                    pose = trial;                                        // update(x) is kept ...
-#pragma unroll
-                    for (int k = 0; k < 27; ++k) h[k] = wsum(h2[k]);      // ... and with it the system at the new pose
-                } else {
-                    lambda *= ni;
-                    ni *= 2;                                             // pop(): the trial pose is simply dropped
-                    if (!isfinite(lambda)) { lam_finite = false; break; }
-                }
-                ++qmax;
-                ++lm_trials;
-            } while (rho < 0 && qmax < 10);
-            ++lm_its;
-            if (qmax == 10 || rho == 0 || !lam_finite) break;            // Terminate
-        }
-        num_good = (int)classify();
-        if (round == drop) robust_on = false;
-    }
+            for (int k = 0; k < 27; ++k) h[k] = wsum(h2[k]);              // ... and with it the system at the new pose
+        },
+        [&]() {},                                                        // pop(): the trial pose is simply dropped
+        [&]() -> int { return (int)classify(); });
     if (lane == 0) pose_to_T(pose, P.cam_T);
     for (int o = lane; o < P.n_obj; o += 64) {                           // fixed objects: the same quaternion round trip as csrc/lm_cam.hip
         Pose ob;
@@ -203,7 +162,7 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(1, 1))) void
         const int e = lane + 64 * j;
         if (e < ne) P.level[e] = (uint8_t)((lvl >> j) & 1u);
     }
-    if (lane == 0) { P.stats[0] = rounds; P.stats[1] = lm_its; P.stats[2] = lm_trials; P.stats[3] = num_good; }
+    if (lane == 0) n.store(P.stats);
 }
 
 int lm_cam2_max_edges() { return LC2_MAX_EDGES; }

@@ -3,6 +3,7 @@
 #pragma once
 #include <type_traits>
 
+#include "lm_schedule.h"
 #include "suo_internal.h"
 
 namespace suo {
@@ -684,7 +685,7 @@ DEV double edge_chi2(const LmProblem& P, int e, const double* err) {
 // computeActiveErrors + activeRobustChi2; with_jac also stores the edge Jacobians (linearizeOplus) and the
 // Huber-weighted information / gradient factors used by constructQuadraticForm.  Threads over edges.
 // this thread's share of the edges [e_begin, e_end): returns its partial (robustified) chi2
-// (t0, stride): this thread's position in the loop -- one workgroup by default, a whole grid in csrc/lm_grid.hip
+// (t0, stride): this thread's position in the loop -- one workgroup by default, a whole grid in csrc/lm_dist.hip
 DEV double edge_pass_partial(const LmProblem& P, int e_begin, int e_end, bool robust_on, bool with_jac, int t0 = threadIdx.x,
                              int stride = LM_THREADS) {
     double c = 0;
@@ -808,6 +809,48 @@ DEV void unpack_sym21(const double* s, double* A) {
     int u = 0;
     for (int r = 0; r < 6; ++r)
         for (int c = r; c < 6; ++c) { A[r * 6 + c] = s[u]; A[c * 6 + r] = s[u]; ++u; }
+}
+
+// ---- one vertex's 6x6 system in registers: h = [J^T W J packed upper (21) | J^T W r (6)] (the one-wave kernels: lm_cam*, lm_frame*) ----
+// A = H + lambda I (full), b6 = the gradient
+DEV void sym21_to_system(const double (&h)[27], double lambda, double* A, double* b6) {
+    int u = 0;
+#pragma unroll
+    for (int r = 0; r < 6; ++r)
+#pragma unroll
+        for (int c = r; c < 6; ++c) { A[r * 6 + c] = h[u]; A[c * 6 + r] = h[u]; ++u; }
+#pragma unroll
+    for (int d = 0; d < 6; ++d) { A[d * 7] += lambda; b6[d] = h[21 + d]; }
+}
+// h += one edge's J^T W J and J^T W r: J = the vertex's 2x6 Jacobian (rows at J[0], J[6]), (i0, i1, i2) the weighted information, (g0, g1) = -W r.
+// FUSED: accumulate with explicit fma (half the instructions) or as a * b + c * d under -ffp-contract=off: they round differently, so every kernel
+// keeps the form it was written with.
+template <bool FUSED>
+DEV void accumulate_jtwj(const double* J, double i0, double i1, double i2, double g0, double g1, double (&h)[27]) {
+    double wj0[6], wj1[6];                            // W J rows
+#pragma unroll
+    for (int c = 0; c < 6; ++c) { wj0[c] = i0 * J[c] + i1 * J[6 + c]; wj1[c] = i1 * J[c] + i2 * J[6 + c]; }
+    int u = 0;
+#pragma unroll
+    for (int r = 0; r < 6; ++r)
+#pragma unroll
+        for (int c = r; c < 6; ++c) {
+            if (FUSED) h[u] = fma(J[6 + r], wj1[c], fma(J[r], wj0[c], h[u]));
+            else h[u] += J[r] * wj0[c] + J[6 + r] * wj1[c];
+            ++u;
+        }
+#pragma unroll
+    for (int r = 0; r < 6; ++r) {
+        if (FUSED) h[21 + r] = fma(J[6 + r], g1, fma(J[r], g0, h[21 + r]));
+        else h[21 + r] += J[r] * g0 + J[6 + r] * g1;
+    }
+}
+// max |diag| of that block (computeLambdaInit's share of one vertex)
+DEV double sym21_max_abs_diag(const double (&h)[27]) {
+    double md = 0;
+#pragma unroll
+    for (int d = 0; d < 6; ++d) md = fmax(md, fabs(h[diag21[d]]));
+    return md;
 }
 
 }  // namespace suo

@@ -8,7 +8,7 @@
 //     local:   every rank solves the SAME reduced system (blockdiag(Hoo + lambda I) - S) x_o = b_o - r,
 //              back-substitutes its own cameras, updates poses, evaluates its part of chi2
 //     RCCL:    all-reduce(sum) of [chi2, step-scale] -> identical accept / reject and lambda on every rank
-// which is exactly the system the single-GPU kernels (csrc/lm.hip, csrc/lm_grid.hip) form; g2o's lambda schedule
+// which is exactly the system the single-GPU kernel (csrc/lm.hip) forms; g2o's lambda schedule
 // (optimization_algorithm_levenberg.cpp:58-150) runs on the host between phases (suo_slam_amd/ba_dist.py).
 //
 // A rank's share of a large graph is thousands of edges, so every data-parallel step of a phase is its own grid-strided
@@ -20,7 +20,6 @@
 
 namespace suo {
 
-constexpr int DIAG21[6] = {0, 6, 11, 15, 18, 20};
 constexpr int BA_WGS = 64;                     // workgroups of the grid-strided steps
 // scratch (device, per context): [0, BA_WGS) workgroup partials | [BA_WGS] failure counter (as double bits of an int)
 constexpr int BA_SCRATCH_DOUBLES = BA_WGS + 8;
@@ -152,7 +151,7 @@ __global__ __launch_bounds__(LM_THREADS) void ba_linearize_tail_kernel(const LmP
     double md = 0;
     for (int idx = threadIdx.x; idx < P.n_cam * 6; idx += LM_THREADS) {
         const int c = idx / 6;
-        if (!P.cam_fixed[c]) md = fmax(md, fabs(P.Hcc[36 * c + DIAG21[idx - c * 6]]));
+        if (!P.cam_fixed[c]) md = fmax(md, fabs(P.Hcc[36 * c + diag21[idx - c * 6]]));
     }
     md = block_max(md, red);
     if (threadIdx.x == 0) {
@@ -538,8 +537,8 @@ __device__ void ba_ctl_lin(const LmProblem& P, double* __restrict__ ctl, const d
         for (int r = 0; r < world; ++r) maxd = fmax(maxd, lin[1 + 27 * P.n_obj + r]);
         for (int o = 0; o < P.n_obj; ++o)
             if (!P.obj_fixed[o])
-                for (int d = 0; d < 6; ++d) maxd = fmax(maxd, fabs(lin[1 + 27 * o + DIAG21[d]]));
-        ctl[CTL_LAMBDA] = 1e-5 * maxd;
+                for (int d = 0; d < 6; ++d) maxd = fmax(maxd, fabs(lin[1 + 27 * o + diag21[d]]));
+        ctl[CTL_LAMBDA] = lm_lambda_init(maxd);
         ctl[CTL_NI] = 2;
     }
     ctl[CTL_QMAX] = 0; ctl[CTL_RHO] = 0;
@@ -558,31 +557,18 @@ __device__ void ba_decide(double* __restrict__ ctl, const double* __restrict__ r
     if ((int)ctl[CTL_STATE] != ST_TRIAL) return;
     const int world = (int)ctl[CTL_WORLD];
     double lambda = ctl[CTL_LAMBDA], ni = ctl[CTL_NI], current = ctl[CTL_CHI];
-    double temp = 1.7976931348623157e308, scale = 0;
+    double temp = LM_CHI2_FAILED, scale = 0;
     if ((int)(red[2] + 0.5) == world) { temp = red[0]; scale = red[1] + red[3]; }
-    const double rho = (current - temp) / (scale + 1e-3);
-    bool lam_finite = true;
-    int qmax = (int)ctl[CTL_QMAX];
-    if (rho > 0 && isfinite(temp)) {
-        const double r21 = 2 * rho - 1;
-        double alpha = 1. - r21 * r21 * r21;
-        alpha = fmin(alpha, 2. / 3.);
-        lambda *= fmax(1. / 3., alpha);
-        ni = 2;
-        current = temp;
-    } else {
-        lambda *= ni;
-        ni *= 2;
-        ctl[CTL_RESTORE] = 1;                                  // pop()
-        if (!isfinite(lambda)) lam_finite = false;
-    }
-    if (lam_finite) { ++qmax; ctl[CTL_TRIALS] += 1; }
-    ctl[CTL_LAMBDA] = lambda; ctl[CTL_NI] = ni; ctl[CTL_CHI] = current; ctl[CTL_RHO] = rho; ctl[CTL_QMAX] = qmax;
-    if (lam_finite && rho < 0 && qmax < 10) return;            // another trial on the same linearisation
+    LmTrials tr;
+    tr.qmax = (int)ctl[CTL_QMAX];
+    if (!tr.verdict<false>(lambda, ni, current, temp, scale)) ctl[CTL_RESTORE] = 1;      // pop()
+    if (tr.lam_finite) { tr.count(); ctl[CTL_TRIALS] += 1; }
+    ctl[CTL_LAMBDA] = lambda; ctl[CTL_NI] = ni; ctl[CTL_CHI] = current; ctl[CTL_RHO] = tr.rho; ctl[CTL_QMAX] = tr.qmax;
+    if (tr.lam_finite && tr.another()) return;                       // another trial on the same linearisation
     ctl[CTL_LM_ITS] += 1;
     const int it = (int)ctl[CTL_IT] + 1;
     ctl[CTL_IT] = it;
-    ctl[CTL_STATE] = (qmax == 10 || rho == 0 || !lam_finite || it >= (int)ctl[CTL_ITS]) ? ST_DONE : ST_LINEARIZE;
+    ctl[CTL_STATE] = (tr.terminate() || it >= (int)ctl[CTL_ITS]) ? ST_DONE : ST_LINEARIZE;
 }
 __global__ __launch_bounds__(LM_THREADS) void ba_ctl_decide_kernel(const LmProblem* __restrict__ Pp, double* __restrict__ ctl, const double* __restrict__ red) {
     __shared__ int sh_restore;

@@ -155,16 +155,7 @@ __global__ __launch_bounds__(64 * MAXW) void lm_frame_kernel(const LmProblem* __
             if constexpr (WITH_H) {
                 const double i0 = wgt * E.info[0], i1 = wgt * E.info[1], i2 = wgt * E.info[2];
                 const double g0 = -(E.info[0] * er[0] + E.info[1] * er[1]) * wgt, g1 = -(E.info[1] * er[0] + E.info[2] * er[1]) * wgt;
-                double wj0[6], wj1[6];
-#pragma unroll
-                for (int cc = 0; cc < 6; ++cc) { wj0[cc] = i0 * Jo[cc] + i1 * Jo[6 + cc]; wj1[cc] = i1 * Jo[cc] + i2 * Jo[6 + cc]; }
-                int u = 0;
-#pragma unroll
-                for (int r = 0; r < 6; ++r)
-#pragma unroll
-                    for (int cc = r; cc < 6; ++cc) h[u++] += Jo[r] * wj0[cc] + Jo[6 + r] * wj1[cc];
-#pragma unroll
-                for (int r = 0; r < 6; ++r) h[21 + r] += Jo[r] * g0 + Jo[6 + r] * g1;
+                accumulate_jtwj<false>(Jo, i0, i1, i2, g0, g1, h);
             }
         };
         if (free_obj) {
@@ -180,102 +171,64 @@ __global__ __launch_bounds__(64 * MAXW) void lm_frame_kernel(const LmProblem* __
         return wsum(c);
     };
 
-    double ex[4];
-    int num_good;
-    {
-        const double g = P.init_with_outliers ? classify(true) : classify(false);
-        exchange(g, 0, 0, 0, ex);
-        num_good = P.init_with_outliers ? P.n_edge : (int)ex[0];
-    }
-    bool robust_on = true;
-    int rounds = 0, lm_its = 0, lm_trials = 0;
-    const int drop = (P.n_rounds / 2) > 1 ? (P.n_rounds / 2) : 1;
-
-    for (int round = 0; round < P.n_rounds; ++round) {
-        if (P.n_edge < 4 || num_good < 4) break;
-        ++rounds;
-        double nact = 0;                                         // any active edge at all? (g2o: nothing to optimise -> no iterations)
-        if (free_obj) {
-            if (e_first >= 0 && lvl0 == 0) nact += 1;
-            for (int j = 64 + lane; j < n_own; j += 64) nact += P.level[nth_edge(j)] == 0 ? 1.0 : 0.0;
-        }
-        exchange(wsum(nact), 0, 0, 0, ex);
-        const int iterations = ex[0] > 0 ? P.its[round] : 0;
-        double lambda = -1, ni = 2;
-        for (int it = 0; it < iterations; ++it) {
-            // ---- errors, chi2, the object's 6x6 system ------------------------------------------------------
-            double Ro[9], h[27];
+    double ex[4], h[27];                                         // h: the object's 6x6 system at the standing pose
+    Pose trial;
+    const LmCounters n = lm_run_rounds<true>(
+        P,
+        [&]() -> int {
+            const double g = P.init_with_outliers ? classify(true) : classify(false);
+            exchange(g, 0, 0, 0, ex);
+            return P.init_with_outliers ? P.n_edge : (int)ex[0];
+        },
+        [&]() -> bool {                                          // any active edge at all? (g2o: nothing to optimise -> no iterations)
+            double nact = 0;
+            if (free_obj) {
+                if (e_first >= 0 && lvl0 == 0) nact += 1;
+                for (int j = 64 + lane; j < n_own; j += 64) nact += P.level[nth_edge(j)] == 0 ? 1.0 : 0.0;
+            }
+            exchange(wsum(nact), 0, 0, 0, ex);
+            return ex[0] > 0;
+        },
+        [&](bool robust_on, int, double& max_diag) -> double {   // errors, chi2, the object's 6x6 system
+            double Ro[9];
             q_to_R(pose.q, Ro);
 #pragma unroll
             for (int k = 0; k < 27; ++k) h[k] = 0;
             const double chi_o = edge_pass(Ro, pose.t, robust_on, std::true_type{}, h);
             wsum_many<27>(h);
             double md = 0;
-            if (free_obj) {
-                const int diag21[6] = {0, 6, 11, 15, 18, 20};
-#pragma unroll
-                for (int d = 0; d < 6; ++d) md = fmax(md, fabs(h[diag21[d]]));
-            }
+            if (free_obj) md = sym21_max_abs_diag(h);
             exchange(chi_o, 0, 0, md, ex);
-            double currentChi = ex[0];
-            if (it == 0) { lambda = 1e-5 * ex[3]; ni = 2; }      // computeLambdaInit: tau * max |diag H| over all free vertices
-            // ---- trials ---------------------------------------------------------------------------------------
-            double rho = 0;
-            int qmax = 0;
-            bool lam_finite = true;
-            do {
-                double A[36], b6[6], x[6] = {0, 0, 0, 0, 0, 0};
-                {
-                    int u = 0;
-#pragma unroll
-                    for (int r = 0; r < 6; ++r)
-#pragma unroll
-                        for (int c = r; c < 6; ++c) { A[r * 6 + c] = h[u]; A[c * 6 + r] = h[u]; ++u; }
-#pragma unroll
-                    for (int d = 0; d < 6; ++d) { A[d * 7] += lambda; b6[d] = h[21 + d]; }
+            max_diag = ex[3];                                    // over all free vertices
+            return ex[0];
+        },
+        [&](double lambda, bool robust_on) -> LmTrial {
+            double A[36], b6[6], x[6] = {0, 0, 0, 0, 0, 0};
+            sym21_to_system(h, lambda, A, b6);
+            bool ok_o = true;
+            trial = pose;
+            double sc_o = 0;
+            if (free_obj) {
+                ok_o = spd_solve6(A, b6, x);                      // every lane, identically
+                if (ok_o) {
+                    pose_oplus(trial, x);
+                    for (int d = 0; d < 6; ++d) sc_o += x[d] * (lambda * x[d] + h[21 + d]);      // computeScale: sum x (lambda x + b)
                 }
-                bool ok_o = true;
-                Pose trial = pose;
-                double sc_o = 0;
-                if (free_obj) {
-                    ok_o = spd_solve6(A, b6, x);                  // every lane, identically
-                    if (ok_o) {
-                        pose_oplus(trial, x);
-                        for (int d = 0; d < 6; ++d) sc_o += x[d] * (lambda * x[d] + h[21 + d]);      // computeScale: sum x (lambda x + b)
-                    }
-                }
-                double Rt[9];
-                q_to_R(trial.q, Rt);
-                // (a failed block anywhere rejects the whole trial: the chi2 evaluated here is then discarded)
-                const double temp_o = edge_pass(Rt, trial.t, robust_on, std::false_type{}, h);
-                exchange(temp_o, sc_o, ok_o ? 0.0 : 1.0, 0, ex);
-                const bool ok2 = ex[2] == 0.0;
-                const double tempChi = ok2 ? ex[0] : 1.7976931348623157e308;
-                const double sc = ok2 ? ex[1] : 0.0;
-                rho = (currentChi - tempChi) / (sc + 1e-3);
-                if (rho > 0 && isfinite(tempChi)) {
-                    double alpha = 1. - pow(2 * rho - 1, 3.0);
-                    alpha = fmin(alpha, 2. / 3.);
-                    lambda *= fmax(1. / 3., alpha);
-                    ni = 2;
-                    currentChi = tempChi;
-                    pose = trial;                                 // update(x) is kept
-                } else {
-                    lambda *= ni;
-                    ni *= 2;                                      // pop(): the trial pose is simply dropped
-                    if (!isfinite(lambda)) { lam_finite = false; break; }
-                }
-                ++qmax;
-                ++lm_trials;
-            } while (rho < 0 && qmax < 10);
-            ++lm_its;
-            if (qmax == 10 || rho == 0 || !lam_finite) break;    // Terminate
-        }
-        // ---- re-classification (object_slam.py:877-896), chi2 at the accepted state ---------------------------
-        exchange(classify(false), 0, 0, 0, ex);
-        num_good = (int)ex[0];
-        if (round == drop) robust_on = false;
-    }
+            }
+            double Rt[9];
+            q_to_R(trial.q, Rt);
+            // (a failed block anywhere rejects the whole trial: the chi2 evaluated here is then discarded)
+            const double temp_o = edge_pass(Rt, trial.t, robust_on, std::false_type{}, h);
+            exchange(temp_o, sc_o, ok_o ? 0.0 : 1.0, 0, ex);
+            const bool ok2 = ex[2] == 0.0;
+            return {ex[0], ok2 ? ex[1] : 0.0, ok2};
+        },
+        [&]() { pose = trial; },                                 // update(x) is kept
+        [&]() {},                                                // pop(): the trial pose is simply dropped
+        [&]() -> int {                                           // object_slam.py:877-896, chi2 at the accepted state
+            exchange(classify(false), 0, 0, 0, ex);
+            return (int)ex[0];
+        });
     if (free_obj && lane == 0) pose_to_T(pose, P.obj_T + 12 * w);      // (a fixed object keeps the bits it came with)
     if (e_first >= 0) P.level[e_first] = (uint8_t)lvl0;
     for (int c = threadIdx.x; c < P.n_cam; c += blockDim.x) {    // cameras are fixed: the same quaternion round trip as csrc/lm.hip
@@ -283,7 +236,7 @@ __global__ __launch_bounds__(64 * MAXW) void lm_frame_kernel(const LmProblem* __
         pose_from_T(P.cam_T + 12 * c, cam);
         pose_to_T(cam, P.cam_T + 12 * c);
     }
-    if (threadIdx.x == 0) { P.stats[0] = rounds; P.stats[1] = lm_its; P.stats[2] = lm_trials; P.stats[3] = num_good; }
+    if (threadIdx.x == 0) n.store(P.stats);
 }
 
 // problems without a free camera and with at most LF_MAX_OBJ objects (the caller checks); one workgroup each, a wave per object

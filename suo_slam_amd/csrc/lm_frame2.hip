@@ -174,48 +174,34 @@ DEV void lm_frame2_body(const LmProblem& P, double* Es) {
                 if constexpr (WITH_H) {
                     const double i0 = wgt * E[9], i1 = wgt * E[10], i2 = wgt * E[11];
                     const double g0 = -(E[9] * er[0] + E[10] * er[1]) * wgt, g1 = -(E[10] * er[0] + E[11] * er[1]) * wgt;
-                    double wj0[6], wj1[6];
-#pragma unroll
-                    for (int cc = 0; cc < 6; ++cc) { wj0[cc] = i0 * Jo[cc] + i1 * Jo[6 + cc]; wj1[cc] = i1 * Jo[cc] + i2 * Jo[6 + cc]; }
-                    int u = 0;
-#pragma unroll
-                    for (int r = 0; r < 6; ++r)
-#pragma unroll
-                        for (int cc = r; cc < 6; ++cc) { h[u] = fma(Jo[6 + r], wj1[cc], fma(Jo[r], wj0[cc], h[u])); ++u; }     // (explicit fused accumulation: half the instructions)
-#pragma unroll
-                    for (int r = 0; r < 6; ++r) h[21 + r] = fma(Jo[6 + r], g1, fma(Jo[r], g0, h[21 + r]));
+                    accumulate_jtwj<true>(Jo, i0, i1, i2, g0, g1, h);      // (explicit fused accumulation: half the instructions)
                 }
             }
         }
         return gsum<G>(c);
     };
 
-    int num_good;
-    {
-        const double g = P.init_with_outliers ? classify(true) : classify(false);
-        num_good = P.init_with_outliers ? P.n_edge : (int)g;
-    }
-    bool robust_on = true;
-    int rounds = 0, lm_its = 0, lm_trials = 0;
-    const int drop = (P.n_rounds / 2) > 1 ? (P.n_rounds / 2) : 1;
-
-    for (int round = 0; round < P.n_rounds; ++round) {
-        if (P.n_edge < 4 || num_good < 4) break;
-        ++rounds;
-        double nact = 0;                                         // any active edge at all? (g2o: nothing to optimise -> no iterations)
-        for (int j = 0; j < epl; ++j) {
-            const int k = sub + j * G;
-            if (free_obj && k < n_own && !((lvl >> j) & 1u)) nact += 1;
-        }
-        const int iterations = osum(gsum<G>(nact)) > 0 ? P.its[round] : 0;
-        double lambda = -1, ni = 2;
-        // The linearisation of iteration it + 1 is taken at the pose iteration it accepted -- the very pose whose chi2 the accepting trial
-        // has just evaluated edge by edge.  So every trial pass also accumulates J^T W J / J^T W r at ITS pose (h2): accepted, they ARE the
-        // next iteration's system (same inputs, same instructions: bit-identical to linearising again) and the separate pass per
-        // iteration is gone; rejected (rare: 104 trials for 100 iterations on the bench frame), they are dropped.
-        double h[27], chi_o = 0;
-        for (int it = 0; it < iterations; ++it) {
-            // ---- errors, chi2, every object's 6x6 system --------------------------------------------------------
+    // The linearisation of iteration it + 1 is taken at the pose iteration it accepted -- the very pose whose chi2 the accepting trial
+    // has just evaluated edge by edge.  So every trial pass also accumulates J^T W J / J^T W r at ITS pose (h2): accepted, they ARE the
+    // next iteration's system (same inputs, same instructions: bit-identical to linearising again) and the separate pass per
+    // iteration is gone; rejected (rare: 104 trials for 100 iterations on the bench frame), they are dropped.
+    double h[27], h2[27], chi_o = 0, temp_o = 0;                 // the objects' systems and chi2 at the standing poses / at the trial poses
+    Pose trial;
+    const LmCounters n = lm_run_rounds<false>(
+        P,
+        [&]() -> int {
+            const double g = P.init_with_outliers ? classify(true) : classify(false);
+            return P.init_with_outliers ? P.n_edge : (int)g;
+        },
+        [&]() -> bool {                                          // any active edge at all? (g2o: nothing to optimise -> no iterations)
+            double nact = 0;
+            for (int j = 0; j < epl; ++j) {
+                const int k = sub + j * G;
+                if (free_obj && k < n_own && !((lvl >> j) & 1u)) nact += 1;
+            }
+            return osum(gsum<G>(nact)) > 0;
+        },
+        [&](bool robust_on, int it, double& max_diag) -> double {      // errors, chi2, every object's 6x6 system
             if (it == 0) {
                 double Ro[9];
                 q_to_R(pose.q, Ro);
@@ -227,85 +213,47 @@ DEV void lm_frame2_body(const LmProblem& P, double* Es) {
 #pragma unroll
                 for (int k = 0; k < 27; ++k) h[k] = gsum<G>(h[k]);
             }
-            double currentChi = osum(chi_o);
+            const double currentChi = osum(chi_o);
             LF2_T(2);
-            if (it == 0) {                                       // computeLambdaInit: tau * max |diag H| over all free vertices
-                double md = 0;
-                if (free_obj) {
-                    const int diag21[6] = {0, 6, 11, 15, 18, 20};
-#pragma unroll
-                    for (int d = 0; d < 6; ++d) md = fmax(md, fabs(h[diag21[d]]));
+            if (it == 0) max_diag = omax(free_obj ? sym21_max_abs_diag(h) : 0.0);      // over all free vertices
+            return currentChi;
+        },
+        [&](double lambda, bool robust_on) -> LmTrial {
+            double A[36], b6[6], x[6] = {0, 0, 0, 0, 0, 0};
+            sym21_to_system(h, lambda, A, b6);
+            bool ok_o = true;
+            trial = pose;
+            double sc_o = 0;
+            LF2_T(0);
+            if (free_obj) {
+                ok_o = spd_solve6(A, b6, x);                      // every group its own system, in lock-step
+                LF2_T(3);
+                if (ok_o) {
+                    pose_oplus(trial, x);
+                    for (int d = 0; d < 6; ++d) sc_o += x[d] * (lambda * x[d] + h[21 + d]);      // computeScale: sum x (lambda x + b)
                 }
-                lambda = 1e-5 * omax(md);
-                ni = 2;
+                LF2_T(4);
             }
-            // ---- trials ---------------------------------------------------------------------------------------
-            double rho = 0;
-            int qmax = 0;
-            bool lam_finite = true;
-            do {
-                double A[36], b6[6], x[6] = {0, 0, 0, 0, 0, 0};
-                {
-                    int u = 0;
+            double Rt[9];
+            q_to_R(trial.q, Rt);
 #pragma unroll
-                    for (int r = 0; r < 6; ++r)
+            for (int k = 0; k < 27; ++k) h2[k] = 0;
+            // (a failed block anywhere rejects the whole trial: the chi2 evaluated here is then discarded)
+            temp_o = edge_pass(Rt, trial.t, robust_on, std::true_type{}, h2);
+            LF2_T(5);
+            const double s_bad = osum(ok_o ? 0.0 : 1.0), s_chi = osum(temp_o), s_sc = osum(sc_o);      // (independent: they overlap)
+            const bool ok2 = s_bad == 0.0;
+            LF2_T(6);
+            return {s_chi, ok2 ? s_sc : 0.0, ok2};
+        },
+        [&]() {
+            pose = trial;                                         // update(x) is kept
 #pragma unroll
-                        for (int c = r; c < 6; ++c) { A[r * 6 + c] = h[u]; A[c * 6 + r] = h[u]; ++u; }
-#pragma unroll
-                    for (int d = 0; d < 6; ++d) { A[d * 7] += lambda; b6[d] = h[21 + d]; }
-                }
-                bool ok_o = true;
-                Pose trial = pose;
-                double sc_o = 0;
-                LF2_T(0);
-                if (free_obj) {
-                    ok_o = spd_solve6(A, b6, x);                  // every group its own system, in lock-step
-                    LF2_T(3);
-                    if (ok_o) {
-                        pose_oplus(trial, x);
-                        for (int d = 0; d < 6; ++d) sc_o += x[d] * (lambda * x[d] + h[21 + d]);      // computeScale: sum x (lambda x + b)
-                    }
-                    LF2_T(4);
-                }
-                double Rt[9], h2[27];
-                q_to_R(trial.q, Rt);
-#pragma unroll
-                for (int k = 0; k < 27; ++k) h2[k] = 0;
-                // (a failed block anywhere rejects the whole trial: the chi2 evaluated here is then discarded)
-                const double temp_o = edge_pass(Rt, trial.t, robust_on, std::true_type{}, h2);
-                LF2_T(5);
-                const double s_bad = osum(ok_o ? 0.0 : 1.0), s_chi = osum(temp_o), s_sc = osum(sc_o);      // (independent: they overlap)
-                const bool ok2 = s_bad == 0.0;
-                const double tempChi = ok2 ? s_chi : 1.7976931348623157e308;
-                const double sc = ok2 ? s_sc : 0.0;
-                LF2_T(6);
-                rho = (currentChi - tempChi) / (sc + 1e-3);
-                if (rho > 0 && isfinite(tempChi)) {
-                    const double r21 = 2 * rho - 1;
-                    double alpha = 1. - r21 * r21 * r21;
-                    alpha = fmin(alpha, 2. / 3.);
-                    lambda *= fmax(1. / 3., alpha);
-                    ni = 2;
-                    currentChi = tempChi;
-                    pose = trial;                                 // update(x) is kept
-#pragma unroll
-                    for (int k = 0; k < 27; ++k) h[k] = gsum<G>(h2[k]);      // ... and with it the system at the new pose
-                    chi_o = temp_o;
-                } else {
-                    lambda *= ni;
-                    ni *= 2;                                      // pop(): the trial pose is simply dropped
-                    if (!isfinite(lambda)) { lam_finite = false; break; }
-                }
-                ++qmax;
-                ++lm_trials;
-            } while (rho < 0 && qmax < 10);
-            ++lm_its;
-            if (qmax == 10 || rho == 0 || !lam_finite) break;    // Terminate
-        }
-        // ---- re-classification (object_slam.py:877-896), chi2 at the accepted state ---------------------------
-        num_good = (int)classify(false);
-        if (round == drop) robust_on = false;
-    }
+            for (int k = 0; k < 27; ++k) h[k] = gsum<G>(h2[k]);      // ... and with it the system at the new pose
+            chi_o = temp_o;
+        },
+        [&]() {},                                                // pop(): the trial pose is simply dropped
+        [&]() -> int { return (int)classify(false); });          // object_slam.py:877-896, chi2 at the accepted state
     if (free_obj && sub == 0) pose_to_T(pose, P.obj_T + 12 * og);      // (a fixed object keeps the bits it came with)
     for (int j = 0; j < epl; ++j) {
         const int k = sub + j * G;
@@ -315,13 +263,13 @@ DEV void lm_frame2_body(const LmProblem& P, double* Es) {
         Pose cam;
         pose_from_T(P.cam_T, cam);
         pose_to_T(cam, P.cam_T);
-        P.stats[0] = rounds; P.stats[1] = lm_its; P.stats[2] = lm_trials; P.stats[3] = num_good;
+        n.store(P.stats);
     }
 #ifdef SUO_LF2_PROFILE
     LF2_T(7);
     if (blockIdx.x == 0 && lane == 0)
         printf("lm_frame2 G=%d epl=%d its=%d trials=%d cycles: misc %lld  edges+H %lld  gsum+osum %lld  solve %lld  oplus %lld  trial edges %lld  osum x3 %lld  rest %lld\n",
-               G, epl, lm_its, lm_trials, pt[0], pt[1], pt[2], pt[3], pt[4], pt[5], pt[6], pt[7]);
+               G, epl, n.lm_its, n.lm_trials, pt[0], pt[1], pt[2], pt[3], pt[4], pt[5], pt[6], pt[7]);
 #endif
 }
 

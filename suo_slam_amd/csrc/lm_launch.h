@@ -28,8 +28,6 @@ int lm_cam2_max_edges();
 int launch_lm_frame(const void* problems_dev, int n_problems, int max_obj, hipStream_t s);
 int launch_lm_frame2(const void* problems_dev, int n_problems, int max_obj, int max_edges, hipStream_t s);
 int lm_frame2_max_edges();
-int launch_lm_grid(const void* problem_dev, void* scratch_dev, int n_wgs, hipStream_t s);       // (csrc/lm_grid.hip: rounds 4-5's route for one large graph; tuning builds only)
-size_t lm_grid_scratch_bytes();
 // ---- the phases of one LM trial (csrc/lm_dist.hip); ctl: the control block of the device-resident schedule, fold_ctl: its step folded into the tail kernel ----
 size_t ba_scratch_doubles();
 int launch_ba_init(const void* P, hipStream_t s);

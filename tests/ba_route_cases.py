@@ -28,7 +28,7 @@ def route_codes():
     return {m.group(1): int(m.group(2)) for m in re.finditer(r"#define\s+SUO_LM_ROUTE_([A-Z0-9_]+)\s+(\d+)", hdr)}
 
 
-TUNING_ONLY_ROUTES = {"GRID"}    # lm_grid_kernel is linked into -DSUO_TUNING builds only
+TUNING_ONLY_ROUTES: set = set()  # every route of include/suo_hip.h is in the product library
 
 
 # ---- graph builders ---------------------------------------------------------------------------------------------------------------------------------
@@ -213,6 +213,8 @@ _c("frame_17_objects_lm_big", ["LM_BIG"])(lambda r: [frame(r, [35] * 17)])      
 _c("tracking_1024", ["CAM2"], TRACKING_ITS, True)(lambda r: [tracking(r, [128] * 8)])
 _c("tracking_1025", ["CAM"], TRACKING_ITS, True)(lambda r: [tracking(r, [129] + [128] * 7)])
 _c("tracking_second_fixed_camera", ["CAM"], TRACKING_ITS, True)(lambda r: [tracking(r, [20] * 6, n_fixed_cams=1)])
+# the default iteration budget on lm_cam_kernel: trials are rejected here (pop() through memory, lambda * ni), which no TRACKING_ITS case reaches
+_c("tracking_rejected_trials_cam", ["CAM"], None, True)(lambda r: [tracking(r, [12] * 5, n_fixed_cams=1)])
 # one global graph: LM below 512 edges, the device-resident phases from 512; > 16 free objects: the host-scheduled phases at any size
 _c("global_511", ["LM"])(lambda r: [global_graph(r, 511, 8, 6)])
 _c("global_512", ["PHASES"])(lambda r: [global_graph(r, 512, 8, 6)])

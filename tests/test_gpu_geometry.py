@@ -281,8 +281,7 @@ def test_global_bundle_adjustment_matches_oracle(ba, n_cam, n_obj):
     """Global mode: first camera fixed, all other cameras and all objects free (object_slam.py:746-778).
     HIP eliminates cameras by Schur complement; the oracle solves the full dense system.  Below 512 edges one
     workgroup runs the whole adjustment (csrc/lm.hip); the larger graphs (612 - 5400 edges) take the phase kernels
-    of csrc/lm_dist.hip under the device-resident schedule, driven from C (ba_drive.hip: optimize_phases_one_rank;
-    rounds 4-5: the grid-barrier kernel of csrc/lm_grid.hip)."""
+    of csrc/lm_dist.hip under the device-resident schedule, driven from C (ba_drive.hip: optimize_phases_one_rank)."""
     rng = np.random.default_rng(n_cam * 7 + n_obj)
     P, obj_gt = _multi_view_scene(rng, n_cam, n_obj)
     got, ref = _compare_ba(ba, P)

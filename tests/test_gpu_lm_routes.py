@@ -76,6 +76,8 @@ def test_case_matches_the_oracle_on_its_route(ba, name):
                         assert np.array_equal(a, b), (name, route)
         for P, (got, ref) in zip(probs, results):
             assert got[4][0] >= 1 and ref[4][3] >= 4, (got[4], ref[4])             # the rounds ran: not a no-op comparison
+            if name == "tracking_rejected_trials_cam":
+                assert got[4][2] > got[4][1], got[4]                               # the kernel itself rejected trials: pop() and lambda * ni ran
             if name.startswith("degenerate_outlier_object"):
                 # the object all of whose measurements are gross outliers keeps no inlier: its block is lambda I from round 1 on
                 cut = [o for o in range(len(P["obj_T"])) if not ref[2][P["edge_obj"] == o].any()]

@@ -8,10 +8,15 @@ import numpy as np
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import bench  # noqa: E402
 from suo_slam_amd import ba, lambdatwist  # noqa: E402
+from suo_slam_amd import geometry as geo, synthetic as S  # noqa: E402
 
 L = int(sys.argv[1]) if len(sys.argv) > 1 else 8
 n = int(sys.argv[2]) if len(sys.argv) > 2 else 50
 pool = bench.make_pool(np.random.default_rng(0), 16, L)
+for fr in pool:                                      # PnP inputs: the valid model keypoints and their normalised detections
+    m = fr["model_kps_masks"]
+    fr["pnp_xs"] = [fr["model_kps"][o][m[o]].astype(np.float64) for o in range(L)]
+    fr["pnp_ys"] = [geo.normalize_uv(fr["uv"][o][m[o]].astype(np.float64), fr["K_bbox"][o]) for o in range(L)]
 tp = tb = tl = 0.0
 stats = []
 for i in range(n + 5):
@@ -19,8 +24,8 @@ for i in range(n + 5):
     t0 = time.perf_counter()
     T, status, info = lambdatwist.pnp_batch(fr["pnp_xs"], fr["pnp_ys"], 1e-3, seed=i, return_info=True)
     t1 = time.perf_counter()
-    B = fr["ba"]
-    prob = ba.Problem(B["cam_T"], B["cam_fixed"], T[:, :3, :], B["obj_fixed"], B["edge_cam"], B["edge_obj"], B["edge_camk"], B["edge_p"],
+    B = S.frame_to_ba_problem(fr, T)
+    prob = ba.Problem(B["cam_T"], B["cam_fixed"], B["obj_T"], B["obj_fixed"], B["edge_cam"], B["edge_obj"], B["edge_camk"], B["edge_p"],
                       B["edge_uv"], B["edge_info"], B["edge_inlier"], its=(10, 10, 40, 40))
     t2 = time.perf_counter()
     ba.optimize_batch([prob])
