@@ -744,7 +744,44 @@ int suo_pose_errors_vsd(void* mesh_db, int n, const int* model_index, const doub
                         int n_images, const float* depth_test, const int* image_index, double delta, int n_taus, const double* taus, int normalized_by_diameter,
                         const double* diameter, double* errors, long long* counts);
 
-/* ---- SLAM-mode hypothesis scoring ------------------------------------------
+/* ---- BOP scene_gt_info and ground-truth masks ------------------------------------------
+ * What bop_toolkit's scripts/calc_gt_info.py:74-176 and scripts/calc_gt_masks.py:77-127 compute for n ground-truth instances: model_index[i] under the pose
+ * T[i] and the camera K[i] (as for suo_render_depth) against the test depth image image_index[i] of depth_test [n_images][height][width] (mm, host floats).
+ * Every entry is new; nothing above changes.
+ *
+ * suo_gt_info, per instance:
+ *   render         on a canvas of 3 width x 3 height with the principal point (cx + width, cy + height), the sums formed on the host in fp64, under the rules
+ *                  of suo_render_depth above, unchanged (the Z <= 0 deviation included).  depth_gt is the central width x height window of the canvas.  The
+ *                  canvas exists tile by tile in LDS only; it is never written to memory.
+ *   px_count_all   covered samples of the whole canvas.
+ *   distances      over the window, for image pixel (x, y) and the ORIGINAL K, misc.depth_im_to_dist_im (misc.py:166-189; not the _fast form of the VSD error
+ *                  above: the order of operations differs):  Xs = ((x - cx) d) (1 / fx),  Ys = ((y - cy) d) (1 / fy),  dist = sqrt((Xs^2 + Ys^2) + d^2), fp64
+ *                  on the float32 depth widened exactly.
+ *   visib          (float32(dist_gt) - float32(dist_test) <= float32(delta) or dist_test == 0) and dist_gt > 0        (visibility.py:9-42, mode 'bop19')
+ *   px_count_valid pixels with dist_gt > 0 and dist_test > 0;   px_count_visib   pixels with visib.
+ *   bbox_visib     [xmin, ymin, xmax - xmin, ymax - ymin] of visib: no + 1, no clipping (misc.calc_2d_bbox).
+ *   bbox_obj       the same box of the covered samples of the whole canvas in image coordinates (canvas minus the offset): may be negative or exceed the image.
+ *   both boxes     are [-1, -1, -1, -1] when px_count_visib == 0, also when px_count_all > 0 (calc_gt_info.py:155-166).
+ *   px_counts      [n][3]: all, valid, visib.  visib_fract = px_count_visib / float(px_count_all), 0.0 when px_count_all == 0, is the caller's division.
+ * suo_gt_masks: the same on the plain width x height canvas with (cx, cy), as calc_gt_masks.py renders: mask = 255 (dist_gt > 0), mask_visib = 255 visib, uint8
+ * [n][height][width]; either may be NULL.
+ * Test depth that is no measurement: a NaN gives a NaN distance -- not 0, so not "missing" -- and every comparison with it is false: the pixel is neither
+ * valid nor visible.  A negative depth d has the distance of |d| (the squares lose the sign): the pixel is valid, and visible when dist_gt - that <= delta.
+ * +-inf gives dist_test = inf (valid, and visible), or NaN where x == cx or y == cy (0 * inf).  The test image is read at window pixels only, whatever it holds.
+ * The device writes integers only, reduced per wave, per workgroup and then by one integer atomic per quantity: the values of an instance do not depend on
+ * the batch, its order or the tiling.  The rasterisation rule itself stays unpinned as in N6 (no GL here); everything after the render is pinned by the
+ * toolkit's two scripts run unmodified over the numpy rasteriser (tests/golden/make_gt_info_golden.py).
+ * Host buffers, blocking.  n = 0 returns 0.  SUO_ERR_ARG with a message, before anything is launched: as for suo_pose_errors_vsd (a null pointer, non-finite
+ * T, K or delta, a model or image index out of range, a model without faces, width or height < 1), and a size whose canvas 3 width x 3 height exceeds what
+ * the rasteriser's pixel boxes take (9 width height > 2^28).  More instances than one launch takes (1024, fewer with many triangles) are split inside. */
+int suo_gt_info(void* mesh_db, int n, const int* model_index, const double* T, const double* K, int width, int height,
+                int n_images, const float* depth_test, const int* image_index, double delta,
+                long long* px_counts /*[n][3]: all, valid, visib*/, int* bbox_obj /*[n][4]*/, int* bbox_visib /*[n][4]*/);
+int suo_gt_masks(void* mesh_db, int n, const int* model_index, const double* T, const double* K, int width, int height,
+                 int n_images, const float* depth_test, const int* image_index, double delta,
+                 uint8_t* mask /*[n][height][width], may be NULL*/, uint8_t* mask_visib /*may be NULL*/);
+
+/* ---- SLAM-mode hypothesis scoring------------------------------------------
  * Replaces the per-pair numpy of ObjectSLAM.__estimate_camera_pose's hypothesis loop (lib/object_slam.py:1000-1066) and of
  * __maybe_reinit_objects' inlier counts (:619-690): count_k [ z_k > 0 and chi2_k <= chi2_max ] for n_pairs (pose, detection) pairs in one launch.
  * A detection is written once into a device-resident store (suo_slam_store_put; host rows [n][SUO_SLAM_ROW] doubles:

@@ -160,6 +160,8 @@ SIGNATURES = {
     "suo_render_depth": (C.c_int, [VP, C.c_int, VP, VP, VP, C.c_int, C.c_int, VP]),
     "suo_vsd_from_depth": (C.c_int, [C.c_int, C.c_int, C.c_int, VP, VP, C.c_int, VP, VP, VP, C.c_double, C.c_int, VP, C.c_int, VP, VP, VP]),
     "suo_pose_errors_vsd": (C.c_int, [VP, C.c_int, VP, VP, VP, VP, C.c_int, C.c_int, C.c_int, VP, VP, C.c_double, C.c_int, VP, C.c_int, VP, VP, VP]),
+    "suo_gt_info": (C.c_int, [VP, C.c_int, VP, VP, VP, C.c_int, C.c_int, C.c_int, VP, VP, C.c_double, VP, VP, VP]),
+    "suo_gt_masks": (C.c_int, [VP, C.c_int, VP, VP, VP, C.c_int, C.c_int, C.c_int, VP, VP, C.c_double, VP, VP]),
     "suo_slam_store_create": (VP, [C.c_int]),
     "suo_slam_store_destroy": (None, [VP]),
     "suo_slam_store_put": (C.c_int, [VP, C.c_int, C.c_int, VP]),

@@ -22,6 +22,8 @@ Opt-in since row N6, with nothing above changed when it is not asked for: a mesh
     BopErrors.render_depth(obj_ids, T, K, hw)       Renderer.render_object(...)["depth"]       -> HIP, csrc/raster.hip (suo_render_depth)
     BopErrors.vsd(obj_ids, T_est, T_gt, K, depth_images, image_index, delta, taus, normalized)
                                                     pose_error.vsd (cost 'step', mode 'bop19')  -> HIP, csrc/eval_vsd.hip (suo_pose_errors_vsd)
+    BopErrors.gt_info / .gt_masks(obj_ids, T_gt, K, depth_images, image_index, delta)
+                                                    scripts/calc_gt_info.py, calc_gt_masks.py   -> HIP, csrc/gt_info.hip (row N7; bop_gt_info.py walks a tree)
     overlapping_sphere_projections(radius, p1, p2)  misc.overlapping_sphere_projections (the gate of eval_calc_errors.py:295-312)
     Bop19Meter(..., depth_loader=..., vsd_delta=15) adds "vsd" (one recall per tau and threshold, eval_bop19.py:178-225) and "ar", the mean of the three.
 """
@@ -205,6 +207,44 @@ class BopErrors:
                                                     dd.ctypes.data, e.ctypes.data, c.ctypes.data), "suo_pose_errors_vsd")
             errors[sl], counts[sl] = e, c
         return (errors, counts) if return_counts else errors
+
+    def _gt_args(self, obj_ids, T_gt, K, depth_images, image_index):
+        n = len(obj_ids)
+        idx = np.array([self._index[int(o)] for o in obj_ids], np.int32)
+        Tn = _pack34(T_gt, n)
+        Kn = np.ascontiguousarray(np.broadcast_to(np.asarray(K, np.float64).reshape(-1, 3, 3), (n, 3, 3))).reshape(n, 9)
+        image_index = [int(i) for i in image_index]
+        used = sorted(set(image_index))
+        test = np.ascontiguousarray(np.stack([np.asarray(depth_images[i], np.float32) for i in used]))
+        assert test.ndim == 3, "the depth images of a call must have one size"
+        ii = np.array([used.index(i) for i in image_index], np.int32)
+        return n, idx, Tn, Kn, test, ii
+
+    def gt_info(self, obj_ids, T_gt, K, depth_images, image_index, delta=15):
+        """What scripts/calc_gt_info.py writes per ground-truth instance (row N7; include/suo_hip.h: suo_gt_info): a list of dictionaries with the toolkit's
+        six keys -- px_count_all / valid / visib, visib_fract, bbox_obj, bbox_visib -- as Python int / float.  Poses [n,3|4,4], K [n,3,3] or one [3,3],
+        ``depth_images`` a sequence of float32 [H,W] in mm, ``image_index[n]`` into it."""
+        if len(obj_ids) == 0:
+            return []
+        n, idx, Tn, Kn, test, ii = self._gt_args(obj_ids, T_gt, K, depth_images, image_index)
+        counts, bo, bv = np.zeros((n, 3), np.int64), np.zeros((n, 4), np.int32), np.zeros((n, 4), np.int32)
+        _lib.check(self.lib.suo_gt_info(self._h, n, idx.ctypes.data, Tn.ctypes.data, Kn.ctypes.data, test.shape[2], test.shape[1], len(test), test.ctypes.data,
+                                        ii.ctypes.data, float(delta), counts.ctypes.data, bo.ctypes.data, bv.ctypes.data), "suo_gt_info")
+        out = []
+        for c, o, v in zip(counts.tolist(), bo.tolist(), bv.tolist()):
+            out.append({"px_count_all": c[0], "px_count_valid": c[1], "px_count_visib": c[2], "visib_fract": c[2] / float(c[0]) if c[0] > 0 else 0.0,
+                        "bbox_obj": o, "bbox_visib": v})
+        return out
+
+    def gt_masks(self, obj_ids, T_gt, K, depth_images, image_index, delta=15):
+        """``(mask, mask_visib)`` uint8 [n,H,W], 0 / 255, as scripts/calc_gt_masks.py writes them (include/suo_hip.h: suo_gt_masks)."""
+        if len(obj_ids) == 0:
+            return np.zeros((0, 0, 0), np.uint8), np.zeros((0, 0, 0), np.uint8)
+        n, idx, Tn, Kn, test, ii = self._gt_args(obj_ids, T_gt, K, depth_images, image_index)
+        mask, mask_visib = np.zeros((n,) + test.shape[1:], np.uint8), np.zeros((n,) + test.shape[1:], np.uint8)
+        _lib.check(self.lib.suo_gt_masks(self._h, n, idx.ctypes.data, Tn.ctypes.data, Kn.ctypes.data, test.shape[2], test.shape[1], len(test), test.ctypes.data,
+                                         ii.ctypes.data, float(delta), mask.ctypes.data, mask_visib.ctypes.data), "suo_gt_masks")
+        return mask, mask_visib
 
 
 def overlapping_sphere_projections(radius, p1, p2):

@@ -20,6 +20,7 @@
 #include "../../include/suo_hip.h"
 #include "suo_internal.h"
 #include "mesh_db.h"
+#include "visib.h"
 
 namespace suo {
 
@@ -71,9 +72,8 @@ __global__ __launch_bounds__(VS_BLOCK) void vsd_kernel(VsdArgs a) {
         const double Dt = sqrt((tx * tx + ty * ty) + dt * dt);
         const double Dg = sqrt((gx * gx + gy * gy) + (double)dg * (double)dg);
         const double De = sqrt((ex * ex + ey * ey) + (double)de * (double)de);
-        const float ft = (float)Dt;
-        const bool vg = (((float)Dg - ft) <= a.delta || Dt == 0.0) && Dg > 0.0;
-        const bool ve = ((((float)De - ft) <= a.delta || Dt == 0.0) && De > 0.0) || (vg && De > 0.0);
+        const bool vg = visib_bop19(Dg, Dt, a.delta);
+        const bool ve = visib_bop19(De, Dt, a.delta) || (vg && De > 0.0);
         if (vg || ve) ++n_union;
         if (vg && ve) {
             ++n_inter;

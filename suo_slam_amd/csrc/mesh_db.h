@@ -59,6 +59,12 @@ int bop_maxima_enqueue_locked(MeshDb* db, const char* who, int n, const int* mod
 // csrc/raster.hip.  check_render_args: the argument rules of suo_render_depth (SUO_ERR_ARG with the message set, nothing launched).
 // render_depth_locked: enqueue n renders on db->stream (caller holds db->mu and has checked the arguments); on return *img_dev is [n][height][width]
 // float32 depth and *rbox_dev [n][4] the renders' clipped pixel boxes (x0, y0, x1, y1; x0 > x1: nothing drawn), both valid until the next render.
+// render_setup_locked: the first half of a render, shared with csrc/gt_info_api.hip -- stages the n renders and enqueues raster_setup_kernel; *args then
+// names the triangle records and the renders' pixel boxes on the device (args->out is left null: the tile pass and its epilogue are the caller's).
+// grow_buffer: a grow-only device buffer, with a pinned host twin when host is not null.
+struct RasterArgs;
+int grow_buffer(char** dev, char** host, size_t* cap, size_t bytes);
+int render_setup_locked(MeshDb* db, const char* who, int n, const int* model_index, const double* T, const double* K, int width, int height, RasterArgs* args);
 int check_render_args(const char* who, MeshDb* db, int n, const int* model_index, const double* T, const double* K, int width, int height);
 int render_depth_locked(MeshDb* db, int n, const int* model_index, const double* T, const double* K, int width, int height, float** img_dev, int** rbox_dev);
 

@@ -13,7 +13,8 @@
 // The grid covers the tiles of the whole image, not of the render's box: that box is known on the device only, and a workgroup whose tile misses it writes
 // its zeros and leaves without reading a triangle -- cheaper than a host round trip between the two kernels, and no memset of the images is needed.
 // An integer minimum does not depend on the order of its operands and a sample's value does not depend on the lane that computes it, so a render has the
-// same bits alone, in a batch and for any tiling.
+// same bits alone, in a batch and for any tiling.  The tile pass itself (sampling, the two routes of a triangle) is csrc/raster_tile.h: csrc/gt_info.hip
+// runs it under another epilogue.
 #include <limits.h>
 #include <math.h>
 #include <string.h>
@@ -24,25 +25,9 @@
 #include "../../include/suo_hip.h"
 #include "suo_internal.h"
 #include "mesh_db.h"
+#include "raster_tile.h"
 
 namespace suo {
-
-constexpr int RS_BLOCK = 256;
-constexpr int RS_TILE = 64;                      // tile side in pixels
-constexpr int RS_SMALL = 32;                     // most samples of (triangle box ∩ tile) a single lane walks
-
-struct RasterArgs {
-    const float* pts; const int* off;            // mesh database
-    const int* faces; const int* foff;
-    const int* model;                            // [n]
-    const double* T; const double* K;            // [n][12], [n][9]
-    const int* rec_off;                          // [n] first triangle record of a render
-    int4* box;                                   // [records] clipped pixel box x0, y0, x1, y1 (x0 > x1: draws nothing)
-    double* geo;                                 // [records][9] u0 v0 u1 v1 u2 v2 1/Z0 1/Z1 1/Z2
-    int* rbox;                                   // [n][4] the render's box, staged as INT_MAX, INT_MAX, -1, -1
-    float* out;                                  // [n][h][w]
-    int w, h, tiles_x;
-};
 
 __global__ __launch_bounds__(RS_BLOCK) void raster_setup_kernel(RasterArgs a) {
     const int r = blockIdx.y, m = a.model[r];
@@ -97,44 +82,6 @@ __global__ __launch_bounds__(RS_BLOCK) void raster_setup_kernel(RasterArgs a) {
     }
 }
 
-// One triangle, ready to be sampled.  With s = sign(area2) the weights w_i = s E_i(sample) are >= 0 inside for either winding; E_0 belongs to the edge 1 -> 2
-// (the weight of vertex 0), E_1 to 2 -> 0, E_2 to 0 -> 1, E_PQ(p) = (Qx - Px)(py - Py) - (Qy - Py)(px - Px).  The inward normal of an edge is
-// s (-(Qy - Py), Qx - Px); the edge is a left edge when its x component is positive, a top edge (rows grow downwards) when that is zero and y positive.
-struct Tri {
-    double u0, v0, u1, v1, u2, v2, q0, q1, q2, s, A;
-    bool tl0, tl1, tl2;
-};
-
-__device__ __forceinline__ bool top_left(double s, double dx, double dy) {
-    const double nx = s * -dy, ny = s * dx;
-    return nx > 0.0 || (nx == 0.0 && ny > 0.0);
-}
-
-__device__ __forceinline__ Tri load_tri(const double* g) {
-    Tri t;
-    t.u0 = g[0]; t.v0 = g[1]; t.u1 = g[2]; t.v1 = g[3]; t.u2 = g[4]; t.v2 = g[5]; t.q0 = g[6]; t.q1 = g[7]; t.q2 = g[8];
-    const double area2 = (t.u1 - t.u0) * (t.v2 - t.v0) - (t.v1 - t.v0) * (t.u2 - t.u0);
-    t.s = area2 < 0.0 ? -1.0 : 1.0;
-    t.A = t.s * area2;
-    t.tl0 = top_left(t.s, t.u2 - t.u1, t.v2 - t.v1);
-    t.tl1 = top_left(t.s, t.u0 - t.u2, t.v0 - t.v2);
-    t.tl2 = top_left(t.s, t.u1 - t.u0, t.v1 - t.v0);
-    return t;
-}
-
-// the sample of pixel (x, y) against one triangle; zb: the tile's z-buffer, (lx, ly) the pixel within the tile
-__device__ __forceinline__ void shade(const Tri& t, int x, int y, unsigned* zb, int lx, int ly) {
-    const double px = (double)x + 0.5, py = (double)y + 0.5;
-    const double w0 = t.s * ((t.u2 - t.u1) * (py - t.v1) - (t.v2 - t.v1) * (px - t.u1));
-    const double w1 = t.s * ((t.u0 - t.u2) * (py - t.v2) - (t.v0 - t.v2) * (px - t.u2));
-    const double w2 = t.s * ((t.u1 - t.u0) * (py - t.v0) - (t.v1 - t.v0) * (px - t.u0));
-    const bool in = (w0 > 0.0 || (w0 == 0.0 && t.tl0)) && (w1 > 0.0 || (w1 == 0.0 && t.tl1)) && (w2 > 0.0 || (w2 == 0.0 && t.tl2));
-    if (!in) return;
-    const double iz = ((w0 * t.q0 + w1 * t.q1) + w2 * t.q2) / t.A;
-    const float z = (float)(1.0 / iz);
-    atomicMin(&zb[ly * RS_TILE + lx], __float_as_uint(z));
-}
-
 __global__ __launch_bounds__(RS_BLOCK) void raster_tile_kernel(RasterArgs a) {
     __shared__ unsigned zb[RS_TILE * RS_TILE];
     __shared__ int big[RS_BLOCK];
@@ -145,45 +92,7 @@ __global__ __launch_bounds__(RS_BLOCK) void raster_tile_kernel(RasterArgs a) {
     for (int i = tid; i < RS_TILE * RS_TILE; i += RS_BLOCK) zb[i] = 0xFFFFFFFFu;
     if (tid < 2) nbig[tid] = 0;
     __syncthreads();
-    const int rx0 = a.rbox[r * 4], ry0 = a.rbox[r * 4 + 1], rx1 = a.rbox[r * 4 + 2], ry1 = a.rbox[r * 4 + 3];
-    if (rx0 <= X1 && rx1 >= X0 && ry0 <= Y1 && ry1 >= Y0) {                    // uniform over the workgroup
-        const int m = a.model[r], F = a.foff[m + 1] - a.foff[m];
-        const int4* box = a.box + a.rec_off[r];
-        const double* geo = a.geo + (size_t)a.rec_off[r] * 9;
-        int phase = 0;
-        for (int base = 0; base < F; base += RS_BLOCK, phase ^= 1) {
-            const int f = base + tid;
-            if (f < F) {
-                const int4 b = box[f];
-                const int ix0 = max(b.x, X0), iy0 = max(b.y, Y0), ix1 = min(b.z, X1), iy1 = min(b.w, Y1);
-                if (ix0 <= ix1 && iy0 <= iy1) {
-                    if ((ix1 - ix0 + 1) * (iy1 - iy0 + 1) > RS_SMALL) big[atomicAdd(&nbig[phase], 1)] = f;      // at most one entry per lane: the list cannot overflow
-                    else {
-                        const Tri t = load_tri(geo + (size_t)f * 9);
-                        for (int y = iy0; y <= iy1; ++y)
-                            for (int x = ix0; x <= ix1; ++x) shade(t, x, y, zb, x - X0, y - Y0);
-                    }
-                }
-            }
-            __syncthreads();
-            if (tid == 0) nbig[phase ^ 1] = 0;                                  // the next chunk's counter: nobody touches it before the barrier below
-            const int nb = nbig[phase];
-            for (int e = 0; e < nb; ++e) {
-                const int g = big[e];
-                const int4 b = box[g];
-                const int ix0 = max(b.x, X0), iy0 = max(b.y, Y0), ix1 = min(b.z, X1), iy1 = min(b.w, Y1);
-                const int bw = ix1 - ix0 + 1, cnt = bw * (iy1 - iy0 + 1);
-                if (tid < cnt) {
-                    const Tri t = load_tri(geo + (size_t)g * 9);
-                    for (int p = tid; p < cnt; p += RS_BLOCK) {
-                        const int y = iy0 + p / bw, x = ix0 + p % bw;
-                        shade(t, x, y, zb, x - X0, y - Y0);
-                    }
-                }
-            }
-            __syncthreads();
-        }
-    }
+    if (tile_meets_render(a, r, X0, Y0, X1, Y1)) draw_tile(a, r, X0, Y0, X1, Y1, zb, big, nbig);      // uniform over the workgroup
     // the tile leaves: 0xFFFFFFFF -> 0.0f; four pixels of a row per lane, one 16-byte store where the row allows
     float* out = a.out + (size_t)r * a.h * a.w;
     const bool vec = (a.w & 3) == 0;
@@ -207,7 +116,7 @@ __global__ __launch_bounds__(RS_BLOCK) void raster_tile_kernel(RasterArgs a) {
     }
 }
 
-static int grow(char** dev, char** host, size_t* cap, size_t bytes) {
+int grow_buffer(char** dev, char** host, size_t* cap, size_t bytes) {
     if (bytes <= *cap) return SUO_OK;
     const size_t ncap = (std::max(bytes, *cap * 2) + 4095) & ~(size_t)4095;
     if (*dev) (void)hipFree(*dev);
@@ -235,7 +144,7 @@ int check_render_args(const char* who, MeshDb* db, int n, const int* model_index
     return SUO_OK;
 }
 
-int render_depth_locked(MeshDb* db, int n, const int* model_index, const double* T, const double* K, int width, int height, float** img_out, int** rbox_out) {
+int render_setup_locked(MeshDb* db, const char* who, int n, const int* model_index, const double* T, const double* K, int width, int height, RasterArgs* out) {
     long long records = 0;
     int fmax_ = 0;
     std::vector<int> rec_off(n);
@@ -244,15 +153,14 @@ int render_depth_locked(MeshDb* db, int n, const int* model_index, const double*
         rec_off[i] = (int)records;
         records += F;
         fmax_ = std::max(fmax_, F);
-        if (records > INT_MAX / 16) { suo_set_error("suo_render_depth: %lld triangle records exceed one call", records); return SUO_ERR_ARG; }
+        if (records > INT_MAX / 16) { suo_set_error("%s: %lld triangle records exceed one call", who, records); return SUO_ERR_ARG; }
     }
     // staged block: T[n][12] | K[n][9] | model[n] | rec_off[n] | rbox[n][4]   then device-only: box[records] (16 bytes each) | geo[records][9]
     const size_t o_t = 0, o_k = (size_t)n * 96, o_model = o_k + (size_t)n * 72, o_rec = o_model + (size_t)n * 4, o_rbox = o_rec + (size_t)n * 4;
     const size_t staged = (o_rbox + (size_t)n * 16 + 15) & ~(size_t)15;
     const size_t o_box = staged, o_geo = o_box + (size_t)records * 16, total = o_geo + (size_t)records * 72;
     int rc;
-    if ((rc = grow(&db->ras_dev, &db->ras_host, &db->ras_cap, total))) return rc;
-    if ((rc = grow(&db->img_dev, nullptr, &db->img_cap, (size_t)n * height * width * sizeof(float)))) return rc;
+    if ((rc = grow_buffer(&db->ras_dev, &db->ras_host, &db->ras_cap, total))) return rc;
     memcpy(db->ras_host + o_t, T, (size_t)n * 96);
     memcpy(db->ras_host + o_k, K, (size_t)n * 72);
     memcpy(db->ras_host + o_model, model_index, (size_t)n * 4);
@@ -265,10 +173,21 @@ int render_depth_locked(MeshDb* db, int n, const int* model_index, const double*
     a.T = (const double*)(db->ras_dev + o_t); a.K = (const double*)(db->ras_dev + o_k);
     a.model = (const int*)(db->ras_dev + o_model); a.rec_off = (const int*)(db->ras_dev + o_rec); a.rbox = (int*)(db->ras_dev + o_rbox);
     a.box = (int4*)(db->ras_dev + o_box); a.geo = (double*)(db->ras_dev + o_geo);
-    a.out = (float*)db->img_dev; a.w = width; a.h = height;
+    a.out = nullptr; a.w = width; a.h = height;
     a.tiles_x = (width + RS_TILE - 1) / RS_TILE;
-    const int tiles = a.tiles_x * ((height + RS_TILE - 1) / RS_TILE);
     hipLaunchKernelGGL(raster_setup_kernel, dim3((fmax_ + RS_BLOCK - 1) / RS_BLOCK, n), dim3(RS_BLOCK), 0, db->stream, a);
+    SUO_HIP_CHECK(hipGetLastError());
+    *out = a;
+    return SUO_OK;
+}
+
+int render_depth_locked(MeshDb* db, int n, const int* model_index, const double* T, const double* K, int width, int height, float** img_out, int** rbox_out) {
+    int rc;
+    if ((rc = grow_buffer(&db->img_dev, nullptr, &db->img_cap, (size_t)n * height * width * sizeof(float)))) return rc;
+    RasterArgs a;
+    if ((rc = render_setup_locked(db, "suo_render_depth", n, model_index, T, K, width, height, &a))) return rc;
+    a.out = (float*)db->img_dev;
+    const int tiles = a.tiles_x * ((height + RS_TILE - 1) / RS_TILE);
     hipLaunchKernelGGL(raster_tile_kernel, dim3(tiles, n), dim3(RS_BLOCK), 0, db->stream, a);
     SUO_HIP_CHECK(hipGetLastError());
     *img_out = a.out;
