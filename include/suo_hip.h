@@ -531,6 +531,34 @@ int suo_pose_covariances_pairs(const suo_ba_problem* problem, int n_pair, const 
 int suo_pose_covariances_pairs_batch(const suo_ba_problem* problems, int n, const int* n_pair, const int32_t* const* pair_a, const int32_t* const* pair_b,
                                      double* const* cam_cov, double* const* obj_cov, double* const* cross, double* const* rel, int* status /*[n][3]*/);
 
+/* ---- pose covariances of maps beyond 16 objects and between cameras ----------------------------------------------------------------
+ * suo_pose_covariances_graph is suo_pose_covariances_pairs -- the same Hessian, perturbation, vertex coding, zeros for fixed vertices, NaN rules, status [3],
+ * buffers and blocking -- with its two refusals lifted:
+ *   Free objects.  Any number of free objects next to free cameras up to SUO_POSE_COV_GRAPH_MAX_OBJ = 64.  The cap is what the scratch costs: the reduced system
+ *                and its inverse live in the arena, 2 * 8 * (6 * 64)^2 bytes = 2.4 MB per problem at the cap (device and pinned host mirror), and a lane of the
+ *                column kernel holds 6 * cap / 64 = 6 elements of a row of the factor in registers.  More: SUO_ERR_ARG naming the count and the cap, nothing is launched.
+ *   (camera a, camera b):  T_AtoB = T_b * T_a^-1,   delta_rel = delta_b - A delta_a,   A = Ad(T_b T_a^-1)
+ *                          rel = Sigma_bb + A Sigma_aa A^T - A Sigma_ab - Sigma_ba A^T
+ *                          cross = Sigma_ab: rows are vertex a, columns are vertex b.
+ *   - A fixed camera contributes zeros: (gauge, c) gives Sigma_cc, (c, gauge) gives A Sigma_cc A^T, two fixed cameras 36 zeros.
+ *   - (c, c): cross is the marginal block and rel is 36 zeros exactly.
+ *   - Where free cameras meet free objects, Sigma_cc' (c != c') = Y_c Sigma_OO Y_c'^T: dense, also where the two cameras share no object.
+ *     Without a free object the cross block of two cameras is zero and rel comes from the marginal blocks.
+ *   - (a, b) is the transpose of (b, a) to the bit, as for the object pairs.
+ *   - A pair touching a NaN vertex gives 36 NaNs in both blocks and is counted in status[2].
+ *   Bits.        A problem that suo_pose_covariances_pairs answers and that has no (camera, camera) pair runs on the kernels of that entry: every output is
+ *                bit-identical to it.  Every other problem with free cameras next to free objects runs on the device-memory form, whatever its object count.
+ *                A problem's result does not depend on the rest of the batch, and two calls give the same bits.
+ * Kernels (csrc/pose_cov_graph.hip, fp64, fixed summation order, vector stores only): S, S^-1 = Sigma_OO and every camera's Z = Y Sigma_OO in device memory; one
+ * workgroup per problem assembles and factors S (block-6 Cholesky), then a wave per column of Sigma_OO, a wave per camera, a thread per pair entry, each phase a launch
+ * of its own -- data crosses workgroups only at launch boundaries.  The pair kernel of csrc/pose_cov.hip propagates, as for the other entries. */
+#define SUO_POSE_COV_GRAPH_MAX_OBJ 64
+int suo_pose_covariances_graph(const suo_ba_problem* problem, int n_pair, const int32_t* pair_a, const int32_t* pair_b, double* cam_cov /*[n_cam][36]*/,
+                               double* obj_cov /*[n_obj][36]*/, double* cross /*[n_pair][36]*/, double* rel /*[n_pair][36]*/,
+                               int* status /*[3]: NaN cam blocks, NaN obj blocks, NaN pairs*/);
+int suo_pose_covariances_graph_batch(const suo_ba_problem* problems, int n, const int* n_pair, const int32_t* const* pair_a, const int32_t* const* pair_b,
+                                     double* const* cam_cov, double* const* obj_cov, double* const* cross, double* const* rel, int* status /*[n][3]*/);
+
 /* ---- phase-wise bundle adjustment for the multi-GPU global pose graph ------------------------
  * Cameras are partitioned across GPUs; each rank builds a context over ITS cameras' edges and ALL objects, and
  * a host driver (suo_slam_amd/ba_dist.py) runs g2o's LM schedule with two all-reduces per trial (RCCL):

@@ -108,10 +108,15 @@ def pose_covariances_pairs_batch(problems, pairs):
     object o is n_cam + o; (camera, object) in either order or (object, object)): cross [P,6,6] = Sigma_ab, rows vertex a; rel [P,6,6] = the covariance of
     T_OtoC = T_c T_o, or of T_AtoB = T_b^-1 T_a (include/suo_hip.h: suo_pose_covariances_pairs).  Per problem (cam_cov, obj_cov, cross, rel, status [3] = NaN
     camera blocks, NaN object blocks, NaN pairs).  One call for the whole list; the problems are not modified."""
+    return _pairs_batch(problems, pairs, "suo_pose_covariances_pairs_batch")
+
+
+def _pairs_batch(problems, pairs, entry):
+    """the shared body of pose_covariances_pairs_batch and pose_covariances_graph_batch: `entry` is the C function, both have one signature"""
     if not problems:
         return []
     if len(pairs) != len(problems):
-        raise ValueError("pose_covariances_pairs_batch: one pair list per problem")
+        raise ValueError(f"{entry[4:]}: one pair list per problem")
     lib = _lib.lib()
     _lib.require_gpu()
     n = len(problems)
@@ -131,11 +136,22 @@ def pose_covariances_pairs_batch(problems, pairs):
         n_pair[i] = P
         keep.append((a, b))
         out.append(bufs[2:] + (status[i],))
-    _lib.check(lib.suo_pose_covariances_pairs_batch(C.cast(arr, C.c_void_p), n, n_pair.ctypes.data, *[C.cast(c, C.c_void_p) for c in ptrs], status.ctypes.data),
-               "suo_pose_covariances_pairs_batch")
+    _lib.check(getattr(lib, entry)(C.cast(arr, C.c_void_p), n, n_pair.ctypes.data, *[C.cast(c, C.c_void_p) for c in ptrs], status.ctypes.data), entry)
     return out
 
 
 def pose_covariances_pairs(*args, pairs, **kw):
     """The arguments of optimize() plus pairs [P,2]; returns (cam_cov [C,6,6], obj_cov [O,6,6], cross [P,6,6], rel [P,6,6], status [3])."""
     return pose_covariances_pairs_batch([Problem(*args, **kw)], [pairs])[0]
+
+
+def pose_covariances_graph_batch(problems, pairs):
+    """pose_covariances_pairs_batch without its two limits (include/suo_hip.h: suo_pose_covariances_graph): free cameras next to up to 64 free objects, and
+    (camera a, camera b) pairs -- cross = Sigma_ab, rel = the covariance of T_b T_a^-1, the motion between the two views.  The same return values; bit-identical
+    to pose_covariances_pairs_batch wherever that answers and no (camera, camera) pair is asked for."""
+    return _pairs_batch(problems, pairs, "suo_pose_covariances_graph_batch")
+
+
+def pose_covariances_graph(*args, pairs, **kw):
+    """The arguments of optimize() plus pairs [P,2]; returns (cam_cov [C,6,6], obj_cov [O,6,6], cross [P,6,6], rel [P,6,6], status [3])."""
+    return pose_covariances_graph_batch([Problem(*args, **kw)], [pairs])[0]

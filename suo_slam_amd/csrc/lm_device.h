@@ -283,6 +283,9 @@ struct LmProblem {
     // optional pairs of suo_pose_covariances_pairs (n_cpair = 0: none): vertices coded camera c = c, object o = n_cam + o; per pair the cross block Sigma_ab
     // (rows a, columns b) and the covariance of the relative pose, 36 row-major doubles each; cov_status then has a third entry, the pairs with NaN blocks
     int n_cpair; const int* cpair_a; const int* cpair_b; double* cov_cross; double* cov_rel;
+    // scratch of cov_form 3 (csrc/pose_cov_graph.hip; nullptr otherwise), nsm = 6 * free objects: the reduced system and its factor [nsm][nsm + 1], Sigma_OO
+    // [nsm][nsm], Z = Y Sigma_OO of every camera [n_cam][6][nsm] (all three at the pitch of the ns the kernel finds), and [0] ok [1] ns [2 + s] the object in slot s
+    double* cov_S; double* cov_Sinv; double* cov_Z; int* cov_hdr;
 };
 DEV int pair_hi(const LmProblem& P, int p) { return P.pair_end ? P.pair_end[p] : P.pair_start[p + 1]; }
 

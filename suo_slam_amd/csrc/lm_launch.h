@@ -48,5 +48,11 @@ int launch_pose_cov_diag(const void* problems_dev, int n_problems, hipStream_t s
 // cov_form 2: one workgroup per problem, <= 16 free objects; pairs: the instantiation that also writes the cross blocks of LmProblem::cpair_a / cpair_b
 int launch_pose_cov_coupled(const void* problems_dev, int n_problems, int max_free_obj, hipStream_t s, bool pairs = false);
 int launch_pose_cov_pairs(const void* problems_dev, int n_problems, int max_pairs, hipStream_t s);        // every form, behind the two: cross / rel of the pairs
+// cov_form 3 (csrc/pose_cov_graph.hip): free cameras next to up to POSE_COV_GRAPH_MAX_OBJ free objects, the reduced system in the arena's scratch -- four launches
+// (factor, columns of the inverse, cameras, cross blocks of the pairs), sized by the largest form-3 problem; launch_pose_cov_pairs goes behind it.
+// The cap: a lane of the column kernel holds 6 * cap / 64 elements of a row in registers and a wave ns doubles in LDS; S, Sigma_OO cost 2 * 8 * (6 cap)^2 bytes of
+// scratch per problem (2.4 MB at 64), mirrored by the arena's pinned host copy.
+constexpr int POSE_COV_GRAPH_MAX_OBJ = 64;
+int launch_pose_cov_graph(const void* problems_dev, int n_problems, int max_free_obj, int max_cam, int max_pairs, hipStream_t s);
 int launch_debug_cholesky(const double* A, const double* b, int ns, double* x, int* ok, hipStream_t s);
 }  // namespace suo

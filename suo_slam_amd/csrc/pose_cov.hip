@@ -15,18 +15,21 @@
 //      S^-1 = Sigma_OO are the substitutions against the identity, dealt to the four waves (wave_cholesky_substitute: no workgroup barrier between columns), and stay
 //      in LDS: a camera's block Hcc^-1 + Y Sigma_OO Y^T, Y = Hcc^-1 Hco over the objects it sees, needs the off-diagonal blocks between them.  A wave per camera
 //      forms Z = Y Sigma_OO (6 x ns) and Z Y^T in the LDS the factor no longer needs.  A free vertex without a counted edge gets no row in the system.
+//   3  the same system in device memory, spread over the grid (suo_pose_covariances_graph: more than 16 free objects, (camera, camera) pairs): csrc/pose_cov_graph.hip.
 // Pairs (suo_pose_covariances_pairs): the cross block Sigma_ab and the covariance of the relative pose of requested vertex pairs (camera, object) / (object, object).
 //   Forms 0 and 1 couple nothing, so every cross block between two different vertices is zero.  In form 2 the PAIRS instantiation of the coupled kernel writes, for
 //   the requested pairs whose two vertices are in the system, Sigma_co = -Z[:, slot(o)] from the camera wave that holds Z (dense over the objects: also where the
 //   camera does not see the object) and Sigma_ab from Sinv; the marginal entries keep the <false> instantiation, which compiles the pair work out.
 //   pose_cov_pairs_kernel runs behind both kernels, a workgroup per 64 pairs of a problem and a thread per (pair, entry): it fills the blocks that are zeros (a fixed vertex,
 //   forms 0 / 1), NaNs (a vertex whose marginal block is NaN) or the marginal block itself (a == b), and propagates  Sigma_cc + A Sigma_oo A^T + Sigma_co A^T +
-//   A Sigma_oc, A = Ad(T_c),  or  B (Sigma_aa + Sigma_bb - Sigma_ab - Sigma_ba) B^T, B = Ad(T_b^-1)  (include/suo_hip.h).
+//   A Sigma_oc, A = Ad(T_c),  or  B (Sigma_aa + Sigma_bb - Sigma_ab - Sigma_ba) B^T, B = Ad(T_b^-1)  (include/suo_hip.h); for the graph entry also (camera a, camera b):
+//   Sigma_bb + A Sigma_aa A^T - A Sigma_ab - Sigma_ba A^T, A = Ad(T_b T_a^-1), with a zero cross block in forms 0 / 1 and form 3's Z_a Y_b^T otherwise.
 // Vector stores only, no atomics; every sum runs in a fixed order, so two runs give the same bits, and a problem's result does not depend on the rest of the batch.
 #include <algorithm>
 
 #include "lm_device.h"
 #include "lm_launch.h"
+#include "pose_cov_device.h"
 
 namespace suo {
 
@@ -213,99 +216,12 @@ __global__ __launch_bounds__(LM_THREADS) void pose_cov_coupled_kernel(const LmPr
     int* sh = (int*)pc_lds;                     // [0] ok  [1] ns  [2 + s] the object in slot s
     const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
     const double nan = __longlong_as_double(0x7ff8000000000000ll);
-    // ---- the state as the LM kernels hold it; level 1 = not counted -------------------------------------------------------------
-    for (int c = tid; c < P.n_cam; c += LM_THREADS) pose_from_T(P.cam_T + 12 * c, P.cam[c]);
-    for (int o = tid; o < P.n_obj; o += LM_THREADS) pose_from_T(P.obj_T + 12 * o, P.obj[o]);
-    for (int e = tid; e < P.n_edge; e += LM_THREADS) P.level[e] = P.edge_inlier[e] ? 0 : 1;
-    if (tid == 0) sh[0] = 1;
-    __syncthreads();
-    (void)edge_pass_partial(P, 0, P.n_edge, false, true);      // Jacobians, weight 1
-    __syncthreads();
-    accumulate_pairs(P);                                        // per pair Hcc (21) Hoo (21) Hco (36), edge order
-    __syncthreads();
-    // ---- per vertex: its diagonal block (pairs in CSR order) and whether any counted edge reaches it (xc / xo [6 v]: scratch) ----
-    for (int idx = tid; idx < P.n_cam * 21; idx += LM_THREADS) {
-        const int c = idx / 21, k = idx - c * 21;
-        double s = 0;
-        if (!P.cam_fixed[c])
-            for (int a = P.cam_pair_ptr[c]; a < P.cam_pair_ptr[c + 1]; ++a) s += P.pair_part[90 * (size_t)P.cam_pair_idx[a] + k];
-        P.Hcc[36 * c + k] = s;
-    }
-    for (int idx = tid; idx < P.n_obj * 21; idx += LM_THREADS) {
-        const int o = idx / 21, k = idx - o * 21;
-        double s = 0;
-        if (!P.obj_fixed[o])
-            for (int a = P.obj_pair_ptr[o]; a < P.obj_pair_ptr[o + 1]; ++a) s += P.pair_part[90 * (size_t)P.obj_pair_idx[a] + 21 + k];
-        P.Hoo[36 * o + k] = s;
-    }
-    for (int v = tid; v < P.n_cam + P.n_obj; v += LM_THREADS) {
-        const bool is_cam = v < P.n_cam;
-        const int i = is_cam ? v : v - P.n_cam;
-        int n = 0;
-        if (!(is_cam ? P.cam_fixed[i] : P.obj_fixed[i])) {
-            const int* ptr = is_cam ? P.cam_pair_ptr : P.obj_pair_ptr;
-            const int* pidx = is_cam ? P.cam_pair_idx : P.obj_pair_idx;
-            for (int a = ptr[i]; a < ptr[i + 1]; ++a)
-                for (int e = P.pair_start[pidx[a]]; e < P.pair_start[pidx[a] + 1]; ++e) n += P.level[e] == 0 ? 1 : 0;
-        }
-        (is_cam ? P.xc : P.xo)[6 * i] = n > 0 ? 1.0 : 0.0;
-    }
-    __syncthreads();
-    auto cam_in = [&](int c) { return !P.cam_fixed[c] && P.xc[6 * c] > 0; };
-    if (tid == 0) {
-        int n = 0;
-        for (int o = 0; o < P.n_obj; ++o) {
-            const bool in = !P.obj_fixed[o] && P.xo[6 * o] > 0 && n < LM_MAX_SCHUR_OBJ;
-            P.obj_slot[o] = in ? n : -1;
-            if (in) { sh[2 + n] = o; ++n; }
-        }
-        sh[1] = 6 * n;
-    }
-    for (int c = tid; c < P.n_cam; c += LM_THREADS) {
-        if (!cam_in(c)) continue;
-        double A[36], Ai[36];
-        unpack_sym21(P.Hcc + 36 * c, A);
-        if (!spd_inverse6(A, Ai)) { sh[0] = 0; for (int i = 0; i < 36; ++i) Ai[i] = 0; }
-        for (int i = 0; i < 36; ++i) P.Hcc_inv[36 * c + i] = Ai[i];
-    }
-    __syncthreads();
-    const int ns = __builtin_amdgcn_readfirstlane(sh[1]), sp = ns + 1;
+    // ---- linearisation, per-vertex blocks, slots, Hcc^-1, Y and S: csrc/pose_cov_device.h, shared with form 3 (csrc/pose_cov_graph.hip) -----------------------
+    const int ns = pc_assemble_blocks(P, sh, LM_MAX_SCHUR_OBJ), sp = ns + 1;
+    auto cam_in = [&](int c) { return pc_cam_in(P, c); };
     double* Sinv = pc_lds + PC_HEAD;
     double* S = Sinv + ns * ns;
-    // ---- Y[p] = Hcc^-1 Hco[p];  S = blockdiag(Hoo) - sum_c Hco(c, o1)^T Y(c, o2), cameras in CSR order (csrc/lm.hip) --------------
-    for (int idx = tid; idx < P.n_pair * 36; idx += LM_THREADS) {
-        const int p = idx / 36, rc = idx - p * 36, r = rc / 6, cc = rc - r * 6;
-        const int c = P.pair_cam[p];
-        double s = 0;
-        if (cam_in(c) && P.obj_slot[P.pair_obj[p]] >= 0) {
-            const double* Hco = P.pair_part + 90 * (size_t)p + 42;
-            for (int k = 0; k < 6; ++k) s += P.Hcc_inv[36 * c + r * 6 + k] * Hco[k * 6 + cc];
-        }
-        P.Y[idx] = s;
-    }
-    for (int idx = tid; idx < ns * sp; idx += LM_THREADS) S[idx] = 0;
-    __syncthreads();
-    for (int idx = tid; idx < ns * ns; idx += LM_THREADS) {
-        const int row = idx / ns, col = idx - row * ns;
-        const int s1 = row / 6, i = row - s1 * 6, s2 = col / 6, j = col - s2 * 6;
-        const int o1 = sh[2 + s1], o2 = sh[2 + s2];
-        double acc = 0;
-        if (s1 == s2) {
-            const int rr = i < j ? i : j, c2 = i < j ? j : i;
-            acc = P.Hoo[36 * o1 + rr * 6 - rr * (rr - 1) / 2 + (c2 - rr)];
-        }
-        double sub = 0;
-        for (int a = P.obj_pair_ptr[o1]; a < P.obj_pair_ptr[o1 + 1]; ++a) {
-            const int p1 = P.obj_pair_idx[a], c = P.pair_cam[p1];
-            const int p2 = P.cam_obj_pair[(size_t)c * P.n_obj + o2];      // the same camera's pair with object o2
-            if (!cam_in(c) || p2 < 0) continue;
-            const double* H1 = P.pair_part + 90 * (size_t)p1 + 42;       // Hco(c, o1), row = camera dof
-            const double* Y2 = P.Y + 36 * (size_t)p2;
-            for (int k = 0; k < 6; ++k) sub += H1[k * 6 + i] * Y2[k * 6 + j];
-        }
-        S[row * sp + col] = acc - sub;
-    }
-    __syncthreads();
+    pc_assemble_schur(P, sh, ns, S, sp);
     // ---- S = L L^T once; column c of Sigma_OO = S^-1 is the solve against e_c, one wave per column ----------------------------------
     wg_cholesky_factor(S, sp, ns, tid, LM_THREADS, &sh[0]);
     for (int col = wv; col < ns; col += LM_THREADS / 64) {
@@ -421,9 +337,14 @@ DEV void pc_ad_row(const double* T, bool inverse, int r, double (&row)[6]) {
 }
 
 // entry (r, c) of  Scc + A Soo A^T + Sco A^T + A Sco^T  (S1 = Scc, S2 = Soo, X = Sigma_co or, x_transposed, Sigma_oc)  or, obj_obj, of
-// A (Saa + Sbb - Sab - Sab^T) A^T  (S1 = Saa, S2 = Sbb, X = Sigma_ab); Ar / Ac: rows r and c of A; X == nullptr: a cross block of zeros
-DEV double pc_rel_entry(bool obj_obj, const double* S1, const double* S2, const double* X, bool x_transposed, const double (&Ar)[6], const double (&Ac)[6], int r, int c) {
-    auto x = [&](int i, int j) { return !X ? 0.0 : (x_transposed ? X[6 * j + i] : X[6 * i + j]); };
+// A (Saa + Sbb - Sab - Sab^T) A^T  (S1 = Saa, S2 = Sbb, X = Sigma_ab); Ar / Ac: rows r and c of A; X == nullptr: a cross block of zeros.  x_negated: the
+// first form with -X, which is the (camera a, camera b) pair's  Sbb + A Saa A^T - Sba A^T - A Sab  (S1 = Sbb, S2 = Saa, X = Sigma_ab, x_transposed)
+DEV double pc_rel_entry(bool obj_obj, const double* S1, const double* S2, const double* X, bool x_transposed, const double (&Ar)[6], const double (&Ac)[6], int r, int c,
+                        bool x_negated = false) {
+    auto x = [&](int i, int j) {
+        const double v = !X ? 0.0 : (x_transposed ? X[6 * j + i] : X[6 * i + j]);
+        return x_negated ? -v : v;
+    };
     double acc = obj_obj ? 0.0 : S1[6 * r + c];
     for (int k = 0; k < 6; ++k) {
         double row = 0;
@@ -474,14 +395,31 @@ __global__ __launch_bounds__(LM_THREADS) void pose_cov_pairs_kernel(const LmProb
         const bool a_fixed = a_cam ? P.cam_fixed[a] : P.obj_fixed[a - P.n_cam], b_fixed = b_cam ? P.cam_fixed[b] : P.obj_fixed[b - P.n_cam];
         double* cross = P.cov_cross + 36 * (size_t)q;
         if (isnan(Sa[0]) || isnan(Sb[0])) { cross[rc] = nan; P.cov_rel[idx] = nan; continue; }
-        // Sigma_ab: the marginal block (a == b), zeros (a fixed vertex; forms 0 / 1 couple nothing), or what the coupled kernel wrote -- that block is only read
-        // here: the other threads of the pair read it too
-        const bool same = a == b, zero = !same && (a_fixed || b_fixed || P.cov_form != 2);
+        // Sigma_ab: the marginal block (a == b), zeros (a fixed vertex; forms 0 / 1 couple nothing), or what the coupled kernel (form 3: pcg_cross_kernel of
+        // csrc/pose_cov_graph.hip) wrote -- that block is only read here: the other threads of the pair read it too
+        const bool same = a == b, zero = !same && (a_fixed || b_fixed || P.cov_form < 2);
         const double* X = same ? Sa : (zero ? nullptr : cross);
         if (same) cross[rc] = Sa[rc];
         if (zero) cross[rc] = 0.0;
         double Ar[6], Ac[6], m_rc, m_cr;
-        if (!a_cam && !b_cam) {
+        if (a_cam && b_cam) {
+            // (camera a, camera b) of suo_pose_covariances_graph: T_b T_a^-1, delta_rel = delta_b - A delta_a, A = Ad(T_b T_a^-1); (c, c) is the identity, exactly
+            if (same) { P.cov_rel[idx] = 0.0; continue; }
+            const double* Ta = P.cam_T + 12 * (size_t)a;
+            const double* Tb = P.cam_T + 12 * (size_t)b;
+            double Trel[12];
+#pragma unroll
+            for (int i = 0; i < 3; ++i) {
+#pragma unroll
+                for (int j = 0; j < 3; ++j) Trel[4 * i + j] = (Tb[4 * i] * Ta[4 * j] + Tb[4 * i + 1] * Ta[4 * j + 1]) + Tb[4 * i + 2] * Ta[4 * j + 2];       // R_b R_a^T
+            }
+#pragma unroll
+            for (int i = 0; i < 3; ++i) Trel[4 * i + 3] = Tb[4 * i + 3] - ((Trel[4 * i] * Ta[3] + Trel[4 * i + 1] * Ta[7]) + Trel[4 * i + 2] * Ta[11]);
+            pc_ad_row(Trel, false, r, Ar);
+            pc_ad_row(Trel, false, c, Ac);
+            m_rc = pc_rel_entry(false, Sb, Sa, X, true, Ar, Ac, r, c, true);
+            m_cr = pc_rel_entry(false, Sb, Sa, X, true, Ac, Ar, c, r, true);
+        } else if (!a_cam && !b_cam) {
             const double* Tb = P.obj_T + 12 * (size_t)(b - P.n_cam);
             pc_ad_row(Tb, true, r, Ar);
             pc_ad_row(Tb, true, c, Ac);

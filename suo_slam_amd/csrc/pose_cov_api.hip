@@ -1,5 +1,6 @@
-// Host-buffer entry points of the pose covariances (include/suo_hip.h: suo_pose_covariances / suo_pose_covariances_pairs and their batch forms): staged through the arena of
-// suo_optimize_batch (csrc/ba_stage.hip), one H2D, the kernels of csrc/pose_cov.hip, one D2H of the blocks.  The caller's problem is read only.
+// Host-buffer entry points of the pose covariances (include/suo_hip.h: suo_pose_covariances / suo_pose_covariances_pairs / suo_pose_covariances_graph and their batch
+// forms): staged through the arena of suo_optimize_batch (csrc/ba_stage.hip), one H2D, the kernels of csrc/pose_cov.hip and csrc/pose_cov_graph.hip, one D2H of the
+// blocks.  The caller's problem is read only.
 #include <string.h>
 
 #include <algorithm>
@@ -8,14 +9,19 @@
 
 using namespace suo;
 
+static_assert(POSE_COV_GRAPH_MAX_OBJ == SUO_POSE_COV_GRAPH_MAX_OBJ, "the cap the header documents");
+
 // Which kernel of csrc/pose_cov.hip takes every problem of the batch, decided ONCE, on the host (the counterpart of csrc/ba_api.hip: plan_ba_batch).
 // A problem's form depends on that problem alone, so a batch gives every member the bits it gets alone.
 struct CovPlan {
-    std::vector<int> form;           // LmProblem::cov_form: 0 no free camera, 1 no free object (and a free camera), 2 coupled
-    bool diag = false, coupled = false;
-    int max_free_obj = 0;            // over the coupled problems: sizes the reduced system's LDS
+    std::vector<int> form;           // LmProblem::cov_form: 0 no free camera, 1 no free object (and a free camera), 2 coupled in LDS, 3 coupled in device memory
+    bool diag = false, coupled = false, graph = false;
+    int max_free_obj = 0;            // over the form-2 problems: sizes the reduced system's LDS
+    int graph_free_obj = 0, graph_cam = 0;      // over the form-3 problems: size the grids of csrc/pose_cov_graph.hip
 };
-static int plan_cov_batch(const suo_ba_problem* probs, int n_prob, CovPlan& plan) {
+// graph (the suo_pose_covariances_graph entries): a coupled problem the old entries answer -- at most 16 free objects, no (camera, camera) pair -- keeps form 2 and
+// with it their bits; every other coupled problem takes form 3, up to POSE_COV_GRAPH_MAX_OBJ free objects.  The old entries refuse what form 2 does not hold.
+static int plan_cov_batch(const suo_ba_problem* probs, int n_prob, CovPlan& plan, bool graph = false, const CovPairs* pairs = nullptr) {
     plan.form.assign(n_prob, 0);
     for (int i = 0; i < n_prob; ++i) {
         const suo_ba_problem& q = probs[i];
@@ -28,6 +34,22 @@ static int plan_cov_batch(const suo_ba_problem* probs, int n_prob, CovPlan& plan
         for (int c = 0; c < q.n_cam; ++c) nfc += q.cam_fixed[c] ? 0 : 1;
         if (nfc == 0) { plan.form[i] = 0; plan.diag = true; continue; }
         if (nfo == 0) { plan.form[i] = 1; plan.diag = true; continue; }
+        if (graph) {
+            bool cam_cam = false;
+            // (the lists are validated behind the plan, as for the old entries: only compare here)
+            for (int k = 0; pairs && pairs->a[i] && pairs->b[i] && !cam_cam && k < pairs->n[i]; ++k) cam_cam = pairs->a[i][k] < q.n_cam && pairs->b[i][k] < q.n_cam;
+            if (nfo > POSE_COV_GRAPH_MAX_OBJ) {
+                suo_set_error("suo_pose_covariances_graph: problem %d has %d free objects next to %d free cameras; the device-memory form takes at most %d", i, nfo, nfc,
+                              POSE_COV_GRAPH_MAX_OBJ);
+                return SUO_ERR_ARG;
+            }
+            if (cam_cam || nfo > LM_MAX_SCHUR_OBJ) {
+                plan.form[i] = 3; plan.graph = true;
+                plan.graph_free_obj = std::max(plan.graph_free_obj, nfo);
+                plan.graph_cam = std::max(plan.graph_cam, q.n_cam);
+                continue;
+            }
+        }
         if (nfo > LM_MAX_SCHUR_OBJ) {
             suo_set_error("suo_pose_covariances: problem %d has %d free objects next to %d free cameras; the coupled form keeps the reduced system and its inverse "
                           "in LDS and takes at most %d", i, nfo, nfc, LM_MAX_SCHUR_OBJ);
@@ -41,10 +63,11 @@ static int plan_cov_batch(const suo_ba_problem* probs, int n_prob, CovPlan& plan
 
 // The shared body of the entries.  pairs == nullptr: the marginal entry -- the coupled kernel without the pair work, no pair kernel, status [n][2].
 // With pairs: the PAIRS instantiation, the pair kernel behind both, status [n][3]; cross / rel (one pointer per problem) and their members may be null.
+// graph: the suo_pose_covariances_graph entries -- (camera, camera) pairs are served and coupled problems may take form 3.
 static int cov_batch(const suo_ba_problem* probs, int n_prob, double* const* cam_cov, double* const* obj_cov, int* status, const CovPairs* pairs, double* const* cross,
-                     double* const* rel, const char* who) {
+                     double* const* rel, const char* who, bool graph = false) {
     CovPlan plan;
-    int rc = plan_cov_batch(probs, n_prob, plan);
+    int rc = plan_cov_batch(probs, n_prob, plan, graph, pairs);
     if (rc != SUO_OK) return rc;
     for (int i = 0; pairs && i < n_prob; ++i) {
         const int n = pairs->n[i], nc = probs[i].n_cam, nv = probs[i].n_cam + probs[i].n_obj;
@@ -52,7 +75,7 @@ static int cov_batch(const suo_ba_problem* probs, int n_prob, double* const* cam
         for (int q = 0; q < n; ++q) {
             const int a = pairs->a[i][q], b = pairs->b[i][q];
             if (a < 0 || a >= nv || b < 0 || b >= nv) { suo_set_error("%s: problem %d: pair %d = (%d, %d) names a vertex outside [0, %d)", who, i, q, a, b, nv); return SUO_ERR_ARG; }
-            if (a < nc && b < nc) { suo_set_error("%s: problem %d: pair %d = (%d, %d) is (camera, camera); pairs are (camera, object) or (object, object)", who, i, q, a, b); return SUO_ERR_ARG; }
+            if (!graph && a < nc && b < nc) { suo_set_error("%s: problem %d: pair %d = (%d, %d) is (camera, camera); pairs are (camera, object) or (object, object)", who, i, q, a, b); return SUO_ERR_ARG; }
         }
     }
     std::lock_guard<std::mutex> lock(g_arena.mu);
@@ -63,6 +86,7 @@ static int cov_batch(const suo_ba_problem* probs, int n_prob, double* const* cam
     hipStream_t s = g_arena.stream;
     if (plan.diag) { rc = launch_pose_cov_diag(P, n_prob, s); if (rc != SUO_OK) return rc; }
     if (plan.coupled) { rc = launch_pose_cov_coupled(P, n_prob, plan.max_free_obj, s, pairs != nullptr); if (rc != SUO_OK) return rc; }
+    if (plan.graph) { rc = launch_pose_cov_graph(P, n_prob, plan.graph_free_obj, plan.graph_cam, *std::max_element(pairs->n, pairs->n + n_prob), s); if (rc != SUO_OK) return rc; }
     if (pairs) { rc = launch_pose_cov_pairs(P, n_prob, *std::max_element(pairs->n, pairs->n + n_prob), s); if (rc != SUO_OK) return rc; }
     SUO_HIP_CHECK(hipMemcpyAsync(g_arena.host + st.cov_begin, g_arena.dev + st.cov_begin, st.cov_end - st.cov_begin, hipMemcpyDeviceToHost, s));
     SUO_HIP_CHECK(hipStreamSynchronize(s));
@@ -103,6 +127,20 @@ int suo_pose_covariances_pairs(const suo_ba_problem* problem, int n_pair, const 
                                double* rel, int* status) {
     if (!problem) { suo_set_error("suo_pose_covariances_pairs: null argument"); return SUO_ERR_ARG; }
     return suo_pose_covariances_pairs_batch(problem, 1, &n_pair, &pair_a, &pair_b, &cam_cov, &obj_cov, &cross, &rel, status);
+}
+
+int suo_pose_covariances_graph_batch(const suo_ba_problem* probs, int n_prob, const int* n_pair, const int32_t* const* pair_a, const int32_t* const* pair_b,
+                                     double* const* cam_cov, double* const* obj_cov, double* const* cross, double* const* rel, int* status) {
+    if (n_prob <= 0) return SUO_OK;
+    if (!probs || !n_pair || !pair_a || !pair_b) { suo_set_error("suo_pose_covariances_graph_batch: null argument"); return SUO_ERR_ARG; }
+    const CovPairs pairs{n_pair, pair_a, pair_b};
+    return cov_batch(probs, n_prob, cam_cov, obj_cov, status, &pairs, cross, rel, "suo_pose_covariances_graph", true);
+}
+
+int suo_pose_covariances_graph(const suo_ba_problem* problem, int n_pair, const int32_t* pair_a, const int32_t* pair_b, double* cam_cov, double* obj_cov, double* cross,
+                               double* rel, int* status) {
+    if (!problem) { suo_set_error("suo_pose_covariances_graph: null argument"); return SUO_ERR_ARG; }
+    return suo_pose_covariances_graph_batch(problem, 1, &n_pair, &pair_a, &pair_b, &cam_cov, &obj_cov, &cross, &rel, status);
 }
 
 }  // extern "C"

@@ -686,24 +686,27 @@ class ObjectSLAM(DeviceRoutes):
         self._cull_after_optimize(list(obj_index.keys()), curr_only, view_curr)
 
     @_on_stream
-    def pose_covariances(self, view_ids=None, relative=False):
+    def pose_covariances(self, view_ids=None, relative=False, trajectory=False):
         """6x6 marginal covariances of the current map: {"cams": {view_id: 6x6}, "objs": {obj_id: 6x6}} for every key of cam_poses (or those in view_ids) and
         obj_poses, from the global graph of build_problem() at the stored poses and inlier flags (ba.pose_covariances: rows / columns [omega, upsilon] of the
         left update; zeros for the gauge camera, NaNs for a vertex no counted measurement reaches).  These blocks are relative to the gauge camera.
         relative=True adds "rel": {(view_id, obj_id): 6x6} for every selected view and every object of the map: the covariance of the T_OtoC = T_GtoC T_OtoG that
-        collect_results reports, which does not depend on the gauge (ba.pose_covariances_pairs, the same single device call).  Changes nothing in the map."""
+        collect_results reports, which does not depend on the gauge.  trajectory=True adds "rel_cams": {(view_a, view_b): 6x6} for consecutive selected views in
+        cam_poses order: the covariance of T_b T_a^-1, the motion between the two views (NaN where a view is not in the graph).  One device call
+        (ba.pose_covariances_graph: any number of objects up to its cap; the bits of ba.pose_covariances / ba.pose_covariances_pairs wherever those answer).
+        Changes nothing in the map."""
         nan = np.full((6, 6), np.nan)
         cams = {v: nan.copy() for v in self.cam_poses if view_ids is None or v in view_ids}
         objs = {o: nan.copy() for o in self.obj_poses}
         built = self.build_problem(False)
         if built is not None:
             prob, (cam_index, obj_index, _, _, _) = built
-            if relative:
-                keys = [(v, o) for v in cams if v in cam_index for o in obj_index]
-                pairs = np.array([(cam_index[v], len(cam_index) + obj_index[o]) for v, o in keys], np.int32).reshape(-1, 2)
-                cam_cov, obj_cov, _, rel_cov, _ = _ba.pose_covariances_pairs_batch([prob], [pairs])[0]
-            else:
-                cam_cov, obj_cov, _ = _ba.pose_covariances_batch([prob])[0]
+            keys = [(v, o) for v in cams if v in cam_index for o in obj_index] if relative else []
+            pairs = [(cam_index[v], len(cam_index) + obj_index[o]) for v, o in keys]
+            views = list(cams)
+            steps = [(a, b) for a, b in zip(views[:-1], views[1:]) if a in cam_index and b in cam_index] if trajectory else []
+            pairs += [(cam_index[a], cam_index[b]) for a, b in steps]
+            cam_cov, obj_cov, _, rel_cov, _ = _ba.pose_covariances_graph_batch([prob], [np.array(pairs, np.int32).reshape(-1, 2)])[0]
             for v, i in cam_index.items():
                 if v in cams:
                     cams[v] = cam_cov[i].copy()
@@ -715,6 +718,12 @@ class ObjectSLAM(DeviceRoutes):
             if built is not None:
                 for k, S6 in zip(keys, rel_cov):
                     out["rel"][k] = S6.copy()
+        if trajectory:
+            views = list(cams)
+            out["rel_cams"] = {k: nan.copy() for k in zip(views[:-1], views[1:])}
+            if built is not None:
+                for k, S6 in zip(steps, rel_cov[len(keys):]):
+                    out["rel_cams"][k] = S6.copy()
         return out
 
     @_on_stream
