@@ -493,7 +493,8 @@ int suo_debug_lm_routes(const suo_ba_problem* problems, int n_problems, int* rou
  *                  counts them.  Vertices in other connected blocks are unaffected.  The call never faults and never loops on a bad pivot.
  *                  (Affected: without a free camera, or without a free object, every vertex is a block of its own; where free cameras meet free objects, a vertex
  *                  without a counted edge is left out of the system, and a bad pivot of what remains marks every free vertex of that problem.)
- *                - the chi2 scale is not applied: this is the covariance under the stated information matrices.
+ *                - the chi2 scale is not applied: this is the covariance under the stated information matrices.  suo_residual_statistics below reports the scale
+ *                  (summary[5] = s0^2); a caller who wants the scaled covariance multiplies.
  * Host buffers, blocking, staged through the arena of suo_optimize_batch; the problem is not modified (its, n_rounds, chi2_thr, huber_delta, stats are not read).
  * cam_cov [n_cam][36], obj_cov [n_obj][36] (either may be NULL), status [2] = number of NaN camera blocks, NaN object blocks (may be NULL); the batch form takes
  * one pointer per problem and status [n][2], and gives every problem the bits it gets alone.  Kernels (csrc/pose_cov.hip, fp64, fixed summation order):
@@ -558,6 +559,49 @@ int suo_pose_covariances_graph(const suo_ba_problem* problem, int n_pair, const 
                                int* status /*[3]: NaN cam blocks, NaN obj blocks, NaN pairs*/);
 int suo_pose_covariances_graph_batch(const suo_ba_problem* problems, int n, const int* n_pair, const int32_t* const* pair_a, const int32_t* const* pair_b,
                                      double* const* cam_cov, double* const* obj_cov, double* const* cross, double* const* rel, int* status /*[n][3]*/);
+
+/* ---- per-edge leverages, studentised residuals and the chi2 scale ------------------------------------------------------------------
+ * What the covariances above leave open: by how much the adjustment itself says they are too small or too large (the chi2 scale s0^2, which they do not apply),
+ * and which measurements carry the misfit.  The state, the Hessian, the perturbation, the vertex coding and the NaN rules are those of suo_pose_covariances_graph.
+ *   Counted.     An edge is counted when edge_inlier == 1 and its camera and object are not both fixed: the edges H is summed over.
+ *   v_e          = uv - pi(T_c T_o p), the residual.
+ *   J_e          = [J_c J_o], the 2x12 Jacobian in the [omega, upsilon] left-update convention of csrc/lm_device.h, with zero columns for a fixed vertex.
+ *   Omega_e      from edge_info.
+ *   Sigma_e      the joint 12x12 of the edge's two vertices, cut out of Sigma = H^-1: [[Sigma_cc, Sigma_co], [Sigma_oc, Sigma_oo]].
+ * For EVERY edge, counted or not:
+ *   chi2_e       = v_e^T Omega_e v_e, with no Huber weight.
+ *   P_e          = J_e Sigma_e J_e^T, the covariance of the predicted measurement, reported as (xx, xy, yy).
+ *   lev_e        = tr(P_e Omega_e), the leverage.  For counted edges 0 <= lev_e <= 2 and 2 - lev_e is the edge's redundancy; over the counted edges of a problem
+ *                sum lev_e = n exactly, n the number of rows of H (six per free vertex that a counted edge reaches): this is tr(Sigma H).
+ *   t_e          = v_e^T (Omega_e^-1 + s P_e)^-1 v_e, s = -1 for a counted edge and s = +1 otherwise: the studentised statistic, chi2(2) under the model, of a
+ *                measurement inside the estimate (its residual has covariance Omega^-1 - P) or outside it (Omega^-1 + P).  An edge with both vertices fixed has
+ *                P_e = 0, so t_e = chi2_e, to the bit.
+ *   No redundancy.  Let R_e = I + s P_e Omega_e (so that t_e = (Omega_e v_e)^T R_e^-1 v_e).  If det R_e <= 1e-9, or a diagonal entry of R_e is <= 0, then t_e is NaN
+ *                and the edge is counted in status[3]: such an edge cannot be checked -- an object held by exactly three keypoints in a single-view frame is an
+ *                example.  chi2_e, P_e and lev_e are still reported.  The threshold is part of the rule, not a tolerance.
+ *   NaN vertex.  If either vertex of an edge is NaN in the marginal call, P_e, lev_e and t_e are NaN and the edge is counted in status[2]; chi2_e is still finite.
+ * Per vertex, over its counted edges in ascending edge index: (count, sum chi2_e, sum (2 - lev_e)); the ratio of the last two is a per-vertex variance component.
+ * Per problem, summary[6]: m (counted edges), n, sum chi2_e, sum lev_e, dof = 2 m - n, s0^2 = sum chi2_e / dof -- NaN when dof <= 0 or when any counted edge is NaN
+ * (status[2]).  The sums run over the counted edges in ascending edge index in a tree whose shape depends on n_edge alone.
+ * s0^2 is the factor by which the reported covariances would be multiplied to agree with the residuals; no entry of this library applies it (the pose NEES of
+ * suo_pose_nees is measured under whatever covariance the caller hands it).
+ * Host buffers, blocking, staged through the arena of suo_optimize_batch; the problem is not modified.  Every output pointer may be NULL:
+ *   cam_cov [n_cam][36], obj_cov [n_obj][36]   those of suo_pose_covariances_graph on the same problem, bit for bit, as are status[0..1]
+ *   edge_chi2 [E], edge_pcov [E][3], edge_lev [E], edge_t [E]      in the caller's edge order
+ *   cam_stat [n_cam][3], obj_stat [n_obj][3]
+ *   summary [6], status [4] = NaN camera blocks, NaN object blocks, NaN edges, edges without redundancy
+ * It accepts what suo_pose_covariances_graph accepts (every form, up to SUO_POSE_COV_GRAPH_MAX_OBJ free objects next to free cameras) and refuses what it refuses,
+ * SUO_ERR_ARG and nothing launched.  n_edge == 0 is legal: summary = {0, 0, 0, 0, 0, NaN}, cam_cov / obj_cov what the graph entry gives.  The batch form takes one
+ * pointer per problem, summary [n][6] and status [n][4]; a problem's outputs do not depend on the rest of the batch, and two calls give the same bits.
+ * Kernels: the graph entry's, asked for the cross blocks of the distinct (camera, object) pairs that carry an edge, then csrc/resid_stats.hip behind them (fp64, fixed
+ * summation order, vector stores only, no atomics): a thread per edge, the three 6x6 blocks of a pair staged once per wave in LDS; then a wave per vertex for the
+ * per-vertex triples (a fixed tree over the vertex's ascending edge list) and one workgroup per problem for the summary. */
+int suo_residual_statistics(const suo_ba_problem* problem, double* cam_cov /*[n_cam][36]*/, double* obj_cov /*[n_obj][36]*/, double* edge_chi2 /*[E]*/,
+                            double* edge_pcov /*[E][3]*/, double* edge_lev /*[E]*/, double* edge_t /*[E]*/, double* cam_stat /*[n_cam][3]*/,
+                            double* obj_stat /*[n_obj][3]*/, double* summary /*[6]*/, int* status /*[4]*/);
+int suo_residual_statistics_batch(const suo_ba_problem* problems, int n, double* const* cam_cov, double* const* obj_cov, double* const* edge_chi2,
+                                  double* const* edge_pcov, double* const* edge_lev, double* const* edge_t, double* const* cam_stat, double* const* obj_stat,
+                                  double* summary /*[n][6]*/, int* status /*[n][4]*/);
 
 /* ---- phase-wise bundle adjustment for the multi-GPU global pose graph ------------------------
  * Cameras are partitioned across GPUs; each rank builds a context over ITS cameras' edges and ALL objects, and
@@ -703,7 +747,8 @@ int suo_pose_errors_bop(void* mesh_db, int n, const int* model_index, const doub
  *                |v|^2 < 1e-8 and for the V^-1 coefficient below theta^2 < 0.09, closed forms above.  Covered: 0 <= theta <= 3.0 rad to a few ulp of
  *                (1 + |xi|); beyond 3.0 only finiteness and |omega| <= pi are promised.
  *   NEES.        xi^T Sigma^-1 xi through the Cholesky factor of Sigma (cov [n][36] row-major, rows and columns [omega, upsilon]; the lower triangle is read).
- *                The chi2 scale is STILL NOT applied: this is the NEES under the stated covariance.
+ *                The chi2 scale is STILL NOT applied: this is the NEES under the covariance the caller hands over -- the unscaled one, unless the caller has
+ *                multiplied it by the s0^2 that suo_residual_statistics reports.
  *   NaN rules.   nees[i] is NaN for a block with a non-finite entry (all 36 are looked at), for a pivot that is not positive (this includes the 36 zeros of a
  *                fixed vertex), and for a pair whose MSSD meets a non-finite distance (a NaN or overflowing pose): that pair also gets sym_index -1 and NaN xi
  *                and T_ref.  status[0] counts the NaN results.  The call never faults and never loops on a bad block; the other pairs of the batch are unaffected.

@@ -155,3 +155,40 @@ def pose_covariances_graph_batch(problems, pairs):
 def pose_covariances_graph(*args, pairs, **kw):
     """The arguments of optimize() plus pairs [P,2]; returns (cam_cov [C,6,6], obj_cov [O,6,6], cross [P,6,6], rel [P,6,6], status [3])."""
     return pose_covariances_graph_batch([Problem(*args, **kw)], [pairs])[0]
+
+
+RESID_KEYS = ("cam_cov", "obj_cov", "edge_chi2", "edge_pcov", "edge_lev", "edge_t", "cam_stat", "obj_stat")
+
+
+def residual_statistics_batch(problems):
+    """Per-edge leverages, studentised residuals and the chi2 scale of each Problem at the state it holds (include/suo_hip.h: suo_residual_statistics), one call
+    for the whole list.  Per problem a dict: cam_cov [C,6,6] / obj_cov [O,6,6] (those of pose_covariances_graph, bit for bit), and for EVERY edge, in the caller's
+    order, edge_chi2 [E] = v^T Omega v, edge_pcov [E,3] = J Sigma J^T as (xx, xy, yy), edge_lev [E] = tr(P Omega), edge_t [E] = v^T (Omega^-1 -/+ P)^-1 v (minus for a
+    counted edge; NaN where the edge has no redundancy or touches a NaN vertex); cam_stat [C,3] / obj_stat [O,3] = (count, sum chi2, sum 2 - lev) over the vertex's
+    counted edges; summary [6] = m, n, sum chi2, sum lev, dof = 2 m - n, s0^2 = sum chi2 / dof (NaN when dof <= 0); status [4] = NaN camera blocks, NaN object
+    blocks, NaN edges, edges without redundancy.  The problems are not modified."""
+    if not problems:
+        return []
+    lib = _lib.lib()
+    _lib.require_gpu()
+    n = len(problems)
+    arr = (_lib.BaProblem * n)()
+    ptrs = [(C.c_void_p * n)() for _ in RESID_KEYS]
+    summary = np.zeros((n, 6))
+    status = np.zeros((n, 4), np.int32)
+    out = []
+    for i, (s, p) in enumerate(zip(arr, problems)):
+        p._fill(s)
+        nc, no, E = len(p.cam_T), len(p.obj_T), len(p.edge_cam)
+        bufs = (np.zeros((nc, 6, 6)), np.zeros((no, 6, 6)), np.zeros(E), np.zeros((E, 3)), np.zeros(E), np.zeros(E), np.zeros((nc, 3)), np.zeros((no, 3)))
+        for col, buf in zip(ptrs, bufs):
+            col[i] = buf.ctypes.data
+        out.append(dict(zip(RESID_KEYS, bufs), summary=summary[i], status=status[i]))
+    _lib.check(lib.suo_residual_statistics_batch(C.cast(arr, C.c_void_p), n, *[C.cast(c, C.c_void_p) for c in ptrs], summary.ctypes.data, status.ctypes.data),
+               "suo_residual_statistics_batch")
+    return out
+
+
+def residual_statistics(*args, **kw):
+    """The arguments of optimize(); returns the dict of residual_statistics_batch at the poses and inlier flags given."""
+    return residual_statistics_batch([Problem(*args, **kw)])[0]

@@ -74,10 +74,11 @@ int prep_problem(const suo_ba_problem& q, int index, Prep& P, const char* who) {
 
 // The arena layout of a batch, every array on a 16-byte boundary: the structs, then every problem's inputs (one H2D up to in_end), then the outputs that are not
 // inputs too (one D2H up to out_end), then device-only scratch.  Each Prep::S gets its sizes and its addresses, counted from `base`.
-static void lay_out(const suo_ba_problem* probs, int n_prob, const int* cov_form, const CovPairs* pairs, char* base, Staged& st) {
+static void lay_out(const suo_ba_problem* probs, int n_prob, const int* cov_form, const CovPairs* pairs, bool resid, char* base, Staged& st) {
     Layout L;
     auto put = [&](auto*& p, size_t n) { p = (std::remove_reference_t<decltype(p)>)((uintptr_t)base + L.take(sizeof(*p) * n)); };
     st.o_structs = L.take(sizeof(LmProblem) * (size_t)n_prob);
+    st.o_rs = L.take(resid ? sizeof(RsProblem) * (size_t)n_prob : 0);
     for (int i = 0; i < n_prob; ++i) {
         LmProblem& S = st.prep[i].S;
         S = LmProblem();
@@ -90,6 +91,9 @@ static void lay_out(const suo_ba_problem* probs, int n_prob, const int* cov_form
         put(S.cam_obj_pair, C * O);
         S.n_cpair = pairs ? pairs->n[i] : 0;
         put(S.cpair_a, (size_t)S.n_cpair); put(S.cpair_b, (size_t)S.n_cpair);
+        RsProblem& R = st.prep[i].R;
+        R = RsProblem();
+        if (resid) { put(R.order, E); put(R.vptr, C + O + 1); put(R.vedge, 2 * E); }
     }
     st.in_end = L.off;
     for (int i = 0; i < n_prob; ++i) { LmProblem& S = st.prep[i].S; put(S.edge_chi2, S.n_edge); put(S.stats, 4); }
@@ -105,7 +109,12 @@ static void lay_out(const suo_ba_problem* probs, int n_prob, const int* cov_form
     }
     st.cov_begin = L.off;
     for (int i = 0; i < n_prob; ++i) { LmProblem& S = st.prep[i].S; put(S.cam_cov, 36 * (size_t)S.n_cam); put(S.obj_cov, 36 * (size_t)S.n_obj); put(S.cov_status, 3);
-                                       put(S.cov_cross, 36 * (size_t)S.n_cpair); put(S.cov_rel, 36 * (size_t)S.n_cpair); }
+                                       put(S.cov_cross, 36 * (size_t)S.n_cpair); put(S.cov_rel, 36 * (size_t)S.n_cpair);
+                                       if (!resid) continue;
+                                       const size_t E = S.n_edge, V = (size_t)S.n_cam + S.n_obj;
+                                       RsProblem& R = st.prep[i].R;
+                                       put(R.chi2, E); put(R.pcov, 3 * E); put(R.lev, E); put(R.t, E); put(R.flag, E); put(R.vstat, 3 * V);
+                                       put(R.summary, 6); put(R.status, 2); }
     st.cov_end = L.off;
     // cov_form 3 (csrc/pose_cov_graph.hip): the reduced system, its inverse and every camera's Z in device memory, sized by the free objects -- no slot limit
     for (int i = 0; cov_form && i < n_prob; ++i) {
@@ -119,16 +128,16 @@ static void lay_out(const suo_ba_problem* probs, int n_prob, const int* cov_form
 }
 
 // host prep + arena layout + H2D of one batch of problems
-int stage_problems(const suo_ba_problem* probs, int n_prob, Arena& A, Staged& st, const char* who, const int* cov_form, const CovPairs* pairs) {
+int stage_problems(const suo_ba_problem* probs, int n_prob, Arena& A, Staged& st, const char* who, const int* cov_form, const CovPairs* pairs, bool resid) {
     st.prep.assign(n_prob, Prep());
     for (int i = 0; i < n_prob; ++i) {
         int rc = prep_problem(probs[i], i, st.prep[i], who);
         if (rc != SUO_OK) return rc;
     }
-    lay_out(probs, n_prob, cov_form, pairs, nullptr, st);          // sizes first: the arena may move when it grows
+    lay_out(probs, n_prob, cov_form, pairs, resid, nullptr, st);          // sizes first: the arena may move when it grows
     int rc = A.ensure(st.total);
     if (rc != SUO_OK) return rc;
-    lay_out(probs, n_prob, cov_form, pairs, A.dev, st);
+    lay_out(probs, n_prob, cov_form, pairs, resid, A.dev, st);
     for (int i = 0; i < n_prob; ++i) {
         const suo_ba_problem& q = probs[i];
         Prep& P = st.prep[i];
@@ -163,6 +172,18 @@ int stage_problems(const suo_ba_problem* probs, int n_prob, Arena& A, Staged& st
         if (S.n_cpair > 0) {
             memcpy(A.mirror(S.cpair_a), pairs->a[i], sizeof(int) * S.n_cpair);
             memcpy(A.mirror(S.cpair_b), pairs->b[i], sizeof(int) * S.n_cpair);
+        }
+        if (resid) {
+            // every vertex's edges by the caller's index, ascending: the order the per-vertex sums of csrc/resid_stats.hip walk
+            memcpy(A.mirror(P.R.order), P.order.data(), sizeof(int) * E);
+            int* vptr = A.mirror(P.R.vptr); int* vedge = A.mirror(P.R.vedge);
+            const int V = q.n_cam + q.n_obj;
+            std::fill(vptr, vptr + V + 1, 0);
+            for (int e = 0; e < E; ++e) { vptr[q.edge_cam[e] + 1]++; vptr[q.n_cam + q.edge_obj[e] + 1]++; }
+            for (int v = 0; v < V; ++v) vptr[v + 1] += vptr[v];
+            std::vector<int> at(vptr, vptr + V);
+            for (int e = 0; e < E; ++e) { vedge[at[q.edge_cam[e]]++] = e; vedge[at[q.n_cam + q.edge_obj[e]]++] = e; }
+            memcpy(A.host + st.o_rs + sizeof(RsProblem) * (size_t)i, &P.R, sizeof(RsProblem));
         }
         memcpy(A.host + st.o_structs + sizeof(LmProblem) * (size_t)i, &S, sizeof(LmProblem));
     }

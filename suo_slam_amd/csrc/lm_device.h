@@ -287,6 +287,16 @@ struct LmProblem {
     // [nsm][nsm], Z = Y Sigma_OO of every camera [n_cam][6][nsm] (all three at the pitch of the ns the kernel finds), and [0] ok [1] ns [2 + s] the object in slot s
     double* cov_S; double* cov_Sinv; double* cov_Z; int* cov_hdr;
 };
+// The arrays of suo_residual_statistics (csrc/resid_stats.hip), one struct per problem beside its LmProblem (whose size the LM kernels copy: it stays as it is).
+// In: order [n_edge] the caller's index of (sorted) edge k; vptr [n_cam + n_obj + 1] / vedge [2 n_edge] the caller's indices of every vertex's edges, ascending.
+// Out, all by the CALLER's edge index: chi2, pcov [3] (xx, xy, yy), lev, t, flag (RS_COUNTED | RS_NAN | RS_NORED); vstat [n_cam + n_obj][3] (count, sum chi2,
+// sum 2 - lev); summary [6]; status [2] = NaN edges, edges without redundancy.  The pairs of LmProblem::cpair_a / cpair_b are then the problem's own pairs: pair p's
+// Sigma_co is cov_cross [36 p].
+struct RsProblem {
+    const int* order; const int* vptr; const int* vedge;
+    double* chi2; double* pcov; double* lev; double* t; uint8_t* flag; double* vstat; double* summary; int* status;
+};
+constexpr int RS_COUNTED = 1, RS_NAN = 2, RS_NORED = 4;
 DEV int pair_hi(const LmProblem& P, int p) { return P.pair_end ? P.pair_end[p] : P.pair_start[p + 1]; }
 
 // Cholesky factorisation, forward and backward substitution of the ns x ns reduced (object) system by the WHOLE workgroup, blocked
@@ -663,10 +673,8 @@ DEV bool edge_active(const LmProblem& P, int e) {
     return P.level[e] == 0 && !(P.cam_fixed[P.pair_cam[p]] && P.obj_fixed[P.pair_obj[p]]);
 }
 
-DEV void edge_error(const LmProblem& P, int e, double* err, double* pw_out, double* pc_out) {
-    const int p = P.edge_pair[e];
-    const Pose& cam = P.cam[P.pair_cam[p]];
-    const Pose& obj = P.obj[P.pair_obj[p]];
+// the residual of edge e at the poses given (edge_error: at the poses the problem holds)
+DEV void edge_error_at(const LmProblem& P, int e, const Pose& cam, const Pose& obj, double* err, double* pw_out, double* pc_out) {
     double Ro[9], Rc[9], pw[3], pc[3];
     q_to_R(obj.q, Ro);
     q_to_R(cam.q, Rc);
@@ -680,9 +688,38 @@ DEV void edge_error(const LmProblem& P, int e, double* err, double* pw_out, doub
     err[1] = P.edge_uv[2 * e + 1] - (k[1] * pc[1] / pc[2] + k[3]);
     if (pw_out) { for (int r = 0; r < 3; ++r) { pw_out[r] = pw[r]; pc_out[r] = pc[r]; } }
 }
+DEV void edge_error(const LmProblem& P, int e, double* err, double* pw_out, double* pc_out) {
+    const int p = P.edge_pair[e];
+    edge_error_at(P, e, P.cam[P.pair_cam[p]], P.obj[P.pair_obj[p]], err, pw_out, pc_out);
+}
 DEV double edge_chi2(const LmProblem& P, int e, const double* err) {
     const double* I = P.edge_info + 3 * e;
     return err[0] * (I[0] * err[0] + I[1] * err[1]) + err[1] * (I[1] * err[0] + I[2] * err[1]);
+}
+
+// linearizeOplus of edge e: J [24] = Jc (2 x 6) | Jo (2 x 6), the derivative of the residual by [omega, upsilon] of the left update of its camera and of its
+// object; pw / pc: the point in the world and in the camera (edge_error_at).  The one derivation: the LM kernels, the pose covariances' Hessian
+// (csrc/pose_cov_device.h) and the residual statistics (csrc/resid_stats.hip) all call it.
+DEV void edge_jacobian(const LmProblem& P, int e, const Pose& cam, const double* pw, const double* pc, double* J) {
+    double Rc[9];
+    q_to_R(cam.q, Rc);
+    const double* k = P.edge_k + 4 * e;
+    const double PJ[6] = {-(k[0] / pc[2]), 0, k[0] * pc[0] / (pc[2] * pc[2]), 0, -(k[1] / pc[2]), k[1] * pc[1] / (pc[2] * pc[2])};
+    double PR[6];
+    // (every small loop here is unrolled explicitly: left rolled, Dw / Dc were indexed at run time and lived in scratch memory)
+#pragma unroll
+    for (int r = 0; r < 2; ++r)
+#pragma unroll
+        for (int cc = 0; cc < 3; ++cc) PR[3 * r + cc] = PJ[3 * r] * Rc[cc] + PJ[3 * r + 1] * Rc[3 + cc] + PJ[3 * r + 2] * Rc[6 + cc];
+    const double Dw[18] = {0, pw[2], -pw[1], 1, 0, 0, -pw[2], 0, pw[0], 0, 1, 0, pw[1], -pw[0], 0, 0, 0, 1};
+    const double Dc[18] = {0, pc[2], -pc[1], 1, 0, 0, -pc[2], 0, pc[0], 0, 1, 0, pc[1], -pc[0], 0, 0, 0, 1};
+#pragma unroll
+    for (int r = 0; r < 2; ++r)
+#pragma unroll
+        for (int cc = 0; cc < 6; ++cc) {
+            J[6 * r + cc] = PJ[3 * r] * Dc[cc] + PJ[3 * r + 1] * Dc[6 + cc] + PJ[3 * r + 2] * Dc[12 + cc];            // Jc
+            J[12 + 6 * r + cc] = PR[3 * r] * Dw[cc] + PR[3 * r + 1] * Dw[6 + cc] + PR[3 * r + 2] * Dw[12 + cc];       // Jo
+        }
 }
 
 // computeActiveErrors + activeRobustChi2; with_jac also stores the edge Jacobians (linearizeOplus) and the
@@ -702,26 +739,8 @@ DEV double edge_pass_partial(const LmProblem& P, int e_begin, int e_end, bool ro
         double w = 1.0;
         c += robust_on ? huber_rho(c2, P.huber_delta, w) : c2;
         if (with_jac) {
-            double Rc[9];
-            q_to_R(P.cam[P.pair_cam[P.edge_pair[e]]].q, Rc);
-            const double* k = P.edge_k + 4 * e;
-            const double PJ[6] = {-(k[0] / pc[2]), 0, k[0] * pc[0] / (pc[2] * pc[2]), 0, -(k[1] / pc[2]), k[1] * pc[1] / (pc[2] * pc[2])};
-            double PR[6];
-            // (every small loop here is unrolled explicitly: left rolled, Dw / Dc were indexed at run time and lived in scratch memory)
-#pragma unroll
-            for (int r = 0; r < 2; ++r)
-#pragma unroll
-                for (int cc = 0; cc < 3; ++cc) PR[3 * r + cc] = PJ[3 * r] * Rc[cc] + PJ[3 * r + 1] * Rc[3 + cc] + PJ[3 * r + 2] * Rc[6 + cc];
-            const double Dw[18] = {0, pw[2], -pw[1], 1, 0, 0, -pw[2], 0, pw[0], 0, 1, 0, pw[1], -pw[0], 0, 0, 0, 1};
-            const double Dc[18] = {0, pc[2], -pc[1], 1, 0, 0, -pc[2], 0, pc[0], 0, 1, 0, pc[1], -pc[0], 0, 0, 0, 1};
             double* J = P.jac + 29 * (size_t)e;
-#pragma unroll
-            for (int r = 0; r < 2; ++r)
-#pragma unroll
-                for (int cc = 0; cc < 6; ++cc) {
-                    J[6 * r + cc] = PJ[3 * r] * Dc[cc] + PJ[3 * r + 1] * Dc[6 + cc] + PJ[3 * r + 2] * Dc[12 + cc];            // Jc
-                    J[12 + 6 * r + cc] = PR[3 * r] * Dw[cc] + PR[3 * r + 1] * Dw[6 + cc] + PR[3 * r + 2] * Dw[12 + cc];       // Jo
-                }
+            edge_jacobian(P, e, P.cam[P.pair_cam[P.edge_pair[e]]], pw, pc, J);
             const double* I = P.edge_info + 3 * e;
             J[24] = w * I[0]; J[25] = w * I[1]; J[26] = w * I[2];
             J[27] = -(I[0] * er[0] + I[1] * er[1]) * w;

@@ -54,5 +54,8 @@ int launch_pose_cov_pairs(const void* problems_dev, int n_problems, int max_pair
 // scratch per problem (2.4 MB at 64), mirrored by the arena's pinned host copy.
 constexpr int POSE_COV_GRAPH_MAX_OBJ = 64;
 int launch_pose_cov_graph(const void* problems_dev, int n_problems, int max_free_obj, int max_cam, int max_pairs, hipStream_t s);
+// ---- per-edge leverages, studentised residuals and the chi2 scale (csrc/resid_stats.hip): behind the covariance kernels of every form and the pair kernel, the
+// problems staged with stage_problems(..., resid = true) and their own (camera, object) pairs as cpair_a / cpair_b; an edge kernel and a reduction, two launches
+int launch_resid_stats(const void* problems_dev, const void* rs_dev /* RsProblem [n_problems] */, int n_problems, int max_edges, int max_vertices, hipStream_t s);
 int launch_debug_cholesky(const double* A, const double* b, int ns, double* x, int* ok, hipStream_t s);
 }  // namespace suo

@@ -1,6 +1,6 @@
 // Host-buffer entry points of the pose covariances (include/suo_hip.h: suo_pose_covariances / suo_pose_covariances_pairs / suo_pose_covariances_graph and their batch
 // forms): staged through the arena of suo_optimize_batch (csrc/ba_stage.hip), one H2D, the kernels of csrc/pose_cov.hip and csrc/pose_cov_graph.hip, one D2H of the
-// blocks.  The caller's problem is read only.
+// blocks.  The caller's problem is read only.  suo_residual_statistics goes the same way with csrc/resid_stats.hip behind the covariance kernels.
 #include <string.h>
 
 #include <algorithm>
@@ -102,7 +102,95 @@ static int cov_batch(const suo_ba_problem* probs, int n_prob, double* const* cam
     return SUO_OK;
 }
 
+// suo_residual_statistics: the graph entry's plan, staging and launches, asked for the cross blocks of every problem's own (camera, object) pairs -- in the order
+// prep_problem deals them (by camera, then by object), so that pair p of the staged problem is pair p of the request -- and csrc/resid_stats.hip behind them.
+// Forms 0 and 1 couple nothing (Sigma_co = 0): they get no pairs.
+struct ResidOut {
+    double* const* cam_cov; double* const* obj_cov; double* const* chi2; double* const* pcov; double* const* lev; double* const* t; double* const* cam_stat;
+    double* const* obj_stat; double* summary; int* status;
+};
+static int resid_batch(const suo_ba_problem* probs, int n_prob, const ResidOut& out) {
+    const char* who = "suo_residual_statistics";
+    CovPlan plan;
+    int rc = plan_cov_batch(probs, n_prob, plan, true);
+    if (rc != SUO_OK) return rc;
+    std::vector<std::vector<int32_t>> pa(n_prob), pb(n_prob);
+    std::vector<int> np(n_prob, 0);
+    std::vector<const int32_t*> pa_ptr(n_prob), pb_ptr(n_prob);
+    int max_pairs = 0, max_edges = 0, max_vertices = 0;
+    for (int i = 0; i < n_prob; ++i) {
+        const suo_ba_problem& q = probs[i];
+        max_edges = std::max(max_edges, q.n_edge);
+        max_vertices = std::max(max_vertices, q.n_cam + q.n_obj);
+        if (plan.form[i] >= 2) {
+            if (q.n_edge > 0 && (!q.edge_cam || !q.edge_obj)) { suo_set_error("%s: null edge lists in problem %d", who, i); return SUO_ERR_ARG; }
+            std::vector<uint8_t> seen((size_t)q.n_cam * q.n_obj, 0);
+            for (int e = 0; e < q.n_edge; ++e) {
+                if (q.edge_cam[e] < 0 || q.edge_cam[e] >= q.n_cam || q.edge_obj[e] < 0 || q.edge_obj[e] >= q.n_obj) {
+                    suo_set_error("%s: edge %d of problem %d references a missing vertex", who, e, i);
+                    return SUO_ERR_ARG;
+                }
+                seen[(size_t)q.edge_cam[e] * q.n_obj + q.edge_obj[e]] = 1;
+            }
+            for (int c = 0; c < q.n_cam; ++c)
+                for (int o = 0; o < q.n_obj; ++o)
+                    if (seen[(size_t)c * q.n_obj + o]) { pa[i].push_back(c); pb[i].push_back(q.n_cam + o); }
+        }
+        np[i] = (int)pa[i].size(); pa_ptr[i] = pa[i].data(); pb_ptr[i] = pb[i].data();
+        max_pairs = std::max(max_pairs, np[i]);
+    }
+    const CovPairs pairs{np.data(), pa_ptr.data(), pb_ptr.data()};
+    std::lock_guard<std::mutex> lock(g_arena.mu);
+    Staged st;
+    rc = stage_problems(probs, n_prob, g_arena, st, who, plan.form.data(), &pairs, true);
+    if (rc != SUO_OK) return rc;
+    const void* P = g_arena.dev + st.o_structs;
+    hipStream_t s = g_arena.stream;
+    if (plan.diag) { rc = launch_pose_cov_diag(P, n_prob, s); if (rc != SUO_OK) return rc; }
+    if (plan.coupled) { rc = launch_pose_cov_coupled(P, n_prob, plan.max_free_obj, s, true); if (rc != SUO_OK) return rc; }
+    if (plan.graph) { rc = launch_pose_cov_graph(P, n_prob, plan.graph_free_obj, plan.graph_cam, max_pairs, s); if (rc != SUO_OK) return rc; }
+    if (max_pairs > 0) { rc = launch_pose_cov_pairs(P, n_prob, max_pairs, s); if (rc != SUO_OK) return rc; }
+    rc = launch_resid_stats(P, g_arena.dev + st.o_rs, n_prob, max_edges, max_vertices, s);
+    if (rc != SUO_OK) return rc;
+    SUO_HIP_CHECK(hipMemcpyAsync(g_arena.host + st.cov_begin, g_arena.dev + st.cov_begin, st.cov_end - st.cov_begin, hipMemcpyDeviceToHost, s));
+    SUO_HIP_CHECK(hipStreamSynchronize(s));
+    auto member = [&](double* const* list, int i) { return list ? list[i] : nullptr; };
+    for (int i = 0; i < n_prob; ++i) {
+        const LmProblem& S = st.prep[i].S;
+        const RsProblem& R = st.prep[i].R;
+        const size_t E = S.n_edge, C = S.n_cam, O = S.n_obj;
+        if (double* d = member(out.cam_cov, i)) memcpy(d, g_arena.mirror(S.cam_cov), sizeof(double) * 36 * C);
+        if (double* d = member(out.obj_cov, i)) memcpy(d, g_arena.mirror(S.obj_cov), sizeof(double) * 36 * O);
+        if (double* d = member(out.chi2, i)) memcpy(d, g_arena.mirror(R.chi2), sizeof(double) * E);
+        if (double* d = member(out.pcov, i)) memcpy(d, g_arena.mirror(R.pcov), sizeof(double) * 3 * E);
+        if (double* d = member(out.lev, i)) memcpy(d, g_arena.mirror(R.lev), sizeof(double) * E);
+        if (double* d = member(out.t, i)) memcpy(d, g_arena.mirror(R.t), sizeof(double) * E);
+        if (double* d = member(out.cam_stat, i)) memcpy(d, g_arena.mirror(R.vstat), sizeof(double) * 3 * C);
+        if (double* d = member(out.obj_stat, i)) memcpy(d, g_arena.mirror(R.vstat) + 3 * C, sizeof(double) * 3 * O);
+        if (out.summary) memcpy(out.summary + 6 * (size_t)i, g_arena.mirror(R.summary), sizeof(double) * 6);
+        if (out.status) {
+            memcpy(out.status + 4 * (size_t)i, g_arena.mirror(S.cov_status), sizeof(int) * 2);
+            memcpy(out.status + 4 * (size_t)i + 2, g_arena.mirror(R.status), sizeof(int) * 2);
+        }
+    }
+    return SUO_OK;
+}
+
 extern "C" {
+
+int suo_residual_statistics_batch(const suo_ba_problem* probs, int n_prob, double* const* cam_cov, double* const* obj_cov, double* const* edge_chi2,
+                                  double* const* edge_pcov, double* const* edge_lev, double* const* edge_t, double* const* cam_stat, double* const* obj_stat,
+                                  double* summary, int* status) {
+    if (n_prob <= 0) return SUO_OK;
+    if (!probs) { suo_set_error("suo_residual_statistics_batch: null argument"); return SUO_ERR_ARG; }
+    return resid_batch(probs, n_prob, ResidOut{cam_cov, obj_cov, edge_chi2, edge_pcov, edge_lev, edge_t, cam_stat, obj_stat, summary, status});
+}
+
+int suo_residual_statistics(const suo_ba_problem* problem, double* cam_cov, double* obj_cov, double* edge_chi2, double* edge_pcov, double* edge_lev, double* edge_t,
+                            double* cam_stat, double* obj_stat, double* summary, int* status) {
+    if (!problem) { suo_set_error("suo_residual_statistics: null argument"); return SUO_ERR_ARG; }
+    return suo_residual_statistics_batch(problem, 1, &cam_cov, &obj_cov, &edge_chi2, &edge_pcov, &edge_lev, &edge_t, &cam_stat, &obj_stat, summary, status);
+}
 
 int suo_pose_covariances_batch(const suo_ba_problem* probs, int n_prob, double* const* cam_cov, double* const* obj_cov, int* status) {
     if (n_prob <= 0) return SUO_OK;

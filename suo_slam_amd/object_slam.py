@@ -686,7 +686,7 @@ class ObjectSLAM(DeviceRoutes):
         self._cull_after_optimize(list(obj_index.keys()), curr_only, view_curr)
 
     @_on_stream
-    def pose_covariances(self, view_ids=None, relative=False, trajectory=False):
+    def pose_covariances(self, view_ids=None, relative=False, trajectory=False, scaled=False):
         """6x6 marginal covariances of the current map: {"cams": {view_id: 6x6}, "objs": {obj_id: 6x6}} for every key of cam_poses (or those in view_ids) and
         obj_poses, from the global graph of build_problem() at the stored poses and inlier flags (ba.pose_covariances: rows / columns [omega, upsilon] of the
         left update; zeros for the gauge camera, NaNs for a vertex no counted measurement reaches).  These blocks are relative to the gauge camera.
@@ -694,7 +694,9 @@ class ObjectSLAM(DeviceRoutes):
         collect_results reports, which does not depend on the gauge.  trajectory=True adds "rel_cams": {(view_a, view_b): 6x6} for consecutive selected views in
         cam_poses order: the covariance of T_b T_a^-1, the motion between the two views (NaN where a view is not in the graph).  One device call
         (ba.pose_covariances_graph: any number of objects up to its cap; the bits of ba.pose_covariances / ba.pose_covariances_pairs wherever those answer).
-        Changes nothing in the map."""
+        scaled=True multiplies every returned block by the chi2 scale s0^2 of the same graph (residual_statistics()["summary"]["s0_sq"]) and adds
+        "variance_factor": NaN, and with it every block, when the graph has no redundancy (dof <= 0) or does not build.  Without it the blocks are the
+        covariance under the stated information matrices.  Changes nothing in the map."""
         nan = np.full((6, 6), np.nan)
         cams = {v: nan.copy() for v in self.cam_poses if view_ids is None or v in view_ids}
         objs = {o: nan.copy() for o in self.obj_poses}
@@ -724,7 +726,48 @@ class ObjectSLAM(DeviceRoutes):
             if built is not None:
                 for k, S6 in zip(steps, rel_cov[len(keys):]):
                     out["rel_cams"][k] = S6.copy()
+        if scaled:
+            s0_sq = float(_ba.residual_statistics_batch([prob])[0]["summary"][5]) if built is not None else float("nan")
+            for blocks in out.values():
+                for k in blocks:
+                    blocks[k] = blocks[k] * s0_sq
+            out["variance_factor"] = s0_sq
         return out
+
+    @_on_stream
+    def residual_statistics(self, view_ids=None):
+        """How well the measurements of the current map agree with its poses, from the global graph of build_problem() at the stored poses and inlier flags
+        (ba.residual_statistics; include/suo_hip.h: suo_residual_statistics):
+          "summary"  {"m": counted keypoints, "n": rows of the Hessian, "chi2": their sum of v^T Omega v, "leverage": their sum of leverages (= n), "dof": 2 m - n,
+                      "s0_sq": chi2 / dof, the factor pose_covariances(scaled=True) applies; NaN without redundancy, "status": the entry's four counts}
+          "cams"     {view_id: (count, chi2, redundancy)} over the view's counted keypoints, for every key of cam_poses (or those in view_ids); "objs" {obj_id: ...}
+                     likewise for every key of obj_poses.  chi2 / redundancy is the vertex's variance component; (0, 0.0, 0.0) for a vertex outside the graph.
+          "edges"    {(view_id, obj_id): {"chi2", "leverage", "t"}}, one array entry per keypoint of the detection in its stored order (apply_problem's book-keeping):
+                     t is the studentised statistic, chi2(2) under the model whether the keypoint is counted or not; NaN where it cannot be checked.
+        Changes nothing in the map."""
+        cams = {v: (0, 0.0, 0.0) for v in self.cam_poses if view_ids is None or v in view_ids}
+        objs = {o: (0, 0.0, 0.0) for o in self.obj_poses}
+        nan = float("nan")
+        summary = {"m": 0, "n": 0, "chi2": 0.0, "leverage": 0.0, "dof": 0, "s0_sq": nan, "status": [0, 0, 0, 0]}
+        edges = {}
+        built = self.build_problem(False)
+        if built is not None:
+            prob, (cam_index, obj_index, e_ref, _, _) = built
+            r = _ba.residual_statistics_batch([prob])[0]
+            s = r["summary"]
+            summary = {"m": int(s[0]), "n": int(s[1]), "chi2": float(s[2]), "leverage": float(s[3]), "dof": int(s[4]), "s0_sq": float(s[5]),
+                       "status": [int(x) for x in r["status"]]}
+            triple = lambda row: (int(row[0]), float(row[1]), float(row[2]))
+            for v, i in cam_index.items():
+                if v in cams:
+                    cams[v] = triple(r["cam_stat"][i])
+            for o, j in obj_index.items():
+                objs[o] = triple(r["obj_stat"][j])
+            for v, o, first, n in e_ref.segs:
+                if v in cams:
+                    edges[(v, o)] = {"chi2": r["edge_chi2"][first:first + n].copy(), "leverage": r["edge_lev"][first:first + n].copy(),
+                                     "t": r["edge_t"][first:first + n].copy()}
+        return {"summary": summary, "cams": cams, "objs": objs, "edges": edges}
 
     @_on_stream
     def optimize(self, curr_only=False):
