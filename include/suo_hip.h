@@ -603,6 +603,41 @@ int suo_residual_statistics_batch(const suo_ba_problem* problems, int n, double*
                                   double* const* edge_pcov, double* const* edge_lev, double* const* edge_t, double* const* cam_stat, double* const* obj_stat,
                                   double* summary /*[n][6]*/, int* status /*[n][4]*/);
 
+/* ---- covariance of a tracked camera with the map's uncertainty carried in ------------------------------------------------------------
+ * For the camera-tracking graph (every object fixed at its map pose) suo_pose_covariances reports Hcc^-1: the covariance of a camera tracked against a perfectly
+ * known map.  The map has a covariance of its own, Sigma_OO (suo_pose_covariances_graph reports it), and the tracker does not estimate it: it "considers" it.
+ * The covariance of what the tracker actually computes is the Schmidt consider covariance
+ *     P_c = Hcc^-1 + G Sigma_OO G^T,    G = Hcc^-1 [B_c1 ... B_cn],    B_co = sum over the counted edges e of (c, o) of J_c^T Omega J_o
+ * with the Jacobians, the perturbation (left update exp(delta) * T, delta = [omega, upsilon]) and Ad(T) of the blocks above.
+ *   Problem.     Every object is fixed; a free object is SUO_ERR_ARG and nothing is launched.  Any number of cameras: they are independent of each other here.
+ *                n_obj <= SUO_POSE_COV_GRAPH_MAX_OBJ; more is SUO_ERR_ARG naming the count.
+ *   map_cov      [6 n_obj][6 n_obj] row-major: the covariance of the stacked object perturbations in the problem's object order -- the objects' diagonal blocks and
+ *                (object a, object b) cross blocks of suo_pose_covariances_graph.  Only the upper triangle with the diagonal is read, and mirrored; the lower
+ *                triangle is ignored.  An object whose diagonal block has NaN at its (0, 0) entry is "not in the map": its edges are not counted, its cross and rel
+ *                blocks are 36 NaNs, no other entry of its rows and columns is read, and status[1] counts it.  An object first initialised from this very view is
+ *                not independent of the view's measurements and is excluded this way.  map_cov must not contain the measurements of the problem's own edges.
+ *   Counted.     An edge is counted when edge_inlier == 1, its camera is free and its object is in the map.  No Huber weight, no lambda.
+ * Per camera c, every block 36 row-major doubles:
+ *   fixed_map_cov [n_cam][36]         Hcc^-1.  With every object in the map this is cam_cov of suo_pose_covariances on the same problem, bit for bit.
+ *   cam_cov       [n_cam][36]         P_c, exactly symmetric.
+ *   cross         [n_cam][n_obj][36]  Sigma_co = -(G Sigma_OO)[:, o]: rows are the camera, columns the object.  Dense: also for objects the camera does not see.
+ *   rel           [n_cam][n_obj][36]  the covariance of T_OtoC = T_c T_o:  P_c + A Sigma_oo A^T + Sigma_co A^T + A Sigma_oc,  A = Ad(T_c).  Exactly symmetric.
+ *   - A fixed camera: cam_cov, fixed_map_cov and cross are zeros and rel = A Sigma_oo A^T.
+ *   - A free camera without a counted edge, or whose Hcc meets a non-positive pivot: every block of that camera is NaN; status[0] counts such cameras.  The call
+ *     never faults and never loops on one.
+ *   - The chi2 scale is not applied.
+ * Host buffers, blocking, staged through the arena of suo_optimize_batch; the problem is not modified.  Every output pointer may be NULL.  status [2] = NaN cameras,
+ * objects not in the map.  The batch form takes one pointer per problem and status [n][2]; a problem's bits do not depend on the rest of the batch, and two calls give
+ * the same bits.  Kernels (fp64, fixed summation order, vector stores only, no atomics): Hcc^-1 by the camera form of csrc/pose_cov.hip; then csrc/track_cov.hip,
+ * one workgroup per (problem, camera): a thread per object sums B_co over the pair's edges in ascending edge index, G (6 x 6 n_obj) lives in LDS, Z = G Sigma_OO is
+ * a thread per column accumulating in ascending row of Sigma_OO, which is read once per camera from device memory, Z G^T is a fixed tree per entry; cross is -Z
+ * written out and rel follows per object. */
+int suo_tracking_covariances(const suo_ba_problem* problem, const double* map_cov /*[6 n_obj][6 n_obj]*/, double* cam_cov /*[n_cam][36]*/,
+                             double* fixed_map_cov /*[n_cam][36]*/, double* cross /*[n_cam][n_obj][36]*/, double* rel /*[n_cam][n_obj][36]*/,
+                             int* status /*[2]: NaN cameras, objects not in the map*/);
+int suo_tracking_covariances_batch(const suo_ba_problem* problems, int n, const double* const* map_cov, double* const* cam_cov, double* const* fixed_map_cov,
+                                   double* const* cross, double* const* rel, int* status /*[n][2]*/);
+
 /* ---- phase-wise bundle adjustment for the multi-GPU global pose graph ------------------------
  * Cameras are partitioned across GPUs; each rank builds a context over ITS cameras' edges and ALL objects, and
  * a host driver (suo_slam_amd/ba_dist.py) runs g2o's LM schedule with two all-reduces per trial (RCCL):

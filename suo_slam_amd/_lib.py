@@ -145,6 +145,8 @@ SIGNATURES = {
     "suo_pose_covariances_graph_batch": (C.c_int, [VP, C.c_int, VP, VP, VP, VP, VP, VP, VP, VP]),
     "suo_residual_statistics": (C.c_int, [VP] * 11),
     "suo_residual_statistics_batch": (C.c_int, [VP, C.c_int] + [VP] * 10),
+    "suo_tracking_covariances": (C.c_int, [VP] * 7),
+    "suo_tracking_covariances_batch": (C.c_int, [VP, C.c_int] + [VP] * 6),
     "suo_frame_geom_covariances": (C.c_int, [VP, VP]),
     "suo_frame_geom_create": (C.c_int, [C.c_int, C.c_int, C.POINTER(VP)]),
     "suo_frame_geom_destroy": (None, [VP]),

@@ -157,6 +157,48 @@ def pose_covariances_graph(*args, pairs, **kw):
     return pose_covariances_graph_batch([Problem(*args, **kw)], [pairs])[0]
 
 
+TRACK_KEYS = ("cam_cov", "fixed_map_cov", "cross", "rel")
+
+
+def tracking_covariances_batch(problems, map_covs):
+    """The covariance of every tracked camera of each Problem with the map's uncertainty carried in (include/suo_hip.h: suo_tracking_covariances).  Every object
+    of a Problem is fixed (the curr_only graph); map_covs[i] [6 O, 6 O] is the covariance of its stacked object perturbations, e.g. assembled from
+    pose_covariances_graph -- only the upper triangle is read, and an object whose block starts with NaN is not in the map.  Per problem a dict: cam_cov [C,6,6] =
+    Hcc^-1 + G Sigma G^T, fixed_map_cov [C,6,6] = Hcc^-1 (pose_covariances' camera blocks, bit for bit, when every object is in the map), cross [C,O,6,6] = Sigma_co
+    (rows the camera), rel [C,O,6,6] = the covariance of T_c T_o, status [2] = NaN cameras, objects not in the map.  One call for the whole list; the problems are
+    not modified."""
+    if not problems:
+        return []
+    if len(map_covs) != len(problems):
+        raise ValueError("tracking_covariances_batch: one map covariance per problem")
+    lib = _lib.lib()
+    _lib.require_gpu()
+    n = len(problems)
+    arr = (_lib.BaProblem * n)()
+    ptrs = [(C.c_void_p * n)() for _ in range(5)]           # map_cov, cam_cov, fixed_map_cov, cross, rel
+    status = np.zeros((n, 2), np.int32)
+    out, keep = [], []
+    for i, (s, p, m) in enumerate(zip(arr, problems, map_covs)):
+        p._fill(s)
+        nc, no = len(p.cam_T), len(p.obj_T)
+        m = np.ascontiguousarray(m, np.float64)
+        if m.shape != (6 * no, 6 * no):
+            raise ValueError(f"tracking_covariances_batch: problem {i}: map covariance of shape {m.shape}, expected {(6 * no, 6 * no)}")
+        bufs = (m, np.zeros((nc, 6, 6)), np.zeros((nc, 6, 6)), np.zeros((nc, no, 6, 6)), np.zeros((nc, no, 6, 6)))
+        for col, buf in zip(ptrs, bufs):
+            col[i] = buf.ctypes.data
+        keep.append(m)
+        out.append(dict(zip(TRACK_KEYS, bufs[1:]), status=status[i]))
+    _lib.check(lib.suo_tracking_covariances_batch(C.cast(arr, C.c_void_p), n, *[C.cast(c, C.c_void_p) for c in ptrs], status.ctypes.data),
+               "suo_tracking_covariances_batch")
+    return out
+
+
+def tracking_covariances(*args, map_cov, **kw):
+    """The arguments of optimize() plus map_cov [6 O, 6 O]; returns the dict of tracking_covariances_batch at the poses and inlier flags given."""
+    return tracking_covariances_batch([Problem(*args, **kw)], [map_cov])[0]
+
+
 RESID_KEYS = ("cam_cov", "obj_cov", "edge_chi2", "edge_pcov", "edge_lev", "edge_t", "cam_stat", "obj_stat")
 
 

@@ -37,6 +37,7 @@ struct Staged {
     std::vector<Prep> prep;
     size_t o_structs = 0, o_rs = 0, in_end = 0, out_end = 0, total = 0;      // arena: [LmProblem structs | inputs | in_end: outputs | out_end: scratch | total]
     size_t cov_begin = 0, cov_end = 0;                             // inside the scratch: every problem's cam_cov / obj_cov / cov_status / cov_cross / cov_rel (csrc/pose_cov_api.hip reads them back)
+    size_t o_extra = 0;                                            // stage_problems(..., extra): that many bytes behind the scratch, the caller's to lay out (csrc/track_cov_api.hip)
 };
 
 // `who`: the entry the caller called, for the error texts.  prep_problem is the host half of stage_problems (validation, stable sort by pair, pair CSR).
@@ -44,8 +45,9 @@ int prep_problem(const suo_ba_problem& q, int index, Prep& P, const char* who);
 // cov_form (optional, [n_prob]): LmProblem::cov_form of every problem (csrc/pose_cov_api.hip: plan_cov_batch); pairs (optional): its vertex pairs
 struct CovPairs { const int* n; const int32_t* const* a; const int32_t* const* b; };      // per problem: the count and the two index lists
 // resid: also the arrays of suo_residual_statistics (one RsProblem per problem at o_rs), its outputs inside [cov_begin, cov_end); without it they take no room
+// extra: bytes reserved at Staged::o_extra, neither filled nor copied here
 int stage_problems(const suo_ba_problem* probs, int n_prob, Arena& A, Staged& st, const char* who, const int* cov_form = nullptr, const CovPairs* pairs = nullptr,
-                   bool resid = false);
+                   bool resid = false, size_t extra = 0);
 int fetch_results(suo_ba_problem* probs, int n_prob, Arena& A, Staged& st);
 
 }  // namespace suo

@@ -74,7 +74,7 @@ int prep_problem(const suo_ba_problem& q, int index, Prep& P, const char* who) {
 
 // The arena layout of a batch, every array on a 16-byte boundary: the structs, then every problem's inputs (one H2D up to in_end), then the outputs that are not
 // inputs too (one D2H up to out_end), then device-only scratch.  Each Prep::S gets its sizes and its addresses, counted from `base`.
-static void lay_out(const suo_ba_problem* probs, int n_prob, const int* cov_form, const CovPairs* pairs, bool resid, char* base, Staged& st) {
+static void lay_out(const suo_ba_problem* probs, int n_prob, const int* cov_form, const CovPairs* pairs, bool resid, size_t extra, char* base, Staged& st) {
     Layout L;
     auto put = [&](auto*& p, size_t n) { p = (std::remove_reference_t<decltype(p)>)((uintptr_t)base + L.take(sizeof(*p) * n)); };
     st.o_structs = L.take(sizeof(LmProblem) * (size_t)n_prob);
@@ -124,20 +124,22 @@ static void lay_out(const suo_ba_problem* probs, int n_prob, const int* cov_form
         for (int o = 0; o < S.n_obj; ++o) nsm += probs[i].obj_fixed[o] ? 0 : 6;
         put(S.cov_S, nsm * (nsm + 1)); put(S.cov_Sinv, nsm * nsm); put(S.cov_Z, 6 * (size_t)S.n_cam * nsm); put(S.cov_hdr, 2 + (size_t)S.n_obj);
     }
+    st.o_extra = L.take(extra);
     st.total = L.off;
 }
 
 // host prep + arena layout + H2D of one batch of problems
-int stage_problems(const suo_ba_problem* probs, int n_prob, Arena& A, Staged& st, const char* who, const int* cov_form, const CovPairs* pairs, bool resid) {
+int stage_problems(const suo_ba_problem* probs, int n_prob, Arena& A, Staged& st, const char* who, const int* cov_form, const CovPairs* pairs, bool resid,
+                   size_t extra) {
     st.prep.assign(n_prob, Prep());
     for (int i = 0; i < n_prob; ++i) {
         int rc = prep_problem(probs[i], i, st.prep[i], who);
         if (rc != SUO_OK) return rc;
     }
-    lay_out(probs, n_prob, cov_form, pairs, resid, nullptr, st);          // sizes first: the arena may move when it grows
+    lay_out(probs, n_prob, cov_form, pairs, resid, extra, nullptr, st);          // sizes first: the arena may move when it grows
     int rc = A.ensure(st.total);
     if (rc != SUO_OK) return rc;
-    lay_out(probs, n_prob, cov_form, pairs, resid, A.dev, st);
+    lay_out(probs, n_prob, cov_form, pairs, resid, extra, A.dev, st);
     for (int i = 0; i < n_prob; ++i) {
         const suo_ba_problem& q = probs[i];
         Prep& P = st.prep[i];

@@ -317,25 +317,6 @@ __global__ __launch_bounds__(LM_THREADS) void pose_cov_coupled_kernel(const LmPr
     }
 }
 
-// row r of Ad(T) = [[R, 0], [[t]x R, R]] of the pose T (row-major 3x4), or of Ad(T^-1) (R^T, -R^T t)
-DEV void pc_ad_row(const double* T, bool inverse, int r, double (&row)[6]) {
-    double R[9], t[3];
-#pragma unroll
-    for (int i = 0; i < 3; ++i) {
-#pragma unroll
-        for (int j = 0; j < 3; ++j) R[3 * i + j] = inverse ? T[4 * j + i] : T[4 * i + j];
-    }
-#pragma unroll
-    for (int i = 0; i < 3; ++i) t[i] = inverse ? -(T[i] * T[3] + T[4 + i] * T[7] + T[8 + i] * T[11]) : T[4 * i + 3];
-    const int i = r % 3, i1 = (i + 1) % 3, i2 = (i + 2) % 3;
-#pragma unroll
-    for (int j = 0; j < 3; ++j) {
-        const double tx = t[i1] * R[3 * i2 + j] - t[i2] * R[3 * i1 + j];     // ([t]x R)[i][j]
-        row[j] = r < 3 ? R[3 * i + j] : tx;
-        row[3 + j] = r < 3 ? 0.0 : R[3 * i + j];
-    }
-}
-
 // entry (r, c) of  Scc + A Soo A^T + Sco A^T + A Sco^T  (S1 = Scc, S2 = Soo, X = Sigma_co or, x_transposed, Sigma_oc)  or, obj_obj, of
 // A (Saa + Sbb - Sab - Sab^T) A^T  (S1 = Saa, S2 = Sbb, X = Sigma_ab); Ar / Ac: rows r and c of A; X == nullptr: a cross block of zeros.  x_negated: the
 // first form with -X, which is the (camera a, camera b) pair's  Sbb + A Saa A^T - Sba A^T - A Sab  (S1 = Sbb, S2 = Saa, X = Sigma_ab, x_transposed)

@@ -6,6 +6,26 @@
 
 namespace suo {
 
+// row r of Ad(T) = [[R, 0], [[t]x R, R]] of the pose T (row-major 3x4), or of Ad(T^-1) (R^T, -R^T t); the pair kernel of csrc/pose_cov.hip and
+// csrc/track_cov.hip propagate with it
+DEV void pc_ad_row(const double* T, bool inverse, int r, double (&row)[6]) {
+    double R[9], t[3];
+#pragma unroll
+    for (int i = 0; i < 3; ++i) {
+#pragma unroll
+        for (int j = 0; j < 3; ++j) R[3 * i + j] = inverse ? T[4 * j + i] : T[4 * i + j];
+    }
+#pragma unroll
+    for (int i = 0; i < 3; ++i) t[i] = inverse ? -(T[i] * T[3] + T[4 + i] * T[7] + T[8 + i] * T[11]) : T[4 * i + 3];
+    const int i = r % 3, i1 = (i + 1) % 3, i2 = (i + 2) % 3;
+#pragma unroll
+    for (int j = 0; j < 3; ++j) {
+        const double tx = t[i1] * R[3 * i2 + j] - t[i2] * R[3 * i1 + j];     // ([t]x R)[i][j]
+        row[j] = r < 3 ? R[3 * i + j] : tx;
+        row[3 + j] = r < 3 ? 0.0 : R[3 * i + j];
+    }
+}
+
 DEV bool pc_cam_in(const LmProblem& P, int c) { return !P.cam_fixed[c] && P.xc[6 * c] > 0; }
 
 // Linearises at the state the problem holds, sums Hcc / Hoo per vertex, marks the vertices a counted edge reaches (xc / xo [6 v]), deals the slots of the reduced

@@ -607,18 +607,22 @@ class ObjectSLAM(DeviceRoutes):
         self.view_ids.append(view_id)
 
     # ---------------------------------------------------------------------------------------------
-    def build_problem(self, curr_only=False):
+    def build_problem(self, curr_only=False, view=None, exclude_views=()):
         """Graph construction of optimize() (object_slam.py:713-839) as a flat SoA for suo_optimize.
-        Returns (problem, bookkeeping) or None when the reference would return early."""
+        Returns (problem, bookkeeping) or None when the reference would return early.
+        view: the view whose curr_only graph is built (default: the last one).  exclude_views: views whose cameras and detections the global graph leaves out
+        (map_covariance); the gauge is then the first camera that remains.  The defaults give the graphs optimize() runs."""
         if len(self.view_ids) == 0:
             return None
         num_cam_edges, num_obj_edges = defaultdict(int), defaultdict(int)
         obj_ids = list(self.obj_poses.keys())
-        view_curr = self.view_ids[-1]
+        view_curr = self.view_ids[-1] if view is None else view
         if curr_only:
-            if view_curr not in self.cam_poses:
+            if view_curr not in self.cam_poses or view_curr not in self.detections:
                 return None
             dets = {view_curr: self.detections[view_curr]}
+        elif exclude_views:
+            dets = {v: d for v, d in self.detections.items() if v not in exclude_views}
         else:
             dets = self.detections
         for v, det in dets.items():
@@ -631,7 +635,7 @@ class ObjectSLAM(DeviceRoutes):
         if curr_only and num_cam_edges[view_curr] < 3:
             return None
         obj_index = {o: j for j, o in enumerate(o for o in obj_ids if num_obj_edges[o] > 0)}
-        cam_views = [view_curr] if curr_only else list(self.cam_poses.keys())
+        cam_views = [view_curr] if curr_only else [v for v in self.cam_poses.keys() if v not in exclude_views]
         cam_index, cam_fixed = {}, []
         for i, v in enumerate(cam_views):
             if num_cam_edges[v] > 0:
@@ -732,6 +736,65 @@ class ObjectSLAM(DeviceRoutes):
                 for k in blocks:
                     blocks[k] = blocks[k] * s0_sq
             out["variance_factor"] = s0_sq
+        return out
+
+    @_on_stream
+    def map_covariance(self, exclude_views=()):
+        """(obj_ids, Sigma_OO): the joint covariance [6 n, 6 n] of every object of obj_poses, in that order, from the global graph of build_problem() without the
+        cameras and detections of exclude_views, at the stored poses and inlier flags -- the objects' blocks and every (object, object) cross block of
+        ba.pose_covariances_graph, assembled dense (rows / columns [omega, upsilon] of the left update, relative to the gauge camera).  The rows and columns of an
+        object that graph does not reach are NaN: tracking_covariance() treats it as not in the map.  Changes nothing in the map."""
+        obj_ids = list(self.obj_poses.keys())
+        Sigma = np.full((6 * len(obj_ids), 6 * len(obj_ids)), np.nan)
+        built = self.build_problem(False, exclude_views=tuple(exclude_views))
+        if built is not None:
+            prob, (cam_index, obj_index, _, _, _) = built
+            nc, objs = len(cam_index), list(obj_index)
+            pairs = [(nc + obj_index[a], nc + obj_index[b]) for i, a in enumerate(objs) for b in objs[i + 1:]]
+            _, obj_cov, cross, _, _ = _ba.pose_covariances_graph_batch([prob], [np.array(pairs, np.int32).reshape(-1, 2)])[0]
+            at = {o: 6 * i for i, o in enumerate(obj_ids)}
+            for o, j in obj_index.items():
+                Sigma[at[o]:at[o] + 6, at[o]:at[o] + 6] = obj_cov[j]
+            for (ja, jb), X in zip(pairs, cross):
+                a, b = at[objs[ja - nc]], at[objs[jb - nc]]
+                Sigma[a:a + 6, b:b + 6] = X
+                Sigma[b:b + 6, a:a + 6] = X.T
+        return obj_ids, Sigma
+
+    @_on_stream
+    def tracking_covariance(self, view_id=None, map_cov=None):
+        """The covariance of a tracked camera with the map's uncertainty carried in (ba.tracking_covariances; include/suo_hip.h: suo_tracking_covariances), from the
+        curr_only graph of view_id (default: the last view) at the stored poses and inlier flags:
+          "cam"            6x6, Hcc^-1 + G Sigma_OO G^T: the covariance of the camera as the tracker estimates it, against objects it holds at their map poses
+          "cam_fixed_map"  6x6, Hcc^-1: what pose tracking against a perfectly known map would give (ba.pose_covariances of the same graph)
+          "cross"          {obj_id: 6x6} Sigma_co, rows the camera; "rel" {obj_id: 6x6} the covariance of T_OtoC = T_GtoC T_OtoG, for every object of that graph
+          "status"         [NaN cameras, objects of the graph that are not in the map]
+        map_cov is the pair map_covariance() returns.  ASSUMPTION: it must not contain this view's measurements -- the formula takes the map's errors and the view's
+        keypoint noise as independent.  None computes map_covariance(exclude_views=(view_id,)), which rebuilds the global graph; the intended use is to call
+        map_covariance() once after a global adjustment and to pass it for the views that follow until the next one.  An object the map covariance does not hold
+        (NaN block, or missing from its obj_ids: e.g. first initialised from this very view) is left out: its keypoints are not counted and its blocks are NaN.
+        Every block is NaN when the view has no curr_only graph.  Changes nothing in the map."""
+        view = self.view_ids[-1] if view_id is None and self.view_ids else view_id
+        nan = np.full((6, 6), np.nan)
+        out = {"cam": nan.copy(), "cam_fixed_map": nan.copy(), "cross": {}, "rel": {}, "status": [1, 0]}
+        built = self.build_problem(True, view=view) if self.view_ids else None
+        if built is None:
+            return out
+        prob, (_, obj_index, _, _, _) = built
+        obj_ids, Sigma = self.map_covariance(exclude_views=(view,)) if map_cov is None else map_cov
+        objs = list(obj_index)
+        sub = np.full((6 * len(objs), 6 * len(objs)), np.nan)
+        rows = {o: 6 * i for i, o in enumerate(obj_ids)}
+        have = [j for j, o in enumerate(objs) if o in rows]
+        if have:
+            src = np.concatenate([np.arange(rows[objs[j]], rows[objs[j]] + 6) for j in have])
+            dst = np.concatenate([np.arange(6 * j, 6 * j + 6) for j in have])
+            sub[np.ix_(dst, dst)] = np.asarray(Sigma)[np.ix_(src, src)]
+        r = _ba.tracking_covariances_batch([prob], [sub])[0]
+        out["cam"], out["cam_fixed_map"] = r["cam_cov"][0].copy(), r["fixed_map_cov"][0].copy()
+        out["cross"] = {o: r["cross"][0, j].copy() for o, j in obj_index.items()}
+        out["rel"] = {o: r["rel"][0, j].copy() for o, j in obj_index.items()}
+        out["status"] = [int(x) for x in r["status"]]
         return out
 
     @_on_stream
