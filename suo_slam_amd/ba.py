@@ -75,27 +75,29 @@ def optimize(*args, **kw):
     return p.cam_T.reshape(-1, 3, 4), p.obj_T.reshape(-1, 3, 4), p.inlier, p.chi2, p.stats
 
 
+def _call_batch(entry, problems, bufs, *flat, lead=()):
+    """One call of a covariance batch entry of the C ABI: (BaProblem array, n, *lead, one pointer column per buffer of bufs[i], *flat).  bufs[i]: problem i's
+    arrays, one per column, in the entry's order; lead / flat: arrays with one row per problem.  Everything stays alive until the call has returned."""
+    _lib.require_gpu()
+    n = len(problems)
+    arr = (_lib.BaProblem * n)()
+    for s, p in zip(arr, problems):
+        p._fill(s)
+    cols = [(C.c_void_p * n)(*[b.ctypes.data for b in col]) for col in zip(*bufs)]
+    _lib.check(getattr(_lib.lib(), entry)(C.cast(arr, C.c_void_p), n, *[a.ctypes.data for a in lead], *[C.cast(c, C.c_void_p) for c in cols],
+                                   *[a.ctypes.data for a in flat]), entry)
+
+
 def pose_covariances_batch(problems):
     """6x6 marginal covariances of every camera and object pose of each Problem at the state it holds (cam_T, obj_T, inlier): the diagonal blocks of the inverse
     Gauss-Newton Hessian, rows and columns [omega, upsilon] of the left update exp(delta) T (include/suo_hip.h: suo_pose_covariances).  One call for the whole
     list; per problem (cam_cov [C,6,6], obj_cov [O,6,6], status [2] = NaN camera blocks, NaN object blocks).  The problems are not modified."""
     if not problems:
         return []
-    lib = _lib.lib()
-    _lib.require_gpu()
-    n = len(problems)
-    arr = (_lib.BaProblem * n)()
-    out = []
-    cams, objs = (C.c_void_p * n)(), (C.c_void_p * n)()
-    status = np.zeros((n, 2), np.int32)
-    for i, (s, p) in enumerate(zip(arr, problems)):
-        p._fill(s)
-        cc, oc = np.zeros((len(p.cam_T), 6, 6)), np.zeros((len(p.obj_T), 6, 6))
-        cams[i], objs[i] = cc.ctypes.data, oc.ctypes.data
-        out.append((cc, oc, status[i]))
-    _lib.check(lib.suo_pose_covariances_batch(C.cast(arr, C.c_void_p), n, C.cast(cams, C.c_void_p), C.cast(objs, C.c_void_p), status.ctypes.data),
-               "suo_pose_covariances_batch")
-    return out
+    status = np.zeros((len(problems), 2), np.int32)
+    bufs = [(np.zeros((len(p.cam_T), 6, 6)), np.zeros((len(p.obj_T), 6, 6))) for p in problems]
+    _call_batch("suo_pose_covariances_batch", problems, bufs, status)
+    return [b + (st,) for b, st in zip(bufs, status)]
 
 
 def pose_covariances(*args, **kw):
@@ -117,27 +119,15 @@ def _pairs_batch(problems, pairs, entry):
         return []
     if len(pairs) != len(problems):
         raise ValueError(f"{entry[4:]}: one pair list per problem")
-    lib = _lib.lib()
-    _lib.require_gpu()
-    n = len(problems)
-    arr = (_lib.BaProblem * n)()
-    out, keep = [], []
-    ptrs = [(C.c_void_p * n)() for _ in range(6)]           # pair_a, pair_b, cam_cov, obj_cov, cross, rel
-    n_pair = np.zeros(n, np.int32)
-    status = np.zeros((n, 3), np.int32)
-    for i, (s, p, pr) in enumerate(zip(arr, problems, pairs)):
-        p._fill(s)
+    _lib.require_gpu()                                      # (before the argument checks below, as ever)
+    status = np.zeros((len(problems), 3), np.int32)
+    bufs = []                                               # pair_a, pair_b, cam_cov, obj_cov, cross, rel
+    for p, pr in zip(problems, pairs):
         pr = np.asarray(pr, np.int32).reshape(-1, 2)
-        a, b = np.ascontiguousarray(pr[:, 0]), np.ascontiguousarray(pr[:, 1])
-        P = len(pr)
-        bufs = (a, b, np.zeros((len(p.cam_T), 6, 6)), np.zeros((len(p.obj_T), 6, 6)), np.zeros((P, 6, 6)), np.zeros((P, 6, 6)))
-        for col, buf in zip(ptrs, bufs):
-            col[i] = buf.ctypes.data
-        n_pair[i] = P
-        keep.append((a, b))
-        out.append(bufs[2:] + (status[i],))
-    _lib.check(getattr(lib, entry)(C.cast(arr, C.c_void_p), n, n_pair.ctypes.data, *[C.cast(c, C.c_void_p) for c in ptrs], status.ctypes.data), entry)
-    return out
+        bufs.append((np.ascontiguousarray(pr[:, 0]), np.ascontiguousarray(pr[:, 1]), np.zeros((len(p.cam_T), 6, 6)), np.zeros((len(p.obj_T), 6, 6)),
+                     np.zeros((len(pr), 6, 6)), np.zeros((len(pr), 6, 6))))
+    _call_batch(entry, problems, bufs, status, lead=(np.array([len(b[0]) for b in bufs], np.int32),))
+    return [b[2:] + (st,) for b, st in zip(bufs, status)]
 
 
 def pose_covariances_pairs(*args, pairs, **kw):
@@ -171,27 +161,17 @@ def tracking_covariances_batch(problems, map_covs):
         return []
     if len(map_covs) != len(problems):
         raise ValueError("tracking_covariances_batch: one map covariance per problem")
-    lib = _lib.lib()
-    _lib.require_gpu()
-    n = len(problems)
-    arr = (_lib.BaProblem * n)()
-    ptrs = [(C.c_void_p * n)() for _ in range(5)]           # map_cov, cam_cov, fixed_map_cov, cross, rel
-    status = np.zeros((n, 2), np.int32)
-    out, keep = [], []
-    for i, (s, p, m) in enumerate(zip(arr, problems, map_covs)):
-        p._fill(s)
+    _lib.require_gpu()                                      # (before the shape check below, as ever)
+    status = np.zeros((len(problems), 2), np.int32)
+    bufs = []                                               # map_cov, cam_cov, fixed_map_cov, cross, rel
+    for i, (p, m) in enumerate(zip(problems, map_covs)):
         nc, no = len(p.cam_T), len(p.obj_T)
         m = np.ascontiguousarray(m, np.float64)
         if m.shape != (6 * no, 6 * no):
             raise ValueError(f"tracking_covariances_batch: problem {i}: map covariance of shape {m.shape}, expected {(6 * no, 6 * no)}")
-        bufs = (m, np.zeros((nc, 6, 6)), np.zeros((nc, 6, 6)), np.zeros((nc, no, 6, 6)), np.zeros((nc, no, 6, 6)))
-        for col, buf in zip(ptrs, bufs):
-            col[i] = buf.ctypes.data
-        keep.append(m)
-        out.append(dict(zip(TRACK_KEYS, bufs[1:]), status=status[i]))
-    _lib.check(lib.suo_tracking_covariances_batch(C.cast(arr, C.c_void_p), n, *[C.cast(c, C.c_void_p) for c in ptrs], status.ctypes.data),
-               "suo_tracking_covariances_batch")
-    return out
+        bufs.append((m, np.zeros((nc, 6, 6)), np.zeros((nc, 6, 6)), np.zeros((nc, no, 6, 6)), np.zeros((nc, no, 6, 6))))
+    _call_batch("suo_tracking_covariances_batch", problems, bufs, status)
+    return [dict(zip(TRACK_KEYS, b[1:]), status=st) for b, st in zip(bufs, status)]
 
 
 def tracking_covariances(*args, map_cov, **kw):
@@ -211,24 +191,14 @@ def residual_statistics_batch(problems):
     blocks, NaN edges, edges without redundancy.  The problems are not modified."""
     if not problems:
         return []
-    lib = _lib.lib()
-    _lib.require_gpu()
-    n = len(problems)
-    arr = (_lib.BaProblem * n)()
-    ptrs = [(C.c_void_p * n)() for _ in RESID_KEYS]
-    summary = np.zeros((n, 6))
-    status = np.zeros((n, 4), np.int32)
-    out = []
-    for i, (s, p) in enumerate(zip(arr, problems)):
-        p._fill(s)
+    summary = np.zeros((len(problems), 6))
+    status = np.zeros((len(problems), 4), np.int32)
+    bufs = []
+    for p in problems:
         nc, no, E = len(p.cam_T), len(p.obj_T), len(p.edge_cam)
-        bufs = (np.zeros((nc, 6, 6)), np.zeros((no, 6, 6)), np.zeros(E), np.zeros((E, 3)), np.zeros(E), np.zeros(E), np.zeros((nc, 3)), np.zeros((no, 3)))
-        for col, buf in zip(ptrs, bufs):
-            col[i] = buf.ctypes.data
-        out.append(dict(zip(RESID_KEYS, bufs), summary=summary[i], status=status[i]))
-    _lib.check(lib.suo_residual_statistics_batch(C.cast(arr, C.c_void_p), n, *[C.cast(c, C.c_void_p) for c in ptrs], summary.ctypes.data, status.ctypes.data),
-               "suo_residual_statistics_batch")
-    return out
+        bufs.append((np.zeros((nc, 6, 6)), np.zeros((no, 6, 6)), np.zeros(E), np.zeros((E, 3)), np.zeros(E), np.zeros(E), np.zeros((nc, 3)), np.zeros((no, 3))))
+    _call_batch("suo_residual_statistics_batch", problems, bufs, summary, status)
+    return [dict(zip(RESID_KEYS, b), summary=sm, status=st) for b, sm, st in zip(bufs, summary, status)]
 
 
 def residual_statistics(*args, **kw):

@@ -1,5 +1,6 @@
 // Staging shared by the host entries of the geometry kernels (csrc/pnp_api.hip, csrc/ba_api.hip, csrc/ba_ctx.hip, csrc/ba_drive.hip): the caller's host arrays go
-// into one device arena (one H2D), results come back in one D2H; everything between the two copies runs on the GPU.
+// into one device arena (one H2D), results come back in one D2H; everything between the two copies runs on the GPU.  It stages what suo_optimize_batch needs and
+// nothing else; an entry with arrays of its own beside the problems (the covariance entries: csrc/cov_stage.hip) asks for rooms (Staged::room_bytes).
 #pragma once
 #include <mutex>
 #include <type_traits>
@@ -23,7 +24,9 @@ extern Arena g_arena;       // one per process for suo_pnp* and suo_optimize_bat
 
 struct Layout {
     size_t off = 0;
+    char* base = nullptr;                      // what put() counts from; nullptr in a sizing pass
     size_t take(size_t bytes) { size_t o = off; off = (off + bytes + 15) & ~(size_t)15; return o; }
+    template <class T> void put(T*& p, size_t n) { p = (T*)((uintptr_t)base + take(sizeof(T) * n)); }
 };
 
 // One problem, prepared on the host: edges sorted by (camera, object) pair (order[k] = the caller's index of sorted edge k), the pair lists and their CSRs;
@@ -31,23 +34,26 @@ struct Layout {
 struct Prep {
     std::vector<int> order, edge_pair, pair_cam, pair_obj, pair_start, cam_ptr, cam_idx, obj_ptr, obj_idx, cam_obj;
     LmProblem S;
-    RsProblem R;             // stage_problems(..., resid = true) only
 };
 struct Staged {
     std::vector<Prep> prep;
-    size_t o_structs = 0, o_rs = 0, in_end = 0, out_end = 0, total = 0;      // arena: [LmProblem structs | inputs | in_end: outputs | out_end: scratch | total]
-    size_t cov_begin = 0, cov_end = 0;                             // inside the scratch: every problem's cam_cov / obj_cov / cov_status / cov_cross / cov_rel (csrc/pose_cov_api.hip reads them back)
-    size_t o_extra = 0;                                            // stage_problems(..., extra): that many bytes behind the scratch, the caller's to lay out (csrc/track_cov_api.hip)
+    size_t o_structs = 0, in_end = 0, out_end = 0, total = 0;      // arena: [LmProblem structs | inputs, room 0 | in_end: outputs | out_end: scratch, rooms 1, 2 | total]
+    // Rooms of the caller's beside the problems (csrc/cov_stage.hip), 16-byte aligned: [0] inputs, inside [0, in_end); [1] outputs and [2] scratch, behind the LM
+    // scratch.  room_bytes: asked for before stage_prepared; room: their DEVICE addresses after it.
+    size_t room_bytes[3] = {0, 0, 0};
+    char* room[3] = {nullptr, nullptr, nullptr};
 };
 
-// `who`: the entry the caller called, for the error texts.  prep_problem is the host half of stage_problems (validation, stable sort by pair, pair CSR).
+// `who`: the entry the caller called, for the error texts.  Staging is three steps: prep_problems, the host half (prep_problem of every problem: validation,
+// stable sort by pair, pair CSR) -- room sizes may depend on what it finds --; stage_prepared, the arena layout and the LM inputs into the pinned mirror -- the
+// caller may then set pointer fields of Prep::S and write its rooms through Arena::mirror --; upload, the LmProblem structs into the mirror and the H2D of
+// [0, in_end), or without room 0, which upload_room then sends in a copy of its own.  stage_problems: all three, no rooms.
 int prep_problem(const suo_ba_problem& q, int index, Prep& P, const char* who);
-// cov_form (optional, [n_prob]): LmProblem::cov_form of every problem (csrc/pose_cov_api.hip: plan_cov_batch); pairs (optional): its vertex pairs
-struct CovPairs { const int* n; const int32_t* const* a; const int32_t* const* b; };      // per problem: the count and the two index lists
-// resid: also the arrays of suo_residual_statistics (one RsProblem per problem at o_rs), its outputs inside [cov_begin, cov_end); without it they take no room
-// extra: bytes reserved at Staged::o_extra, neither filled nor copied here
-int stage_problems(const suo_ba_problem* probs, int n_prob, Arena& A, Staged& st, const char* who, const int* cov_form = nullptr, const CovPairs* pairs = nullptr,
-                   bool resid = false, size_t extra = 0);
+int prep_problems(const suo_ba_problem* probs, int n_prob, Staged& st, const char* who);
+int stage_prepared(const suo_ba_problem* probs, int n_prob, Arena& A, Staged& st);
+int upload(Arena& A, Staged& st, bool with_room = true);
+int upload_room(Arena& A, Staged& st);
+int stage_problems(const suo_ba_problem* probs, int n_prob, Arena& A, Staged& st, const char* who);
 int fetch_results(suo_ba_problem* probs, int n_prob, Arena& A, Staged& st);
 
 }  // namespace suo

@@ -73,73 +73,62 @@ int prep_problem(const suo_ba_problem& q, int index, Prep& P, const char* who) {
 }
 
 // The arena layout of a batch, every array on a 16-byte boundary: the structs, then every problem's inputs (one H2D up to in_end), then the outputs that are not
-// inputs too (one D2H up to out_end), then device-only scratch.  Each Prep::S gets its sizes and its addresses, counted from `base`.
-static void lay_out(const suo_ba_problem* probs, int n_prob, const int* cov_form, const CovPairs* pairs, bool resid, size_t extra, char* base, Staged& st) {
+// inputs too (one D2H up to out_end), then device-only scratch.  Each Prep::S gets its sizes and its addresses, counted from `base`; the caller's rooms
+// (Staged::room) close the inputs and the scratch.
+static void lay_out(const suo_ba_problem* probs, int n_prob, char* base, Staged& st) {
     Layout L;
-    auto put = [&](auto*& p, size_t n) { p = (std::remove_reference_t<decltype(p)>)((uintptr_t)base + L.take(sizeof(*p) * n)); };
+    L.base = base;
+    auto room = [&](int k) { st.room[k] = (char*)((uintptr_t)base + L.take(st.room_bytes[k])); };
     st.o_structs = L.take(sizeof(LmProblem) * (size_t)n_prob);
-    st.o_rs = L.take(resid ? sizeof(RsProblem) * (size_t)n_prob : 0);
     for (int i = 0; i < n_prob; ++i) {
         LmProblem& S = st.prep[i].S;
         S = LmProblem();
         S.n_cam = probs[i].n_cam; S.n_obj = probs[i].n_obj; S.n_edge = probs[i].n_edge; S.n_pair = (int)st.prep[i].pair_cam.size();
         const size_t E = S.n_edge, C = S.n_cam, O = S.n_obj, NP = S.n_pair;
-        put(S.cam_T, 12 * C); put(S.obj_T, 12 * O); put(S.cam_fixed, C); put(S.obj_fixed, O);
-        put(S.edge_pair, E); put(S.edge_k, 4 * E); put(S.edge_p, 3 * E); put(S.edge_uv, 2 * E); put(S.edge_info, 3 * E); put(S.edge_inlier, E);
-        put(S.pair_cam, NP); put(S.pair_obj, NP); put(S.pair_start, NP + 1);
-        put(S.cam_pair_ptr, C + 1); put(S.cam_pair_idx, NP); put(S.obj_pair_ptr, O + 1); put(S.obj_pair_idx, NP);
-        put(S.cam_obj_pair, C * O);
-        S.n_cpair = pairs ? pairs->n[i] : 0;
-        put(S.cpair_a, (size_t)S.n_cpair); put(S.cpair_b, (size_t)S.n_cpair);
-        RsProblem& R = st.prep[i].R;
-        R = RsProblem();
-        if (resid) { put(R.order, E); put(R.vptr, C + O + 1); put(R.vedge, 2 * E); }
+        L.put(S.cam_T, 12 * C); L.put(S.obj_T, 12 * O); L.put(S.cam_fixed, C); L.put(S.obj_fixed, O);
+        L.put(S.edge_pair, E); L.put(S.edge_k, 4 * E); L.put(S.edge_p, 3 * E); L.put(S.edge_uv, 2 * E); L.put(S.edge_info, 3 * E); L.put(S.edge_inlier, E);
+        L.put(S.pair_cam, NP); L.put(S.pair_obj, NP); L.put(S.pair_start, NP + 1);
+        L.put(S.cam_pair_ptr, C + 1); L.put(S.cam_pair_idx, NP); L.put(S.obj_pair_ptr, O + 1); L.put(S.obj_pair_idx, NP);
+        L.put(S.cam_obj_pair, C * O);
     }
+    room(0);
     st.in_end = L.off;
-    for (int i = 0; i < n_prob; ++i) { LmProblem& S = st.prep[i].S; put(S.edge_chi2, S.n_edge); put(S.stats, 4); }
+    for (int i = 0; i < n_prob; ++i) { LmProblem& S = st.prep[i].S; L.put(S.edge_chi2, S.n_edge); L.put(S.stats, 4); }
     st.out_end = L.off;
     for (int i = 0; i < n_prob; ++i) {
         LmProblem& S = st.prep[i].S;
         const size_t E = S.n_edge, C = S.n_cam, O = S.n_obj, NP = S.n_pair;
-        put(S.cam, C); put(S.obj, O); put(S.cam_bak, C); put(S.obj_bak, O);
-        put(S.err, 2 * E); put(S.level, E); put(S.pair_part, 90 * NP);
-        put(S.Hcc, 36 * C); put(S.bc, 6 * C); put(S.Hoo, 36 * O); put(S.bo, 6 * O);
-        put(S.Hcc_inv, 36 * C); put(S.Y, 36 * NP); put(S.yc, 6 * C); put(S.xc, 6 * C); put(S.xo, 6 * O); put(S.obj_slot, O);
-        put(S.jac, 29 * E);
+        L.put(S.cam, C); L.put(S.obj, O); L.put(S.cam_bak, C); L.put(S.obj_bak, O);
+        L.put(S.err, 2 * E); L.put(S.level, E); L.put(S.pair_part, 90 * NP);
+        L.put(S.Hcc, 36 * C); L.put(S.bc, 6 * C); L.put(S.Hoo, 36 * O); L.put(S.bo, 6 * O);
+        L.put(S.Hcc_inv, 36 * C); L.put(S.Y, 36 * NP); L.put(S.yc, 6 * C); L.put(S.xc, 6 * C); L.put(S.xo, 6 * O); L.put(S.obj_slot, O);
+        L.put(S.jac, 29 * E);
     }
-    st.cov_begin = L.off;
-    for (int i = 0; i < n_prob; ++i) { LmProblem& S = st.prep[i].S; put(S.cam_cov, 36 * (size_t)S.n_cam); put(S.obj_cov, 36 * (size_t)S.n_obj); put(S.cov_status, 3);
-                                       put(S.cov_cross, 36 * (size_t)S.n_cpair); put(S.cov_rel, 36 * (size_t)S.n_cpair);
-                                       if (!resid) continue;
-                                       const size_t E = S.n_edge, V = (size_t)S.n_cam + S.n_obj;
-                                       RsProblem& R = st.prep[i].R;
-                                       put(R.chi2, E); put(R.pcov, 3 * E); put(R.lev, E); put(R.t, E); put(R.flag, E); put(R.vstat, 3 * V);
-                                       put(R.summary, 6); put(R.status, 2); }
-    st.cov_end = L.off;
-    // cov_form 3 (csrc/pose_cov_graph.hip): the reduced system, its inverse and every camera's Z in device memory, sized by the free objects -- no slot limit
-    for (int i = 0; cov_form && i < n_prob; ++i) {
-        if (cov_form[i] != 3) continue;
-        LmProblem& S = st.prep[i].S;
-        size_t nsm = 0;
-        for (int o = 0; o < S.n_obj; ++o) nsm += probs[i].obj_fixed[o] ? 0 : 6;
-        put(S.cov_S, nsm * (nsm + 1)); put(S.cov_Sinv, nsm * nsm); put(S.cov_Z, 6 * (size_t)S.n_cam * nsm); put(S.cov_hdr, 2 + (size_t)S.n_obj);
-    }
-    st.o_extra = L.take(extra);
+    room(1); room(2);
     st.total = L.off;
 }
 
-// host prep + arena layout + H2D of one batch of problems
-int stage_problems(const suo_ba_problem* probs, int n_prob, Arena& A, Staged& st, const char* who, const int* cov_form, const CovPairs* pairs, bool resid,
-                   size_t extra) {
+int prep_problems(const suo_ba_problem* probs, int n_prob, Staged& st, const char* who) {
     st.prep.assign(n_prob, Prep());
     for (int i = 0; i < n_prob; ++i) {
         int rc = prep_problem(probs[i], i, st.prep[i], who);
         if (rc != SUO_OK) return rc;
     }
-    lay_out(probs, n_prob, cov_form, pairs, resid, extra, nullptr, st);          // sizes first: the arena may move when it grows
+    return SUO_OK;
+}
+
+int stage_problems(const suo_ba_problem* probs, int n_prob, Arena& A, Staged& st, const char* who) {
+    int rc = prep_problems(probs, n_prob, st, who);
+    if (rc == SUO_OK) rc = stage_prepared(probs, n_prob, A, st);
+    return rc != SUO_OK ? rc : upload(A, st);
+}
+
+// arena layout + pinned mirror of one prepared batch of problems
+int stage_prepared(const suo_ba_problem* probs, int n_prob, Arena& A, Staged& st) {
+    lay_out(probs, n_prob, nullptr, st);          // sizes first: the arena may move when it grows
     int rc = A.ensure(st.total);
     if (rc != SUO_OK) return rc;
-    lay_out(probs, n_prob, cov_form, pairs, resid, extra, A.dev, st);
+    lay_out(probs, n_prob, A.dev, st);
     for (int i = 0; i < n_prob; ++i) {
         const suo_ba_problem& q = probs[i];
         Prep& P = st.prep[i];
@@ -170,26 +159,18 @@ int stage_problems(const suo_ba_problem* probs, int n_prob, Arena& A, Staged& st
         memcpy(A.mirror(S.cam_obj_pair), P.cam_obj.data(), sizeof(int) * P.cam_obj.size());
         for (int k = 0; k < 8; ++k) S.its[k] = k < q.n_rounds ? q.its[k] : 0;
         S.n_rounds = q.n_rounds; S.init_with_outliers = q.init_with_outliers; S.chi2_thr = q.chi2_thr; S.huber_delta = q.huber_delta;
-        S.cov_form = cov_form ? cov_form[i] : 0;
-        if (S.n_cpair > 0) {
-            memcpy(A.mirror(S.cpair_a), pairs->a[i], sizeof(int) * S.n_cpair);
-            memcpy(A.mirror(S.cpair_b), pairs->b[i], sizeof(int) * S.n_cpair);
-        }
-        if (resid) {
-            // every vertex's edges by the caller's index, ascending: the order the per-vertex sums of csrc/resid_stats.hip walk
-            memcpy(A.mirror(P.R.order), P.order.data(), sizeof(int) * E);
-            int* vptr = A.mirror(P.R.vptr); int* vedge = A.mirror(P.R.vedge);
-            const int V = q.n_cam + q.n_obj;
-            std::fill(vptr, vptr + V + 1, 0);
-            for (int e = 0; e < E; ++e) { vptr[q.edge_cam[e] + 1]++; vptr[q.n_cam + q.edge_obj[e] + 1]++; }
-            for (int v = 0; v < V; ++v) vptr[v + 1] += vptr[v];
-            std::vector<int> at(vptr, vptr + V);
-            for (int e = 0; e < E; ++e) { vedge[at[q.edge_cam[e]]++] = e; vedge[at[q.n_cam + q.edge_obj[e]]++] = e; }
-            memcpy(A.host + st.o_rs + sizeof(RsProblem) * (size_t)i, &P.R, sizeof(RsProblem));
-        }
-        memcpy(A.host + st.o_structs + sizeof(LmProblem) * (size_t)i, &S, sizeof(LmProblem));
     }
-    SUO_HIP_CHECK(hipMemcpyAsync(A.dev, A.host, st.in_end, hipMemcpyHostToDevice, A.stream));
+    return SUO_OK;
+}
+
+int upload(Arena& A, Staged& st, bool with_room) {
+    for (size_t i = 0; i < st.prep.size(); ++i) memcpy(A.host + st.o_structs + sizeof(LmProblem) * i, &st.prep[i].S, sizeof(LmProblem));
+    SUO_HIP_CHECK(hipMemcpyAsync(A.dev, A.host, with_room ? st.in_end : (size_t)(st.room[0] - A.dev), hipMemcpyHostToDevice, A.stream));
+    return SUO_OK;
+}
+
+int upload_room(Arena& A, Staged& st) {
+    SUO_HIP_CHECK(hipMemcpyAsync(st.room[0], A.mirror(st.room[0]), st.room_bytes[0], hipMemcpyHostToDevice, A.stream));
     return SUO_OK;
 }
 

@@ -287,7 +287,8 @@ struct LmProblem {
     // [nsm][nsm], Z = Y Sigma_OO of every camera [n_cam][6][nsm] (all three at the pitch of the ns the kernel finds), and [0] ok [1] ns [2 + s] the object in slot s
     double* cov_S; double* cov_Sinv; double* cov_Z; int* cov_hdr;
 };
-// The arrays of suo_residual_statistics (csrc/resid_stats.hip), one struct per problem beside its LmProblem (whose size the LM kernels copy: it stays as it is).
+// The arrays of suo_residual_statistics (csrc/resid_stats.hip), one struct per problem beside its LmProblem (whose size the LM kernels copy: it stays as it is),
+// laid out and filled by csrc/cov_stage.hip (CovRequest::resid); csrc/ba_stage.hip does not know it.
 // In: order [n_edge] the caller's index of (sorted) edge k; vptr [n_cam + n_obj + 1] / vedge [2 n_edge] the caller's indices of every vertex's edges, ascending.
 // Out, all by the CALLER's edge index: chi2, pcov [3] (xx, xy, yy), lev, t, flag (RS_COUNTED | RS_NAN | RS_NORED); vstat [n_cam + n_obj][3] (count, sum chi2,
 // sum 2 - lev); summary [6]; status [2] = NaN edges, edges without redundancy.  The pairs of LmProblem::cpair_a / cpair_b are then the problem's own pairs: pair p's

@@ -1,5 +1,6 @@
 // Host launchers of the geometry kernels (csrc/pnp.hip, csrc/lm*.hip, csrc/lm_dist.hip), declared ONCE: the files that define them and the files that call them
-// (csrc/pnp_api.hip, csrc/ba_*.hip, csrc/frame_geom.hip) include this header, and default arguments live here only.
+// (csrc/pnp_api.hip, csrc/ba_*.hip, csrc/cov_stage.hip -- the one caller of the covariance chain --, csrc/*_cov_api.hip, csrc/frame_geom.hip) include this header,
+// and default arguments live here only.
 #pragma once
 #include "suo_internal.h"
 
@@ -55,10 +56,11 @@ int launch_pose_cov_pairs(const void* problems_dev, int n_problems, int max_pair
 constexpr int POSE_COV_GRAPH_MAX_OBJ = 64;
 int launch_pose_cov_graph(const void* problems_dev, int n_problems, int max_free_obj, int max_cam, int max_pairs, hipStream_t s);
 // ---- per-edge leverages, studentised residuals and the chi2 scale (csrc/resid_stats.hip): behind the covariance kernels of every form and the pair kernel, the
-// problems staged with stage_problems(..., resid = true) and their own (camera, object) pairs as cpair_a / cpair_b; an edge kernel and a reduction, two launches
+// problems staged by stage_cov with CovRequest::resid (csrc/cov_stage.h): an RsProblem each and their own (camera, object) pairs as cpair_a / cpair_b; an edge
+// kernel and a reduction, two launches
 int launch_resid_stats(const void* problems_dev, const void* rs_dev /* RsProblem [n_problems] */, int n_problems, int max_edges, int max_vertices, hipStream_t s);
 // ---- consider covariance of tracked cameras (csrc/track_cov.hip): behind launch_pose_cov_diag on problems of cov_form 1; tc_dev = n_problems TcProblem structs
-// (csrc/track_cov.h), one workgroup per (problem, camera)
+// (csrc/track_cov.h) laid out by stage_cov, one workgroup per (problem, camera)
 int launch_track_cov(const void* problems_dev, const void* tc_dev, int n_problems, int max_cam, int max_obj, hipStream_t s);
 int launch_debug_cholesky(const double* A, const double* b, int ns, double* x, int* ok, hipStream_t s);
 }  // namespace suo

@@ -5,7 +5,7 @@
 //   Sigma  = H^-1; the result is its 6x6 diagonal block per vertex, 36 row-major doubles: zeros for a fixed vertex, NaNs for a free vertex without a counted edge
 //            and for every block of a system whose factorisation meets a non-positive pivot.  The chi2 scale is not applied.
 //
-// Three forms, chosen per problem on the host (csrc/pose_cov_api.hip: plan_cov_batch -> LmProblem::cov_form):
+// Three forms, chosen per problem on the host (csrc/cov_stage.hip: plan_cov_batch -> LmProblem::cov_form):
 //   0  no free camera: H is block-diagonal over the objects.  One wave per problem in the lane layout of csrc/lm_frame2.hip -- G = 8 lanes own an object (G = 4 from
 //      9 objects on), lane (object, sub) walks the object's edges sub, sub + G, ...; the 21 packed entries of the block meet inside the group by log2(G) DPP steps;
 //      every group inverts its own block by Cholesky in registers.  Problems of more than 64 / G objects are walked in passes: nothing couples the objects.

@@ -3,7 +3,7 @@
 // (camera, camera) pair.  Definitions, NaN rules and outputs are those of csrc/pose_cov.hip; the assembly is shared with its form 2 (csrc/pose_cov_device.h).
 //
 // Per problem the arena holds S (ns x (ns + 1), later its factor), Sigma_OO (ns x ns), Z = Y Sigma_OO of every camera (6 x ns each) and a header [ok, ns, the object
-// of every slot] (csrc/ba_stage.hip), ns = 6 * free objects with a counted edge.  A phase hands data to other workgroups only across a launch boundary: a CU's vector
+// of every slot] (csrc/cov_stage.hip), ns = 6 * free objects with a counted edge.  A phase hands data to other workgroups only across a launch boundary: a CU's vector
 // L1 is not refreshed by another CU's stores and the per-XCD L2s are not coherent inside a kernel, so there is no grid barrier and no flag.  Four launches:
 //   1  pcg_factor_kernel    one workgroup per problem: assembly, then S = L L^T in place, blocked by 6 -- the diagonal 6 x 6 redundantly in registers, the panel
 //                           (a row per thread, kept in LDS for the update: 6 doubles per row), the trailing update in 16 x 16 tiles over the workgroup.

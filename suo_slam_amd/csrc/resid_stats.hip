@@ -2,7 +2,7 @@
 //
 // Runs BEHIND the pose-covariance kernels of the problem's cov_form and the pair kernel (csrc/pose_cov.hip, csrc/pose_cov_graph.hip), on their stream: cam_cov / obj_cov
 // hold Sigma_cc / Sigma_oo of every vertex, and for cov_form >= 2 cov_cross [36 p] holds Sigma_co of the problem's own pair p (rows the camera) -- the host entry
-// asks for exactly those pairs (csrc/pose_cov_api.hip).  Forms 0 and 1 couple nothing: Sigma_co = 0 and no pair was asked for.
+// asks for exactly those pairs (csrc/cov_stage.hip).  Forms 0 and 1 couple nothing: Sigma_co = 0 and no pair was asked for.
 //
 //   rs_edge_kernel     a thread per (sorted) edge, 64 consecutive edges per wave.  v and J = [Jc Jo] come from lm_device.h (edge_error_at, edge_jacobian: the functions the
 //                      Hessian was built from), at Poses made from cam_T / obj_T the way pc_assemble_blocks makes them.  Edges are sorted by pair, so a wave's edges span a
