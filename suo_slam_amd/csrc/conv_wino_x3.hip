@@ -41,6 +41,7 @@ __device__ __forceinline__ void x_sub16(x_f32x16& z, const x_f32x16& t) { z -= t
 
 constexpr int X_CK = 16, X_PKH = 20, X_TH = 8, X_TW = 16, X_IH = 10, X_IW = 18, X_NPIX = X_IH * X_IW;
 
+#ifndef SUO_WX3_DMA_TU                                         // (csrc/conv_wino_x3_dma.hip compiles this file again for the DMA kernels alone: host code once)
 // host: U[n][c][comp] = (G g G^T)[xi][nu] in fp64 (BN scale folded in), rounded once to fp32, split into three bf16 terms (csrc/bf16x3.h);
 //   Up3[chunk][comp][nb][plane][lane][e] = term `plane` of +-U[nb*32 + (lane&31)][chunk*16 + 8*(lane>>5) + e][comp]     (B operand of
 //   v_mfma_f32_32x32x16_bf16: lane l supplies k = 8 (l >> 5) .. + 7 of column l & 31); the components of row xi = 3 are stored negated
@@ -118,6 +119,7 @@ void pack_wino_weight_f16x2(const float* W, int N, int C, int Np, int Cp, const 
 
 // host: conv3 weight of the fused tail, two fp16 planes: the layout of pack_gemm_weight_f16x2 (csrc/gemm_bf16x3.hip)
 void pack_tail_weight_f16x2(const float* W3, int N2, int K, uint16_t* out, float* oscale_out) { pack_gemm_weight_f16x2(W3, N2, K, out, oscale_out); }
+#endif
 
 // NT = output channels / 32: 4 (128 channels: wave w owns n-tile w and all 16 components) or 2 (64 -> 64 channels: wave (wc, wn) owns n-tile wn and
 // the 8 components of rows xi = 2 wc, 2 wc + 1 -- one accumulator each, no fold; the two halves meet through LDS before the epilogue, as in
@@ -134,9 +136,27 @@ void pack_tail_weight_f16x2(const float* W3, int N2, int K, uint16_t* out, float
 // through LDS after the K loop; a thread of the transform computes ONE row of B^T d B (four components); the tail's conv3 gives every wave one 32-channel n-tile of
 // the 256.  Each output element is the same sum of the same products in the same order, except that Y = (R0 + R1) + R2 / (R3' - R2) + R1 pairs its rows as the
 // 64-channel form does, where the four-wave form folds per chunk: results agree to fp32 rounding of that last addition, not bit for bit.
-template <bool FUSE, bool UP = false, bool TX3 = false, int NT = 4, int NP = 3, bool NEXT = false, bool W8 = false>
+// DMA (the four-wave fp16 form; SUO_WINO_HALO_DMA=0 keeps the register-staged path, see conv3x3_wino_f16x2_dma below): the halo of chunk c + 1 goes from global memory
+// STRAIGHT into the other halo buffer (buffer_load_dwordx4 ... lds: no VGPR destination, no ds_write_b128), 12 registers less across the transform.
+//  - Layout: one wave-instruction writes 1 KiB lane-linear, so the pixel pitch is 16 floats (no padding) and float4 slot idx = tid + 256 i holds pixel P = idx >> 2
+//    (P = 18 R + col) and channel quad (idx & 3) ^ ((R >> 1) & 3): the swizzle is on the SOURCE address (which quad a lane fetches; the four lanes of a pixel still
+//    fetch its 64 contiguous bytes) and, the same one, in the transform's read addresses.  Bank arithmetic of the transform's ds_read_b128: a 16-lane group is 4 tile
+//    rows t_ty x 4 consecutive tile columns t_tx of ONE quad tq; slot mod 16 = 4 (P mod 4) + (tq ^ ((R >> 1) & 3)), P = 36 t_ty + 2 t_tx + const: P mod 4 takes two
+//    values (the parity of t_tx), (R >> 1) & 3 = (t_ty + const) & 3 four: 8 distinct 16-byte slots for 16 lanes, 2-way (unswizzled: 8-way; the padded pitch 20 of the
+//    register path: conflict-free).  R >> 1 is t_ty or t_ty + 1 for a thread's four rows: two base addresses, every read a constant offset from one of them.
+//  - Pixels outside the map (and slots 720-767): their lanes' offset is BUF_OOB in every chunk, and the slots are zeroed once with plain stores before the first DMA,
+//    so it does not matter whether an out-of-range lane of the instruction writes zero or nothing.  Crop ends: the per-crop descriptor, as for the register path.
+//  - The DMA is an asm statement (hipcc would wait vmcnt(0) for a DMA it knows of at the next ds_read): hipcc does not count it, so its own counted waits for the weight
+//    loads only become stricter (vmcnt retires in order).  DMA(c + 1) is issued at the top of chunk c -- the last reads of that buffer ended before the first barrier
+//    of chunk c - 1 -- and is retired before the barrier that closes chunk c: pairs 1 .. NPAIR - 1 have waited for weights requested after it; the explicit
+//    vmcnt(4) there (the next chunk's first pair = 4 loads may stay in flight) states it.  The buffer is read one barrier later, at the top of chunk c + 1.
+//  - The exact factor 2^s rides on the transform's first differences (32 products instead of 12; scaling by a power of two commutes with the additions: same bits), the
+//    guard's running maximum on three ds_read_b128 of the lane's own slots of the landed buffer (the same elements the register path saw; max |x| 2^s = max |x 2^s|).
+// A third weight slot for the freed registers (weights two pairs ahead) measured SLOWER than two (profiles/REJECTED.md): the ring stays two deep in both paths.
+template <bool FUSE, bool UP = false, bool TX3 = false, int NT = 4, int NP = 3, bool NEXT = false, bool W8 = false, bool DMA = false>
 __global__ __launch_bounds__(W8 ? 512 : 256) __attribute__((amdgpu_waves_per_eu(2))) void wino3x3_x3_kernel(const ConvArgs a) {
     static_assert(NT == 4 || (NT == 2 && !FUSE), "64-channel form: plain convolution only");
+    static_assert(!DMA || (NP == 2 && !W8), "halo by LDS-DMA: the four-wave fp16 form");
     static_assert(!W8 || (NT == 4 && NP == 2 && !NEXT && (TX3 || !FUSE)), "eight waves: the fp16 form of the 128-channel kernel, without the next block's conv1");
     constexpr int NTHR = W8 ? 512 : 256;
     static_assert(!NEXT || (FUSE && TX3 && NP == 2), "the next block's conv1 rides on the fp16 tail");
@@ -171,16 +191,38 @@ __global__ __launch_bounds__(W8 ? 512 : 256) __attribute__((amdgpu_waves_per_eu(
 
     // ---- halo staging (as csrc/conv_wino.hip): 180 pixels x 4 float4 per chunk over 256 threads -----------------------------
     constexpr int NF4 = X_NPIX * 4, NLD = (NF4 + NTHR - 1) / NTHR;
+    constexpr int HP = DMA ? 16 : X_PKH;                      // floats per pixel of a halo buffer
+    static_assert(!DMA || (NLD == 3 && NLD * NTHR * 4 <= HSZ), "LDS-DMA staging: three 1 KiB pieces per wave inside a halo buffer");
     int avoff[NLD];
 #pragma unroll
     for (int i = 0; i < NLD; ++i) {
         const int idx = tid + i * NTHR;
-        const int pix = idx >> 2, cc = idx & 3;
+        const int pix = idx >> 2;
         const int py = pix / X_IW, px = pix - py * X_IW;
+        const int cc = DMA ? (idx & 3) ^ ((py >> 1) & 3) : idx & 3;      // DMA: slot idx holds this quad of the pixel (see the kernel's comment)
         const int iy = iy0 + py, ix = ix0 + px;
         const bool ok = idx < NF4 && iy >= 0 && iy < a.H && ix >= 0 && ix < a.W;
         avoff[i] = ok ? ((iy * a.W + ix) * a.C + cc * 4) * 4 : BUF_OOB;
     }
+    // DMA: chunk c -> halo buffer buf, three pieces of 1 KiB per wave at float4 slots (256 i + 64 w) + lane.  M0 = the piece's LDS byte address, written and restored
+    // inside the statement (hipcc reserves M0 and does not see it used here)
+    const unsigned lds_w = __builtin_amdgcn_readfirstlane((unsigned)(size_t)&S[0]) + w * 1024;
+    auto dma = [&](int c, int buf) {
+        if constexpr (DMA) {
+            const unsigned d0 = lds_w + buf * (HSZ * 4), d1 = d0 + NTHR * 16, d2 = d0 + 2 * NTHR * 16;
+            const int soff = c * X_CK * 4;
+            unsigned keep;
+            asm volatile("s_mov_b32 %0, m0\n\t"
+                         "s_nop 4\n\t"
+                         "s_mov_b32 m0, %5\n\ts_nop 0\n\tbuffer_load_dwordx4 %1, %4, %8 offen lds\n\t"
+                         "s_mov_b32 m0, %6\n\ts_nop 0\n\tbuffer_load_dwordx4 %2, %4, %8 offen lds\n\t"
+                         "s_mov_b32 m0, %7\n\ts_nop 0\n\tbuffer_load_dwordx4 %3, %4, %8 offen lds\n\t"
+                         "s_mov_b32 m0, %0"
+                         : "=&s"(keep)
+                         : "v"(avoff[0]), "v"(avoff[NLD > 1 ? 1 : 0]), "v"(avoff[NLD > 2 ? 2 : 0]), "s"(in_srd), "s"(d0), "s"(d1), "s"(d2), "s"(soff)
+                         : "memory");
+        }
+    };
     x_f32x4 areg[NLD];
     auto gload = [&](int c) {
 #pragma unroll
@@ -197,6 +239,13 @@ __global__ __launch_bounds__(W8 ? 512 : 256) __attribute__((amdgpu_waves_per_eu(
                 dmax = s2_track(s2_track(dmax, areg[i][0], areg[i][1]), areg[i][2], areg[i][3]);
             }
             if (idx < NF4) *(x_f32x4*)&Hin[buf][(idx >> 2) * X_PKH + (idx & 3) * 4] = areg[i];
+        }
+    };
+    auto dtrack = [&](int buf) {                              // DMA: the guard's running max over the lane's own slots of a landed buffer (unscaled: times xs at the end)
+#pragma unroll
+        for (int i = 0; i < NLD; ++i) {
+            const x_f32x4 v = *(const x_f32x4*)&Hin[buf][(tid + i * NTHR) * 4];
+            dmax = s2_track(s2_track(dmax, v[0], v[1]), v[2], v[3]);
         }
     };
     // ---- weights: Up3[(chunk * 16 + comp)][nb][plane][lane][8 bf16]: 3 KB per (component, n-tile), three 16-byte loads per lane -----
@@ -217,7 +266,9 @@ __global__ __launch_bounds__(W8 ? 512 : 256) __attribute__((amdgpu_waves_per_eu(
     const int tt = tid & 31, tq = (tid >> 5) & 3, th = (tid >> 7) & 1;
     const int tv = __builtin_amdgcn_readfirstlane(tid >> 8);   // W8: which of the half's two rows this thread computes (0: first - third, 1: second +- other)
     const int t_ty = tt >> 3, t_tx = tt & 7;
-    const int hbase = ((2 * t_ty + th) * X_IW + 2 * t_tx) * X_PKH + tq * 4;
+    const int hbase = ((2 * t_ty + th) * X_IW + 2 * t_tx) * HP + (DMA ? (tq ^ t_ty) : tq) * 4;
+    // DMA: the quad's slot is tq ^ ((R >> 1) & 3), R = the halo row: R >> 1 = t_ty for the thread's rows up to 2 t_ty + 1, t_ty + 1 for the rows from 2 t_ty + 2
+    const int hbase1 = DMA ? ((2 * t_ty + th) * X_IW + 2 * t_tx) * HP + (tq ^ ((t_ty + 1) & 3)) * 4 : hbase;
     // V element offset of (component 0, tile tt, channels 4 tq ..): row tt, half (tq >> 1) swapped where bits 2, 3 of tt differ, 4 bf16 = 8 bytes
     const int vbase = tt * VROW + ((((tq >> 1) ^ (((tt >> 2) ^ (tt >> 3)) & 1)) * 8) + (tq & 1) * 4);
     auto vstore = [&](int comp, x_f32x4 v) {
@@ -239,7 +290,7 @@ __global__ __launch_bounds__(W8 ? 512 : 256) __attribute__((amdgpu_waves_per_eu(
     };
     // rows of B^T d:  half 0 (input rows 0,1,2): xi0 = r0 - r2, xi1 = r1 + r2;  half 1 (rows 1,2,3): xi3 = r1 - r3, xi2 = r2 - r1
     // = (first - third, second +- other) with `other` = third / first row of the half's three: the row is picked by address, the sign is a scalar
-    const int hother = th ? 0 : 2 * X_IW * X_PKH;
+    const int hother = th ? 0 : 2 * X_IW * HP;
     const float hsign = th ? -1.f : 1.f;
     auto transform = [&](int buf) {
         const float* hs = &Hin[buf][hbase];
@@ -261,13 +312,17 @@ __global__ __launch_bounds__(W8 ? 512 : 256) __attribute__((amdgpu_waves_per_eu(
             vstore(xi * 4 + 3, x_sub4(e[1], e[3]));
             return;
         }
+        // (DMA: rows 0 / 2 of the thread's three are in the slots of hbase / hbase1, the middle row and `other` in those of one each, by the half)
+        const float* hs2 = &Hin[buf][hbase1];
+        const float* hs1 = th ? hs2 : hs;
+        const float* hsx = th ? hs : hs2;
         x_f32x4 L0[4], L1[4], L2[4], Lx[4];
 #pragma unroll
         for (int c = 0; c < 4; ++c) {
-            L0[c] = *(const x_f32x4*)(hs + c * X_PKH);
-            L1[c] = *(const x_f32x4*)(hs + (X_IW + c) * X_PKH);
-            L2[c] = *(const x_f32x4*)(hs + (2 * X_IW + c) * X_PKH);
-            Lx[c] = *(const x_f32x4*)(hs + hother + c * X_PKH);
+            L0[c] = *(const x_f32x4*)(hs + c * HP);
+            L1[c] = *(const x_f32x4*)(hs1 + (X_IW + c) * HP);
+            L2[c] = *(const x_f32x4*)(hs2 + (2 * X_IW + c) * HP);
+            Lx[c] = *(const x_f32x4*)(hsx + hother + c * HP);
         }
         x_f32x4 eA[4], eB[4];
 #pragma unroll
@@ -275,6 +330,7 @@ __global__ __launch_bounds__(W8 ? 512 : 256) __attribute__((amdgpu_waves_per_eu(
             eA[c] = x_sub4(L0[c], L2[c]);
             eB[c] = x_f32x4{__builtin_fmaf(Lx[c][0], hsign, L1[c][0]), __builtin_fmaf(Lx[c][1], hsign, L1[c][1]), __builtin_fmaf(Lx[c][2], hsign, L1[c][2]),
                             __builtin_fmaf(Lx[c][3], hsign, L1[c][3])};                      // (a product by +-1 is exact: with or without contraction the same value)
+            if constexpr (DMA) { eA[c] *= xs; eB[c] *= xs; }                                 // the site's 2^s, exact: the register path applies it to the staged elements
         }
         const int xiA = th ? 3 : 0, xiB = th ? 2 : 1;
         // columns: nu0 = c0 - c2, nu1 = c1 + c2, nu2 = c2 - c1, nu3 = c1 - c3
@@ -326,10 +382,21 @@ __global__ __launch_bounds__(W8 ? 512 : 256) __attribute__((amdgpu_waves_per_eu(
     // A operand of component comp: tile = lane & 31, channels 8 (lane >> 5) .. + 7 (the half, swapped as the rows were written)
     const int afoff = (lane & 31) * VROW + (((lane >> 5) ^ (((lane >> 2) ^ (lane >> 3)) & 1)) * 8);
     x_u32x4 bring[2][2][NP];                                  // [slot][which][plane]
-    gload(0);
+    if constexpr (DMA) {
+#pragma unroll
+        for (int i = 0; i < NLD; ++i)                         // the slots no DMA of this lane ever fills (pixels outside the map, the pad behind slot 719), in both buffers
+            if (avoff[i] == BUF_OOB) {
+                *(x_f32x4*)&Hin[0][(tid + i * NTHR) * 4] = x_f32x4{0.f, 0.f, 0.f, 0.f};
+                *(x_f32x4*)&Hin[1][(tid + i * NTHR) * 4] = x_f32x4{0.f, 0.f, 0.f, 0.f};
+            }
+        dma(0, 0);
+    } else {
+        gload(0);
+    }
     bload(comp_of(0, 0), bring[0][0]);
     bload(comp_of(0, 1), bring[0][1]);
-    sstore(0);
+    if constexpr (DMA) asm volatile("s_waitcnt vmcnt(0)" ::: "memory");      // chunk 0 has landed (and, once, the first pair's weights)
+    else sstore(0);
     __syncthreads();
 
 #ifdef SUO_WX3_PROF
@@ -341,12 +408,16 @@ __global__ __launch_bounds__(W8 ? 512 : 256) __attribute__((amdgpu_waves_per_eu(
     for (int c = 0; c < nch; ++c) {
         const int buf = c & 1;
         const bool more = c + 1 < nch;
-        if (more) gload(c + 1);
+        if (more) {
+            if constexpr (DMA) dma(c + 1, buf ^ 1);
+            else gload(c + 1);
+        }
         transform(buf);
+        if constexpr (DMA) dtrack(buf);
         XPROF(0);
         __syncthreads();
         XPROF(1);
-        if (more) sstore(buf ^ 1);
+        if (more && !DMA) sstore(buf ^ 1);
         XPROF(2);
 #pragma unroll
         for (int pair = 0; pair < NPAIR; ++pair) {
@@ -379,9 +450,11 @@ __global__ __launch_bounds__(W8 ? 512 : 256) __attribute__((amdgpu_waves_per_eu(
             __builtin_amdgcn_sched_barrier(0);
         }
         XPROF(3);
+        if constexpr (DMA) asm volatile("s_waitcnt vmcnt(4)" ::: "memory");      // chunk c + 1 has landed; the next pair's four weight loads stay in flight
         __syncthreads();
         XPROF(4);
     }
+    if constexpr (DMA) dmax *= xs;
 #ifdef SUO_WX3_PROF
     if (blockIdx.x == 1000 && (tid & 63) == 0) printf("wave %d cycles: transform %lld  barrier1 %lld  sstore %lld  mfma+fold %lld  barrier2 %lld\n", w, pt[0], pt[1], pt[2], pt[3], pt[4]);
 #endif
@@ -788,6 +861,7 @@ __global__ __launch_bounds__(W8 ? 512 : 256) __attribute__((amdgpu_waves_per_eu(
     }
 }
 
+#ifndef SUO_WX3_DMA_TU
 // Launches of at most one workgroup per CU (<= 256 tiles: a one-frame call, a SLAM pass) take the eight-wave form of the fp16 kernel (W8): there the
 // workgroup's latency IS the launch's duration.  SUO_WINO_W8=0 (supported switch, include/suo_hip.h; read when a launch is issued -- a network's captured
 // graph keeps the form it was captured with, whatever the variable says at a replay): the four-wave form everywhere (A/B);
@@ -797,12 +871,20 @@ bool conv3x3_wino_f16x2_w8(long tiles) {
     return tiles > 0 && tiles <= upto && env_switch("SUO_WINO_W8", 1) != 0;
 }
 
+// The four-wave fp16 kernels stage their halo by LDS-DMA (the kernel's comment: DMA).  SUO_WINO_HALO_DMA=0 (supported switch, include/suo_hip.h; read when a launch is
+// issued, like SUO_WINO_W8 -- a network's captured graph keeps the path it was captured with): the register-staged path (A/B, tests/test_gpu_wino_halo_dma.py: the two
+// paths agree bit for bit).  The DMA kernels are instantiated in csrc/conv_wino_x3_dma.hip (this file compiled again, below): launchers there.
+bool conv3x3_wino_f16x2_dma() { return env_switch("SUO_WINO_HALO_DMA", 1) != 0; }
+int launch_conv3x3_wino_f16x2_dma(const ConvArgs& a, hipStream_t s, int tiles);          // 64 -> 64 or 128 -> 128 by a.N
+int launch_conv3x3_wino_f16x2_fused_dma(const ConvArgs& a, hipStream_t s, int tiles);    // with / without a.up, a.n_W1
+
 // a.Wp = weights packed by pack_wino_weight_bf16x3 / _f16x2 (uint16 under a float pointer); 128 -> 128 or 64 -> 64 channels
 template <int NP>
 static int launch_wino_split(const ConvArgs& a, hipStream_t s) {
     if (NP == 2 && (!a.oscale || !a.range_flag)) { suo_set_error("conv3x3_wino_f16x2: oscale / range_flag missing"); return SUO_ERR_ARG; }
     if (a.OH == a.H && a.OW == a.W && a.N == 64 && a.C == 64) {
         const int tiles64 = ((a.OW + X_TW - 1) / X_TW) * ((a.OH + X_TH - 1) / X_TH) * a.L;
+        if (NP == 2 && conv3x3_wino_f16x2_dma()) return launch_conv3x3_wino_f16x2_dma(a, s, tiles64);
         hipLaunchKernelGGL((wino3x3_x3_kernel<false, false, false, 2, NP>), dim3(tiles64), dim3(256), 0, s, a);
         SUO_HIP_CHECK(hipGetLastError());
         return SUO_OK;
@@ -813,6 +895,7 @@ static int launch_wino_split(const ConvArgs& a, hipStream_t s) {
     }
     const int tiles = ((a.OW + X_TW - 1) / X_TW) * ((a.OH + X_TH - 1) / X_TH) * a.L;
     if (NP == 2 && conv3x3_wino_f16x2_w8(tiles)) hipLaunchKernelGGL((wino3x3_x3_kernel<false, false, false, 4, 2, false, true>), dim3(tiles), dim3(512), 0, s, a);
+    else if (NP == 2 && conv3x3_wino_f16x2_dma()) return launch_conv3x3_wino_f16x2_dma(a, s, tiles);
     else hipLaunchKernelGGL((wino3x3_x3_kernel<false, false, false, 4, NP>), dim3(tiles), dim3(256), 0, s, a);
     SUO_HIP_CHECK(hipGetLastError());
     return SUO_OK;
@@ -827,16 +910,19 @@ int launch_conv3x3_wino_f16x2_fused(const ConvArgs& a, hipStream_t s) {
         return SUO_ERR_ARG;
     }
     const int tiles = ((a.OW + X_TW - 1) / X_TW) * ((a.OH + X_TH - 1) / X_TH) * a.L;
+    const bool dma = conv3x3_wino_f16x2_dma();
     if (a.n_W1) {                                      // ... with the next block's conv1 on the tile (all of n_* set)
         if (!a.n_scale || !a.n_shift || !a.n_osc1 || !a.n_b1 || !a.n_out) { suo_set_error("conv3x3_wino_f16x2_fused: incomplete next-block arguments"); return SUO_ERR_ARG; }
         // (with an up-sampled addend the kernel would need 14-23 registers more than the 256 a two-workgroup-per-CU kernel has: it spilled and measured
         //  SLOWER than the two launches, profiles/REJECTED.md -- not built; csrc/net.hip does not ask for it)
         if (a.up) { suo_set_error("conv3x3_wino_f16x2_fused: the next block's conv1 cannot ride on a tail with an up-sampled addend"); return SUO_ERR_ARG; }
+        if (dma) return launch_conv3x3_wino_f16x2_fused_dma(a, s, tiles);
         hipLaunchKernelGGL((wino3x3_x3_kernel<true, false, true, 4, 2, true>), dim3(tiles), dim3(256), 0, s, a);
     } else if (conv3x3_wino_f16x2_w8(tiles)) {
         if (a.up) hipLaunchKernelGGL((wino3x3_x3_kernel<true, true, true, 4, 2, false, true>), dim3(tiles), dim3(512), 0, s, a);
         else hipLaunchKernelGGL((wino3x3_x3_kernel<true, false, true, 4, 2, false, true>), dim3(tiles), dim3(512), 0, s, a);
-    } else if (a.up) hipLaunchKernelGGL((wino3x3_x3_kernel<true, true, true, 4, 2>), dim3(tiles), dim3(256), 0, s, a);
+    } else if (dma) return launch_conv3x3_wino_f16x2_fused_dma(a, s, tiles);
+    else if (a.up) hipLaunchKernelGGL((wino3x3_x3_kernel<true, true, true, 4, 2>), dim3(tiles), dim3(256), 0, s, a);
     else hipLaunchKernelGGL((wino3x3_x3_kernel<true, false, true, 4, 2>), dim3(tiles), dim3(256), 0, s, a);
     SUO_HIP_CHECK(hipGetLastError());
     return SUO_OK;
@@ -858,5 +944,21 @@ int launch_conv3x3_wino_x3_fused(const ConvArgs& a, hipStream_t s) {
     SUO_HIP_CHECK(hipGetLastError());
     return SUO_OK;
 }
+
+#else      // SUO_WX3_DMA_TU: the launchers of the DMA kernels (arguments checked by the callers above)
+int launch_conv3x3_wino_f16x2_dma(const ConvArgs& a, hipStream_t s, int tiles) {
+    if (a.N == 64) hipLaunchKernelGGL((wino3x3_x3_kernel<false, false, false, 2, 2, false, false, true>), dim3(tiles), dim3(256), 0, s, a);
+    else hipLaunchKernelGGL((wino3x3_x3_kernel<false, false, false, 4, 2, false, false, true>), dim3(tiles), dim3(256), 0, s, a);
+    SUO_HIP_CHECK(hipGetLastError());
+    return SUO_OK;
+}
+int launch_conv3x3_wino_f16x2_fused_dma(const ConvArgs& a, hipStream_t s, int tiles) {
+    if (a.n_W1) hipLaunchKernelGGL((wino3x3_x3_kernel<true, false, true, 4, 2, true, false, true>), dim3(tiles), dim3(256), 0, s, a);
+    else if (a.up) hipLaunchKernelGGL((wino3x3_x3_kernel<true, true, true, 4, 2, false, false, true>), dim3(tiles), dim3(256), 0, s, a);
+    else hipLaunchKernelGGL((wino3x3_x3_kernel<true, false, true, 4, 2, false, false, true>), dim3(tiles), dim3(256), 0, s, a);
+    SUO_HIP_CHECK(hipGetLastError());
+    return SUO_OK;
+}
+#endif
 
 }  // namespace suo

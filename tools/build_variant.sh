@@ -8,11 +8,11 @@ C=$ROOT/suo_slam_amd/csrc
 V=$ROOT/suo_slam_amd/variants
 mkdir -p $V
 FL="--offload-arch=gfx950 -O3 -std=c++17 -fPIC -ffp-contract=off -DSUO_TUNING"     # the tuning knobs of csrc/tune.h read the environment in these builds only
-VAR="conv conv_wino conv_wino_x3 gemm_persist gemm_bf16x3 conv_small res_small res_small_x3 stem_x3 lm_frame lm_frame2 lm_dist ba_stage ba_api ba_ctx ba_drive net net_weights misc"
+VAR="conv conv_wino conv_wino_x3 conv_wino_x3_dma gemm_persist gemm_bf16x3 conv_small res_small res_small_x3 stem_x3 lm_frame lm_frame2 lm_dist ba_stage ba_api ba_ctx ba_drive net net_weights misc"
 for f in $VAR; do /opt/rocm/bin/hipcc $FL "$@" -c $C/$f.hip -o $V/${f}_$NAME.o & done
 wait
 OBJS=""
-for f in capi calibrate pnp pnp_api lm lm_big lm_cam lm_cam2 pose_cov pose_cov_api ba_comm frame_geom eval eval_bop raster eval_vsd slam_score slam_vote; do OBJS="$OBJS $C/$f.o"; done
+for o in $C/*.o; do f=$(basename $o .o); case " $VAR " in *" $f "*) ;; *) OBJS="$OBJS $o";; esac; done      # every other object of the product build (suo_slam_amd/build.py), as it stands
 for f in $VAR; do OBJS="$OBJS $V/${f}_$NAME.o"; done
 /opt/rocm/bin/hipcc --offload-arch=gfx950 -shared -fPIC -o $V/libsuo_hip_$NAME.so $OBJS -ldl
 rm -f $V/*_$NAME.o
