@@ -334,6 +334,15 @@ int suo_stem_f16x2(const void* img_dev, int fmt, int H, int W, const float* boxe
 int suo_stem_f16x2_next(const void* img_dev, int fmt, int H, int W, const float* boxes_dev, const int* box_img_dev, int L, const uint16_t* wh_dev, const float* oscale_dev,
                         const float* bias_dev, float* out_dev, const float* n_scale_dev, const float* n_shift_dev, const uint16_t* n_w1h_dev, const float* n_osc1_dev,
                         const float* n_b1_dev, float* n_out_dev, unsigned* range_flag_dev, void* stream);
+/* Tests only, not thread-safe.  Device pointers to 2^s (one float each; csrc/f16x2.h: a site's activation factor) that the per-stage f16x2 entries above put into
+ * their kernel arguments from now on:
+ *   in    - the entry's input site (suo_conv1x1_f16x2_ex / _pool, suo_conv3x3_wino_f16x2_n, conv2 of the fused tails, conv1 of suo_res_block_f16x2, lin of the chain head)
+ *   inner - the second site: the tail's conv3, the block's conv2, the chain head's tmpOut
+ *   third - the one-launch block's conv3
+ *   next  - the NEXT conv1 of the tail and of the stem (the stem's own site keeps 2^4: its input is the frame)
+ * NULL = the default 2^4; all four NULL restores the behaviour without the hook bit for bit.  The caller passes per-channel factors that belong to the shift
+ * (ldexp(oscale, 4 - s) of what the packers return) and keeps the pointers alive while they are set.  suo_net_* never reads them. */
+int suo_debug_f16x2_stage_sites(const float* in, const float* inner, const float* third, const float* next);
 int suo_maxpool2(const float* in_dev, float* out_dev, int L, int H, int W, int C, void* stream);
 int suo_upsample2_add(const float* up1_dev, const float* low_dev, float* out_dev, int L, int H, int W, int C, void* stream);
 

@@ -121,6 +121,7 @@ SIGNATURES = {
     "suo_ba_lm_solve_update_dev": (C.c_int, [VP, C.c_int, C.c_int, VP, VP, VP, VP, VP]),
     "suo_ba_lm_unit_one_rank_dev": (C.c_int, [VP, C.c_int, VP, VP, VP, VP, VP, VP]),
     "suo_ba_lm_decide_dev": (C.c_int, [VP, VP, VP, VP]),
+    "suo_debug_f16x2_stage_sites": (C.c_int, [VP, VP, VP, VP]),
     "suo_debug_ba_jacobians": (C.c_int, [VP, C.c_int, VP, VP]),
     "suo_debug_cholesky_solve": (C.c_int, [VP, VP, C.c_int, VP, VP]),
     "suo_debug_lm_routes": (C.c_int, [VP, C.c_int, VP, VP]),

@@ -17,6 +17,12 @@ void suo_set_error(const char* fmt, ...) {
 
 struct suo_net { suo::Net* impl; };
 
+// suo_debug_f16x2_stage_sites: the device pointers to 2^s that the per-stage f16x2 entries below hand to their kernels (tests only; Net never reads them)
+static const float* g_site_in = nullptr;
+static const float* g_site_inner = nullptr;
+static const float* g_site_third = nullptr;
+static const float* g_site_next = nullptr;
+
 extern "C" {
 
 const char* suo_last_error(void) { return g_err; }
@@ -88,6 +94,10 @@ int suo_net_get_f16x2_shifts(const suo_net* net, int* out, int n) {
 int suo_net_set_f16x2_shifts(suo_net* net, const int* shifts, int n) {
     if (!net) { suo_set_error("suo_net_set_f16x2_shifts: null net"); return SUO_ERR_ARG; }
     return net->impl->set_f16x2_shifts(shifts, n);
+}
+int suo_debug_f16x2_stage_sites(const float* in, const float* inner, const float* third, const float* next) {
+    g_site_in = in; g_site_inner = inner; g_site_third = third; g_site_next = next;
+    return SUO_OK;
 }
 int suo_f16x2_shift_for(float amax, int ksize, int* out) {
     if (!suo::s2_site_shift(amax, ksize, out)) { suo_set_error("suo_f16x2_shift_for: amax %g / ksize %d not accepted (finite amax >= 0, ksize 1 or 3)", (double)amax, ksize); return SUO_ERR_ARG; }
@@ -221,7 +231,7 @@ int suo_conv1x1_f16x2_pool(const float* a1_dev, int lda1, int K1, const float* p
     suo::GemmArgs g = {};
     g.A1 = a1_dev; g.lda1 = lda1; g.K1 = K1; g.pro_scale = pro_scale_dev; g.pro_shift = pro_shift_dev; g.A2 = a2_dev; g.lda2 = lda2; g.K2 = a2_dev ? K2 : 0;
     g.bias = bias_dev; g.R = r_dev; g.ldr = ldr; g.out = out_dev; g.ldo = ldo; g.M = M; g.N = N; g.n_valid = N; g.relu = relu;
-    g.pool_out = pool_out_dev; g.pool_H = H; g.pool_W = W; g.oscale = oscale_dev; g.range_flag = range_flag_dev;
+    g.pool_out = pool_out_dev; g.pool_H = H; g.pool_W = W; g.oscale = oscale_dev; g.range_flag = range_flag_dev; g.xscale = g_site_in;
     return suo::launch_gemm_f16x2_args(g, w16_dev, (hipStream_t)stream);
 }
 
@@ -242,7 +252,7 @@ int suo_conv3x3_wino_f16x2_n(const float* in, int L, int H, int W, int channels,
                              unsigned* range_flag_dev, void* stream) {
     suo::ConvArgs c = {};
     c.in = in; c.L = L; c.H = H; c.W = W; c.C = channels; c.Wp = (const float*)wq16; c.bias = bias; c.out = out; c.OH = H; c.OW = W; c.N = channels; c.relu = relu;
-    c.oscale = oscale; c.range_flag = range_flag_dev;
+    c.oscale = oscale; c.range_flag = range_flag_dev; c.xscale = g_site_in;
     return suo::launch_conv3x3_wino_f16x2(c, (hipStream_t)stream);
 }
 
@@ -258,6 +268,7 @@ int suo_conv3x3_wino_f16x2_conv1x1_skip_up(const float* in, int L, int H, int W,
     suo::ConvArgs c = {};
     c.in = in; c.L = L; c.H = H; c.W = W; c.C = 128; c.Wp = (const float*)wq16; c.bias = bias2; c.out = nullptr; c.OH = H; c.OW = W; c.N = 128; c.relu = 1;
     c.W3p = (const float*)w3p16; c.bias3 = bias3; c.R = skip; c.out2 = out; c.N2 = 256; c.up = up; c.oscale = oscale2; c.oscale3 = oscale3; c.range_flag = range_flag_dev;
+    c.xscale = g_site_in; c.xscale3 = g_site_inner;
     if (up && ((H | W) & 1)) { suo_set_error("suo_conv3x3_wino_f16x2_conv1x1_skip_up: odd map size"); return SUO_ERR_ARG; }
     return suo::launch_conv3x3_wino_f16x2_fused(c, (hipStream_t)stream);
 }
@@ -269,7 +280,8 @@ int suo_conv3x3_wino_f16x2_conv1x1_skip_up_next(const float* in, int L, int H, i
     suo::ConvArgs c = {};
     c.in = in; c.L = L; c.H = H; c.W = W; c.C = 128; c.Wp = (const float*)wq16; c.bias = bias2; c.out = nullptr; c.OH = H; c.OW = W; c.N = 128; c.relu = 1;
     c.W3p = (const float*)w3p16; c.bias3 = bias3; c.R = skip; c.out2 = out; c.N2 = 256; c.up = up; c.oscale = oscale2; c.oscale3 = oscale3; c.range_flag = range_flag_dev;
-    c.n_scale = next_scale; c.n_shift = next_shift; c.n_W1 = (const float*)next_w1h; c.n_osc1 = next_osc1; c.n_b1 = next_b1; c.n_out = next_out;
+    c.xscale = g_site_in; c.xscale3 = g_site_inner;
+    c.n_scale = next_scale; c.n_shift = next_shift; c.n_W1 = (const float*)next_w1h; c.n_osc1 = next_osc1; c.n_b1 = next_b1; c.n_out = next_out; c.n_xscale = g_site_next;
     if (!next_w1h) { suo_set_error("suo_conv3x3_wino_f16x2_conv1x1_skip_up_next: next_w1h is NULL"); return SUO_ERR_ARG; }
     if (up && ((H | W) & 1)) { suo_set_error("suo_conv3x3_wino_f16x2_conv1x1_skip_up_next: odd map size"); return SUO_ERR_ARG; }
     return suo::launch_conv3x3_wino_f16x2_fused(c, (hipStream_t)stream);
@@ -398,13 +410,14 @@ int suo_res_block_f16x2(const float* x, int L, int H, int W, int pool_in, const 
     suo::ResBlockArgs a = {};
     a.x = x; a.L = L; a.H = H; a.W = W; a.pool_in = pool_in; a.pro_scale = pro_scale; a.pro_shift = pro_shift;
     a.W1 = (const float*)w1h; a.b1 = b1; a.W2 = (const float*)w2h; a.b2 = b2; a.W3 = (const float*)w3h; a.b3 = b3; a.up = up; a.out = out;
-    a.osc1 = osc1; a.osc2 = osc2; a.osc3 = osc3; a.range_flag = range_flag_dev;
+    a.osc1 = osc1; a.osc2 = osc2; a.osc3 = osc3; a.range_flag = range_flag_dev; a.xs1 = g_site_in; a.xs2 = g_site_inner; a.xs3 = g_site_third;
     return suo::launch_res_block_f16x2(a, (hipStream_t)stream);
 }
 
 int suo_conv1x1_chain_head_f16x2(const float* a, int lda, int M, const uint16_t* w1h, const float* osc1, const float* bias1, const uint16_t* w2h, const float* osc2,
                                  const float* bias2, float* out_nchw, int n_valid, int hw, unsigned* range_flag_dev, void* stream) {
-    return suo::launch_gemm_chain_head(a, lda, M, w1h, osc1, bias1, w2h, osc2, bias2, out_nchw, n_valid, hw, range_flag_dev, (hipStream_t)stream);
+    return suo::launch_gemm_chain_head(a, lda, M, w1h, osc1, bias1, w2h, osc2, bias2, out_nchw, n_valid, hw, range_flag_dev, (hipStream_t)stream, g_site_in,
+                                       g_site_inner);
 }
 
 int suo_pack_stem_weight_bf16x3(const float* w, int Cw, const float* scale, uint16_t* out) {
@@ -429,7 +442,7 @@ int suo_stem_f16x2_next(const void* img, int fmt, int H, int W, const float* box
                         float* out, const float* n_scale, const float* n_shift, const uint16_t* n_w1h, const float* n_osc1, const float* n_b1, float* n_out,
                         unsigned* range_flag_dev, void* stream) {
     if (!oscale || !range_flag_dev) { suo_set_error("suo_stem_f16x2_next: null argument"); return SUO_ERR_ARG; }
-    const suo::StemNext nx = {n_scale, n_shift, n_w1h, n_osc1, n_b1, n_out};
+    const suo::StemNext nx = {n_scale, n_shift, n_w1h, n_osc1, n_b1, n_out, g_site_next};
     return suo::launch_stem_x3(img, fmt, H, W, boxes, box_img, L, wh, bias, out, (hipStream_t)stream, oscale, range_flag_dev, &nx);
 }
 

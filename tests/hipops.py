@@ -1,4 +1,5 @@
 """Thin test helpers that call the per-stage C-ABI entry points of libsuo_hip.so on torch CUDA tensors."""
+import contextlib
 import ctypes as C
 
 import numpy as np
@@ -216,6 +217,36 @@ def _flag():
     return torch.zeros(1, dtype=torch.int32, device="cuda")
 
 
+# Site shifts (csrc/f16x2.h: activations enter a convolution's split times 2^s) the helpers below run at: None = the default s = 4.
+_SITES = {"in": None, "inner": None, "third": None, "next": None}
+
+
+@contextlib.contextmanager
+def sites(in_=None, inner=None, third=None, next=None):
+    """Run the f16x2 helpers below at the given site shifts (suo_debug_f16x2_stage_sites; the sites as include/suo_hip.h names them): uploads 2^s, sets the hook and
+    has the helpers pass ldexp(oscale, 4 - s) for the convolution whose input site is at s -- what Net::set_f16x2_shifts does to a network's factor arrays.
+    Cleared on exit, also when the body raises.  Not nestable."""
+    shifts = {"in": in_, "inner": inner, "third": third, "next": next}
+    assert all(v is None for v in _SITES.values()), "hipops.sites does not nest"
+    xs = {k: dev(np.array([np.ldexp(1.0, v)], np.float32)) if v is not None else None for k, v in shifts.items()}
+    lib = _lib.lib()
+    _lib.check(lib.suo_debug_f16x2_stage_sites(P(xs["in"]), P(xs["inner"]), P(xs["third"]), P(xs["next"])), "suo_debug_f16x2_stage_sites")
+    _SITES.update(shifts)
+    try:
+        yield
+    finally:
+        for k in _SITES:
+            _SITES[k] = None
+        torch.cuda.synchronize()                                   # (no launch still reads xs when it is freed)
+        _lib.check(lib.suo_debug_f16x2_stage_sites(None, None, None, None), "suo_debug_f16x2_stage_sites")
+
+
+def _osc(osc, site):
+    """The per-channel factors 2^-(t_n + 4) of a packer as the device array of the convolution whose input is `site`: 2^-(t_n + s) at the shift in effect (exact)."""
+    s = _SITES[site]
+    return dev(osc if s is None else np.ldexp(osc, 4 - s).astype(np.float32))
+
+
 def pack_gemm_f16x2(w):
     """-> (planes int16 cuda [2*N*K], oscale cuda [N], oscale numpy)"""
     w = np.ascontiguousarray(w, np.float32)
@@ -232,7 +263,8 @@ def conv1x1_f16x2(a1, w1, bias, pro=None, a2=None, w2=None, res=None, relu=False
     N = w1.shape[0]
     K2 = a2.shape[1] if a2 is not None else 0
     full = np.concatenate([w1, w2], 1) if a2 is not None else w1
-    w16, osc, _ = pack_gemm_f16x2(full)
+    w16, _, osc = pack_gemm_f16x2(full)
+    osc = _osc(osc, "in")
     b = dev(bias)
     out = torch.empty((M, N), device="cuda")
     flag = _flag()
@@ -260,12 +292,12 @@ def _pack_f16x2(w2, w3=None):
     _lib.check(lib.suo_pack_wino_weight_f16x2(w2.ctypes.data, n, n, q.ctypes.data, o2.ctypes.data), "pack_wino_f16x2")
     wq = torch.from_numpy(q.view(np.int16)).cuda()
     if w3 is None:
-        return wq, dev(o2)
+        return wq, _osc(o2, "in")
     w3 = np.ascontiguousarray(w3, np.float32)
     t = np.empty(2 * 256 * 128, np.uint16)
     o3 = np.empty(256, np.float32)
     _lib.check(lib.suo_pack_tail_weight_f16x2(w3.ctypes.data, 256, 128, t.ctypes.data, o3.ctypes.data), "pack_tail_f16x2")
-    return wq, dev(o2), torch.from_numpy(t.view(np.int16)).cuda(), dev(o3)
+    return wq, _osc(o2, "in"), torch.from_numpy(t.view(np.int16)).cuda(), _osc(o3, "inner")
 
 
 def conv3x3_wino_f16x2(x_nhwc, w, bias, relu=False):
@@ -335,7 +367,8 @@ def conv3x3_wino_f16x2_tail_next(x_nhwc, w2, b2, w3, b3, skip_nhwc, up_nhwc, n_p
     """The fused Residual tail on two fp16 terms WITH the next block's conv1 (csrc/conv_wino_x3.hip, NEXT): returns (out [L,H,W,256], next_mid1 [L,H,W,128], flag)."""
     L, H, W, C = x_nhwc.shape
     wq, o2, w3p, o3 = _pack_f16x2(w2, w3)
-    w1h, osc1, _ = pack_gemm_f16x2(n_w1)
+    w1h, _, osc1 = pack_gemm_f16x2(n_w1)
+    osc1 = _osc(osc1, "next")
     out = torch.empty((L, H, W, 256), device="cuda")
     nxt = torch.full((L, H, W, 128), -7.0, device="cuda")
     b2d, b3d, ns, nt, nb = dev(b2), dev(b3), dev(n_pro[0]), dev(n_pro[1]), dev(n_b1)
@@ -358,7 +391,7 @@ def res_block_f16x2(x_nhwc, pro, w1, b1, w2, b2, w3, b3, up_nhwc=None, pool_in=F
     _lib.check(lib.suo_pack_res_block_f16x2(w1.ctypes.data, w2.ctypes.data, None, w3.ctypes.data, p1.ctypes.data, p2.ctypes.data, p3.ctypes.data, o1.ctypes.data,
                                             o2.ctypes.data, o3.ctypes.data), "suo_pack_res_block_f16x2")
     dw = [torch.from_numpy(t.view(np.int16)).cuda() for t in (p1, p2, p3)]
-    do = [dev(t) for t in (o1, o2, o3)]
+    do = [_osc(o1, "in"), _osc(o2, "inner"), _osc(o3, "third")]
     d = [dev(t) for t in (pro[0], pro[1], b1, b2, b3)]
     out = torch.empty((L, H, W, 256), device="cuda")
     flag = _flag()
@@ -371,8 +404,9 @@ def res_block_f16x2(x_nhwc, pro, w1, b1, w2, b2, w3, b3, up_nhwc=None, pool_in=F
 def conv1x1_chain_head_f16x2(a, w1, b1, w2, b2, n_valid, hw):
     """csrc/gemm_bf16x3.hip: gemm_chain_head_kernel.  a [M,256] cuda; w1 [256,256], b1 [256]; w2 [64,256] (rows >= n_valid zero), b2 [64] -> (NCHW [M/hw, n_valid, hw], flag)."""
     M = a.shape[0]
-    w1h, o1, _ = pack_gemm_f16x2(w1)
-    w2h, o2, _ = pack_gemm_f16x2(w2)
+    w1h, _, o1 = pack_gemm_f16x2(w1)
+    w2h, _, o2 = pack_gemm_f16x2(w2)
+    o1, o2 = _osc(o1, "in"), _osc(o2, "inner")
     b1d, b2d = dev(b1), dev(b2)
     out = torch.full((M // hw, n_valid, hw), float("nan"), device="cuda")
     flag = _flag()
@@ -380,3 +414,29 @@ def conv1x1_chain_head_f16x2(a, w1, b1, w2, b2, n_valid, hw):
                "suo_conv1x1_chain_head_f16x2")
     torch.cuda.synchronize()
     return out, int(flag.item())
+
+
+def stem_f16x2(imgd, fmt, boxes, idx, w, scale, bias, nxt=None):
+    """csrc/stem_x3.hip with NP = 2 on 480 x 640 frames: RoIAlign + conv 7x7 / 2 + BN + ReLU; nxt = (pro_scale, pro_shift, w1 [64,64], b1 [64]): the first Residual block's
+    conv1 in the same launch (suo_stem_f16x2_next).  The stem's own site stays at 2^4; conv1's is the `next` site.  Returns (out [L,128,128,64], mid or None, flag)."""
+    lib = _lib.lib()
+    L = len(boxes)
+    w = np.ascontiguousarray(w, np.float32)
+    wh, osc = np.empty(14 * 2 * 2 * 64 * 8, np.uint16), np.empty(64, np.float32)
+    _lib.check(lib.suo_pack_stem_weight_f16x2(w.ctypes.data, w.shape[1], scale.ctypes.data, wh.ctypes.data, osc.ctypes.data), "suo_pack_stem_weight_f16x2")
+    whd, od, bd = torch.from_numpy(wh.view(np.int16)).cuda(), dev(osc), dev(bias)
+    boxd, idxd = dev(boxes), torch.from_numpy(idx).cuda()
+    flag = _flag()
+    out = torch.full((L, 128, 128, 64), -7.0, device="cuda")
+    if nxt is None:
+        _lib.check(lib.suo_stem_f16x2(P(imgd), fmt, 480, 640, P(boxd), P(idxd), L, P(whd), P(od), P(bd), P(out), P(flag), S()), "suo_stem_f16x2")
+        torch.cuda.synchronize()
+        return out, None, int(flag.item())
+    w1h, _, o1 = pack_gemm_f16x2(nxt[2])
+    o1 = _osc(o1, "next")
+    psd, ptd, b1d = dev(nxt[0]), dev(nxt[1]), dev(nxt[3])
+    mid = torch.full((L, 128, 128, 64), -7.0, device="cuda")
+    _lib.check(lib.suo_stem_f16x2_next(P(imgd), fmt, 480, 640, P(boxd), P(idxd), L, P(whd), P(od), P(bd), P(out), P(psd), P(ptd), P(w1h), P(o1), P(b1d), P(mid), P(flag), S()),
+               "suo_stem_f16x2_next")
+    torch.cuda.synchronize()
+    return out, mid, int(flag.item())

@@ -1,4 +1,5 @@
-"""Per-element forward-error gates of the bf16x3 kernels (the network's default matrix-pipe form, csrc/bf16x3.h).
+"""Per-element forward-error gates of the bf16x3 kernels (csrc/bf16x3.h: the network's range-safe matrix-pipe form -- what SUO_F16X2=0 selects and what a
+call falls back to when an activation leaves fp16's range; the default form is the two-term fp16 one, csrc/f16x2.h, held to the same gates by tests/test_gpu_f16x2.py).
 
 The other kernel tests bound the LARGEST error by the output RANGE; a split that lost its small terms only where they sit next to large
 ones, or that pulled every product toward zero, would pass those.  Here every output element i is held to a bound that scales with ITS
