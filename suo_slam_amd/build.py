@@ -34,8 +34,6 @@ def build(force: bool = False, verbose: bool = True) -> str:
         deps = [src] + hdrs
         if src.endswith("lm_big.hip"):
             deps.append(os.path.join(CSRC, "lm.hip"))        # lm_big.hip re-compiles lm.hip with 1024 threads
-        if src.endswith("conv_wino_x3_dma.hip"):
-            deps.append(os.path.join(CSRC, "conv_wino_x3.hip"))      # ... and conv_wino_x3_dma.hip conv_wino_x3.hip for its DMA kernels
         if force or _stale(obj, deps):
             cmd = [HIPCC] + FLAGS + ["-c", src, "-o", obj]
             if verbose:

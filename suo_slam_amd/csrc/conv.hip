@@ -20,6 +20,7 @@
 #include <type_traits>
 
 #include "buffer_ops.h"
+#include "mma_ops.h"
 #include "suo_internal.h"
 #include "tune.h"
 
@@ -43,9 +44,6 @@
 
 namespace suo {
 
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-
 // -DSUO_CONV_PROFILE (tools/micro/conv_prof.hip only): per-workgroup timestamps of the KxK kernel's phases
 #ifdef SUO_CONV_PROFILE
 __device__ long long g_conv_prof[16384 * 8];
@@ -57,12 +55,6 @@ __device__ long long g_conv_prof_clk[16384 * 8];     // the same points on the s
 #endif
 
 size_t packed_weight_floats(int n_pad, int k_pad) { return (size_t)n_pad * (size_t)k_pad; }
-
-__device__ __forceinline__ f32x16 mfma32(float a, float b, f32x16 c) {
-    return __builtin_amdgcn_mfma_f32_32x32x2f32(a, b, c, 0, 0, 0);
-}
-// row of accumulator register r for this lane inside a 32x32 tile (col = lane & 31)
-__device__ __forceinline__ int acc_row(int r, int lane) { return (r & 3) + 8 * (r >> 2) + 4 * (lane >> 5); }
 
 // =================================================================================================
 // 1x1 convolution: out[M,N] = epi( pro(A1)[M,K1] * W1 + A2[M,K2] * W2 + bias (+ R) )
@@ -81,8 +73,7 @@ __global__ __launch_bounds__(WGM* WGN * 64) void gemm1x1_kernel(const GemmArgs a
     // 1-D grid, XCD-aware order (workgroup b runs on XCD b % 8): each XCD gets a contiguous run of tiles with the
     // N-tiles of one pixel tile adjacent, so the A tile they share is fetched from HBM once and re-read from that L2
     const int ntn = a.N / BN;
-    int bid = blockIdx.x;
-    if ((gridDim.x & 7) == 0) bid = (bid & 7) * (gridDim.x >> 3) + (bid >> 3);
+    int bid = xcd_block_id();
     const int m0 = (bid / ntn) * BM, n0 = (bid % ntn) * BN;
     const int nch1 = a.K1 >> 5, nch = nch1 + (a.K2 >> 5);
     const int NB = a.N >> 5;
@@ -189,7 +180,7 @@ __global__ __launch_bounds__(WGM* WGN * 64) void gemm1x1_kernel(const GemmArgs a
                 // stores, 8 full 128-byte lines per instruction, all residual loads in flight before the first store
                 float* T = &As[0][0] + w * (32 * PK);
 #pragma unroll
-                for (int r = 0; r < 16; ++r) T[acc_row(r, lane) * PK + (lane & 31)] = acc[i][j][r];
+                for (int r = 0; r < 16; ++r) T[patch_at<PK>(r, lane)] = acc[i][j][r];
                 __builtin_amdgcn_wave_barrier();
                 const int col = n0 + (wn * TN + j) * 32 + (lane & 7) * 4;
                 const f32x4 bv = *(const f32x4*)(a.bias + col);
@@ -199,7 +190,7 @@ __global__ __launch_bounds__(WGM* WGN * 64) void gemm1x1_kernel(const GemmArgs a
                     const int row = m0 + (wm * TM + i) * 32 + (lane >> 3) + 8 * k;
                     rv[k] = f32x4{0.f, 0.f, 0.f, 0.f};
                     if (a.R && row < a.M && col < a.n_valid) rv[k] = *(const f32x4*)(a.R + (size_t)row * a.ldr + col);
-                    v[k] = *(const f32x4*)&T[((lane >> 3) + 8 * k) * PK + (lane & 7) * 4];
+                    v[k] = patch_row4<PK>(T, lane, k);
                 }
 #pragma unroll
                 for (int k = 0; k < 4; ++k) {
@@ -301,8 +292,7 @@ __global__ __launch_bounds__(WGM* WGN * 64) __attribute__((amdgpu_waves_per_eu(S
     const int tiles_x = (a.OW + TW - 1) / TW, tiles_y = (a.OH + TH - 1) / TH;
     // XCD-aware tile order: workgroup b runs on XCD b % 8 (observed placement; used for speed only), so give each
     // XCD a contiguous run of tiles -- neighbouring tiles share halo rows / columns and then hit the same L2
-    int bid = blockIdx.x;
-    if ((gridDim.x & 7) == 0) bid = (bid & 7) * (gridDim.x >> 3) + (bid >> 3);
+    int bid = xcd_block_id();
     const int l = bid / (tiles_x * tiles_y);
     bid -= l * tiles_x * tiles_y;
     const int ty = bid / tiles_x, tx = bid - ty * tiles_x;
@@ -546,11 +536,11 @@ __global__ __launch_bounds__(WGM* WGN * 64) __attribute__((amdgpu_waves_per_eu(S
                         rv[k] = buf_load(r_srd, off[k], 0);
                     }
 #pragma unroll
-                    for (int r = 0; r < 16; ++r) T[acc_row(r, lane) * 36 + (lane & 31)] = acc2[i][j][r];
+                    for (int r = 0; r < 16; ++r) T[patch_at(r, lane)] = acc2[i][j][r];
                     __builtin_amdgcn_wave_barrier();
 #pragma unroll
                     for (int k = 0; k < 4; ++k) {
-                        const f32x4 o = (*(const f32x4*)&T[((lane >> 3) + 8 * k) * 36 + (lane & 7) * 4] + bv) + rv[k];
+                        const f32x4 o = (patch_row4(T, lane, k) + bv) + rv[k];
                         buf_store(o, o2_srd, off[k]);
                     }
                     __builtin_amdgcn_wave_barrier();
@@ -572,7 +562,7 @@ __global__ __launch_bounds__(WGM* WGN * 64) __attribute__((amdgpu_waves_per_eu(S
             static_assert(2 * ASZ >= WGM * WGN * 32 * 36, "epilogue patch must fit the A buffers");
             float* T = &As[0][0] + w * (32 * 36);
 #pragma unroll
-            for (int r = 0; r < 16; ++r) T[acc_row(r, lane) * 36 + (lane & 31)] = acc[i][j][r];
+            for (int r = 0; r < 16; ++r) T[patch_at(r, lane)] = acc[i][j][r];
             __builtin_amdgcn_wave_barrier();
             const int col = n0 + (wn * TN + j) * 32 + (lane & 7) * 4;
             const f32x4 bv = *(const f32x4*)(a.bias + col);
@@ -582,7 +572,7 @@ __global__ __launch_bounds__(WGM* WGN * 64) __attribute__((amdgpu_waves_per_eu(S
                 const int p = (wm * TM + i) * 32 + pr;
                 const int py = p / TW, px = p - py * TW;
                 const int oy = oy0 + py, ox = ox0 + px;
-                f32x4 o = *(const f32x4*)&T[pr * 36 + (lane & 7) * 4] + bv;
+                f32x4 o = patch_row4_at(T, pr, lane) + bv;
                 if (a.relu) {
 #pragma unroll
                     for (int t = 0; t < 4; ++t) o[t] = fmaxf(o[t], 0.f);

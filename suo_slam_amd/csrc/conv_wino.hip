@@ -18,42 +18,43 @@
 // Numerics: fp32 throughout; the transforms add at most 4 terms on either side, so the result differs from the direct
 // kernel by summation order and by the rounding of U (observed <= 2e-6 of the output range).
 #include "buffer_ops.h"
+#include "mma_ops.h"
 #include "suo_internal.h"
 #include "tune.h"
 
 namespace suo {
 
-typedef float w_f32x4 __attribute__((ext_vector_type(4)));
-typedef float w_f32x16 __attribute__((ext_vector_type(16)));
-
-__device__ __forceinline__ w_f32x16 w_mfma32(float a, float b, w_f32x16 c) { return __builtin_amdgcn_mfma_f32_32x32x2f32(a, b, c, 0, 0, 0); }
-__device__ __forceinline__ int w_acc_row(int r, int lane) { return (r & 3) + 8 * (r >> 2) + 4 * (lane >> 5); }
-
 constexpr int W_CK = 16, W_PKH = 20, W_PKV = 20, W_TH = 8, W_TW = 16, W_IH = 10, W_IW = 18, W_NPIX = W_IH * W_IW;
 constexpr int W_RING = 8;
 
-// host: U[n][c][comp] = (G g G^T)[xi][nu], comp = 4 xi + nu, in fp64; packed as
-//   Up[chunk][comp][s][nb][lane][t] = +-U[nb*32 + (lane&31)][chunk*16 + s*8 + (lane>>5)*4 + t][comp]      (N, C multiples of 32 / 16;
-//   the components of row xi = 3 are stored NEGATED: A^T[.][3] = (0, -1), so their products accumulate straight into Z[1][nu])
-void pack_wino_weight(const float* W, int N, int C, int Np, int Cp, const float* out_scale, float* out) {
+// host: the 16 components U[4 xi + nu] = (G g G^T)[xi][nu] * scale of one filter g[3][3] (scale: the folded BatchNorm factor of its output channel), in fp64,
+// rounded once to fp32.  Row xi = 3 is NEGATED: A^T[.][3] = (0, -1), it enters the output transform with -1 only, so its products accumulate straight
+// into Z[1][nu].  Every packer of Winograd weights (here and csrc/conv_wino_x3.hip) lays out and splits these values.
+void wino_weight_transform(const float* g, double scale, float U[16]) {
     static const double G[4][3] = {{1, 0, 0}, {0.5, 0.5, 0.5}, {0.5, -0.5, 0.5}, {0, 0, 1}};
-    const int nch = Cp / W_CK, NB = Np / 32;
+    double Gg[4][3];
+    for (int i = 0; i < 4; ++i)
+        for (int j = 0; j < 3; ++j) Gg[i][j] = G[i][0] * g[j] + G[i][1] * g[3 + j] + G[i][2] * g[6 + j];
+    for (int i = 0; i < 4; ++i)
+        for (int j = 0; j < 4; ++j) {
+            const double u = (Gg[i][0] * G[j][0] + Gg[i][1] * G[j][1] + Gg[i][2] * G[j][2]) * scale;
+            U[4 * i + j] = (float)(i == 3 ? -u : u);
+        }
+}
+
+// host: U[n][c][comp] = wino_weight_transform of filter (n, c); packed as
+//   Up[chunk][comp][s][nb][lane][t] = +-U[nb*32 + (lane&31)][chunk*16 + s*8 + (lane>>5)*4 + t][comp]      (N, C multiples of 32 / 16)
+void pack_wino_weight(const float* W, int N, int C, int Np, int Cp, const float* out_scale, float* out) {
+    const int NB = Np / 32;
     for (size_t i = 0; i < (size_t)Np * Cp * 16; ++i) out[i] = 0.f;
     for (int n = 0; n < N; ++n)
         for (int c = 0; c < C; ++c) {
-            const float* g = W + ((size_t)n * C + c) * 9;
-            const double sc = out_scale ? (double)out_scale[n] : 1.0;
-            double Gg[4][3], U[4][4];
-            for (int i = 0; i < 4; ++i)
-                for (int j = 0; j < 3; ++j) Gg[i][j] = G[i][0] * g[j] + G[i][1] * g[3 + j] + G[i][2] * g[6 + j];
-            for (int i = 0; i < 4; ++i)
-                for (int j = 0; j < 4; ++j) U[i][j] = (Gg[i][0] * G[j][0] + Gg[i][1] * G[j][1] + Gg[i][2] * G[j][2]) * sc;
+            float U[16];
+            wino_weight_transform(W + ((size_t)n * C + c) * 9, out_scale ? (double)out_scale[n] : 1.0, U);
             const int chunk = c / W_CK, cc = c % W_CK, s = cc / 8, half = (cc % 8) / 4, t = cc % 4;
             const int nb = n / 32, lane = half * 32 + (n % 32);
-            for (int comp = 0; comp < 16; ++comp)
-                out[((((size_t)(chunk * 16 + comp) * 2 + s) * NB + nb) * 64 + lane) * 4 + t] = (float)(comp >= 12 ? -U[comp >> 2][comp & 3] : U[comp >> 2][comp & 3]);      // xi = 3 enters the output transform with -1 only: stored negated
+            for (int comp = 0; comp < 16; ++comp) out[((((size_t)(chunk * 16 + comp) * 2 + s) * NB + nb) * 64 + lane) * 4 + t] = U[comp];
         }
-    (void)nch;
 }
 
 // NT = output channels / 32: 4 (128 channels: wave w owns n-tile w and all 16 components) or 2 (64 channels: wave (wc, wn) owns
@@ -68,8 +69,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2))) void w
     const int tid = threadIdx.x, lane = tid & 63;
     const int w = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int tiles_x = (a.OW + W_TW - 1) / W_TW, tiles_y = (a.OH + W_TH - 1) / W_TH;
-    int bid = blockIdx.x;
-    if ((gridDim.x & 7) == 0) bid = (bid & 7) * (gridDim.x >> 3) + (bid >> 3);          // XCD-aware tile order (csrc/conv.hip)
+    int bid = xcd_block_id();          // XCD-aware tile order (csrc/mma_ops.h)
     const int l = bid / (tiles_x * tiles_y);
     bid -= l * tiles_x * tiles_y;
     const int ty0 = bid / tiles_x, tx0 = bid - ty0 * tiles_x;
@@ -93,7 +93,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2))) void w
         const bool ok = idx < NF4 && iy >= 0 && iy < a.H && ix >= 0 && ix < a.W;
         avoff[i] = ok ? ((iy * a.W + ix) * a.C + cc * 4) * 4 : BUF_OOB;
     }
-    w_f32x4 areg[NLD];
+    f32x4 areg[NLD];
     auto gload = [&](int c) {
 #pragma unroll
         for (int i = 0; i < NLD; ++i) areg[i] = buf_load(in_srd, avoff[i], c * W_CK * 4);
@@ -102,7 +102,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2))) void w
 #pragma unroll
         for (int i = 0; i < NLD; ++i) {
             const int idx = tid + i * 256;
-            if (idx < NF4) *(w_f32x4*)&Hin[buf][(idx >> 2) * W_PKH + (idx & 3) * 4] = areg[i];
+            if (idx < NF4) *(f32x4*)&Hin[buf][(idx >> 2) * W_PKH + (idx & 3) * 4] = areg[i];
         }
     };
     // ---- weights: Up[gg][nb][lane][4], gg = (chunk * 16 + comp) * 2 + s; wave w owns n-tile w ---------------------------
@@ -111,8 +111,8 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2))) void w
     constexpr int NPAIR = NT == 4 ? 8 : 4, KSEQ = NPAIR * 4;                 // component pairs / weight groups per chunk and wave
     const int wvoff = (wn * 64 + lane) * 16;
     const int gtot = nch * 32;
-    w_f32x4 bring[W_RING];
-    auto bload = [&](int gg, w_f32x4& b) {
+    f32x4 bring[W_RING];
+    auto bload = [&](int gg, f32x4& b) {
         const int gc = gg < gtot ? gg : gtot - 1;
         b = buf_load(w_srd, wvoff, gc * NB * 1024);
     };
@@ -123,15 +123,15 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2))) void w
     const int vbase = tt * W_PKV + tq * 4;
     auto transform = [&](int buf) {
         const float* hs = &Hin[buf][hbase];
-        w_f32x4 L0[4], L1[4], L2[4];
+        f32x4 L0[4], L1[4], L2[4];
 #pragma unroll
         for (int c = 0; c < 4; ++c) {
-            L0[c] = *(const w_f32x4*)(hs + c * W_PKH);
-            L1[c] = *(const w_f32x4*)(hs + (W_IW + c) * W_PKH);
-            L2[c] = *(const w_f32x4*)(hs + (2 * W_IW + c) * W_PKH);
+            L0[c] = *(const f32x4*)(hs + c * W_PKH);
+            L1[c] = *(const f32x4*)(hs + (W_IW + c) * W_PKH);
+            L2[c] = *(const f32x4*)(hs + (2 * W_IW + c) * W_PKH);
         }
         // rows of B^T d:  half 0 (input rows 0,1,2): xi0 = r0 - r2, xi1 = r1 + r2;  half 1 (rows 1,2,3): xi3 = r1 - r3, xi2 = r2 - r1
-        w_f32x4 eA[4], eB[4];
+        f32x4 eA[4], eB[4];
 #pragma unroll
         for (int c = 0; c < 4; ++c) {
             eA[c] = L0[c] - L2[c];
@@ -141,17 +141,17 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2))) void w
         float* va = &V[(xiA * 4) * 32 * W_PKV + vbase];
         float* vb = &V[(xiB * 4) * 32 * W_PKV + vbase];
         // columns: nu0 = c0 - c2, nu1 = c1 + c2, nu2 = c2 - c1, nu3 = c1 - c3
-        *(w_f32x4*)(va + 0 * 32 * W_PKV) = eA[0] - eA[2];
-        *(w_f32x4*)(va + 1 * 32 * W_PKV) = eA[1] + eA[2];
-        *(w_f32x4*)(va + 2 * 32 * W_PKV) = eA[2] - eA[1];
-        *(w_f32x4*)(va + 3 * 32 * W_PKV) = eA[1] - eA[3];
-        *(w_f32x4*)(vb + 0 * 32 * W_PKV) = eB[0] - eB[2];
-        *(w_f32x4*)(vb + 1 * 32 * W_PKV) = eB[1] + eB[2];
-        *(w_f32x4*)(vb + 2 * 32 * W_PKV) = eB[2] - eB[1];
-        *(w_f32x4*)(vb + 3 * 32 * W_PKV) = eB[1] - eB[3];
+        *(f32x4*)(va + 0 * 32 * W_PKV) = eA[0] - eA[2];
+        *(f32x4*)(va + 1 * 32 * W_PKV) = eA[1] + eA[2];
+        *(f32x4*)(va + 2 * 32 * W_PKV) = eA[2] - eA[1];
+        *(f32x4*)(va + 3 * 32 * W_PKV) = eA[1] - eA[3];
+        *(f32x4*)(vb + 0 * 32 * W_PKV) = eB[0] - eB[2];
+        *(f32x4*)(vb + 1 * 32 * W_PKV) = eB[1] + eB[2];
+        *(f32x4*)(vb + 2 * 32 * W_PKV) = eB[2] - eB[1];
+        *(f32x4*)(vb + 3 * 32 * W_PKV) = eB[1] - eB[3];
     };
 
-    w_f32x16 zero16;
+    f32x16 zero16;
 #pragma unroll
     for (int r = 0; r < 16; ++r) zero16[r] = 0.f;
     // Output transform Y = A^T M A in two steps.  128-channel form: the accumulators are Z[i][nu] = sum_xi A^T[i][xi] M(xi,nu), 8 of
@@ -163,7 +163,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2))) void w
     // (rows xi = 2 wc, 2 wc + 1) and one accumulator per component -- no additions in the channel loop at all; the rows meet in the
     // exchange after it.
     constexpr int NZ = 8;
-    w_f32x16 out[4], Z[NZ];
+    f32x16 out[4], Z[NZ];
 #pragma unroll
     for (int p = 0; p < 4; ++p)
 #pragma unroll
@@ -213,7 +213,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2))) void w
         };
 #pragma unroll
         for (int pair = 0; pair < NPAIR; ++pair) {
-            w_f32x16 ta, tb;
+            f32x16 ta, tb;
             const bool direct = NT == 2 || pair < 4;              // accumulate into their own Z, no scratch, no additions
             const int za = NT == 4 ? pair : 2 * pair, zb = NT == 4 ? 4 + pair : 2 * pair + 1;       // (64-channel form: Z[local component])
             const int ca = comp_of(pair, 0), cb = comp_of(pair, 1);
@@ -222,17 +222,17 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2))) void w
                 const int k = pair * 4 + sg * 2;
                 bload(seq_gg(k + W_RING - 2), bring[(k + W_RING - 2) % W_RING]);      // the two slots the previous step consumed
                 bload(seq_gg(k + W_RING - 1), bring[(k + W_RING - 1) % W_RING]);
-                const w_f32x4 afa = *(const w_f32x4*)(vs + ca * 32 * W_PKV + sg * 8);
-                const w_f32x4 afb = *(const w_f32x4*)(vs + cb * 32 * W_PKV + sg * 8);
+                const f32x4 afa = *(const f32x4*)(vs + ca * 32 * W_PKV + sg * 8);
+                const f32x4 afb = *(const f32x4*)(vs + cb * 32 * W_PKV + sg * 8);
                 __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
                 for (int t = 0; t < 4; ++t) {
                     if (direct) {
-                        Z[za] = w_mfma32(afa[t], bring[k % W_RING][t], Z[za]);
-                        Z[zb] = w_mfma32(afb[t], bring[(k + 1) % W_RING][t], Z[zb]);
+                        Z[za] = mfma32(afa[t], bring[k % W_RING][t], Z[za]);
+                        Z[zb] = mfma32(afb[t], bring[(k + 1) % W_RING][t], Z[zb]);
                     } else {
-                        ta = w_mfma32(afa[t], bring[k % W_RING][t], (sg == 0 && t == 0) ? zero16 : ta);
-                        tb = w_mfma32(afb[t], bring[(k + 1) % W_RING][t], (sg == 0 && t == 0) ? zero16 : tb);
+                        ta = mfma32(afa[t], bring[k % W_RING][t], (sg == 0 && t == 0) ? zero16 : ta);
+                        tb = mfma32(afb[t], bring[(k + 1) % W_RING][t], (sg == 0 && t == 0) ? zero16 : tb);
                     }
                 }
                 __builtin_amdgcn_sched_barrier(0);
@@ -275,25 +275,25 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2))) void w
         const __amdgpu_buffer_rsrc_t up_srd = make_srd(has_up ? a.up + (size_t)l * (crop2 / 4) : a.R, has_up ? crop2 / 4 * sizeof(float) : 0);
         const float b2v = a.bias[w * 32 + (lane & 31)];
         const int w3voff = lane * 16;
-        auto b3load = [&](int q, w_f32x4(&b)[4]) {                // q = k-group of 8 mid channels; the wave's four 32-channel tiles
+        auto b3load = [&](int q, f32x4(&b)[4]) {                // q = k-group of 8 mid channels; the wave's four 32-channel tiles
             const int kg = q < 16 ? q : 15;
 #pragma unroll
             for (int j = 0; j < 4; ++j) b[j] = buf_load(w3_srd, w3voff, (kg * NB2 + wn * 4 + j) * 1024);
         };
         constexpr int R3 = 3;
-        w_f32x4 b3[R3][4];
+        f32x4 b3[R3][4];
 #pragma unroll
         for (int r = 0; r < R3 - 1; ++r) b3load(r, b3[r]);
 #pragma unroll
         for (int p = 0; p < 4; ++p)
 #pragma unroll
             for (int r = 0; r < 16; ++r) {
-                const int t = w_acc_row(r, lane);                               // Winograd tile -> pixel of the 8 x 16 tile
+                const int t = acc_row(r, lane);                               // Winograd tile -> pixel of the 8 x 16 tile
                 const int pix = (2 * (t >> 3) + (p >> 1)) * W_TW + 2 * (t & 7) + (p & 1);
                 M2[pix * MP + w * 32 + (lane & 31)] = fmaxf(out[p][r] + b2v, 0.f);
             }
         __syncthreads();
-        w_f32x16 acc2[2][4];
+        f32x16 acc2[2][4];
 #pragma unroll
         for (int i = 0; i < 2; ++i)
 #pragma unroll
@@ -305,15 +305,15 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2))) void w
         for (int q = 0; q < 16; ++q) {
             b3load(q + R3 - 1, b3[(q + R3 - 1) % R3]);
             __builtin_amdgcn_sched_barrier(0);
-            w_f32x4 af[2];
+            f32x4 af[2];
 #pragma unroll
-            for (int i = 0; i < 2; ++i) af[i] = *(const w_f32x4*)(ms + i * 32 * MP + q * 8);
+            for (int i = 0; i < 2; ++i) af[i] = *(const f32x4*)(ms + i * 32 * MP + q * 8);
 #pragma unroll
             for (int t = 0; t < 4; ++t)
 #pragma unroll
                 for (int i = 0; i < 2; ++i)
 #pragma unroll
-                    for (int j = 0; j < 4; ++j) acc2[i][j] = w_mfma32(af[i][t], b3[q % R3][j][t], acc2[i][j]);
+                    for (int j = 0; j < 4; ++j) acc2[i][j] = mfma32(af[i][t], b3[q % R3][j][t], acc2[i][j]);
             __builtin_amdgcn_sched_barrier(0);
         }
         __syncthreads();                                          // every wave has read the tile: LDS becomes the transposition patches
@@ -323,9 +323,9 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2))) void w
             for (int j = 0; j < 4; ++j) {
                 float* T = M2 + w * (32 * 36);
                 const int col = (wn * 4 + j) * 32 + (lane & 7) * 4;
-                const w_f32x4 bv = *(const w_f32x4*)(a.bias3 + col);
+                const f32x4 bv = *(const f32x4*)(a.bias3 + col);
                 int off[4];
-                w_f32x4 rv[4], uv[UP ? 4 : 1];
+                f32x4 rv[4], uv[UP ? 4 : 1];
 #pragma unroll
                 for (int k = 0; k < 4; ++k) {
                     const int pp = (wm * 2 + i) * 32 + (lane >> 3) + 8 * k;
@@ -338,11 +338,11 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2))) void w
                     if constexpr (UP) uv[k] = buf_load(up_srd, in ? (((oy >> 1) * (a.OW >> 1) + (ox >> 1)) * a.N2 + col) * 4 : BUF_OOB, 0);
                 }
 #pragma unroll
-                for (int r = 0; r < 16; ++r) T[w_acc_row(r, lane) * 36 + (lane & 31)] = acc2[i][j][r];
+                for (int r = 0; r < 16; ++r) T[patch_at(r, lane)] = acc2[i][j][r];
                 __builtin_amdgcn_wave_barrier();
 #pragma unroll
                 for (int k = 0; k < 4; ++k) {
-                    w_f32x4 o = (*(const w_f32x4*)&T[((lane >> 3) + 8 * k) * 36 + (lane & 7) * 4] + bv) + rv[k];
+                    f32x4 o = (patch_row4(T, lane, k) + bv) + rv[k];
                     if constexpr (UP) o += uv[k];
                     buf_store(o, o2_srd, off[k]);
                 }
@@ -363,7 +363,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2))) void w
             for (int r = 0; r < 16; ++r) X[((w * 2 + q) * 16 + r) * 64 + lane] = wc == 0 ? out[2 + q][r] : out[q][r];
         __syncthreads();
         const int pw = (1 - wc) * 2 + wn;
-        w_f32x16 mine[2];
+        f32x16 mine[2];
 #pragma unroll
         for (int q = 0; q < 2; ++q)
 #pragma unroll
@@ -372,18 +372,18 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2))) void w
         __syncthreads();                                          // the exchange area becomes the transposition patches
         float* T = &V[0] + w * (32 * 36);
         const int col = wn * 32 + (lane & 7) * 4;
-        const w_f32x4 bv = *(const w_f32x4*)(a.bias + col);
+        const f32x4 bv = *(const f32x4*)(a.bias + col);
 #pragma unroll
         for (int q = 0; q < 2; ++q) {
             const int p = 2 * wc + q, pi = p >> 1, pj = p & 1;
 #pragma unroll
-            for (int r = 0; r < 16; ++r) T[w_acc_row(r, lane) * 36 + (lane & 31)] = mine[q][r];
+            for (int r = 0; r < 16; ++r) T[patch_at(r, lane)] = mine[q][r];
             __builtin_amdgcn_wave_barrier();
 #pragma unroll
             for (int k = 0; k < 4; ++k) {
                 const int t = (lane >> 3) + 8 * k;
                 const int oy = oy0 + 2 * (t >> 3) + pi, ox = ox0 + 2 * (t & 7) + pj;
-                w_f32x4 o = *(const w_f32x4*)&T[t * 36 + (lane & 7) * 4] + bv;
+                f32x4 o = patch_row4_at(T, t, lane) + bv;
                 if (a.relu) {
 #pragma unroll
                     for (int z = 0; z < 4; ++z) o[z] = fmaxf(o[z], 0.f);
@@ -398,18 +398,18 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2))) void w
     // ---- epilogue: per output position (i,j) transpose the 32 tiles x 32 channels through a wave-private patch -> 16-byte stores
     float* T = &V[0] + w * (32 * 36);
     const int col = w * 32 + (lane & 7) * 4;
-    const w_f32x4 bv = *(const w_f32x4*)(a.bias + col);
+    const f32x4 bv = *(const f32x4*)(a.bias + col);
 #pragma unroll
     for (int p = 0; p < 4; ++p) {
         const int pi = p >> 1, pj = p & 1;
 #pragma unroll
-        for (int r = 0; r < 16; ++r) T[w_acc_row(r, lane) * 36 + (lane & 31)] = out[p][r];
+        for (int r = 0; r < 16; ++r) T[patch_at(r, lane)] = out[p][r];
         __builtin_amdgcn_wave_barrier();
 #pragma unroll
         for (int k = 0; k < 4; ++k) {
             const int t = (lane >> 3) + 8 * k;
             const int oy = oy0 + 2 * (t >> 3) + pi, ox = ox0 + 2 * (t & 7) + pj;
-            w_f32x4 o = *(const w_f32x4*)&T[t * 36 + (lane & 7) * 4] + bv;
+            f32x4 o = patch_row4_at(T, t, lane) + bv;
             if (a.relu) {
 #pragma unroll
                 for (int q = 0; q < 4; ++q) o[q] = fmaxf(o[q], 0.f);

@@ -12,19 +12,13 @@
 #include <stdlib.h>
 #include <string.h>
 
-#include "bf16x3.h"
-#include "f16x2.h"
 #include "buffer_ops.h"
+#include "mma_ops.h"
 #include "suo_internal.h"
 #include "tune.h"
 
 namespace suo {
 
-typedef __bf16 x3_bf16x8 __attribute__((ext_vector_type(8)));
-typedef _Float16 x3_f16x8 __attribute__((ext_vector_type(8)));
-typedef float x3_f32x16 __attribute__((ext_vector_type(16)));
-typedef float x3_f32x4 __attribute__((ext_vector_type(4)));
-typedef unsigned x3_u32x4 __attribute__((ext_vector_type(4)));
 
 #ifndef SUO_X3_F16_WAVES
 #define SUO_X3_F16_WAVES 3      // waves per SIMD the fp16 form is compiled for: 3 = <= 168 registers, THREE workgroups per CU (with a 2-slot weight ring: 152-160
@@ -79,7 +73,6 @@ void pack_gemm_weight_f16x2(const float* W, int N, int K, uint16_t* out, float* 
     }
 }
 
-__device__ __forceinline__ int x3_acc_row(int r, int lane) { return (r & 3) + 8 * (r >> 2) + 4 * (lane >> 5); }
 
 // Workgroup = 128 rows x 128 columns, four waves as 2 x 2 (64 x 64 each = 2 x 2 accumulators), one 16-wide k-step per barrier.
 //   * activations: global fp32 (four adjacent lanes fetch the 64 contiguous bytes a row contributes to a k-step) -> registers -> prologue ->
@@ -115,8 +108,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(NP == 2 ? S
         for (int k = tid; k < g.K1; k += 256) { P[0][k] = NP == 2 ? g.pro_scale[k] * xs : g.pro_scale[k]; P[1][k] = NP == 2 ? g.pro_shift[k] * xs : g.pro_shift[k]; }
     }
     // tile = (row tile, column tile of 128); the column tiles of a row tile are neighbours (the second one finds the activations in L2)
-    int bid = blockIdx.x;
-    if ((gridDim.x & 7) == 0) bid = (bid & 7) * (gridDim.x >> 3) + (bid >> 3);          // XCD-aware tile order
+    int bid = xcd_block_id();          // XCD-aware tile order
     static_assert(NCB == 2 || !POOL, "the pooled epilogue is laid out for 128-column tiles");
     constexpr int BN = 64 * NCB;                                              // columns of the tile
     const int ntn = g.N / BN, NBT = g.N >> 5;
@@ -145,9 +137,9 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(NP == 2 ? S
         avoff2[i] = DUAL && row < M ? (row * g.lda2 + 4 * aq) * 4 : BUF_OOB;
     }
     const int wvoff = lane * 16;
-    x3_f32x4 araw[X3_ASLOTS][X3_NR];
+    f32x4 araw[X3_ASLOTS][X3_NR];
     constexpr int BSL = NP == 2 ? SUO_X3_F16_BSLOTS : X3_BSLOTS;          // weight k-groups in flight
-    x3_u32x4 braw[BSL][NCB][NP];
+    u32x4 braw[BSL][NCB][NP];
     auto requestA = [&](int ks, int slot) {
         if (!DUAL || ks < ns1) {
 #pragma unroll
@@ -162,14 +154,13 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(NP == 2 ? S
         for (int cb = 0; cb < NCB; ++cb)
 #pragma unroll
             for (int p = 0; p < NP; ++p)
-                braw[slot][cb][p] = __builtin_bit_cast(x3_u32x4, buf_load(w_srd, wvoff + p * 1024, ((kg * NBT + 2 * NCB * tn + NCB * wn + cb) * NP) * 1024));
+                braw[slot][cb][p] = __builtin_bit_cast(u32x4, buf_load(w_srd, wvoff + p * 1024, ((kg * NBT + 2 * NCB * tn + NCB * wn + cb) * NP) * 1024));
     };
     float xmax = 0.f;                                                         // NP = 2: largest scaled magnitude this lane split (range guard)
     auto split_store = [&](int ks, int slot, int stage) {
         uint16_t* As = &S[stage][0];
-        typedef unsigned u32x2 __attribute__((ext_vector_type(2)));
-        x3_f32x4 sc, sh;
-        if (PRO) { sc = *(const x3_f32x4*)&P[0][ks * X3_BK + 4 * aq]; sh = *(const x3_f32x4*)&P[1][ks * X3_BK + 4 * aq]; }      // (single K segment only: checked by the launcher)
+        f32x4 sc, sh;
+        if (PRO) { sc = *(const f32x4*)&P[0][ks * X3_BK + 4 * aq]; sh = *(const f32x4*)&P[1][ks * X3_BK + 4 * aq]; }      // (single K segment only: checked by the launcher)
 #pragma unroll
         for (int i = 0; i < X3_NR; ++i) {
             float x[4];
@@ -179,27 +170,17 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(NP == 2 ? S
 #pragma unroll
                 for (int t = 0; t < 4; ++t) x[t] = rok[i] ? fmaxf(fmaf(x[t], sc[t], sh[t]), 0.f) : 0.f;
             }
-            if constexpr (NP == 3) {
-#pragma unroll
-                for (int p = 0; p < 3; ++p) {
-                    const unsigned q0 = s3_pack_rn(x[0], x[1]), q1 = s3_pack_rn(x[2], x[3]);      // (p == 2: the conversion is exact)
-                    *(u32x2*)&As[p * PLANE + (X3_RPP * i + ar) * X3_PITCH + 4 * aq] = u32x2{q0, q1};
-                    if (p < 2) { x[0] -= s3_lo(q0); x[1] -= s3_hi(q0); x[2] -= s3_lo(q1); x[3] -= s3_hi(q1); }      // exact residuals
-                }
-            } else {
+            if constexpr (NP == 2) {
                 if (!PRO) {
 #pragma unroll
                     for (int t = 0; t < 4; ++t) x[t] *= xs;                   // (exact; with a prologue the scale is in sc / sh)
                 }
                 xmax = s2_track(s2_track(xmax, x[0], x[1]), x[2], x[3]);
-                const unsigned h0 = s2_pack_rn(x[0], x[1]), h1 = s2_pack_rn(x[2], x[3]);
-                *(u32x2*)&As[(X3_RPP * i + ar) * X3_PITCH + 4 * aq] = u32x2{h0, h1};
-                const unsigned l0 = s2_lo_pack(x[0], x[1], h0), l1 = s2_lo_pack(x[2], x[3], h1);      // exact residuals, rounded once
-                *(u32x2*)&As[PLANE + (X3_RPP * i + ar) * X3_PITCH + 4 * aq] = u32x2{l0, l1};
             }
+            split_store4<NP, PLANE>(&As[(X3_RPP * i + ar) * X3_PITCH + 4 * aq], x[0], x[1], x[2], x[3]);
         }
     };
-    x3_f32x16 acc[RB][NCB];
+    f32x16 acc[RB][NCB];
 #pragma unroll
     for (int i = 0; i < RB; ++i)
 #pragma unroll
@@ -214,8 +195,6 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(NP == 2 ? S
     for (int u = 0; u < BSL; ++u) requestB(u < ngroups ? u : ngroups - 1, u);
     __syncthreads();                                                          // (scale / shift staged)
     split_store(0, 0, 0);
-    constexpr int TI[6] = {0, 1, 2, 0, 1, 0}, TJ[6] = {2, 1, 0, 1, 0, 0};      // six cross terms, smallest first
-    constexpr int UI[3] = {0, 1, 0}, UJ[3] = {1, 0, 0};                       // NP = 2: hi lo, lo hi, hi hi
     const int ko = 8 * (lane >> 5);
     for (int ks0 = 0; ks0 < nsteps; ks0 += X3_ASLOTS) {
 #pragma unroll
@@ -224,13 +203,13 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(NP == 2 ? S
             __syncthreads();                                                  // stage u & 1 complete; every wave is past its reads of the other stage
             // this step's A fragments are requested first: their LDS latency passes under the split of the next step's activations
             const uint16_t* As = &S[u & 1][0];
-            x3_bf16x8 af[X3_GH][RB][NP];
+            bf16x8 af[X3_GH][RB][NP];
 #pragma unroll
             for (int h = 0; h < X3_GH; ++h)
 #pragma unroll
                 for (int p = 0; p < NP; ++p)
 #pragma unroll
-                    for (int rb = 0; rb < RB; ++rb) af[h][rb][p] = *(const x3_bf16x8*)&As[p * PLANE + (32 * RB * wm + 32 * rb + (lane & 31)) * X3_PITCH + ko + 16 * h];
+                    for (int rb = 0; rb < RB; ++rb) af[h][rb][p] = *(const bf16x8*)&As[p * PLANE + (32 * RB * wm + 32 * rb + (lane & 31)) * X3_PITCH + ko + 16 * h];
             __builtin_amdgcn_sched_barrier(0);
             if (ks + 1 < nsteps) split_store(ks + 1, (u + 1) % X3_ASLOTS, (u + 1) & 1);
             requestA(ks + X3_ASLOTS < nsteps ? ks + X3_ASLOTS : nsteps - 1, u);
@@ -238,23 +217,18 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(NP == 2 ? S
             for (int h = 0; h < X3_GH; ++h) {
                 // weights of this k-group out of their ring slot, then the slot's next request
                 const int slot = (u * X3_GH + h) % BSL, kg = ks * X3_GH + h;
-                x3_u32x4 bw[NCB][NP];
+                u32x4 bw[NCB][NP];
 #pragma unroll
                 for (int cb = 0; cb < NCB; ++cb)
 #pragma unroll
                     for (int p = 0; p < NP; ++p) bw[cb][p] = braw[slot][cb][p];
                 requestB(kg + BSL < ngroups ? kg + BSL : ngroups - 1, slot);
 #pragma unroll
-                for (int t = 0; t < (NP == 3 ? 6 : 3); ++t)
+                for (int t = 0; t < split_terms<NP>(); ++t)             // the cross terms, smallest first (csrc/mma_ops.h)
 #pragma unroll
                     for (int rb = 0; rb < RB; ++rb)
 #pragma unroll
-                        for (int cb = 0; cb < NCB; ++cb) {
-                            if constexpr (NP == 3)
-                                acc[rb][cb] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(af[h][rb][TI[t]], __builtin_bit_cast(x3_bf16x8, bw[cb][TJ[t]]), acc[rb][cb], 0, 0, 0);
-                            else
-                                acc[rb][cb] = __builtin_amdgcn_mfma_f32_32x32x16_f16(__builtin_bit_cast(x3_f16x8, af[h][rb][UI[t]]), __builtin_bit_cast(x3_f16x8, bw[cb][UJ[t]]), acc[rb][cb], 0, 0, 0);
-                        }
+                        for (int cb = 0; cb < NCB; ++cb) acc[rb][cb] = split_mma<NP>(t, af[h][rb], bw[cb], acc[rb][cb]);
             }
             __builtin_amdgcn_sched_barrier(0);
         }
@@ -262,8 +236,8 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(NP == 2 ? S
     __syncthreads();                                                          // the stages are free: the epilogue's patches live there
     if constexpr (NP == 2) s2_raise(g.range_flag, xmax);
     float* T = reinterpret_cast<float*>(&S[0][0]) + w * (32 * 36);
-    x3_f32x4* PX = reinterpret_cast<x3_f32x4*>(reinterpret_cast<float*>(&S[0][0]) + 4 * 32 * 36);      // POOL: 16 KB behind the four patches
-    x3_f32x4 hold[POOL ? 2 : 1][POOL ? 2 : 1][POOL ? 4 : 1];
+    f32x4* PX = reinterpret_cast<f32x4*>(reinterpret_cast<float*>(&S[0][0]) + 4 * 32 * 36);      // POOL: 16 KB behind the four patches
+    f32x4 hold[POOL ? 2 : 1][POOL ? 2 : 1][POOL ? 4 : 1];
     const __amdgpu_buffer_rsrc_t o_srd = make_srd((POOL && !g.out) ? (float*)g.pool_out : g.out, (POOL && !g.out) ? 0 : (size_t)M * ldo * sizeof(float));
     const __amdgpu_buffer_rsrc_t r_srd = make_srd(RES ? g.R : g.out, RES ? (size_t)M * g.ldr * sizeof(float) : 0);
 #pragma unroll
@@ -271,11 +245,11 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(NP == 2 ? S
 #pragma unroll
         for (int cb = 0; cb < NCB; ++cb) {
             const int col = BN * tn + 32 * NCB * wn + 32 * cb + (lane & 7) * 4;
-            x3_f32x4 bv = x3_f32x4{0.f, 0.f, 0.f, 0.f};
-            if (g.bias) bv = *(const x3_f32x4*)(g.bias + col);
-            x3_f32x4 osc = x3_f32x4{1.f, 1.f, 1.f, 1.f};
-            if constexpr (NP == 2) osc = *(const x3_f32x4*)(g.oscale + col);
-            x3_f32x4 rv[RES ? 4 : 1];
+            f32x4 bv = f32x4{0.f, 0.f, 0.f, 0.f};
+            if (g.bias) bv = *(const f32x4*)(g.bias + col);
+            f32x4 osc = f32x4{1.f, 1.f, 1.f, 1.f};
+            if constexpr (NP == 2) osc = *(const f32x4*)(g.oscale + col);
+            f32x4 rv[RES ? 4 : 1];
             if (RES) {
 #pragma unroll
                 for (int k = 0; k < 4; ++k) {
@@ -284,12 +258,12 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(NP == 2 ? S
                 }
             }
 #pragma unroll
-            for (int r = 0; r < 16; ++r) T[x3_acc_row(r, lane) * 36 + (lane & 31)] = acc[rb][cb][r];
+            for (int r = 0; r < 16; ++r) T[patch_at(r, lane)] = acc[rb][cb][r];
             __builtin_amdgcn_wave_barrier();
 #pragma unroll
             for (int k = 0; k < 4; ++k) {
                 const int row = pixel_of(32 * RB * wm + 32 * rb + (lane >> 3) + 8 * k);
-                x3_f32x4 o = *(const x3_f32x4*)&T[((lane >> 3) + 8 * k) * 36 + (lane & 7) * 4];
+                f32x4 o = patch_row4(T, lane, k);
                 if constexpr (NP == 2) o *= osc;                              // back to scale: an exact power of two per column
                 o += bv;
                 if (RES) o += rv[k];                                          // (bias, then the residual: the order of the fp32 kernels)
@@ -299,7 +273,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(NP == 2 ? S
                 }
                 if (!POOL || g.out) buf_store(o, o_srd, row < M ? (row * ldo + col) * 4 : BUF_OOB);
                 if (POOL) {
-                    x3_f32x4 hm;                                              // max over image columns j, j ^ 1 (8 lanes apart within a row of 16: row_ror:8)
+                    f32x4 hm;                                              // max over image columns j, j ^ 1 (8 lanes apart within a row of 16: row_ror:8)
 #pragma unroll
                     for (int q = 0; q < 4; ++q)
                         hm[q] = fmaxf(o[q], __int_as_float(__builtin_amdgcn_mov_dpp(__float_as_int(o[q]), 0x128, 0xf, 0xf, false)));
@@ -323,8 +297,8 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(NP == 2 ? S
                     for (int k = 0; k < 4; ++k) {
                         const int j = 32 * rb + (lane >> 3) + 8 * k;          // even: the pair (j, j + 1)
                         const int col = 128 * tn + 64 * wn + 32 * cb + (lane & 7) * 4;
-                        const x3_f32x4 other = PX[(((wn * 2 + rb) * 2 + cb) * 4 + k) * 32 + (lane >> 4) * 8 + (lane & 7)];
-                        x3_f32x4 v;
+                        const f32x4 other = PX[(((wn * 2 + rb) * 2 + cb) * 4 + k) * 32 + (lane >> 4) * 8 + (lane & 7)];
+                        f32x4 v;
 #pragma unroll
                         for (int q = 0; q < 4; ++q) v[q] = fmaxf(hold[rb][cb][k][q], other[q]);
                         buf_store(v, p_srd, ((prow0 + (j >> 1)) * ldo + col) * 4);
@@ -363,8 +337,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(3))) void g
     const int wm = w >> 1, wn = w & 1;
     const int M = g.M;
     const float xs1 = s2_xscale(g.xs1), xs2 = s2_xscale(g.xs2);
-    int bid = blockIdx.x;
-    if ((gridDim.x & 7) == 0) bid = (bid & 7) * (gridDim.x >> 3) + (bid >> 3);          // XCD-aware tile order
+    int bid = xcd_block_id();          // XCD-aware tile order
     const int m0 = bid * BM;
     const __amdgpu_buffer_rsrc_t a_srd = make_srd(g.A, (size_t)M * g.lda * sizeof(float));
     const __amdgpu_buffer_rsrc_t w1_srd = make_srd(W1, (size_t)N1 * K1 * NP * sizeof(uint16_t));
@@ -374,23 +347,21 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(3))) void g
     const int avoff = arow < M ? (arow * g.lda + 4 * aq) * 4 : BUF_OOB;
     const int wvoff = lane * 16;
     constexpr int BSL = SUO_X3_F16_BSLOTS, nsteps = K1 / X3_BK;
-    constexpr int UI[3] = {0, 1, 0}, UJ[3] = {1, 0, 0};                       // hi lo, lo hi, hi hi
     const int ko = 8 * (lane >> 5);
     float xmax = 0.f;
-    x3_f32x16 acc2;
+    f32x16 acc2;
 #pragma unroll
     for (int r = 0; r < 16; ++r) acc2[r] = 0.f;
-    typedef unsigned u32x2 __attribute__((ext_vector_type(2)));
     for (int tn = 0; tn < 2; ++tn) {
-        x3_f32x4 araw[X3_ASLOTS];
-        x3_u32x4 braw[BSL][NCB][NP];
+        f32x4 araw[X3_ASLOTS];
+        u32x4 braw[BSL][NCB][NP];
         auto requestA = [&](int ks, int slot) { araw[slot] = buf_load(a_srd, avoff, ks * X3_BK * 4); };
         auto requestB = [&](int kg, int slot) {
 #pragma unroll
             for (int cb = 0; cb < NCB; ++cb)
 #pragma unroll
                 for (int p = 0; p < NP; ++p)
-                    braw[slot][cb][p] = __builtin_bit_cast(x3_u32x4, buf_load(w1_srd, wvoff + p * 1024, ((kg * NBT1 + 2 * NCB * tn + NCB * wn + cb) * NP) * 1024));
+                    braw[slot][cb][p] = __builtin_bit_cast(u32x4, buf_load(w1_srd, wvoff + p * 1024, ((kg * NBT1 + 2 * NCB * tn + NCB * wn + cb) * NP) * 1024));
         };
         auto split_store = [&](int slot, int stage) {
             uint16_t* As = &S[stage][0];
@@ -398,12 +369,9 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(3))) void g
 #pragma unroll
             for (int t = 0; t < 4; ++t) x[t] = araw[slot][t] * xs1;
             xmax = s2_track(s2_track(xmax, x[0], x[1]), x[2], x[3]);
-            const unsigned h0 = s2_pack_rn(x[0], x[1]), h1 = s2_pack_rn(x[2], x[3]);
-            *(u32x2*)&As[ar * X3_PITCH + 4 * aq] = u32x2{h0, h1};
-            const unsigned l0 = s2_lo_pack(x[0], x[1], h0), l1 = s2_lo_pack(x[2], x[3], h1);
-            *(u32x2*)&As[PLANE + ar * X3_PITCH + 4 * aq] = u32x2{l0, l1};
+            split_store4<NP, PLANE>(&As[ar * X3_PITCH + 4 * aq], x[0], x[1], x[2], x[3]);
         };
-        x3_f32x16 acc[NCB];
+        f32x16 acc[NCB];
 #pragma unroll
         for (int j = 0; j < NCB; ++j)
 #pragma unroll
@@ -419,57 +387,52 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(3))) void g
                 const int ks = ks0 + u;
                 __syncthreads();
                 const uint16_t* As = &S[u & 1][0];
-                x3_f16x8 af[NP];
+                bf16x8 af[NP];
 #pragma unroll
-                for (int p = 0; p < NP; ++p) af[p] = *(const x3_f16x8*)&As[p * PLANE + (32 * wm + (lane & 31)) * X3_PITCH + ko];
+                for (int p = 0; p < NP; ++p) af[p] = *(const bf16x8*)&As[p * PLANE + (32 * wm + (lane & 31)) * X3_PITCH + ko];
                 __builtin_amdgcn_sched_barrier(0);
                 if (ks + 1 < nsteps) split_store((u + 1) % X3_ASLOTS, (u + 1) & 1);
                 requestA(ks + X3_ASLOTS < nsteps ? ks + X3_ASLOTS : nsteps - 1, u);
                 const int slot = u % BSL;
-                x3_u32x4 bw[NCB][NP];
+                u32x4 bw[NCB][NP];
 #pragma unroll
                 for (int cb = 0; cb < NCB; ++cb)
 #pragma unroll
                     for (int p = 0; p < NP; ++p) bw[cb][p] = braw[slot][cb][p];
                 requestB(ks + BSL < nsteps ? ks + BSL : nsteps - 1, slot);
 #pragma unroll
-                for (int t = 0; t < 3; ++t)
+                for (int t = 0; t < split_terms<NP>(); ++t)
 #pragma unroll
-                    for (int cb = 0; cb < NCB; ++cb)
-                        acc[cb] = __builtin_amdgcn_mfma_f32_32x32x16_f16(af[UI[t]], __builtin_bit_cast(x3_f16x8, bw[cb][UJ[t]]), acc[cb], 0, 0, 0);
+                    for (int cb = 0; cb < NCB; ++cb) acc[cb] = split_mma<NP>(t, af, bw[cb], acc[cb]);
                 __builtin_amdgcn_sched_barrier(0);
             }
         }
         __syncthreads();                                                      // the stages are free (the epilogue's patches live there); the previous half's Y has been consumed
         // the second product's weights for this half (k-steps 8 tn .. 8 tn + 7 of W2, n-tile wn), requested now: they arrive under the epilogue
-        x3_u32x4 b2[8][NP];
+        u32x4 b2[8][NP];
 #pragma unroll
         for (int kk = 0; kk < 8; ++kk)
 #pragma unroll
-            for (int p = 0; p < NP; ++p) b2[kk][p] = __builtin_bit_cast(x3_u32x4, buf_load(w2_srd, wvoff + p * 1024, (((8 * tn + kk) * NB2 + wn) * NP) * 1024));
+            for (int p = 0; p < NP; ++p) b2[kk][p] = __builtin_bit_cast(u32x4, buf_load(w2_srd, wvoff + p * 1024, (((8 * tn + kk) * NB2 + wn) * NP) * 1024));
         float* T = reinterpret_cast<float*>(&S[0][0]) + w * (32 * 36);
 #pragma unroll
         for (int cb = 0; cb < NCB; ++cb) {
             const int lcol = 32 * NCB * wn + 32 * cb + (lane & 7) * 4;       // column within the half
-            const x3_f32x4 bv = *(const x3_f32x4*)(g.bias1 + 128 * tn + lcol), osc = *(const x3_f32x4*)(g.osc1 + 128 * tn + lcol);
+            const f32x4 bv = *(const f32x4*)(g.bias1 + 128 * tn + lcol), osc = *(const f32x4*)(g.osc1 + 128 * tn + lcol);
 #pragma unroll
-            for (int r = 0; r < 16; ++r) T[x3_acc_row(r, lane) * 36 + (lane & 31)] = acc[cb][r];
+            for (int r = 0; r < 16; ++r) T[patch_at(r, lane)] = acc[cb][r];
             __builtin_amdgcn_wave_barrier();
 #pragma unroll
             for (int k = 0; k < 4; ++k) {
                 const int row = 32 * wm + (lane >> 3) + 8 * k;               // row of the tile
-                x3_f32x4 o = *(const x3_f32x4*)&T[((lane >> 3) + 8 * k) * 36 + (lane & 7) * 4];
+                f32x4 o = patch_row4(T, lane, k);
                 o *= osc;
                 o += bv;
                 float y[4];
 #pragma unroll
                 for (int q = 0; q < 4; ++q) y[q] = fmaxf(o[q], 0.f) * xs2;             // what the separate launch stores, times the head site's 2^s for the split
                 xmax = s2_track(s2_track(xmax, y[0], y[1]), y[2], y[3]);
-                const unsigned h0 = s2_pack_rn(y[0], y[1]), h1 = s2_pack_rn(y[2], y[3]);
-                const unsigned l0 = s2_lo_pack(y[0], y[1], h0), l1 = s2_lo_pack(y[2], y[3], h1);
-                const int at = row * 128 + (((lcol >> 3) ^ (row & 15)) << 3) + (lcol & 7);
-                *(u32x2*)&Y[0][at] = u32x2{h0, h1};
-                *(u32x2*)&Y[1][at] = u32x2{l0, l1};
+                split_store4<NP, BM * 128>(&Y[0][row * 128 + (((lcol >> 3) ^ (row & 15)) << 3) + (lcol & 7)], y[0], y[1], y[2], y[3]);
             }
             __builtin_amdgcn_wave_barrier();
         }
@@ -479,12 +442,11 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(3))) void g
 #pragma unroll
             for (int kk = 0; kk < 8; ++kk) {
                 const int chunk = (2 * kk + (lane >> 5)) ^ (yrow & 15);
-                x3_f16x8 af[NP];
+                bf16x8 af[NP];
 #pragma unroll
-                for (int p = 0; p < NP; ++p) af[p] = *(const x3_f16x8*)&Y[p][yrow * 128 + chunk * 8];
+                for (int p = 0; p < NP; ++p) af[p] = *(const bf16x8*)&Y[p][yrow * 128 + chunk * 8];
 #pragma unroll
-                for (int t = 0; t < 3; ++t)
-                    acc2 = __builtin_amdgcn_mfma_f32_32x32x16_f16(af[UI[t]], __builtin_bit_cast(x3_f16x8, b2[kk][UJ[t]]), acc2, 0, 0, 0);
+                for (int t = 0; t < split_terms<NP>(); ++t) acc2 = split_mma<NP>(t, af, b2[kk], acc2);
             }
         }
         // (the next half's first barrier inside its k-loop comes after its first split_store into stage 0 / its reads of nothing of Y: Y is rewritten only in the next
@@ -499,7 +461,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(3))) void g
 #pragma unroll
         for (int q = 0; q < 4; ++q) {
             const int row = m0 + 32 * wm + 8 * q + 4 * (lane >> 5);
-            x3_f32x4 o;
+            f32x4 o;
 #pragma unroll
             for (int j = 0; j < 4; ++j) o[j] = fmaf(acc2[4 * q + j], oc, bb);
             const int img = row / g.hw, pix = row - img * g.hw;

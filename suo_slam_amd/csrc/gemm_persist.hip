@@ -17,15 +17,13 @@
 //     and chunk in the descriptor base / scalar offset -- no 64-bit address registers, which together with the 16-row
 //     epilogue patch (50 KB of LDS in all) lets THREE workgroups share a CU.
 #include "buffer_ops.h"
+#include "mma_ops.h"
 #include "suo_internal.h"
 #include "tune.h"
 
 namespace suo {
 
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-typedef float f32x16 __attribute__((ext_vector_type(16)));
 
-__device__ __forceinline__ int acc_row_s(int r, int lane) { return (r & 3) + 8 * (r >> 2) + 4 * (lane >> 5); }
 
 constexpr int GP_MAX_PRO_K = 512;       // channels of a fused BN-ReLU prologue (scale / shift kept in LDS)
 
@@ -221,11 +219,11 @@ __global__ __launch_bounds__(WGM* WGN * 64) __attribute__((amdgpu_waves_per_eu(S
 #pragma unroll
                 for (int h = 0; h < 2; ++h) {
 #pragma unroll
-                    for (int r = 8 * h; r < 8 * h + 8; ++r) { T[(acc_row_s(r, lane) - 16 * h) * PK + (lane & 31)] = acc[i][j][r]; acc[i][j][r] = 0.f; }
+                    for (int r = 8 * h; r < 8 * h + 8; ++r) { T[(acc_row(r, lane) - 16 * h) * PK + (lane & 31)] = acc[i][j][r]; acc[i][j][r] = 0.f; }
                     __builtin_amdgcn_wave_barrier();
                     f32x4 v[2];
 #pragma unroll
-                    for (int k = 0; k < 2; ++k) v[k] = *(const f32x4*)&T[((lane >> 3) + 8 * k) * PK + (lane & 7) * 4];
+                    for (int k = 0; k < 2; ++k) v[k] = patch_row4<PK>(T, lane, k);
                     f32x4 pm[2];
 #pragma unroll
                     for (int k = 0; k < 2; ++k) {

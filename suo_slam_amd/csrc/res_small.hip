@@ -30,15 +30,15 @@
 #include <string.h>
 
 #include "buffer_ops.h"
+#include "mma_ops.h"
 #include "suo_internal.h"
 #include "tune.h"
 
 namespace suo {
 
-typedef float rs_f32x4 __attribute__((ext_vector_type(4)));
 typedef float rs_f32x2 __attribute__((ext_vector_type(2)));
 
-__device__ __forceinline__ rs_f32x4 rs_mfma(float a, float b, rs_f32x4 c) { return __builtin_amdgcn_mfma_f32_16x16x4f32(a, b, c, 0, 0, 0); }
+__device__ __forceinline__ f32x4 rs_mfma(float a, float b, f32x4 c) { return __builtin_amdgcn_mfma_f32_16x16x4f32(a, b, c, 0, 0, 0); }
 
 // channel (inside its group of 16) that MFMA j = 0..3 of the group multiplies in lane block b = lane >> 4
 __host__ __device__ constexpr int rs_koff(int j, int b) { return 8 * (j >> 1) + (((j & 1) * 4 + b) >> 1) + 4 * (((j & 1) * 4 + b) & 1); }
@@ -125,8 +125,7 @@ __global__ __launch_bounds__(256) void res_block_kernel(const ResBlockArgs a) {
     const int lr = lane & 15, lb = lane >> 4;
     const int H = a.H, W = a.W;
     const int tiles_x = (W + TW - 1) / TW, tiles_y = (H + TH - 1) / TH;
-    int bid = blockIdx.x;
-    if ((gridDim.x & 7) == 0) bid = (bid & 7) * (gridDim.x >> 3) + (bid >> 3);          // XCD-aware tile order (csrc/conv.hip)
+    int bid = xcd_block_id();          // XCD-aware tile order (csrc/mma_ops.h)
     const int l = bid / (tiles_x * tiles_y);
     bid -= l * tiles_x * tiles_y;
     const int ty0 = bid / tiles_x, tx0 = bid - ty0 * tiles_x;
@@ -144,18 +143,18 @@ __global__ __launch_bounds__(256) void res_block_kernel(const ResBlockArgs a) {
     constexpr int R1 = 8, R2 = 6, R3 = 8, NG1 = 16, NG2 = 72, NG3 = 8;
     const int wv12 = (2 * w * 64 + lane) * 16;                  // conv1 / conv2: n-tiles 2 w, 2 w + 1 of 8 (8 KB per group)
     const int wv3 = (4 * w * 64 + lane) * 16;                   // conv3: n-tiles 4 w .. 4 w + 3 of 16 (16 KB per group)
-    rs_f32x4 ring1[R1][2], ring2[R2][2], ring3[R3][4];
-    auto load1 = [&](int g, rs_f32x4 (&b)[2]) {
+    f32x4 ring1[R1][2], ring2[R2][2], ring3[R3][4];
+    auto load1 = [&](int g, f32x4 (&b)[2]) {
         const int gc = g < NG1 ? g : NG1 - 1;
 #pragma unroll
         for (int n = 0; n < 2; ++n) b[n] = buf_load(w1_srd, wv12 + n * 1024, gc * 8192);
     };
-    auto load2 = [&](int g, rs_f32x4 (&b)[2]) {
+    auto load2 = [&](int g, f32x4 (&b)[2]) {
         const int gc = g < NG2 ? g : NG2 - 1;
 #pragma unroll
         for (int n = 0; n < 2; ++n) b[n] = buf_load(w2_srd, wv12 + n * 1024, gc * 8192);
     };
-    auto load3 = [&](int g, rs_f32x4 (&b)[4]) {
+    auto load3 = [&](int g, f32x4 (&b)[4]) {
         const int gc = g < NG3 ? g : NG3 - 1;
 #pragma unroll
         for (int n = 0; n < 4; ++n) b[n] = buf_load(w3_srd, wv3 + n * 1024, gc * 16384);
@@ -166,13 +165,13 @@ __global__ __launch_bounds__(256) void res_block_kernel(const ResBlockArgs a) {
     // ---- 1. stage relu(bn(x)) of tile + halo: thread = (row tid >> 6 + 4 i, channels 4 q .. 4 q + 3, q = tid & 63) -----------------
     const int q = tid & 63;
     {
-        const rs_f32x4 sc = *(const rs_f32x4*)(a.pro_scale + 4 * q), sh = *(const rs_f32x4*)(a.pro_shift + 4 * q);
+        const f32x4 sc = *(const f32x4*)(a.pro_scale + 4 * q), sh = *(const f32x4*)(a.pro_shift + 4 * q);
         // channels 4 q + t sit in group q >> 2, half (q >> 1) & 1; t = 0, 2 go to lane block q & 1, t = 1, 3 to block (q & 1) + 2 (rs_koff)
         const int pos0 = (q & 1) * 64 + (q >> 2) * 4 + 2 * ((q >> 1) & 1);
         constexpr int NB = POOL_IN ? 4 : MT1 * 4;               // rows per thread in flight (every request before the first use)
 #pragma unroll
         for (int i0 = 0; i0 < MT1 * 4; i0 += NB) {
-            rs_f32x4 v[NB][POOL_IN ? 4 : 1];
+            f32x4 v[NB][POOL_IN ? 4 : 1];
 #pragma unroll
             for (int u = 0; u < NB; ++u) {
                 const int row = (tid >> 6) + 4 * (i0 + u);
@@ -191,7 +190,7 @@ __global__ __launch_bounds__(256) void res_block_kernel(const ResBlockArgs a) {
 #pragma unroll
             for (int u = 0; u < NB; ++u) {
                 const int row = (tid >> 6) + 4 * (i0 + u);
-                rs_f32x4 x = v[u][0];
+                f32x4 x = v[u][0];
                 if (POOL_IN) {
 #pragma unroll
                     for (int t = 0; t < 4; ++t) x[t] = fmaxf(fmaxf(v[u][0][t], v[u][1][t]), fmaxf(v[u][2][t], v[u][3][t]));      // (the order of maxpool2_kernel)
@@ -224,19 +223,19 @@ __global__ __launch_bounds__(256) void res_block_kernel(const ResBlockArgs a) {
     RS_T(2);
 
     // ---- 2. conv1: rows = tile + halo, wave w -> channels [32 w, 32 w + 32) ----------------------------------------------------------
-    rs_f32x4 acc1[MT1][2];
+    f32x4 acc1[MT1][2];
 #pragma unroll
     for (int m = 0; m < MT1; ++m)
 #pragma unroll
-        for (int n = 0; n < 2; ++n) acc1[m][n] = rs_f32x4{0.f, 0.f, 0.f, 0.f};
+        for (int n = 0; n < 2; ++n) acc1[m][n] = f32x4{0.f, 0.f, 0.f, 0.f};
     {
         const float* xa = &Xs[lr * XP + lb * 64];
 #pragma unroll
         for (int g = 0; g < NG1; ++g) {
             load1(g + R1 - 1, ring1[(g + R1 - 1) % R1]);
-            rs_f32x4 af[MT1];
+            f32x4 af[MT1];
 #pragma unroll
-            for (int m = 0; m < MT1; ++m) af[m] = *(const rs_f32x4*)(xa + m * 16 * XP + g * 4);
+            for (int m = 0; m < MT1; ++m) af[m] = *(const f32x4*)(xa + m * 16 * XP + g * 4);
             __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
             for (int j = 0; j < 4; ++j)
@@ -271,11 +270,11 @@ __global__ __launch_bounds__(256) void res_block_kernel(const ResBlockArgs a) {
     RS_T(4);
 
     // ---- 3. conv2 (3x3): rows = the tile's pixels, K = chunk (32 channels) -> tap -> 16 channels ------------------------------------
-    rs_f32x4 acc2[MT2][2];
+    f32x4 acc2[MT2][2];
 #pragma unroll
     for (int m = 0; m < MT2; ++m)
 #pragma unroll
-        for (int n = 0; n < 2; ++n) acc2[m][n] = rs_f32x4{0.f, 0.f, 0.f, 0.f};
+        for (int n = 0; n < 2; ++n) acc2[m][n] = f32x4{0.f, 0.f, 0.f, 0.f};
     {
         int arow[MT2][9];
 #pragma unroll
@@ -289,9 +288,9 @@ __global__ __launch_bounds__(256) void res_block_kernel(const ResBlockArgs a) {
             for (int u = 0; u < 18; ++u) {                      // (tap, half): group ch * 18 + u, ring slot u % 6 (18 = 3 * 6)
                 const int g = ch * 18 + u;
                 load2(g + R2 - 1, ring2[(u + R2 - 1) % R2]);
-                rs_f32x4 af[MT2];
+                f32x4 af[MT2];
 #pragma unroll
-                for (int m = 0; m < MT2; ++m) af[m] = *(const rs_f32x4*)&M1[arow[m][u >> 1] + (ch * 2 + (u & 1)) * 4];
+                for (int m = 0; m < MT2; ++m) af[m] = *(const f32x4*)&M1[arow[m][u >> 1] + (ch * 2 + (u & 1)) * 4];
                 __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
                 for (int j = 0; j < 4; ++j)
@@ -322,19 +321,19 @@ __global__ __launch_bounds__(256) void res_block_kernel(const ResBlockArgs a) {
     RS_T(6);
 
     // ---- 4. conv3 (1x1, 128 -> 256): wave w -> channels [64 w, 64 w + 64) ------------------------------------------------------------
-    rs_f32x4 acc3[MT2][4];
+    f32x4 acc3[MT2][4];
 #pragma unroll
     for (int m = 0; m < MT2; ++m)
 #pragma unroll
-        for (int n = 0; n < 4; ++n) acc3[m][n] = rs_f32x4{0.f, 0.f, 0.f, 0.f};
+        for (int n = 0; n < 4; ++n) acc3[m][n] = f32x4{0.f, 0.f, 0.f, 0.f};
     {
         const float* ma = &M2[lr * MP + lb * 32];
 #pragma unroll
         for (int g = 0; g < NG3; ++g) {
             load3(g + R3 - 1, ring3[(g + R3 - 1) % R3]);
-            rs_f32x4 af[MT2];
+            f32x4 af[MT2];
 #pragma unroll
-            for (int m = 0; m < MT2; ++m) af[m] = *(const rs_f32x4*)(ma + m * 16 * MP + g * 4);
+            for (int m = 0; m < MT2; ++m) af[m] = *(const f32x4*)(ma + m * 16 * MP + g * 4);
             __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
             for (int j = 0; j < 4; ++j)
@@ -355,7 +354,7 @@ __global__ __launch_bounds__(256) void res_block_kernel(const ResBlockArgs a) {
             for (int r = 0; r < 4; ++r) P3[(m * 16 + 4 * lb + r) * PP + (4 * w + n) * 16 + lr] = acc3[m][n][r];
     __syncthreads();
     {
-        const rs_f32x4 b3 = *(const rs_f32x4*)(a.b3 + 4 * q);
+        const f32x4 b3 = *(const f32x4*)(a.b3 + 4 * q);
         const size_t ucrop = (size_t)(H / 2) * (W / 2) * C;
         const __amdgpu_buffer_rsrc_t up_srd = make_srd(UP ? a.up + (size_t)l * ucrop : a.x, UP ? ucrop * sizeof(float) : 0);
 #pragma unroll
@@ -363,9 +362,9 @@ __global__ __launch_bounds__(256) void res_block_kernel(const ResBlockArgs a) {
             const int p = (tid >> 6) + 4 * i;
             const int oy = oy0 + p / TW, ox = ox0 + p % TW;
             const bool ok = oy < H && ox < W;
-            rs_f32x4 xr;                                        // the skip: x itself (its 2x2 maximum when the pool is taken here)
+            f32x4 xr;                                        // the skip: x itself (its 2x2 maximum when the pool is taken here)
             if (POOL_IN) {
-                rs_f32x4 v[4];
+                f32x4 v[4];
 #pragma unroll
                 for (int s = 0; s < 4; ++s) v[s] = buf_load(x_srd, ok ? (((2 * oy + (s >> 1)) * XW + 2 * ox + (s & 1)) * C + 4 * q) * 4 : BUF_OOB, 0);
 #pragma unroll
@@ -373,7 +372,7 @@ __global__ __launch_bounds__(256) void res_block_kernel(const ResBlockArgs a) {
             } else {
                 xr = buf_load(x_srd, ok ? ((oy * XW + ox) * C + 4 * q) * 4 : BUF_OOB, 0);
             }
-            rs_f32x4 o = *(const rs_f32x4*)&P3[p * PP + 4 * q] + b3;
+            f32x4 o = *(const f32x4*)&P3[p * PP + 4 * q] + b3;
             o += xr;                                            // (bias, then the skip: the order of the per-layer kernels)
             if (UP) o += buf_load(up_srd, ok ? (((oy >> 1) * (W / 2) + (ox >> 1)) * C + 4 * q) * 4 : BUF_OOB, 0);
             buf_store(o, o_srd, ok ? ((oy * W + ox) * C + 4 * q) * 4 : BUF_OOB);

@@ -20,19 +20,12 @@
 // csrc/res_small.hip on the same inputs; per-element bound as tests/test_gpu_x3_accuracy.py).
 #include <string.h>
 
-#include "bf16x3.h"
-#include "f16x2.h"
 #include "buffer_ops.h"
+#include "mma_ops.h"
 #include "suo_internal.h"
 
 namespace suo {
 
-typedef float r3_f32x4 __attribute__((ext_vector_type(4)));
-typedef float r3_f32x16 __attribute__((ext_vector_type(16)));
-typedef unsigned r3_u32x2 __attribute__((ext_vector_type(2)));
-typedef unsigned r3_u32x4 __attribute__((ext_vector_type(4)));
-typedef __bf16 r3_bf16x8 __attribute__((ext_vector_type(8)));
-typedef _Float16 r3_f16x8 __attribute__((ext_vector_type(8)));
 
 // host: W2[N = 128][C = 128][3][3] (times out_scale[n]) -> [tap][k-step][n-tile][plane][lane][8 bf16] with
 //   term `plane` of W2[nb*32 + (lane&31)][16 ks + 8 (lane>>5) + e][tap]
@@ -68,7 +61,6 @@ void pack_res_conv3x3_f16x2(const float* W, const float* out_scale, uint16_t* ou
     }
 }
 
-__device__ __forceinline__ int r3_acc_row(int r, int lane) { return (r & 3) + 8 * (r >> 2) + 4 * (lane >> 5); }
 
 // rows of the 6 x 10 halo tile, interior first (as csrc/res_small.hip): [0, 32) the 4 x 8 output pixels, then top row, bottom row, left, right
 __device__ __forceinline__ int r3_row(int hy, int hx) {
@@ -125,8 +117,7 @@ __global__ __launch_bounds__(256, NP == 2 ? 2 : 1) void res_block_x3_kernel(cons
     const int lr = lane & 31, lk = lane >> 5;
     const int H = a.H, W = a.W;
     const int tiles_x = (W + TW - 1) / TW, tiles_y = (H + TH - 1) / TH;
-    int bid = blockIdx.x;
-    if ((gridDim.x & 7) == 0) bid = (bid & 7) * (gridDim.x >> 3) + (bid >> 3);          // XCD-aware tile order (csrc/conv.hip)
+    int bid = xcd_block_id();          // XCD-aware tile order (csrc/mma_ops.h)
     const int l = bid / (tiles_x * tiles_y);
     bid -= l * tiles_x * tiles_y;
     const int ty0 = bid / tiles_x, tx0 = bid - ty0 * tiles_x;
@@ -143,23 +134,23 @@ __global__ __launch_bounds__(256, NP == 2 ? 2 : 1) void res_block_x3_kernel(cons
     // ---- weight rings: [k-step][n-tile][plane][lane][16 bytes]; one k-step of one n-tile = 3 KB -------------------------------------
     constexpr int R1 = 4, R2 = 8, R3 = 4, NS1 = 16, NS2 = 72, NS3 = 8;
     const int wv = lane * 16;
-    r3_u32x4 ring1[R1][NP], ring2[R2][NP], ring3[R3][2][NP];
-    auto load1 = [&](int ks, r3_u32x4 (&b)[NP]) {               // conv1: 4 n-tiles, wave w -> tile w
+    u32x4 ring1[R1][NP], ring2[R2][NP], ring3[R3][2][NP];
+    auto load1 = [&](int ks, u32x4 (&b)[NP]) {               // conv1: 4 n-tiles, wave w -> tile w
         const int k = ks < NS1 ? ks : NS1 - 1;
 #pragma unroll
-        for (int p = 0; p < NP; ++p) b[p] = __builtin_bit_cast(r3_u32x4, buf_load(w1_srd, wv + p * 1024, (k * 4 + w) * NP * 1024));
+        for (int p = 0; p < NP; ++p) b[p] = __builtin_bit_cast(u32x4, buf_load(w1_srd, wv + p * 1024, (k * 4 + w) * NP * 1024));
     };
-    auto load2 = [&](int ks, r3_u32x4 (&b)[NP]) {               // conv2: step = tap * 8 + k-step
+    auto load2 = [&](int ks, u32x4 (&b)[NP]) {               // conv2: step = tap * 8 + k-step
         const int k = ks < NS2 ? ks : NS2 - 1;
 #pragma unroll
-        for (int p = 0; p < NP; ++p) b[p] = __builtin_bit_cast(r3_u32x4, buf_load(w2_srd, wv + p * 1024, (k * 4 + w) * NP * 1024));
+        for (int p = 0; p < NP; ++p) b[p] = __builtin_bit_cast(u32x4, buf_load(w2_srd, wv + p * 1024, (k * 4 + w) * NP * 1024));
     };
-    auto load3 = [&](int ks, r3_u32x4 (&b)[2][NP]) {            // conv3: 8 n-tiles, wave w -> tiles 2 w, 2 w + 1
+    auto load3 = [&](int ks, u32x4 (&b)[2][NP]) {            // conv3: 8 n-tiles, wave w -> tiles 2 w, 2 w + 1
         const int k = ks < NS3 ? ks : NS3 - 1;
 #pragma unroll
         for (int j = 0; j < 2; ++j)
 #pragma unroll
-            for (int p = 0; p < NP; ++p) b[j][p] = __builtin_bit_cast(r3_u32x4, buf_load(w3_srd, wv + p * 1024, (k * 8 + 2 * w + j) * NP * 1024));
+            for (int p = 0; p < NP; ++p) b[j][p] = __builtin_bit_cast(u32x4, buf_load(w3_srd, wv + p * 1024, (k * 8 + 2 * w + j) * NP * 1024));
     };
 #pragma unroll
     for (int g = 0; g < R1 - 1; ++g) load1(g, ring1[g]);        // (first touch of the block's weights: under the x staging)
@@ -167,12 +158,12 @@ __global__ __launch_bounds__(256, NP == 2 ? 2 : 1) void res_block_x3_kernel(cons
     // ---- 1. stage relu(bn(x)) of tile + halo as three bf16 planes: thread = (rows tid >> 6 + 4 i, channels 4 q .. 4 q + 3) -------------
     const int q = tid & 63;
     {
-        r3_f32x4 sc = *(const r3_f32x4*)(a.pro_scale + 4 * q), sh = *(const r3_f32x4*)(a.pro_shift + 4 * q);
+        f32x4 sc = *(const f32x4*)(a.pro_scale + 4 * q), sh = *(const f32x4*)(a.pro_shift + 4 * q);
         if constexpr (NP == 2) { const float xs1 = s2_xscale(a.xs1); sc *= xs1; sh *= xs1; }      // fmaf(x, 2^s a, 2^s b) = 2^s fmaf(x, a, b) exactly
         constexpr int NB = POOL_IN ? 4 : 16;                    // rows per thread in flight (every request before the first use)
 #pragma unroll
         for (int i0 = 0; i0 < 16; i0 += NB) {
-            r3_f32x4 v[NB][POOL_IN ? 4 : 1];
+            f32x4 v[NB][POOL_IN ? 4 : 1];
 #pragma unroll
             for (int u = 0; u < NB; ++u) {
                 const int row = (tid >> 6) + 4 * (i0 + u);
@@ -191,26 +182,15 @@ __global__ __launch_bounds__(256, NP == 2 ? 2 : 1) void res_block_x3_kernel(cons
 #pragma unroll
             for (int u = 0; u < NB; ++u) {
                 const int row = (tid >> 6) + 4 * (i0 + u);
-                r3_f32x4 x = v[u][0];
+                f32x4 x = v[u][0];
                 if (POOL_IN) {
 #pragma unroll
                     for (int t = 0; t < 4; ++t) x[t] = fmaxf(fmaxf(v[u][0][t], v[u][1][t]), fmaxf(v[u][2][t], v[u][3][t]));
                 }
 #pragma unroll
                 for (int t = 0; t < 4; ++t) x[t] = fmaxf(fmaf(x[t], sc[t], sh[t]), 0.f);
-                if constexpr (NP == 2) {
-                    gmax = s2_track(s2_track(gmax, x[0], x[1]), x[2], x[3]);
-                    const unsigned h0 = s2_pack_rn(x[0], x[1]), h1 = s2_pack_rn(x[2], x[3]);
-                    *(r3_u32x2*)(XA + row * XPB + q * 8) = r3_u32x2{h0, h1};
-                    *(r3_u32x2*)(XA + XPL + row * XPB + q * 8) = r3_u32x2{s2_lo_pack(x[0], x[1], h0), s2_lo_pack(x[2], x[3], h1)};
-                } else {
-#pragma unroll
-                for (int p = 0; p < 3; ++p) {
-                    const unsigned q0 = s3_pack_rn(x[0], x[1]), q1 = s3_pack_rn(x[2], x[3]);
-                    *(r3_u32x2*)(XA + p * XPL + row * XPB + q * 8) = r3_u32x2{q0, q1};
-                    if (p < 2) { x[0] -= s3_lo(q0); x[1] -= s3_hi(q0); x[2] -= s3_lo(q1); x[3] -= s3_hi(q1); }
-                }
-                }
+                if constexpr (NP == 2) gmax = s2_track(s2_track(gmax, x[0], x[1]), x[2], x[3]);
+                split_store4<NP, XPL>(XA + row * XPB + q * 8, x[0], x[1], x[2], x[3]);
             }
         }
     }
@@ -221,7 +201,7 @@ __global__ __launch_bounds__(256, NP == 2 ? 2 : 1) void res_block_x3_kernel(cons
 #pragma unroll
         for (int r = 0; r < 16; ++r) {
             int hy, hx;
-            const bool real = r3_hyhx(m * 32 + r3_acc_row(r, lane), hy, hx);
+            const bool real = r3_hyhx(m * 32 + acc_row(r, lane), hy, hx);
             const int iy = oy0 - 1 + hy, ix = ox0 - 1 + hx;
             if (real && iy >= 0 && iy < H && ix >= 0 && ix < W) vmask |= 1u << (m * 16 + r);
         }
@@ -230,41 +210,35 @@ __global__ __launch_bounds__(256, NP == 2 ? 2 : 1) void res_block_x3_kernel(cons
     __syncthreads();
     R3_T(2);
 
-    r3_f32x16 zero16;
+    f32x16 zero16;
 #pragma unroll
     for (int r = 0; r < 16; ++r) zero16[r] = 0.f;
-    constexpr int TI[6] = {0, 1, 2, 0, 1, 0}, TJ[6] = {2, 1, 0, 1, 0, 0};      // the six cross terms, smallest first
-    // two independent accumulation chains side by side, their MFMAs alternating (conv2: even / odd k-steps; conv3: the wave's two n-tiles)
-    constexpr int UI[3] = {0, 1, 0}, UJ[3] = {1, 0, 0};                         // NP = 2: hi lo, lo hi, hi hi
-    auto mm = [&](const r3_bf16x8 (&f)[NP], const r3_u32x4 (&bw)[NP], int t, r3_f32x16 acc) -> r3_f32x16 {
-        if constexpr (NP == 2) return __builtin_amdgcn_mfma_f32_32x32x16_f16(__builtin_bit_cast(r3_f16x8, f[UI[t % 3]]), __builtin_bit_cast(r3_f16x8, bw[UJ[t % 3]]), acc, 0, 0, 0);
-        else return __builtin_amdgcn_mfma_f32_32x32x16_bf16(f[TI[t] % NP], __builtin_bit_cast(r3_bf16x8, bw[TJ[t] % NP]), acc, 0, 0, 0);
-    };
-    constexpr int NT = NP == 2 ? 3 : 6;
-    auto mac6x2 = [&](r3_f32x16& accA, const r3_bf16x8 (&fA)[NP], const r3_u32x4 (&bA)[NP], r3_f32x16& accB, const r3_bf16x8 (&fB)[NP], const r3_u32x4 (&bB)[NP]) {
+    // the cross terms of a product block, smallest first (csrc/mma_ops.h).  mac6x2: two independent accumulation chains side by side, their MFMAs
+    // alternating (conv2: even / odd k-steps; conv3: the wave's two n-tiles)
+    auto mac6x2 = [&](f32x16& accA, const bf16x8 (&fA)[NP], const u32x4 (&bA)[NP], f32x16& accB, const bf16x8 (&fB)[NP], const u32x4 (&bB)[NP]) {
 #pragma unroll
-        for (int t = 0; t < NT; ++t) {
-            accA = mm(fA, bA, t, accA);
-            accB = mm(fB, bB, t, accB);
+        for (int t = 0; t < split_terms<NP>(); ++t) {
+            accA = split_mma<NP>(t, fA, bA, accA);
+            accB = split_mma<NP>(t, fB, bB, accB);
         }
     };
-    auto mac6 = [&](r3_f32x16& acc, const r3_bf16x8 (&f)[NP], const r3_u32x4 (&bw)[NP]) {
+    auto mac6 = [&](f32x16& acc, const bf16x8 (&f)[NP], const u32x4 (&bw)[NP]) {
 #pragma unroll
-        for (int t = 0; t < NT; ++t) acc = mm(f, bw, t, acc);
+        for (int t = 0; t < split_terms<NP>(); ++t) acc = split_mma<NP>(t, f, bw, acc);
     };
 
     // ---- 2. conv1: 64 rows x channels [32 w, 32 w + 32) ------------------------------------------------------------------------------
-    r3_f32x16 acc1[2] = {zero16, zero16};
+    f32x16 acc1[2] = {zero16, zero16};
     {
         const unsigned char* xa = XA + lr * XPB + lk * 16;
 #pragma unroll
         for (int ks = 0; ks < NS1; ++ks) {
             load1(ks + R1 - 1, ring1[(ks + R1 - 1) % R1]);
-            r3_bf16x8 af[2][NP];
+            bf16x8 af[2][NP];
 #pragma unroll
             for (int m = 0; m < 2; ++m)
 #pragma unroll
-                for (int p = 0; p < NP; ++p) af[m][p] = *(const r3_bf16x8*)(xa + p * XPL + m * 32 * XPB + ks * 32);
+                for (int p = 0; p < NP; ++p) af[m][p] = *(const bf16x8*)(xa + p * XPL + m * 32 * XPB + ks * 32);
             __builtin_amdgcn_sched_barrier(0);
             mac6(acc1[0], af[0], ring1[ks % R1]);                // (two chains side by side measured SLOWER here: 14.0 k vs 9.3 k cycles)
             if (ring_any) mac6(acc1[1], af[1], ring1[ks % R1]);
@@ -287,7 +261,7 @@ __global__ __launch_bounds__(256, NP == 2 ? 2 : 1) void res_block_x3_kernel(cons
             for (int r = 0; r < 16; ++r) {
                 const bool ok = (vmask >> (m * 16 + r)) & 1u;
                 float v = ok ? (NP == 2 ? fmaxf(fmaf(acc1[m][r], c1, b1), 0.f) : fmaxf(acc1[m][r] + b1, 0.f)) : 0.f;
-                unsigned char* d = M1 + (m * 32 + r3_acc_row(r, lane)) * MPB + ch * 2;
+                unsigned char* d = M1 + (m * 32 + acc_row(r, lane)) * MPB + ch * 2;
                 if constexpr (NP == 2) {
                     gmax = fmaxf(gmax, v);
                     const _Float16 hi = (_Float16)v;
@@ -307,7 +281,7 @@ __global__ __launch_bounds__(256, NP == 2 ? 2 : 1) void res_block_x3_kernel(cons
     R3_T(4);
 
     // ---- 3. conv2 (3x3): 32 rows, tap -> 8 k-steps of 16 channels ---------------------------------------------------------------------
-    r3_f32x16 acc2 = zero16, acc2b = zero16;                     // even / odd k-steps: two chains (summed below)
+    f32x16 acc2 = zero16, acc2b = zero16;                     // even / odd k-steps: two chains (summed below)
     {
         int arow[9];
         const int py = lr / TW, px = lr % TW;
@@ -319,11 +293,11 @@ __global__ __launch_bounds__(256, NP == 2 ? 2 : 1) void res_block_x3_kernel(cons
             for (int ks = 0; ks < 8; ks += 2) {                 // steps tap * 8 + ks, + 1 live in ring slots ks, ks + 1
                 load2(tap * 8 + ks + R2 - 2, ring2[(ks + R2 - 2) % R2]);
                 load2(tap * 8 + ks + R2 - 1, ring2[(ks + R2 - 1) % R2]);
-                r3_bf16x8 af[2][NP];
+                bf16x8 af[2][NP];
 #pragma unroll
                 for (int u = 0; u < 2; ++u)
 #pragma unroll
-                    for (int p = 0; p < NP; ++p) af[u][p] = *(const r3_bf16x8*)(M1 + p * MPL + arow[tap] + (ks + u) * 32);
+                    for (int p = 0; p < NP; ++p) af[u][p] = *(const bf16x8*)(M1 + p * MPL + arow[tap] + (ks + u) * 32);
                 __builtin_amdgcn_sched_barrier(0);
                 mac6x2(acc2, af[0], ring2[ks], acc2b, af[1], ring2[ks + 1]);
                 __builtin_amdgcn_sched_barrier(0);
@@ -342,7 +316,7 @@ __global__ __launch_bounds__(256, NP == 2 ? 2 : 1) void res_block_x3_kernel(cons
 #pragma unroll
         for (int r = 0; r < 16; ++r) {
             float v = NP == 2 ? fmaxf(fmaf(acc2[r], c2, b2), 0.f) : fmaxf(acc2[r] + b2, 0.f);
-            unsigned char* d = M2 + r3_acc_row(r, lane) * MPB + ch * 2;
+            unsigned char* d = M2 + acc_row(r, lane) * MPB + ch * 2;
             if constexpr (NP == 2) {
                 gmax = fmaxf(gmax, v);
                 const _Float16 hi = (_Float16)v;
@@ -362,15 +336,15 @@ __global__ __launch_bounds__(256, NP == 2 ? 2 : 1) void res_block_x3_kernel(cons
     R3_T(6);
 
     // ---- 4. conv3 (1x1, 128 -> 256): channels [64 w, 64 w + 64) -------------------------------------------------------------------------
-    r3_f32x16 acc3[2] = {zero16, zero16};
+    f32x16 acc3[2] = {zero16, zero16};
     {
         const unsigned char* ma = M2 + lr * MPB + lk * 16;
 #pragma unroll
         for (int ks = 0; ks < NS3; ++ks) {
             load3(ks + R3 - 1, ring3[(ks + R3 - 1) % R3]);
-            r3_bf16x8 af[NP];
+            bf16x8 af[NP];
 #pragma unroll
-            for (int p = 0; p < NP; ++p) af[p] = *(const r3_bf16x8*)(ma + p * M2PL + ks * 32);
+            for (int p = 0; p < NP; ++p) af[p] = *(const bf16x8*)(ma + p * M2PL + ks * 32);
             __builtin_amdgcn_sched_barrier(0);
             mac6x2(acc3[0], af, ring3[ks % R3][0], acc3[1], af, ring3[ks % R3][1]);
             __builtin_amdgcn_sched_barrier(0);
@@ -383,11 +357,11 @@ __global__ __launch_bounds__(256, NP == 2 ? 2 : 1) void res_block_x3_kernel(cons
     for (int j = 0; j < 2; ++j) {
         const float c3 = NP == 2 ? a.osc3[(2 * w + j) * 32 + lr] : 1.f;       // back to scale: an exact power of two per column
 #pragma unroll
-        for (int r = 0; r < 16; ++r) P3[r3_acc_row(r, lane) * PP + (2 * w + j) * 32 + lr] = NP == 2 ? acc3[j][r] * c3 : acc3[j][r];
+        for (int r = 0; r < 16; ++r) P3[acc_row(r, lane) * PP + (2 * w + j) * 32 + lr] = NP == 2 ? acc3[j][r] * c3 : acc3[j][r];
     }
     __syncthreads();
     {
-        const r3_f32x4 b3 = *(const r3_f32x4*)(a.b3 + 4 * q);
+        const f32x4 b3 = *(const f32x4*)(a.b3 + 4 * q);
         const size_t ucrop = (size_t)(H / 2) * (W / 2) * C;
         const __amdgpu_buffer_rsrc_t up_srd = make_srd(UP ? a.up + (size_t)l * ucrop : a.x, UP ? ucrop * sizeof(float) : 0);
 #pragma unroll
@@ -395,9 +369,9 @@ __global__ __launch_bounds__(256, NP == 2 ? 2 : 1) void res_block_x3_kernel(cons
             const int p = (tid >> 6) + 4 * i;
             const int oy = oy0 + p / TW, ox = ox0 + p % TW;
             const bool ok = oy < H && ox < W;
-            r3_f32x4 xr;                                        // the skip: x itself (its 2x2 maximum when the pool is taken here)
+            f32x4 xr;                                        // the skip: x itself (its 2x2 maximum when the pool is taken here)
             if (POOL_IN) {
-                r3_f32x4 v[4];
+                f32x4 v[4];
 #pragma unroll
                 for (int s = 0; s < 4; ++s) v[s] = buf_load(x_srd, ok ? (((2 * oy + (s >> 1)) * XW + 2 * ox + (s & 1)) * C + 4 * q) * 4 : BUF_OOB, 0);
 #pragma unroll
@@ -405,7 +379,7 @@ __global__ __launch_bounds__(256, NP == 2 ? 2 : 1) void res_block_x3_kernel(cons
             } else {
                 xr = buf_load(x_srd, ok ? ((oy * XW + ox) * C + 4 * q) * 4 : BUF_OOB, 0);
             }
-            r3_f32x4 o = *(const r3_f32x4*)&P3[p * PP + 4 * q] + b3;
+            f32x4 o = *(const f32x4*)&P3[p * PP + 4 * q] + b3;
             o += xr;                                            // (bias, then the skip: the order of the per-layer kernels)
             if (UP) o += buf_load(up_srd, ok ? (((oy >> 1) * (W / 2) + (ox >> 1)) * C + 4 * q) * 4 : BUF_OOB, 0);
             buf_store(o, o_srd, ok ? ((oy * W + ox) * C + 4 * q) * 4 : BUF_OOB);

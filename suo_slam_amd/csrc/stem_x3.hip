@@ -14,20 +14,13 @@
 #include <stdlib.h>
 #include <string.h>
 
-#include "bf16x3.h"
-#include "f16x2.h"
 #include "buffer_ops.h"
+#include "mma_ops.h"
 #include "roi_sample.h"
 #include "suo_internal.h"
 
 namespace suo {
 
-typedef float sx_f32x4 __attribute__((ext_vector_type(4)));
-typedef float sx_f32x16 __attribute__((ext_vector_type(16)));
-typedef unsigned sx_u32x2 __attribute__((ext_vector_type(2)));
-typedef unsigned sx_u32x4 __attribute__((ext_vector_type(4)));
-typedef __bf16 sx_bf16x8 __attribute__((ext_vector_type(8)));
-typedef _Float16 sx_f16x8 __attribute__((ext_vector_type(8)));
 
 constexpr int SX_STEPS = 14, SX_N = 64;
 
@@ -79,7 +72,6 @@ __device__ long long sx_prof[65536 * 6];
 #define SX_T(i) do { } while (0)
 #endif
 
-__device__ __forceinline__ int sx_acc_row(int r, int lane) { return (r & 3) + 8 * (r >> 2) + 4 * (lane >> 5); }
 
 struct StemArgs {
     const void* img; int fmt, H, W;                     // frame(s): FMT 0 uint8 HWC, FMT 1 float32 CHW
@@ -110,8 +102,7 @@ __global__ __launch_bounds__(256) void stem_x3_kernel(const StemArgs a) {
     const int tid = threadIdx.x, lane = tid & 63;
     const int w = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int wm = w >> 1, wn = w & 1;
-    int bid = blockIdx.x;
-    if ((gridDim.x & 7) == 0) bid = (bid & 7) * (gridDim.x >> 3) + (bid >> 3);          // XCD-aware tile order (csrc/conv.hip)
+    int bid = xcd_block_id();          // XCD-aware tile order (csrc/mma_ops.h)
     const int l = bid >> 7, t = bid & 127;                                   // 16 x 8 tiles per crop
     const int oy0 = (t >> 3) * TH, ox0 = (t & 7) * TW;
     SX_T(0);
@@ -121,12 +112,12 @@ __global__ __launch_bounds__(256) void stem_x3_kernel(const StemArgs a) {
     const __amdgpu_buffer_rsrc_t w_srd = make_srd(a.Wx, (size_t)SX_STEPS * 2 * NP * 1024);
     const int wv = lane * 16;
     constexpr int R = 4;
-    sx_u32x4 ring[R][NP];
+    u32x4 ring[R][NP];
     float gmax = 0.f;                                                       // NP = 2: largest scaled sample this lane staged (range guard)
-    auto loadw = [&](int s, sx_u32x4 (&b)[NP]) {
+    auto loadw = [&](int s, u32x4 (&b)[NP]) {
         const int k = s < SX_STEPS ? s : SX_STEPS - 1;
 #pragma unroll
-        for (int p = 0; p < NP; ++p) b[p] = __builtin_bit_cast(sx_u32x4, buf_load(w_srd, wv + p * 1024, (k * 2 + wn) * NP * 1024));
+        for (int p = 0; p < NP; ++p) b[p] = __builtin_bit_cast(u32x4, buf_load(w_srd, wv + p * 1024, (k * 2 + wn) * NP * 1024));
     };
     // ---- stage: 21 rows x 2 halves x 20 entries; slot -> input pixel (r, xl = 2 j + h) ---------------------------------------------------
     if (FMT == 0) {
@@ -153,15 +144,14 @@ __global__ __launch_bounds__(256) void stem_x3_kernel(const StemArgs a) {
             if constexpr (NP == 2) {
                 c0 *= S2_XSCALE; c1 *= S2_XSCALE; c2 *= S2_XSCALE;
                 gmax = fmaxf(s2_track(gmax, c0, c1), fabsf(c2));
-                const unsigned h0 = s2_pack_rn(c0, c1), h1 = s2_pack_rn(c2, 0.f);
-                *(sx_u32x2*)d = sx_u32x2{h0, h1};
-                *(sx_u32x2*)(d + PLANE_B) = sx_u32x2{s2_lo_pack(c0, c1, h0), s2_lo_pack(c2, 0.f, h1)};
+                split_store4<2, PLANE_B>(d, c0, c1, c2, 0.f);            // (the entry's fourth channel: zero in both planes)
                 return;
             }
+            // (NP = 3 keeps its three-lane chain: split_store4 would carry the zero lane through both residuals -- measured 0.4 - 1.1 % slower, profiles/mma_ops_header.txt)
 #pragma unroll
             for (int p = 0; p < 3; ++p) {
                 const unsigned q0 = s3_pack_rn(c0, c1), q1 = s3_pack_rn(c2, 0.f);
-                *(sx_u32x2*)(d + p * PLANE_B) = sx_u32x2{q0, q1};
+                *(u32x2*)(d + p * PLANE_B) = u32x2{q0, q1};
                 if (p < 2) { c0 -= s3_lo(q0); c1 -= s3_hi(q0); c2 -= s3_lo(q1); }
             }
         };
@@ -208,13 +198,11 @@ __global__ __launch_bounds__(256) void stem_x3_kernel(const StemArgs a) {
     __syncthreads();
     SX_T(1);
 
-    sx_f32x16 acc[2];
+    f32x16 acc[2];
 #pragma unroll
     for (int i = 0; i < 2; ++i)
 #pragma unroll
         for (int r = 0; r < 16; ++r) acc[i][r] = 0.f;
-    constexpr int TI[6] = {0, 1, 2, 0, 1, 0}, TJ[6] = {2, 1, 0, 1, 0, 0};      // the six cross terms, smallest first
-    constexpr int UI[3] = {0, 1, 0}, UJ[3] = {1, 0, 0};                       // NP = 2: hi lo, lo hi, hi hi
     // this lane's pixels: m-tile i of the wave = tile pixels 64 wm + 32 i + (lane & 31)
     int abase[2];
 #pragma unroll
@@ -225,25 +213,20 @@ __global__ __launch_bounds__(256) void stem_x3_kernel(const StemArgs a) {
 #pragma unroll
     for (int s = 0; s < SX_STEPS; ++s) {                        // s = ky * 2 + h
         loadw(s + R - 1, ring[(s + R - 1) % R]);
-        sx_bf16x8 af[2][NP];
+        bf16x8 af[2][NP];
 #pragma unroll
         for (int i = 0; i < 2; ++i)
 #pragma unroll
             for (int p = 0; p < NP; ++p) {
                 const unsigned char* src = A3 + p * PLANE_B + abase[i] + (s >> 1) * ROW_B + (s & 1) * HALF_B;
-                const sx_u32x2 lo = *(const sx_u32x2*)src, hi = *(const sx_u32x2*)(src + 8);      // (8-byte aligned runs: two ds_read_b64)
-                af[i][p] = __builtin_bit_cast(sx_bf16x8, sx_u32x4{lo[0], lo[1], hi[0], hi[1]});
+                const u32x2 lo = *(const u32x2*)src, hi = *(const u32x2*)(src + 8);      // (8-byte aligned runs: two ds_read_b64)
+                af[i][p] = __builtin_bit_cast(bf16x8, u32x4{lo[0], lo[1], hi[0], hi[1]});
             }
         __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
-        for (int tt = 0; tt < (NP == 2 ? 3 : 6); ++tt)
+        for (int tt = 0; tt < split_terms<NP>(); ++tt)          // the cross terms, smallest first (csrc/mma_ops.h)
 #pragma unroll
-            for (int i = 0; i < 2; ++i) {
-                if constexpr (NP == 2)
-                    acc[i] = __builtin_amdgcn_mfma_f32_32x32x16_f16(__builtin_bit_cast(sx_f16x8, af[i][UI[tt]]), __builtin_bit_cast(sx_f16x8, ring[s % R][UJ[tt]]), acc[i], 0, 0, 0);
-                else
-                    acc[i] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(af[i][TI[tt] % NP], __builtin_bit_cast(sx_bf16x8, ring[s % R][TJ[tt] % NP]), acc[i], 0, 0, 0);
-            }
+            for (int i = 0; i < 2; ++i) acc[i] = split_mma<NP>(tt, af[i], ring[s % R], acc[i]);
         __builtin_amdgcn_sched_barrier(0);
     }
     // relu(acc + bias) -> patch [pixel][64], then 16-byte stores
@@ -257,7 +240,7 @@ __global__ __launch_bounds__(256) void stem_x3_kernel(const StemArgs a) {
 #pragma unroll
         for (int i = 0; i < 2; ++i)
 #pragma unroll
-            for (int r = 0; r < 16; ++r) P[(64 * wm + 32 * i + sx_acc_row(r, lane)) * PP + col] = NP == 2 ? fmaxf(fmaf(acc[i][r], oc, b), 0.f) : fmaxf(acc[i][r] + b, 0.f);
+            for (int r = 0; r < 16; ++r) P[(64 * wm + 32 * i + acc_row(r, lane)) * PP + col] = NP == 2 ? fmaxf(fmaf(acc[i][r], oc, b), 0.f) : fmaxf(acc[i][r] + b, 0.f);
     }
     __syncthreads();
     SX_T(3);
@@ -267,22 +250,21 @@ __global__ __launch_bounds__(256) void stem_x3_kernel(const StemArgs a) {
         for (int k = 0; k < 8; ++k) {
             const int idx = tid + 256 * k, p = idx >> 4, q = idx & 15;
             const int oy = oy0 + (p >> 4), ox = ox0 + (p & 15);
-            *(sx_f32x4*)(o + ((size_t)oy * 128 + ox) * SX_N + 4 * q) = *(const sx_f32x4*)&P[p * PP + 4 * q];
+            *(f32x4*)(o + ((size_t)oy * 128 + ox) * SX_N + 4 * q) = *(const f32x4*)&P[p * PP + 4 * q];
         }
     }
     SX_T(4);
     if constexpr (NEXT) {
         // A fragments straight out of the patch (fp32 -> prologue -> split in registers); wave w owns pixels [32 w, 32 w + 32) and all 64 output channels
-        constexpr int UI[3] = {0, 1, 0}, UJ[3] = {1, 0, 0};
         const __amdgpu_buffer_rsrc_t n_srd = make_srd(a.n_W1, (size_t)64 * 64 * 2 * sizeof(uint16_t));
-        sx_u32x4 nb[4][2][2];
+        u32x4 nb[4][2][2];
 #pragma unroll
         for (int ks = 0; ks < 4; ++ks)
 #pragma unroll
             for (int n = 0; n < 2; ++n)
 #pragma unroll
-                for (int pl = 0; pl < 2; ++pl) nb[ks][n][pl] = __builtin_bit_cast(sx_u32x4, buf_load(n_srd, wv + pl * 1024, ((ks * 2 + n) * 2) * 1024));
-        sx_f32x16 acc2[2];
+                for (int pl = 0; pl < 2; ++pl) nb[ks][n][pl] = __builtin_bit_cast(u32x4, buf_load(n_srd, wv + pl * 1024, ((ks * 2 + n) * 2) * 1024));
+        f32x16 acc2[2];
 #pragma unroll
         for (int n = 0; n < 2; ++n)
 #pragma unroll
@@ -296,24 +278,23 @@ __global__ __launch_bounds__(256) void stem_x3_kernel(const StemArgs a) {
             float v[8];
 #pragma unroll
             for (int q = 0; q < 2; ++q) {
-                const sx_f32x4 x = *(const sx_f32x4*)(prow + 16 * ks + 4 * q);
-                const sx_f32x4 sc = *(const sx_f32x4*)(a.n_scale + c0 + 4 * q), sh = *(const sx_f32x4*)(a.n_shift + c0 + 4 * q);
+                const f32x4 x = *(const f32x4*)(prow + 16 * ks + 4 * q);
+                const f32x4 sc = *(const f32x4*)(a.n_scale + c0 + 4 * q), sh = *(const f32x4*)(a.n_shift + c0 + 4 * q);
 #pragma unroll
                 for (int j = 0; j < 4; ++j) v[4 * q + j] = fmaxf(fmaf(x[j], sc[j] * nxs, sh[j] * nxs), 0.f);      // (the GEMM's prologue, scale folded in the same way)
             }
-            sx_u32x4 hi, lo;
+            u32x4 hi, lo;
 #pragma unroll
             for (int j = 0; j < 4; ++j) {
                 gmax2 = s2_track(gmax2, v[2 * j], v[2 * j + 1]);
                 hi[j] = s2_pack_rn(v[2 * j], v[2 * j + 1]);
                 lo[j] = s2_lo_pack(v[2 * j], v[2 * j + 1], hi[j]);
             }
-            const sx_f16x8 af[2] = {__builtin_bit_cast(sx_f16x8, hi), __builtin_bit_cast(sx_f16x8, lo)};
+            const bf16x8 af[2] = {__builtin_bit_cast(bf16x8, hi), __builtin_bit_cast(bf16x8, lo)};
 #pragma unroll
-            for (int tt = 0; tt < 3; ++tt)
+            for (int tt = 0; tt < split_terms<2>(); ++tt)
 #pragma unroll
-                for (int n = 0; n < 2; ++n)
-                    acc2[n] = __builtin_amdgcn_mfma_f32_32x32x16_f16(af[UI[tt]], __builtin_bit_cast(sx_f16x8, nb[ks][n][UJ[tt]]), acc2[n], 0, 0, 0);
+                for (int n = 0; n < 2; ++n) acc2[n] = split_mma<2>(tt, af, nb[ks][n], acc2[n]);
         }
         s2_raise(a.range_flag, gmax2);
         __syncthreads();                                        // every wave has read its rows of the patch (and the first output's stores have read theirs)
@@ -322,7 +303,7 @@ __global__ __launch_bounds__(256) void stem_x3_kernel(const StemArgs a) {
             const int col = 32 * n + (lane & 31);
             const float oc = a.n_osc1[col], b = a.n_b1[col];
 #pragma unroll
-            for (int r = 0; r < 16; ++r) P[(32 * w + sx_acc_row(r, lane)) * PP + col] = fmaxf(fmaf(acc2[n][r], oc, b), 0.f);
+            for (int r = 0; r < 16; ++r) P[(32 * w + acc_row(r, lane)) * PP + col] = fmaxf(fmaf(acc2[n][r], oc, b), 0.f);
         }
         __syncthreads();
         float* o2 = a.n_out + (size_t)l * 128 * 128 * SX_N;
@@ -330,7 +311,7 @@ __global__ __launch_bounds__(256) void stem_x3_kernel(const StemArgs a) {
         for (int k = 0; k < 8; ++k) {
             const int idx = tid + 256 * k, p = idx >> 4, q = idx & 15;
             const int oy = oy0 + (p >> 4), ox = ox0 + (p & 15);
-            *(sx_f32x4*)(o2 + ((size_t)oy * 128 + ox) * SX_N + 4 * q) = *(const sx_f32x4*)&P[p * PP + 4 * q];
+            *(f32x4*)(o2 + ((size_t)oy * 128 + ox) * SX_N + 4 * q) = *(const f32x4*)&P[p * PP + 4 * q];
         }
     }
 }

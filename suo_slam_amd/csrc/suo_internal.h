@@ -84,6 +84,8 @@ int launch_conv3x3(const ConvArgs& a, hipStream_t s);
 bool conv3x3_fusable(const ConvArgs& a);
 // Winograd F(2x2,3x3) form (csrc/conv_wino.hip): weights packed by pack_wino_weight (16 floats per (n, c))
 void pack_wino_weight(const float* W, int N, int C, int Np, int Cp, const float* out_scale, float* out);
+// U[4 xi + nu] = (G g G^T)[xi][nu] * scale of one filter g[9]: fp64, rounded once, row xi = 3 negated -- what every Winograd packer lays out
+void wino_weight_transform(const float* g, double scale, float U[16]);
 int launch_conv3x3_wino(const ConvArgs& a, hipStream_t s);
 int launch_conv3x3_wino_fused(const ConvArgs& a, hipStream_t s);
 bool conv3x3_wino_pays(const ConvArgs& a, long min_tiles = -1);      // enough 8 x 16-pixel tiles (min_tiles < 0: SUO_CONV_WINO_TILES, default 256 -- measured on the fp32-pipe kernel)
