@@ -711,6 +711,17 @@ int suo_debug_ba_jacobians(suo_ba_ctx* ctx, int n_edge, double* jac_out, double*
  * linear_solver_cholmod.h) -- on a dense symmetric A [ns][ns] (HOST, row-major, lower triangle read; ns a multiple of 6, at most 96) and b [ns]: x_out [ns] solves
  * A x = b; *ok_out = 0 when a pivot was not positive (the LM kernels then reject the trial). */
 int suo_debug_cholesky_solve(const double* A, const double* b, int ns, double* x_out, int* ok_out);
+/* Test entry: the SE(3) update every LM kernel applies to a vertex, through the very pose_from_T, pose_oplus and pose_to_T of csrc/lm_device.h (VertexSE3Expmap::
+ * oplusImpl, types_six_dof_expmap.h:100-103; SE3Quat::exp and operator*, se3quat.h:220-254, :101-114).  HOST arrays, blocking, one launch, one thread per pose:
+ * T_in [n][12] row-major 3x4 (R | t), u [n][6] = (omega, upsilon), T_out [n][12] = exp(u) * T_in -- the LEFT update: R' = exp(omega^) R, t' = V(omega) upsilon +
+ * exp(omega^) t -- and, unless q_out is NULL, q_out [n][4]: the unit quaternion (w, x, y, z; w >= 0) the kernels keep after the update, of which T_out's rotation is
+ * the matrix.  The input rotation goes through the Eigen matrix-to-quaternion conversion first (trace > 0: one form; else one of three pivot forms), as when a
+ * problem is loaded.  Coefficients of exp, with th2 = |omega|^2:
+ *   th2 < 1e-10   g2o's shortcut R = V = I + Om + Om^2 (se3quat.h:236-240; not a rotation to second order: the quaternion conversion normalises it);
+ *   th2 < 0.09    eight-term Taylor series in th2 of sin(th) / th, (1 - cos(th)) / th^2, (th - sin(th)) / th^3;
+ *   else          those closed forms.
+ * n <= 0 or a NULL T_in, u or T_out: SUO_ERR_ARG, nothing launched. */
+int suo_debug_pose_oplus(const double* T_in, const double* u, int n, double* T_out, double* q_out);
 
 /* ---- the partitioned adjustment driven from C (csrc/ba_comm.hip, csrc/ba_drive.hip: optimize_dist) ---------------------------------
  * suo_ba_comm: the one collective the schedule above needs -- an in-place SUM all-reduce of n doubles on a device buffer, ordered on a stream.

@@ -23,6 +23,10 @@
  * Pinning: g2o cannot be built in this image (needs Eigen3 / CHOLMOD, absent) => "parity unpinned";
  * pinned instead by finite-difference Jacobian tests, exact recovery on noise-free scenes and the
  * object_slam_demo.py scenario (tests/test_oracle_lm.py).
+ * pose_oplus against exp in mpmath at 50 digits (tests/se3_ref.py, measured by tests/test_se3_ref.py over tests/se3_cases.py): the rotation
+ * within 9e-16 at every angle; the translation within 1.1e-15 of max(1, |t|) from 0.1 rad up, but 8e-15 at 1e-3 rad and 1.5e-12 at 1e-5 rad --
+ * cancellation in the closed forms (1 - cos) / th^2 and (th - sin) / th^3, which se3quat.h uses down to 1e-5 and this file keeps.  The HIP
+ * kernels use Taylor series below 0.3 rad and stay within 3e-16 there: where the two differ at small angles, the mp reference sides with the kernel.
  * Documented deviation: chi2 used for re-classification is recomputed at the
  * accepted state; the reference reads a stale value when an LM call ends on a rejected trial.
  */

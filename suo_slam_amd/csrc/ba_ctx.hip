@@ -227,7 +227,26 @@ int suo_debug_cholesky_solve(const double* A, const double* b, int ns, double* x
     return SUO_OK;
 }
 
-// Test entry: what the LM kernels linearise.  After suo_ba_linearize (edge_pass_partial of csrc/lm_device.h, shared by every LM
+// Test entry: the SE(3) update of every LM kernel (csrc/lm_device.h: pose_from_T, pose_oplus, pose_to_T), one thread per pose, on host arrays: T_out[i] =
+// exp(u[i]) * T_in[i] (row-major 3x4; u = omega, upsilon) and, when q_out is given, the unit quaternion (w, x, y, z) the kernels keep after the update.
+int suo_debug_pose_oplus(const double* T_in, const double* u, int n, double* T_out, double* q_out) {
+    if (!T_in || !u || !T_out || n <= 0) { suo_set_error("suo_debug_pose_oplus: bad argument"); return SUO_ERR_ARG; }
+    double* d = nullptr;
+    const size_t nn = (size_t)n;
+    SUO_HIP_CHECK(hipMalloc((void**)&d, nn * (12 + 6 + 12 + 4) * sizeof(double)));
+    struct Free { double* d; ~Free() { (void)hipFree(d); } } guard{d};
+    double *d_T = d, *d_u = d + 12 * nn, *d_out = d + 18 * nn, *d_q = d + 30 * nn;
+    SUO_HIP_CHECK(hipMemcpy(d_T, T_in, 12 * nn * sizeof(double), hipMemcpyHostToDevice));
+    SUO_HIP_CHECK(hipMemcpy(d_u, u, 6 * nn * sizeof(double), hipMemcpyHostToDevice));
+    int rc = launch_debug_pose_oplus(d_T, d_u, n, d_out, d_q, nullptr);
+    if (rc != SUO_OK) return rc;
+    SUO_HIP_CHECK(hipDeviceSynchronize());
+    SUO_HIP_CHECK(hipMemcpy(T_out, d_out, 12 * nn * sizeof(double), hipMemcpyDeviceToHost));
+    if (q_out) SUO_HIP_CHECK(hipMemcpy(q_out, d_q, 4 * nn * sizeof(double), hipMemcpyDeviceToHost));
+    return SUO_OK;
+}
+
+// Test entry: what the LM kernels linearise. After suo_ba_linearize (edge_pass_partial of csrc/lm_device.h, shared by every LM
 // kernel) the context holds, per edge in the CALLER's edge order: jac[29] = [Jc 2x6 | Jo 2x6 | w*info (xx,xy,yy) | -w*info*err (2)]
 // and err[2].  Inactive edges (outliers, fixed-fixed) keep whatever was there before: call it on all-inlier graphs.
 int suo_debug_ba_jacobians(suo_ba_ctx* c, int n_edge, double* jac_out, double* err_out) {

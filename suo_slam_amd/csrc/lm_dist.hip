@@ -652,6 +652,27 @@ int launch_debug_cholesky(const double* A, const double* b, int ns, double* x, i
     SUO_HIP_CHECK(hipGetLastError());
     return SUO_OK;
 }
+// test entry (suo_debug_pose_oplus): one thread per pose through pose_from_T, pose_oplus and pose_to_T of csrc/lm_device.h, as every LM kernel updates a vertex
+__global__ __launch_bounds__(64) void debug_pose_oplus_kernel(const double* __restrict__ T_in, const double* __restrict__ u, int n, double* __restrict__ T_out,
+                                                               double* __restrict__ q_out) {
+    const int i = blockIdx.x * 64 + threadIdx.x;
+    if (i >= n) return;
+    double T[12], up[6];
+    for (int k = 0; k < 12; ++k) T[k] = T_in[12 * (size_t)i + k];
+    for (int k = 0; k < 6; ++k) up[k] = u[6 * (size_t)i + k];
+    Pose p;
+    pose_from_T(T, p);
+    pose_oplus(p, up);
+    pose_to_T(p, T);
+    for (int k = 0; k < 12; ++k) T_out[12 * (size_t)i + k] = T[k];
+    if (q_out) { for (int k = 0; k < 4; ++k) q_out[4 * (size_t)i + k] = p.q[k]; }
+}
+int launch_debug_pose_oplus(const double* T_in, const double* u, int n, double* T_out, double* q_out, hipStream_t s) {
+    if (n <= 0) { suo_set_error("suo_debug_pose_oplus: n = %d", n); return SUO_ERR_ARG; }
+    hipLaunchKernelGGL(debug_pose_oplus_kernel, dim3((n + 63) / 64), dim3(64), 0, s, T_in, u, n, T_out, q_out);
+    SUO_HIP_CHECK(hipGetLastError());
+    return SUO_OK;
+}
 int launch_ba_ctl_begin(double* ctl, int its, int world, hipStream_t s) {
     hipLaunchKernelGGL(ba_ctl_begin_kernel, dim3(1), dim3(64), 0, s, ctl, its, world);
     SUO_HIP_CHECK(hipGetLastError());

@@ -63,4 +63,5 @@ int launch_resid_stats(const void* problems_dev, const void* rs_dev /* RsProblem
 // (csrc/track_cov.h) laid out by stage_cov, one workgroup per (problem, camera)
 int launch_track_cov(const void* problems_dev, const void* tc_dev, int n_problems, int max_cam, int max_obj, hipStream_t s);
 int launch_debug_cholesky(const double* A, const double* b, int ns, double* x, int* ok, hipStream_t s);
+int launch_debug_pose_oplus(const double* T_in, const double* u, int n, double* T_out, double* q_out, hipStream_t s);    // q_out may be nullptr (device pointers)
 }  // namespace suo

@@ -69,7 +69,8 @@ def anisotropic_noise(rng, n, s_min=0.4, ratio=10.0):
 
 def graph(rng, counts, cam_fixed, obj_fixed, outlier_frac=None, gross_objects=(), perturb=(5e-4, 0.3)):
     """A pose graph with counts[c, o] edges between camera c and object o (each edge its own model point), anisotropic information, outliers as in
-    the module doc; every free vertex starts perturbed from the truth.  gross_objects: objects ALL of whose measurements are gross outliers."""
+    the module doc; every free vertex starts perturbed from the truth by perturb = (rot [rad], trans [mm]).  gross_objects: objects ALL of whose measurements are
+    gross outliers.  The truth rides along under "cam_gt" / "obj_gt" (not in KEYS: no solver sees it)."""
     counts = np.asarray(counts, int)
     n_cam, n_obj = counts.shape
     cam_gt, obj_gt = _cameras(rng, n_cam), _objects(rng, n_obj)
@@ -111,7 +112,8 @@ def graph(rng, counts, cam_fixed, obj_fixed, outlier_frac=None, gross_objects=()
     obj_T = np.stack([T if obj_fixed[o] else S._perturb_pose(T, rng, rot, trans) for o, T in enumerate(obj_gt)])
     return {"cam_T": cam_T, "cam_fixed": cam_fixed, "obj_T": obj_T, "obj_fixed": obj_fixed,
             "edge_cam": np.array(e_cam, np.int32), "edge_obj": np.array(e_obj, np.int32), "edge_camk": np.tile(K_PIX, (E, 1)),
-            "edge_p": np.concatenate(e_p), "edge_uv": np.concatenate(e_uv), "edge_info": np.concatenate(e_info), "edge_inlier": np.ones(E, np.uint8)}
+            "edge_p": np.concatenate(e_p), "edge_uv": np.concatenate(e_uv), "edge_info": np.concatenate(e_info), "edge_inlier": np.ones(E, np.uint8),
+            "cam_gt": cam_gt, "obj_gt": obj_gt}
 
 
 def spread(rng, total, n_cam, n_obj, miss=0.15):
@@ -133,23 +135,23 @@ def spread(rng, total, n_cam, n_obj, miss=0.15):
     return counts
 
 
-def frame(rng, per_obj):
+def frame(rng, per_obj, perturb=(3e-4, 0.2)):
     """Single-view frame: one fixed camera, objects free, per_obj[o] edges each."""
-    return graph(rng, np.array([per_obj]), [1], np.zeros(len(per_obj)), perturb=(3e-4, 0.2))
+    return graph(rng, np.array([per_obj]), [1], np.zeros(len(per_obj)), perturb=perturb)
 
 
-def tracking(rng, per_obj, n_fixed_cams=0):
+def tracking(rng, per_obj, n_fixed_cams=0, perturb=(2e-4, 0.1)):
     """Camera tracking (ObjectSLAM.optimize(curr_only=True)): ONE free camera, every object fixed; n_fixed_cams more (fixed) cameras with their own edges."""
     counts = np.array([per_obj] * (1 + n_fixed_cams))
     cam_fixed = [0] + [1] * n_fixed_cams
-    return graph(rng, counts, cam_fixed, np.ones(len(per_obj)), perturb=(2e-4, 0.1))
+    return graph(rng, counts, cam_fixed, np.ones(len(per_obj)), perturb=perturb)
 
 
-def global_graph(rng, total, n_cam, n_obj, miss=0.15):
+def global_graph(rng, total, n_cam, n_obj, miss=0.15, perturb=(5e-4, 0.3)):
     """The global adjustment: camera 0 fixed (the gauge), every other camera and every object free."""
     cf = np.zeros(n_cam)
     cf[0] = 1
-    return graph(rng, spread(rng, total, n_cam, n_obj, miss), cf, np.zeros(n_obj))
+    return graph(rng, spread(rng, total, n_cam, n_obj, miss), cf, np.zeros(n_obj), perturb=perturb)
 
 
 def with_weak_camera(rng, P, n_kp):
