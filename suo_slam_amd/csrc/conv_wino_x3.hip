@@ -84,6 +84,12 @@ bool conv3x3_wino_f16x2_w8(long tiles) {
 bool conv3x3_wino_f16x2_dma() { return env_switch("SUO_WINO_HALO_DMA", 1) != 0; }
 int launch_conv3x3_wino_f16x2_dma(const ConvArgs& a, hipStream_t s, int tiles);          // 64 -> 64 or 128 -> 128 by a.N
 int launch_conv3x3_wino_f16x2_fused_dma(const ConvArgs& a, hipStream_t s, int tiles);    // with / without a.up, a.n_W1
+// The LDS-DMA form's tail with the up-sampled addend fetches its skip rows by LDS-DMA as well, a block of the epilogue ahead (the kernel's comment: SKD).
+// SUO_WINO_SKIP_DMA=0 (supported switch, include/suo_hip.h; read when a launch is issued, like SUO_WINO_HALO_DMA): the register loads (A/B,
+// tests/test_gpu_wino_skip_dma.py: bit for bit the same).  The other tails have no such form (profiles/REJECTED.md); with SUO_WINO_HALO_DMA=0 none has.
+// Kernel and launcher: csrc/conv_wino_x3_skip_dma.hip.
+bool conv3x3_wino_f16x2_skip_dma() { return env_switch("SUO_WINO_SKIP_DMA", 1) != 0; }
+int launch_conv3x3_wino_f16x2_fused_up_skip_dma(const ConvArgs& a, hipStream_t s, int tiles);
 
 // a.Wp = weights packed by pack_wino_weight_bf16x3 / _f16x2 (uint16 under a float pointer); 128 -> 128 or 64 -> 64 channels
 template <int NP>
@@ -101,7 +107,7 @@ static int launch_wino_split(const ConvArgs& a, hipStream_t s) {
         return SUO_ERR_ARG;
     }
     const int tiles = ((a.OW + X_TW - 1) / X_TW) * ((a.OH + X_TH - 1) / X_TH) * a.L;
-    if (NP == 2 && conv3x3_wino_f16x2_w8(tiles)) hipLaunchKernelGGL((wino3x3_x3_kernel<false, false, false, 4, 2, false, true>), dim3(tiles), dim3(512), 0, s, a);
+    if (NP == 2 && conv3x3_wino_f16x2_w8(tiles)) hipLaunchKernelGGL((wino3x3_x3_kernel<false, false, false, 4, 2, false, false, true>), dim3(tiles), dim3(512), 0, s, a);
     else if (NP == 2 && conv3x3_wino_f16x2_dma()) return launch_conv3x3_wino_f16x2_dma(a, s, tiles);
     else hipLaunchKernelGGL((wino3x3_x3_kernel<false, false, false, 4, NP>), dim3(tiles), dim3(256), 0, s, a);
     SUO_HIP_CHECK(hipGetLastError());
@@ -126,9 +132,9 @@ int launch_conv3x3_wino_f16x2_fused(const ConvArgs& a, hipStream_t s) {
         if (dma) return launch_conv3x3_wino_f16x2_fused_dma(a, s, tiles);
         hipLaunchKernelGGL((wino3x3_x3_kernel<true, false, true, 4, 2, true>), dim3(tiles), dim3(256), 0, s, a);
     } else if (conv3x3_wino_f16x2_w8(tiles)) {
-        if (a.up) hipLaunchKernelGGL((wino3x3_x3_kernel<true, true, true, 4, 2, false, true>), dim3(tiles), dim3(512), 0, s, a);
-        else hipLaunchKernelGGL((wino3x3_x3_kernel<true, false, true, 4, 2, false, true>), dim3(tiles), dim3(512), 0, s, a);
-    } else if (dma) return launch_conv3x3_wino_f16x2_fused_dma(a, s, tiles);
+        if (a.up) hipLaunchKernelGGL((wino3x3_x3_kernel<true, true, true, 4, 2, false, false, true>), dim3(tiles), dim3(512), 0, s, a);
+        else hipLaunchKernelGGL((wino3x3_x3_kernel<true, false, true, 4, 2, false, false, true>), dim3(tiles), dim3(512), 0, s, a);
+    } else if (dma) return a.up && conv3x3_wino_f16x2_skip_dma() ? launch_conv3x3_wino_f16x2_fused_up_skip_dma(a, s, tiles) : launch_conv3x3_wino_f16x2_fused_dma(a, s, tiles);
     else if (a.up) hipLaunchKernelGGL((wino3x3_x3_kernel<true, true, true, 4, 2>), dim3(tiles), dim3(256), 0, s, a);
     else hipLaunchKernelGGL((wino3x3_x3_kernel<true, false, true, 4, 2>), dim3(tiles), dim3(256), 0, s, a);
     SUO_HIP_CHECK(hipGetLastError());

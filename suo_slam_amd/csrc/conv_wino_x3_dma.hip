@@ -6,15 +6,15 @@
 namespace suo {
 
 int launch_conv3x3_wino_f16x2_dma(const ConvArgs& a, hipStream_t s, int tiles) {
-    if (a.N == 64) hipLaunchKernelGGL((wino3x3_x3_kernel<false, false, false, 2, 2, false, false, true>), dim3(tiles), dim3(256), 0, s, a);
-    else hipLaunchKernelGGL((wino3x3_x3_kernel<false, false, false, 4, 2, false, false, true>), dim3(tiles), dim3(256), 0, s, a);
+    if (a.N == 64) hipLaunchKernelGGL((wino3x3_x3_kernel<false, false, false, 2, 2, false, false, false, true>), dim3(tiles), dim3(256), 0, s, a);
+    else hipLaunchKernelGGL((wino3x3_x3_kernel<false, false, false, 4, 2, false, false, false, true>), dim3(tiles), dim3(256), 0, s, a);
     SUO_HIP_CHECK(hipGetLastError());
     return SUO_OK;
 }
 int launch_conv3x3_wino_f16x2_fused_dma(const ConvArgs& a, hipStream_t s, int tiles) {
-    if (a.n_W1) hipLaunchKernelGGL((wino3x3_x3_kernel<true, false, true, 4, 2, true, false, true>), dim3(tiles), dim3(256), 0, s, a);
-    else if (a.up) hipLaunchKernelGGL((wino3x3_x3_kernel<true, true, true, 4, 2, false, false, true>), dim3(tiles), dim3(256), 0, s, a);
-    else hipLaunchKernelGGL((wino3x3_x3_kernel<true, false, true, 4, 2, false, false, true>), dim3(tiles), dim3(256), 0, s, a);
+    if (a.n_W1) hipLaunchKernelGGL((wino3x3_x3_kernel<true, false, true, 4, 2, true, false, false, true>), dim3(tiles), dim3(256), 0, s, a);
+    else if (a.up) hipLaunchKernelGGL((wino3x3_x3_kernel<true, true, true, 4, 2, false, false, false, true>), dim3(tiles), dim3(256), 0, s, a);
+    else hipLaunchKernelGGL((wino3x3_x3_kernel<true, false, true, 4, 2, false, false, false, true>), dim3(tiles), dim3(256), 0, s, a);
     SUO_HIP_CHECK(hipGetLastError());
     return SUO_OK;
 }

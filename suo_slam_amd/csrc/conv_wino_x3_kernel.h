@@ -69,11 +69,24 @@ constexpr int X_CK = 16, X_PKH = 20, X_TH = 8, X_TW = 16, X_IH = 10, X_IW = 18, 
 //    vmcnt(4) there (the next chunk's first pair = 4 loads may stay in flight) states it.  The buffer is read one barrier later, at the top of chunk c + 1.
 //  - The exact factor 2^s rides on the transform's first differences (32 products instead of 12; scaling by a power of two commutes with the additions: same bits), the
 //    guard's running maximum on three ds_read_b128 of the lane's own slots of the landed buffer (the same elements the register path saw; max |x| 2^s = max |x 2^s|).
+// SKD (the DMA form's tail with the up-sampled addend; SUO_WINO_SKIP_DMA=0 keeps the register loads, csrc/conv_wino_x3_skip_dma.hip): the epilogue's skip rows go from
+// a.R into LDS by the same instruction, ONE EPILOGUE BLOCK AHEAD of their use.  Lane (lane >> 3, lane & 7) fetches the 16 bytes this same lane adds: one wave-
+// instruction fills a 1 KiB lane-linear slot, the read back is the lane's own ds_read_b128, nothing crosses lanes and no workgroup barrier is involved.
+//  - Four slots per wave (row groups k = 0..3 of one block at a time) behind everything else in S: 77 952 B per workgroup, two per CU as before.
+//  - Order: block 0's four before pass 0's operand split; block b + 1's slot k right after block b's slot k has been read (lgkmcnt(0) inside the statement), before
+//    block b's store k; pass 1's first block during pass 0's last.  Completion: explicit vmcnt(N), N derived where it is issued.
+//  - A lane whose pixel is outside the map counts its slot as zero by a select: the rows a lane's slot sees differ from block to block (a tile's lower rows may be
+//    outside where its upper rows are not), so zeroing the slots once, as the halo does, would not do.  o, and with it every stored bit, is the register path's.
+//  - The per-column vectors (bias3, oscale3) come from LDS too: a load that hipcc counts, issued while a DMA is in flight, gets a wait that drains the DMA.  The addend's
+//    own loads stay in registers: hipcc's waits for them retire a DMA or two of the block ahead early.
+//  - Measured (profiles/wino_skip_dma.txt): this tail -7 % at 64x64.  The plain tail and the tail with the next block's conv1 were built the same way, also with a
+//    six-slot ring: +-0 and +1 % -- what their skip rows cost is not the exposed round trip; they keep the register loads (profiles/REJECTED.md).
 // A third weight slot for the freed registers (weights two pairs ahead) measured SLOWER than two (profiles/REJECTED.md): the ring stays two deep in both paths.
-template <bool FUSE, bool UP = false, bool TX3 = false, int NT = 4, int NP = 3, bool NEXT = false, bool W8 = false, bool DMA = false>
+template <bool FUSE, bool UP = false, bool TX3 = false, int NT = 4, int NP = 3, bool NEXT = false, bool SKD = false, bool W8 = false, bool DMA = false>
 __global__ __launch_bounds__(W8 ? 512 : 256) __attribute__((amdgpu_waves_per_eu(2))) void wino3x3_x3_kernel(const ConvArgs a) {
     static_assert(NT == 4 || (NT == 2 && !FUSE), "64-channel form: plain convolution only");
     static_assert(!DMA || (NP == 2 && !W8), "halo by LDS-DMA: the four-wave fp16 form");
+    static_assert(!SKD || (DMA && FUSE && TX3 && UP && !NEXT), "skip rows by LDS-DMA: the LDS-DMA form's tail with the up-sampled addend (the form it measured faster on)");
     static_assert(!W8 || (NT == 4 && NP == 2 && !NEXT && (TX3 || !FUSE)), "eight waves: the fp16 form of the 128-channel kernel, without the next block's conv1");
     constexpr int NTHR = W8 ? 512 : 256;
     static_assert(!NEXT || (FUSE && TX3 && NP == 2), "the next block's conv1 rides on the fp16 tail");
@@ -86,7 +99,9 @@ __global__ __launch_bounds__(W8 ? 512 : 256) __attribute__((amdgpu_waves_per_eu(
     constexpr int VFLOATS = NP * VPL / 2;
     // (W8: one workgroup per CU anyway -- the tail's eight transposition patches get their own room behind the operand planes)
     constexpr int TAILF = NP * 8 * (64 * 32 + 32) / 4;        // floats of the tail's operand planes (NP planes x 8 k-steps x (64 pixels x 32 bytes + 32))
-    constexpr int SFLOATS = W8 ? (2 * HSZ + VFLOATS > TAILF + 8 * 32 * 36 ? 2 * HSZ + VFLOATS : TAILF + 8 * 32 * 36) : 2 * HSZ + VFLOATS;
+    constexpr int SKF = SKD ? 4 * 1024 : 0;                   // SKD: four 1 KiB skip-row slots per wave BEHIND everything else -- a DMA into them never meets the K loop's or the tail's own LDS
+    constexpr int SFLOATS = W8 ? (2 * HSZ + VFLOATS > TAILF + 8 * 32 * 36 ? 2 * HSZ + VFLOATS : TAILF + 8 * 32 * 36) : 2 * HSZ + VFLOATS + SKF;
+    static_assert(SFLOATS * 4 <= 80 * 1024, "two workgroups per CU");
     __shared__ __attribute__((aligned(16))) float S[SFLOATS];
     float (*Hin)[HSZ] = reinterpret_cast<float (*)[HSZ]>(&S[0]);
     uint16_t* V = reinterpret_cast<uint16_t*>(&S[2 * HSZ]);
@@ -423,6 +438,53 @@ __global__ __launch_bounds__(W8 ? 512 : 256) __attribute__((amdgpu_waves_per_eu(
         // weights: W3x[(ks * 8 + nb) * 3 + plane][lane][8 bf16], 1 KB each (pack_tail_weight_bf16x3); the wave's n-tiles are w and 4 + w (output channels
         // [32 w, 32 w + 32) and [128 + 32 w, ...): the four waves' first tiles are channels 0-127 in order, which is the K order the NEXT conv1 consumes them in)
         const int w3voff = lane * 16;
+        // SKD: the skip rows by LDS-DMA (the kernel's comment).  Epilogue blocks in the order they run: b = 4 h + 2 j + i; slot k of the wave's buffer holds the 64 lanes'
+        // 16 bytes of row group k of ONE block at a time.  skoff = the lane's byte offset inside the crop's 256-channel tensors (skip, out2), BUF_OOB outside the map:
+        // the value of the epilogue's off[k] (pixel m = 32 i + (lane >> 3) + 8 k: row 2 (m >> 4) + h = 2 (2 i + (k >> 1)) + h and column (lane >> 3) + 8 (k & 1) of the
+        // tile, channel 128 j + 32 w + 4 (lane & 7)) as ONE per-lane term plus wave-uniform ones: asking for the next block's offsets costs an addition and a select, no live registers
+        const int sk_lane = ((oy0 * a.OW + ox0 + (lane >> 3)) * a.N2 + w * 32 + (lane & 7) * 4) * 4;
+        auto skoff = [&](int b, int k) -> int {
+            const int row = 2 * (2 * (b & 1) + (k >> 1)) + (b >> 2);
+            const int xlim = oy0 + row < a.OH ? a.OW - ox0 - 8 * (k & 1) : 0;          // (uniform) the lanes with (lane >> 3) < xlim are inside the map
+            const int lin = sk_lane + ((row * a.OW + 8 * (k & 1)) * a.N2 + 128 * ((b >> 1) & 1)) * 4;
+            return (lane >> 3) < xlim ? lin : BUF_OOB;
+        };
+        const float* RB = &S[2 * HSZ + VFLOATS] + w * 1024;
+        const unsigned rb_w = __builtin_amdgcn_readfirstlane((unsigned)(size_t)&S[2 * HSZ + VFLOATS]) + w * 4096;
+        // one wave-instruction: row group k of block b -> slot k.  lgkmcnt(0) first: the lane's own ds_read_b128 of the slot's previous content (issued before this
+        // statement) has returned before the DMA can overwrite it.  M0 as in the halo's statement
+        auto skdma = [&](int b, int k) {
+            if constexpr (SKD) {
+                unsigned keep;
+                asm volatile("s_waitcnt lgkmcnt(0)\n\t"
+                             "s_mov_b32 %0, m0\n\t"
+                             "s_nop 4\n\t"
+                             "s_mov_b32 m0, %3\n\ts_nop 0\n\tbuffer_load_dwordx4 %1, %2, 0 offen lds\n\t"
+                             "s_mov_b32 m0, %0"
+                             : "=&s"(keep)
+                             : "v"(skoff(b, k)), "s"(r_srd), "s"(rb_w + k * 1024)
+                             : "memory");
+            }
+        };
+        auto skwait = [&](int n) {                            // n folds to a constant in the unrolled epilogue
+            switch (n) {
+                case 3: asm volatile("s_waitcnt vmcnt(3)" ::: "memory"); break;
+                case 4: asm volatile("s_waitcnt vmcnt(4)" ::: "memory"); break;
+                case 5: asm volatile("s_waitcnt vmcnt(5)" ::: "memory"); break;
+                case 6: asm volatile("s_waitcnt vmcnt(6)" ::: "memory"); break;
+                default: asm volatile("s_waitcnt vmcnt(7)" ::: "memory"); break;
+            }
+        };
+        // SKD: the epilogue's per-column vectors come from LDS (staged here once, in the 9.6 KB the tail leaves free behind its patches; visible after pass 0's barrier).
+        // A load that hipcc counts, issued while a DMA is in flight, is waited for with a count that does not know of the DMA: its vmcnt(0) drained the DMA of the block ahead
+        float* CB = &S[NP * PL_STRIDE / 4 + 4 * 32 * 36];
+        if constexpr (SKD) {
+            static_assert(NP * PL_STRIDE + 4 * 32 * 36 * 4 + 2 * 256 * 4 <= (2 * HSZ + VFLOATS) * 4 && NTHR == 256, "column vectors: 256 threads, one column each");
+            CB[tid] = a.bias3[tid];
+            CB[256 + tid] = a.oscale3[tid];
+#pragma unroll
+            for (int k = 0; k < 4; ++k) skdma(0, k);         // block 0: under pass 0's operand split (the conv3 k-loop's first counted wait for its weights retires it too)
+        }
         auto b3load = [&](int ks, u32x4 (&b)[2][NP]) {
             const int k = ks < 8 ? ks : 7;
 #pragma unroll
@@ -490,20 +552,21 @@ __global__ __launch_bounds__(W8 ? 512 : 256) __attribute__((amdgpu_waves_per_eu(
 #pragma unroll
                 for (int i = 0; i < 2; ++i) {
                     const int col = (W8 ? w : 4 * j + w) * 32 + (lane & 7) * 4;
-                    const f32x4 bv = *(const f32x4*)(a.bias3 + col);
+                    const f32x4 bv = SKD ? *(const f32x4*)&CB[col] : *(const f32x4*)(a.bias3 + col);
                     f32x4 osc3 = f32x4{1.f, 1.f, 1.f, 1.f};
-                    if constexpr (NP == 2) osc3 = *(const f32x4*)(a.oscale3 + col);
+                    if constexpr (NP == 2) osc3 = SKD ? *(const f32x4*)&CB[256 + col] : *(const f32x4*)(a.oscale3 + col);
                     f32x4 nsc, nsh;
                     if constexpr (NEXT) { const float nxs = s2_xscale(a.n_xscale); nsc = *(const f32x4*)(a.n_scale + col) * nxs; nsh = *(const f32x4*)(a.n_shift + col) * nxs; }
                     int off[4];
-                    f32x4 rv[4], uv[UP ? 4 : 1];
+                    f32x4 rv[SKD ? 1 : 4], uv[UP ? 4 : 1];
 #pragma unroll
                     for (int k = 0; k < 4; ++k) {
                         const int m = 32 * i + (lane >> 3) + 8 * k;
                         const int oy = oy0 + 2 * (m >> 4) + h, ox = ox0 + (m & 15);
                         const bool in = oy < a.OH && ox < a.OW;
-                        off[k] = in ? ((oy * a.OW + ox) * a.N2 + col) * 4 : BUF_OOB;
-                        rv[k] = buf_load(r_srd, off[k], 0);
+                        if constexpr (SKD) off[k] = skoff(4 * h + 2 * j + i, k);           // (the same value)
+                        else off[k] = in ? ((oy * a.OW + ox) * a.N2 + col) * 4 : BUF_OOB;
+                        if constexpr (!SKD) rv[k] = buf_load(r_srd, off[k], 0);
                         if constexpr (UP && !NEXT) uv[k] = buf_load(up_srd, in ? (((oy >> 1) * (a.OW >> 1) + (ox >> 1)) * a.N2 + col) * 4 : BUF_OOB, 0);
                     }
 #pragma unroll
@@ -518,7 +581,23 @@ __global__ __launch_bounds__(W8 ? 512 : 256) __attribute__((amdgpu_waves_per_eu(
                         }
                         f32x4 o = *(const f32x4*)&T[((lane >> 3) + 8 * k) * 36 + (lane & 7) * 4];
                         if constexpr (NP == 2) o *= osc3;             // back to scale (an exact power of two per column)
-                        o = (o + bv) + rv[k];
+                        if constexpr (SKD) {
+                            // The wave's VMEM instructions behind DMA(b, k) that are certain to have been issued by now -- its own DMAs and the blocks' buf_stores, all
+                            // unconditional and pinned in this order by the asm statements (hipcc's loads in between only make the wait stricter; vmcnt retires loads and
+                            // stores alike in issue order on this target, as hipcc's own counted waits assume):
+                            //   block 0 (requested in one go before the pass): DMA(0, k + 1 .. 3), then a pair {DMA(1, q), store(0, q)} for each q < k          = 3 + k
+                            //   blocks 1-6: store(b - 1, k), the pairs {DMA(b, q), store(b - 1, q)} for q > k and {DMA(b + 1, q), store(b, q)} for q < k         = 7
+                            //   block 7 (requests nothing): store(6, k), the pairs of q > k, store(7, q) for q < k                                             = 7 - k
+                            const int b = 4 * h + 2 * j + i;
+                            skwait(b == 0 ? 3 + k : b == 7 ? 7 - k : 7);
+                            // (a lane outside the map: its slot holds whatever an earlier block's row left there -- the register path's buffer load gives it zero)
+                            const f32x4 r = *(const f32x4*)&RB[k * 256 + lane * 4];
+                            const bool inmap = off[k] != BUF_OOB;
+                            o = (o + bv) + f32x4{inmap ? r[0] : 0.f, inmap ? r[1] : 0.f, inmap ? r[2] : 0.f, inmap ? r[3] : 0.f};
+                            if (b < 7) skdma(b + 1, k);               // slot k is free again: the next block's row group, ahead of this block's stores
+                        } else {
+                            o = (o + bv) + rv[k];
+                        }
                         if constexpr (UP) o += uv[NEXT ? 0 : k];
                         buf_store(o, o2_srd, off[k]);
                         if constexpr (NEXT) {
