@@ -724,6 +724,24 @@ int suo_debug_cholesky_solve(const double* A, const double* b, int ns, double* x
  *   else          those closed forms.
  * n <= 0 or a NULL T_in, u or T_out: SUO_ERR_ARG, nothing launched. */
 int suo_debug_pose_oplus(const double* T_in, const double* u, int n, double* T_out, double* q_out);
+/* Test entry: the refinement half of the PnP kernel (PNP::refine, pnp_ransac.cpp:240-326) on its own, through the very device functions pnp_batch_kernel calls
+ * (csrc/pnp.hip: p4p, count_inliers, select_inliers, refine_normal_eqs, refine_cost, refine_pass, refine_sequence).  HOST arrays, blocking, one launch, one wave per
+ * object; objects are ragged as in suo_pnp_batch: n_pts [n_obj], xs [sum n][3], ys [sum n][2] (normalised), sel_in / sel0_out / sel1_out [sum n] in the same order.
+ * Per object o:
+ *   start      start_idx[o][4] with [0] >= 0: the start is p4p of those four points; else start_qt[o][7] = (q w x y z, t), used as given
+ *   mode[o]    0 SEQUENCE: select, refine 5 iterations at 1e-6, reselect, 3 iterations at 1e-8 unless deltas < 0.05 m -- what suo_pnp_batch runs with do_refine
+ *              1 PASS: one refine pass of max_iter[o] (0 .. 50) iterations at tolerance tol[o] over the points with sel_in != 0
+ *   out_d[o][88]  [0:7] the start (q, t) used  [7:43] H = J'J row-major and [43:49] g = J'r and [49] cost = 1/2 sum |r|^2, all at the start over the first
+ *              selection (columns: the three local coordinates of Ceres' QuaternionParameterization, then t)  [50:57] (q, t) after the first pass  [57:64] the final
+ *              (q, t)  [64:76] the pose after the first pass as row-major 3x4  [76:88] the final pose as 3x4.  PASS: final = after the pass.
+ *   out_i[o][8]   [0] inliers of the start by the RANSAC count rule (1 / z < 0 skips, err < thr^2 counts)  [1] m0, size of the first selection  [2] m1, size of the
+ *              reselection  [3] deltas, flags that changed  [4] 1 when the second pass ran  [5:8] 0.  PASS: m1 = deltas = [4] = 0.
+ *   sel0_out, sel1_out   the two selections as 0 / 1 per point by the refinement's rule (z < 0 drops, err > thr^2 drops); PASS: sel0 = sel_in != 0, sel1 = 0.
+ * Refused with SUO_ERR_ARG, nothing launched, nothing written: n_obj <= 0, a NULL pointer, n_pts[o] < 0 or > 1024, a start index outside [0, n_pts[o]), a mode
+ * other than 0 / 1, max_iter outside 0 .. 50 on a PASS object. */
+int suo_debug_pnp_refine(int n_obj, const int* n_pts, const double* xs, const double* ys, double threshold, const int* mode, const double* start_qt,
+                         const int* start_idx, const int* sel_in, const int* max_iter, const double* tol, double* out_d, int* out_i, int* sel0_out,
+                         int* sel1_out);
 
 /* ---- the partitioned adjustment driven from C (csrc/ba_comm.hip, csrc/ba_drive.hip: optimize_dist) ---------------------------------
  * suo_ba_comm: the one collective the schedule above needs -- an in-place SUM all-reduce of n doubles on a device buffer, ordered on a stream.

@@ -32,6 +32,8 @@ def lib():
         L.orc_pnp_ransac.argtypes = [_dp, _dp, C.c_int, C.c_double, C.c_uint64, C.c_int, _dp, C.POINTER(C.c_int)]
         L.orc_pnp_ransac_draws.restype = C.c_int
         L.orc_pnp_ransac_draws.argtypes = [_dp, _dp, C.c_int, C.c_double, C.c_uint64, _ip, C.c_int, C.c_int, _dp, C.POINTER(C.c_int), C.POINTER(C.c_int)]
+        L.orc_pnp_refine_debug.restype = C.c_int
+        L.orc_pnp_refine_debug.argtypes = [C.c_int, _ip, _dp, _dp, C.c_double, _ip, _dp, _ip, _ip, _ip, _dp, _dp, _ip, _ip, _ip]
         L.orc_ref_rng_seed.restype = None
         L.orc_ref_rng_seed.argtypes = [C.POINTER(C.c_uint32), C.c_uint32]
         L.orc_ref_randui.restype = C.c_int

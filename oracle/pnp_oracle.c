@@ -35,6 +35,8 @@
  *      rho > 1e-3, radius /= max(1/3, 1-(2rho-1)^3) on success, radius /= 2,4,8.. on failure,
  *      termination on function / gradient / parameter tolerance or the iteration cap
  *      (5 its tol 1e-6, then 3 its tol 1e-8 when >= 5% of the inlier set changed).
+ *      Held against an mp reference written from these definitions, not from this file (tests/pnp_refine_ref.py, tests/test_pnp_refine_ref.py, through
+ *      orc_pnp_refine_debug at the end of this file); parity with Ceres itself stays unpinned.
  */
 #include <math.h>
 #include <stdint.h>
@@ -599,4 +601,92 @@ ORC_API int orc_pnp_ransac_draws(const double* xs, const double* ys, int n, doub
     if (best_inliers_out) *best_inliers_out = (int)best;
     if (winner_out) *winner_out = winner;
     return (int)i;
+}
+
+/* Test access to the refinement alone: the inputs and outputs of suo_debug_pnp_refine (include/suo_hip.h), from evaluate_inlier_set, select_inliers,
+ * refine_cost and refine_pass above, unchanged.  H and g at the start are not returned by refine_pass: they are formed here by the same statements as the
+ * top of its loop (a copy for reporting; the poses come from refine_pass itself).  Returns 0, or -1 where the device entry refuses. */
+static void normal_eqs_at(const double* xs, const double* ys, const int* sel, int m, const double* q, const double* t, double* H, double* g) {
+    double R[9];
+    memset(H, 0, 36 * sizeof(double));
+    memset(g, 0, 6 * sizeof(double));
+    quat_to_rot(q, R);
+    for (int k = 0; k < m; ++k) {
+        const double* X = xs + 3 * sel[k];
+        double rx = R[0] * X[0] + R[1] * X[1] + R[2] * X[2];
+        double ry = R[3] * X[0] + R[4] * X[1] + R[5] * X[2];
+        double rz = R[6] * X[0] + R[7] * X[1] + R[8] * X[2];
+        double x = rx + t[0], y = ry + t[1], z = rz + t[2];
+        double iz = 1.0 / z;
+        double r[2] = {x * iz - ys[2 * sel[k]], y * iz - ys[2 * sel[k] + 1]};
+        double P[2][3] = {{iz, 0, -x * iz * iz}, {0, iz, -y * iz * iz}};
+        double D[3][6] = {{0, 2 * rz, -2 * ry, 1, 0, 0}, {-2 * rz, 0, 2 * rx, 0, 1, 0}, {2 * ry, -2 * rx, 0, 0, 0, 1}};
+        double J[2][6];
+        for (int a = 0; a < 2; ++a)
+            for (int c = 0; c < 6; ++c) J[a][c] = P[a][0] * D[0][c] + P[a][1] * D[1][c] + P[a][2] * D[2][c];
+        for (int a = 0; a < 6; ++a) {
+            g[a] += J[0][a] * r[0] + J[1][a] * r[1];
+            for (int c = 0; c < 6; ++c) H[a * 6 + c] += J[0][a] * J[0][c] + J[1][a] * J[1][c];
+        }
+    }
+}
+static void pose_3x4(const double* q, const double* t, double* T) {
+    double R[9];
+    quat_to_rot(q, R);
+    for (int r = 0; r < 3; ++r) { for (int c = 0; c < 3; ++c) T[4 * r + c] = R[3 * r + c]; T[4 * r + 3] = t[r]; }
+}
+ORC_API int orc_pnp_refine_debug(int n_obj, const int* n_pts, const double* xs_all, const double* ys_all, double threshold, const int* mode,
+                                 const double* start_qt, const int* start_idx, const int* sel_in, const int* max_iter, const double* tol, double* out_d,
+                                 int* out_i, int* sel0_out, int* sel1_out) {
+    static int sel[1024], flags[1024];
+    if (n_obj <= 0 || !n_pts || !xs_all || !ys_all || !mode || !start_qt || !start_idx || !sel_in || !max_iter || !tol || !out_d || !out_i || !sel0_out || !sel1_out)
+        return -1;
+    for (int o = 0; o < n_obj; ++o) {
+        if (n_pts[o] < 0 || n_pts[o] > 1024 || (mode[o] != 0 && mode[o] != 1) || (mode[o] == 1 && (max_iter[o] < 0 || max_iter[o] > 50))) return -1;
+        if (start_idx[4 * o] >= 0)
+            for (int k = 0; k < 4; ++k) if (start_idx[4 * o + k] < 0 || start_idx[4 * o + k] >= n_pts[o]) return -1;
+    }
+    const double thr2 = threshold * threshold;
+    int p0 = 0;
+    for (int o = 0; o < n_obj; p0 += n_pts[o], ++o) {
+        const int n = n_pts[o];
+        const double* xs = xs_all + 3 * (size_t)p0;
+        const double* ys = ys_all + 2 * (size_t)p0;
+        double* D = out_d + 88 * (size_t)o;
+        int* I = out_i + 8 * (size_t)o;
+        double q[4], t[3];
+        if (start_idx[4 * o] >= 0) orc_p4p(xs, ys, start_idx + 4 * o, q, t);
+        else { memcpy(q, start_qt + 7 * o, sizeof(q)); memcpy(t, start_qt + 7 * o + 4, sizeof(t)); }
+        memcpy(D, q, sizeof(q));
+        memcpy(D + 4, t, sizeof(t));
+        memset(I, 0, 8 * sizeof(int));
+        I[0] = (int)evaluate_inlier_set(xs, ys, n, threshold, q, t, 0);
+        int m = 0, deltas = 0;
+        if (mode[o] == 0) {
+            m = select_inliers(xs, ys, n, thr2, q, t, sel, flags, 0);
+            for (int i = 0; i < n; ++i) sel0_out[p0 + i] = flags[i];
+        } else {
+            for (int i = 0; i < n; ++i) { sel0_out[p0 + i] = sel_in[p0 + i] != 0; sel1_out[p0 + i] = 0; if (sel_in[p0 + i] != 0) sel[m++] = i; }
+        }
+        I[1] = m;
+        normal_eqs_at(xs, ys, sel, m, q, t, D + 7, D + 43);
+        D[49] = refine_cost(xs, ys, sel, m, q, t);
+        if (mode[o] == 0) refine_pass(xs, ys, sel, m, q, t, 5, 1e-6);
+        else refine_pass(xs, ys, sel, m, q, t, max_iter[o], tol[o]);
+        memcpy(D + 50, q, sizeof(q));
+        memcpy(D + 54, t, sizeof(t));
+        if (mode[o] == 0) {
+            m = select_inliers(xs, ys, n, thr2, q, t, sel, flags, &deltas);
+            /* (with deltas given select_inliers leaves flags as they were: the new flags are the membership of sel) */
+            for (int i = 0; i < n; ++i) sel1_out[p0 + i] = 0;
+            for (int k = 0; k < m; ++k) sel1_out[p0 + sel[k]] = 1;
+            I[2] = m; I[3] = deltas;
+            if (!(deltas < 0.05 * m)) { I[4] = 1; refine_pass(xs, ys, sel, m, q, t, 3, 1e-8); }
+        }
+        memcpy(D + 57, q, sizeof(q));
+        memcpy(D + 61, t, sizeof(t));
+        pose_3x4(D + 50, D + 54, D + 64);
+        pose_3x4(q, t, D + 76);
+    }
+    return 0;
 }

@@ -18,6 +18,10 @@ int launch_pnp_batch(int n_obj, const int* offsets, const double* xs, const doub
 int launch_pnp_batch_counts(int n_obj, const int* offsets, const int* counts, const int* group_first, const double* xs, const double* ys, double threshold, uint64_t seed,
                             const int* iter_tab, const int* iter_tab_off, int do_refine, double* T_out, int* status, int* best_out,
                             int* iters_out, hipStream_t s, const uint64_t* seed_add = nullptr);
+// test entry (suo_debug_pnp_refine): one wave per object through the refinement's own device functions; device pointers, arguments checked by the host entry
+int launch_debug_pnp_refine(int n_obj, const int* offsets, const double* xs, const double* ys, double threshold, const int* mode, const double* start_qt,
+                            const int* start_idx, const int* sel_in, const int* max_iter, const double* tol, double* out_d, int* out_i, int* sel0_out,
+                            int* sel1_out, hipStream_t s);
 // ---- whole LM runs in one launch: problems_dev = n_problems LmProblem structs (csrc/lm_device.h) in device memory ----
 int launch_lm(const void* problems_dev, int n_problems, int lds_bytes, hipStream_t s);
 int launch_lm_big(const void* problems_dev, int n_problems, int lds_bytes, hipStream_t s);

@@ -423,40 +423,46 @@ DEV double refine_cost(const double* xs, const double* ys, int n, unsigned sel, 
     return 0.5 * wave_sum_d(c);
 }
 
+// normal equations of the selected points at (q, t): H = J'J (full, symmetric) and g = J'r, the same values in every lane
+DEV void refine_normal_eqs(const double* xs, const double* ys, int n, unsigned sel, int lane, const double* q, const double* t, double* H, double* g) {
+    double R[9];
+    for (int a = 0; a < 36; ++a) H[a] = 0;
+    for (int a = 0; a < 6; ++a) g[a] = 0;
+    quat_to_rot(q, R);
+    for (int j = 0; j < PNP_MAX_PER_LANE; ++j) {
+        const int i = lane + 64 * j;
+        if (i < n && ((sel >> j) & 1u)) {
+            const double* X = xs + 3 * i;
+            const double rx = R[0] * X[0] + R[1] * X[1] + R[2] * X[2];
+            const double ry = R[3] * X[0] + R[4] * X[1] + R[5] * X[2];
+            const double rz = R[6] * X[0] + R[7] * X[1] + R[8] * X[2];
+            const double x = rx + t[0], y = ry + t[1], z = rz + t[2];
+            const double iz = 1.0 / z;
+            const double r[2] = {x * iz - ys[2 * i], y * iz - ys[2 * i + 1]};
+            const double P[2][3] = {{iz, 0, -x * iz * iz}, {0, iz, -y * iz * iz}};
+            const double D[3][6] = {{0, 2 * rz, -2 * ry, 1, 0, 0}, {-2 * rz, 0, 2 * rx, 0, 1, 0}, {2 * ry, -2 * rx, 0, 0, 0, 1}};
+            double J[2][6];
+            for (int a = 0; a < 2; ++a)
+                for (int c = 0; c < 6; ++c) J[a][c] = P[a][0] * D[0][c] + P[a][1] * D[1][c] + P[a][2] * D[2][c];
+            for (int a = 0; a < 6; ++a) {
+                g[a] += J[0][a] * r[0] + J[1][a] * r[1];
+                for (int c = a; c < 6; ++c) H[a * 6 + c] += J[0][a] * J[0][c] + J[1][a] * J[1][c];
+            }
+        }
+    }
+    for (int a = 0; a < 6; ++a) {
+        g[a] = wave_sum_d(g[a]);
+        for (int c = a; c < 6; ++c) { H[a * 6 + c] = wave_sum_d(H[a * 6 + c]); H[c * 6 + a] = H[a * 6 + c]; }
+    }
+}
+
 __device__ void refine_pass(const double* xs, const double* ys, int n, unsigned sel, int lane, double* q, double* t,
                             int max_iter, double tol) {
     double radius = 1e4, decrease = 2.0;
     double cost = refine_cost(xs, ys, n, sel, lane, q, t);
     for (int it = 0; it < max_iter; ++it) {
-        double H[36], g[6], R[9];
-        for (int a = 0; a < 36; ++a) H[a] = 0;
-        for (int a = 0; a < 6; ++a) g[a] = 0;
-        quat_to_rot(q, R);
-        for (int j = 0; j < PNP_MAX_PER_LANE; ++j) {
-            const int i = lane + 64 * j;
-            if (i < n && ((sel >> j) & 1u)) {
-                const double* X = xs + 3 * i;
-                const double rx = R[0] * X[0] + R[1] * X[1] + R[2] * X[2];
-                const double ry = R[3] * X[0] + R[4] * X[1] + R[5] * X[2];
-                const double rz = R[6] * X[0] + R[7] * X[1] + R[8] * X[2];
-                const double x = rx + t[0], y = ry + t[1], z = rz + t[2];
-                const double iz = 1.0 / z;
-                const double r[2] = {x * iz - ys[2 * i], y * iz - ys[2 * i + 1]};
-                const double P[2][3] = {{iz, 0, -x * iz * iz}, {0, iz, -y * iz * iz}};
-                const double D[3][6] = {{0, 2 * rz, -2 * ry, 1, 0, 0}, {-2 * rz, 0, 2 * rx, 0, 1, 0}, {2 * ry, -2 * rx, 0, 0, 0, 1}};
-                double J[2][6];
-                for (int a = 0; a < 2; ++a)
-                    for (int c = 0; c < 6; ++c) J[a][c] = P[a][0] * D[0][c] + P[a][1] * D[1][c] + P[a][2] * D[2][c];
-                for (int a = 0; a < 6; ++a) {
-                    g[a] += J[0][a] * r[0] + J[1][a] * r[1];
-                    for (int c = a; c < 6; ++c) H[a * 6 + c] += J[0][a] * J[0][c] + J[1][a] * J[1][c];
-                }
-            }
-        }
-        for (int a = 0; a < 6; ++a) {
-            g[a] = wave_sum_d(g[a]);
-            for (int c = a; c < 6; ++c) { H[a * 6 + c] = wave_sum_d(H[a * 6 + c]); H[c * 6 + a] = H[a * 6 + c]; }
-        }
+        double H[36], g[6];
+        refine_normal_eqs(xs, ys, n, sel, lane, q, t, H, g);
         double gmax = 0;
         for (int a = 0; a < 6; ++a) gmax = fmax(gmax, fabs(g[a]));
         if (gmax <= tol) return;
@@ -531,6 +537,30 @@ DEV unsigned select_inliers(const double* xs, const double* ys, int n, double th
     *m_out = m;
     if (deltas_out) *deltas_out = dl;
     return sel;
+}
+
+// what refine_sequence decided on its way, for the test entry (suo_debug_pnp_refine); pnp_batch_kernel passes nullptr
+struct RefineTrace {
+    unsigned sel0, sel1;          // this lane's selection masks: before the first pass, after it
+    int m0, m1, deltas, second;   // their sizes, the flags that changed, whether the second pass ran
+    double qm[4], tm[3];          // the pose after the first pass
+};
+
+// PNP::refine (pnp_ransac.cpp:240-326): select, 5 iterations at 1e-6, reselect, 3 more at 1e-8 unless fewer than 5 % of the flags changed
+DEV void refine_sequence(const double* xs, const double* ys, int n, double thr2, int lane, double* bq, double* bt, RefineTrace* tr) {
+    int m = 0, deltas = 0;
+    unsigned sel = select_inliers(xs, ys, n, thr2, bq, bt, lane, nullptr, &m, nullptr);
+    if (tr) { tr->sel0 = sel; tr->m0 = m; }
+    refine_pass(xs, ys, n, sel, lane, bq, bt, 5, 1e-6);
+    if (tr) {
+        for (int k = 0; k < 4; ++k) tr->qm[k] = bq[k];
+        for (int k = 0; k < 3; ++k) tr->tm[k] = bt[k];
+    }
+    const unsigned prev = sel;
+    sel = select_inliers(xs, ys, n, thr2, bq, bt, lane, &prev, &m, &deltas);
+    const bool second = !((double)deltas < 0.05 * (double)m);
+    if (tr) { tr->sel1 = sel; tr->m1 = m; tr->deltas = deltas; tr->second = second ? 1 : 0; }
+    if (second) refine_pass(xs, ys, n, sel, lane, bq, bt, 3, 1e-8);
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -686,14 +716,7 @@ __global__ __launch_bounds__(64 * PNP_WAVES) void pnp_batch_kernel(const int* __
         }
     }
     if (wv != 0) return;
-    if (solvable && best > 3 && do_refine) {
-        int m = 0, deltas = 0;
-        unsigned sel = select_inliers(xs, ys, n, thr2, bq, bt, lane, nullptr, &m, nullptr);
-        refine_pass(xs, ys, n, sel, lane, bq, bt, 5, 1e-6);
-        const unsigned prev = sel;
-        sel = select_inliers(xs, ys, n, thr2, bq, bt, lane, &prev, &m, &deltas);
-        if (!((double)deltas < 0.05 * (double)m)) refine_pass(xs, ys, n, sel, lane, bq, bt, 3, 1e-8);
-    }
+    if (solvable && best > 3 && do_refine) refine_sequence(xs, ys, n, thr2, lane, bq, bt, nullptr);
     if (lane == 0) {
         double R[9];
         quat_to_rot(bq, R);
@@ -746,6 +769,88 @@ int launch_pnp_batch(int n_obj, const int* offsets, const double* xs, const doub
                      int* iters_out, hipStream_t s) {
     return launch_pnp_batch_counts(n_obj, offsets, nullptr, nullptr, xs, ys, threshold, seed, iter_tab, iter_tab_off, do_refine, T_out, status, best_out,
                                    iters_out, s, nullptr);
+}
+
+// test entry (suo_debug_pnp_refine; layout of out_d / out_i: include/suo_hip.h): one wave per object through the very p4p, count_inliers, select_inliers,
+// refine_normal_eqs, refine_cost, refine_pass and refine_sequence pnp_batch_kernel runs
+__global__ __launch_bounds__(64) void debug_pnp_refine_kernel(const int* __restrict__ offsets, const double* __restrict__ xs_all, const double* __restrict__ ys_all,
+                                                              double threshold, const int* __restrict__ mode, const double* __restrict__ start_qt,
+                                                              const int* __restrict__ start_idx, const int* __restrict__ sel_in, const int* __restrict__ max_iter,
+                                                              const double* __restrict__ tol, double* __restrict__ out_d, int* __restrict__ out_i,
+                                                              int* __restrict__ sel0_out, int* __restrict__ sel1_out) {
+    const int o = blockIdx.x, lane = threadIdx.x & 63;
+    const int p0 = offsets[o], n = offsets[o + 1] - p0;
+    const double* xs = xs_all + 3 * (size_t)p0;
+    const double* ys = ys_all + 2 * (size_t)p0;
+    const double thr2 = threshold * threshold;
+    double q[4], t[3];
+    if (start_idx[4 * o] >= 0) {
+        int idx[4];
+        for (int k = 0; k < 4; ++k) idx[k] = start_idx[4 * o + k];
+        p4p(xs, ys, idx, q, t);
+    } else {
+        for (int k = 0; k < 4; ++k) q[k] = start_qt[7 * o + k];
+        for (int k = 0; k < 3; ++k) t[k] = start_qt[7 * o + 4 + k];
+    }
+    double* D = out_d + 88 * (size_t)o;
+    int* I = out_i + 8 * (size_t)o;
+    if (lane == 0) {
+        for (int k = 0; k < 4; ++k) D[k] = q[k];
+        for (int k = 0; k < 3; ++k) D[4 + k] = t[k];
+        I[0] = (int)count_inliers(xs, ys, n, thr2, q, t);
+    }
+    RefineTrace tr;
+    double H[36], g[6], cost;
+    if (mode[o] == 0) {
+        double q0[4], t0[3];
+        for (int k = 0; k < 4; ++k) q0[k] = q[k];
+        for (int k = 0; k < 3; ++k) t0[k] = t[k];
+        refine_sequence(xs, ys, n, thr2, lane, q, t, &tr);
+        refine_normal_eqs(xs, ys, n, tr.sel0, lane, q0, t0, H, g);
+        cost = refine_cost(xs, ys, n, tr.sel0, lane, q0, t0);
+    } else {
+        unsigned sel = 0;
+        int m = 0;
+        for (int j = 0; j < PNP_MAX_PER_LANE; ++j) {
+            const int i = lane + 64 * j;
+            if (i < n && sel_in[p0 + i] != 0) { sel |= 1u << j; m++; }
+        }
+#pragma unroll
+        for (int w = 32; w > 0; w >>= 1) m += __shfl_xor(m, w, 64);
+        refine_normal_eqs(xs, ys, n, sel, lane, q, t, H, g);
+        cost = refine_cost(xs, ys, n, sel, lane, q, t);
+        refine_pass(xs, ys, n, sel, lane, q, t, max_iter[o], tol[o]);
+        tr.sel0 = sel; tr.sel1 = 0; tr.m0 = m; tr.m1 = 0; tr.deltas = 0; tr.second = 0;
+        for (int k = 0; k < 4; ++k) tr.qm[k] = q[k];
+        for (int k = 0; k < 3; ++k) tr.tm[k] = t[k];
+    }
+    for (int j = 0; j < PNP_MAX_PER_LANE; ++j) {
+        const int i = lane + 64 * j;
+        if (i < n) { sel0_out[p0 + i] = (int)((tr.sel0 >> j) & 1u); sel1_out[p0 + i] = (int)((tr.sel1 >> j) & 1u); }
+    }
+    if (lane == 0) {
+        I[1] = tr.m0; I[2] = tr.m1; I[3] = tr.deltas; I[4] = tr.second; I[5] = I[6] = I[7] = 0;
+        for (int a = 0; a < 36; ++a) D[7 + a] = H[a];
+        for (int a = 0; a < 6; ++a) D[43 + a] = g[a];
+        D[49] = cost;
+        for (int k = 0; k < 4; ++k) { D[50 + k] = tr.qm[k]; D[57 + k] = q[k]; }
+        for (int k = 0; k < 3; ++k) { D[54 + k] = tr.tm[k]; D[61 + k] = t[k]; }
+        double R[9];
+        quat_to_rot(tr.qm, R);
+        for (int r = 0; r < 3; ++r) { for (int c = 0; c < 3; ++c) D[64 + 4 * r + c] = R[3 * r + c]; D[64 + 4 * r + 3] = tr.tm[r]; }
+        quat_to_rot(q, R);
+        for (int r = 0; r < 3; ++r) { for (int c = 0; c < 3; ++c) D[76 + 4 * r + c] = R[3 * r + c]; D[76 + 4 * r + 3] = t[r]; }
+    }
+}
+
+int launch_debug_pnp_refine(int n_obj, const int* offsets, const double* xs, const double* ys, double threshold, const int* mode, const double* start_qt,
+                            const int* start_idx, const int* sel_in, const int* max_iter, const double* tol, double* out_d, int* out_i, int* sel0_out,
+                            int* sel1_out, hipStream_t s) {
+    if (n_obj <= 0) { suo_set_error("suo_debug_pnp_refine: n_obj = %d", n_obj); return SUO_ERR_ARG; }
+    hipLaunchKernelGGL(debug_pnp_refine_kernel, dim3(n_obj), dim3(64), 0, s, offsets, xs, ys, threshold, mode, start_qt, start_idx, sel_in, max_iter, tol, out_d,
+                       out_i, sel0_out, sel1_out);
+    SUO_HIP_CHECK(hipGetLastError());
+    return SUO_OK;
 }
 
 }  // namespace suo

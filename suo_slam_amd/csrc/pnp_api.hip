@@ -117,6 +117,65 @@ int suo_pnp_replay(int n_obj, const int* n_pts, const double* xs, const double* 
     return pnp_batch_impl(n_obj, n_pts, xs, ys, threshold, 0, draws, n_draws, do_refine, T_out, status, best_inliers, iterations, winner);
 }
 
+// Test entry: the refinement half of pnp_batch_kernel on its own (include/suo_hip.h).  Everything is checked before anything is allocated or launched.
+int suo_debug_pnp_refine(int n_obj, const int* n_pts, const double* xs, const double* ys, double threshold, const int* mode, const double* start_qt,
+                         const int* start_idx, const int* sel_in, const int* max_iter, const double* tol, double* out_d, int* out_i, int* sel0_out,
+                         int* sel1_out) {
+    if (n_obj <= 0) { suo_set_error("suo_debug_pnp_refine: n_obj = %d", n_obj); return SUO_ERR_ARG; }
+    if (!n_pts || !xs || !ys || !mode || !start_qt || !start_idx || !sel_in || !max_iter || !tol || !out_d || !out_i || !sel0_out || !sel1_out) {
+        suo_set_error("suo_debug_pnp_refine: null argument");
+        return SUO_ERR_ARG;
+    }
+    std::vector<int> offsets((size_t)n_obj + 1, 0);
+    for (int o = 0; o < n_obj; ++o) {
+        const int n = n_pts[o];
+        if (n < 0 || n > PNP_MAX_POINTS) {
+            suo_set_error("suo_debug_pnp_refine: object %d has %d points, the limit is %d per object", o, n, PNP_MAX_POINTS);
+            return SUO_ERR_ARG;
+        }
+        if (mode[o] != 0 && mode[o] != 1) { suo_set_error("suo_debug_pnp_refine: object %d, mode %d", o, mode[o]); return SUO_ERR_ARG; }
+        if (mode[o] == 1 && (max_iter[o] < 0 || max_iter[o] > 50)) {
+            suo_set_error("suo_debug_pnp_refine: object %d, max_iter %d (0 .. 50)", o, max_iter[o]);
+            return SUO_ERR_ARG;
+        }
+        if (start_idx[4 * o] >= 0)
+            for (int k = 0; k < 4; ++k)
+                if (start_idx[4 * o + k] < 0 || start_idx[4 * o + k] >= n) {
+                    suo_set_error("suo_debug_pnp_refine: object %d starts from point %d, it has %d points", o, start_idx[4 * o + k], n);
+                    return SUO_ERR_ARG;
+                }
+        offsets[o + 1] = offsets[o] + n;
+    }
+    const size_t N = (size_t)n_obj, total = (size_t)offsets[n_obj], tp = total ? total : 1;
+    Layout L;
+    const size_t o_xs = L.take(sizeof(double) * 3 * tp), o_ys = L.take(sizeof(double) * 2 * tp), o_qt = L.take(sizeof(double) * 7 * N),
+                 o_tol = L.take(sizeof(double) * N), o_off = L.take(sizeof(int) * (N + 1)), o_mode = L.take(sizeof(int) * N), o_idx = L.take(sizeof(int) * 4 * N),
+                 o_sel = L.take(sizeof(int) * tp), o_mi = L.take(sizeof(int) * N);
+    const size_t o_d = L.take(sizeof(double) * 88 * N), o_i = L.take(sizeof(int) * 8 * N), o_s0 = L.take(sizeof(int) * tp), o_s1 = L.take(sizeof(int) * tp);
+    char* d = nullptr;
+    SUO_HIP_CHECK(hipMalloc((void**)&d, L.off));
+    struct Free { char* d; ~Free() { (void)hipFree(d); } } guard{d};
+    SUO_HIP_CHECK(hipMemcpy(d + o_xs, xs, sizeof(double) * 3 * total, hipMemcpyHostToDevice));
+    SUO_HIP_CHECK(hipMemcpy(d + o_ys, ys, sizeof(double) * 2 * total, hipMemcpyHostToDevice));
+    SUO_HIP_CHECK(hipMemcpy(d + o_qt, start_qt, sizeof(double) * 7 * N, hipMemcpyHostToDevice));
+    SUO_HIP_CHECK(hipMemcpy(d + o_tol, tol, sizeof(double) * N, hipMemcpyHostToDevice));
+    SUO_HIP_CHECK(hipMemcpy(d + o_off, offsets.data(), sizeof(int) * (N + 1), hipMemcpyHostToDevice));
+    SUO_HIP_CHECK(hipMemcpy(d + o_mode, mode, sizeof(int) * N, hipMemcpyHostToDevice));
+    SUO_HIP_CHECK(hipMemcpy(d + o_idx, start_idx, sizeof(int) * 4 * N, hipMemcpyHostToDevice));
+    SUO_HIP_CHECK(hipMemcpy(d + o_sel, sel_in, sizeof(int) * total, hipMemcpyHostToDevice));
+    SUO_HIP_CHECK(hipMemcpy(d + o_mi, max_iter, sizeof(int) * N, hipMemcpyHostToDevice));
+    int rc = launch_debug_pnp_refine(n_obj, (const int*)(d + o_off), (const double*)(d + o_xs), (const double*)(d + o_ys), threshold, (const int*)(d + o_mode),
+                                     (const double*)(d + o_qt), (const int*)(d + o_idx), (const int*)(d + o_sel), (const int*)(d + o_mi),
+                                     (const double*)(d + o_tol), (double*)(d + o_d), (int*)(d + o_i), (int*)(d + o_s0), (int*)(d + o_s1), nullptr);
+    if (rc != SUO_OK) return rc;
+    SUO_HIP_CHECK(hipDeviceSynchronize());
+    SUO_HIP_CHECK(hipMemcpy(out_d, d + o_d, sizeof(double) * 88 * N, hipMemcpyDeviceToHost));
+    SUO_HIP_CHECK(hipMemcpy(out_i, d + o_i, sizeof(int) * 8 * N, hipMemcpyDeviceToHost));
+    SUO_HIP_CHECK(hipMemcpy(sel0_out, d + o_s0, sizeof(int) * total, hipMemcpyDeviceToHost));
+    SUO_HIP_CHECK(hipMemcpy(sel1_out, d + o_s1, sizeof(int) * total, hipMemcpyDeviceToHost));
+    return SUO_OK;
+}
+
 int suo_pnp(const double* xs, const double* ys, int n, double threshold, double* T_out) {
     int st = 0;
     return suo_pnp_batch(1, &n, xs, ys, threshold, 0, 1, T_out, &st, nullptr, nullptr);
