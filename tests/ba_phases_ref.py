@@ -207,7 +207,8 @@ class PhaseRef:
             MJo = aD @ aTc[:, :3] @ np.hstack([np.abs(_skew(Mqw)), np.eye(3)])
             OJc, OJo, Oe = Om @ Jc, Om @ Jo, Om @ err
             self.edge.append(NS(c=c, o=o, err=err, chi2=chi2, Mchi=Mchi, Jc=Jc, Jo=Jo, Acc=Jc.T @ OJc, Aoo=Jo.T @ OJo, Aco=Jc.T @ OJo, gc=-(Jc.T @ Oe), go=-(Jo.T @ Oe),
-                                MAcc=MJc.T @ aOm @ MJc, MAoo=MJo.T @ aOm @ MJo, MAco=MJc.T @ aOm @ MJo, Mgc=MJc.T @ aOm @ Me, Mgo=MJo.T @ aOm @ Me))
+                                MAcc=MJc.T @ aOm @ MJc, MAoo=MJo.T @ aOm @ MJo, MAco=MJc.T @ aOm @ MJo, Mgc=MJc.T @ aOm @ Me, Mgo=MJo.T @ aOm @ Me,
+                                Om=Om, Me=Me, MJc=MJc, MJo=MJo))      # (the last four: tests/pose_cov_mp_ref.py)
 
     def classify(self):
         """(chi2 float64 [E], M [E], inlier flags [E] under chi2 > chi2_thr -> outlier, chi2 in mp)."""

@@ -1,10 +1,9 @@
-"""Cross blocks and relative-pose covariances of vertex pairs (csrc/pose_cov.hip through suo_pose_covariances_pairs) against the finite-difference numpy
-reference of tests/pose_cov_pairs_ref.py, on the graphs of tests/pose_cov_pair_cases.py.
+"""Cross blocks and relative-pose covariances of vertex pairs (csrc/pose_cov.hip through suo_pose_covariances_pairs) against the mp reference of
+tests/pose_cov_mp_ref.py, on the graphs of tests/pose_cov_pair_cases.py.
 
-Tolerances, with b = pose_cov_ref.bound(ref) = 1e3 eps cond(H_ref) max|Sigma_ref| the bound on every element of Sigma (every input asserts cond <= 1e9 first):
-  cross                        b
-  rel of (camera, object)      b (1 + 6 a)^2, a = max|Ad(T_c)|: 36 products a sigma a of A Sigma_oo A^T plus 2 x 6 products a sigma of the cross terms, plus Sigma_cc
-  rel of (object, object)      4 * 36 * a^2 * b, a = max|Ad(T_b^-1)|: four blocks under B . B^T
+Tolerances, entry by entry, K eps M with K fixed on the CPU by tests/test_pose_cov_mp_ref.py (which also shows each below the old tolerance everywhere):
+  cross     M = the block of M_Sigma
+  rel       M = |J| M_joint |J|^T + |J| |Sigma_joint| |J|^T, J the mp-differenced Jacobian of the relative pose (not the adjoint formula); M == 0 is an exact zero
 Observed error-to-tolerance ratios: profiles/pose_cov.txt."""
 import ctypes as C
 
@@ -14,54 +13,38 @@ import pytest
 from suo_slam_amd import _lib, ba
 from tests import pose_cov_cases as K
 from tests import pose_cov_pair_cases as PK
+from tests import pose_cov_mp_ref as MP
 from tests import pose_cov_pairs_ref as PR
-from tests import pose_cov_ref as R
 
 pytestmark = pytest.mark.gpu
 
 NAMES = ["moved_1x8", "moved_1x9", "moved_1x17", "moved_cam_only", "3x2", "5x16"]
 
 
-def _rel_tol(g, a, b, bound):
-    nc = len(g["cam_T"])
-    if a < nc or b < nc:
-        amax = np.abs(PR.adjoint(PR.vertex_pose(g, min(a, b)))).max()
-        return bound * (1 + 6 * amax) ** 2
-    amax = np.abs(PR.adjoint(np.linalg.inv(PR.vertex_pose(g, b)))).max()
-    return 4 * 36 * amax ** 2 * bound
+def _case(name):
+    """(graph, pairs [P,2], CovRef): the graph a deep copy, the reference shared and read-only"""
+    g = MP.graph(name)
+    return g, PK.pairs_of(g, PK.OBJ_PAIRS.get(name, [(0, 1)])), MP.case(name)
 
 
-def _check(g, pairs, got, ref, ref_pairs, what):
+def _check(g, pairs, got, cr, what):
     """every pair against the reference to its tolerance; NaN blocks exactly where the reference has them and status[2] counting them; rel symmetric with a
     positive diagonal, 36 zeros exactly for two fixed objects"""
-    assert ref["cond"] <= 1e9, (what, ref["cond"])
-    bound = R.bound(ref)
     cam, obj, cross, rel, status = got
-    rcross, rrel, n_nan = ref_pairs
-    assert cross.shape == rcross.shape and rel.shape == rrel.shape
-    nc = len(g["cam_T"])
+    worst, pr = MP.check_pairs(pairs, cross, rel, status[2], cr, what)
     fixed = np.r_[g["cam_fixed"], g["obj_fixed"]].astype(bool)
-    worst = {"cross": 0.0, "cam-obj": 0.0, "obj-obj": 0.0}
     for q, (a, b) in enumerate(pairs):
-        if np.isnan(rrel[q]).any():
-            assert np.isnan(cross[q]).all() and np.isnan(rel[q]).all(), (what, q, a, b)
+        if np.isnan(pr.rel[q]).any():
             continue
-        tol = _rel_tol(g, a, b, bound)
-        e_cross, e_rel = float(np.abs(cross[q] - rcross[q]).max()), float(np.abs(rel[q] - rrel[q]).max())
-        kind = "cam-obj" if min(a, b) < nc else "obj-obj"
-        worst["cross"] = max(worst["cross"], e_cross / bound)
-        worst[kind] = max(worst[kind], e_rel / tol)
-        assert e_cross <= bound, (what, q, a, b, e_cross, bound)
-        assert e_rel <= tol, (what, q, a, b, e_rel, tol)
-        assert np.abs(rel[q] - rel[q].T).max() <= tol, (what, q)
         if fixed[a] and fixed[b]:
             assert not rel[q].any() and not cross[q].any(), (what, q, "two fixed vertices: 36 zeros")
         else:
             assert (np.diag(rel[q]) > 0).all(), (what, q, a, b)
         if fixed[a] or fixed[b]:
             assert not cross[q].any(), (what, q, "a fixed vertex has no cross block")
-    assert list(status) == list(ref["status"]) + [n_nan], (what, status, ref["status"], n_nan)
-    print(f"pose_cov_pairs {what}: bound {bound:.3e}  error / tolerance: cross {worst['cross']:.4f}  rel cam-obj {worst['cam-obj']:.4f}  rel obj-obj {worst['obj-obj']:.4f}")
+    assert list(status[:2]) == list(cr.marginals().status), (what, status)
+    print(f"pose_cov_pairs {what}: error / tolerance: cross {worst['cross']:.4f}  rel cam-obj {worst['cam-obj']:.4f}  rel obj-obj {worst['obj-obj']:.4f}")
+    return pr
 
 
 def _same_bits(x, y):
@@ -70,42 +53,44 @@ def _same_bits(x, y):
 
 @pytest.mark.parametrize("name", NAMES)
 def test_pairs_meet_the_tolerances_and_the_marginal_blocks_keep_their_bits(name):
-    g, pairs, ref, ref_pairs = PK.case(name)
+    g, pairs, ref = _case(name)
     got = ba.pose_covariances_pairs(*K.args(g), pairs=pairs)
-    _check(g, pairs, got, ref, ref_pairs, name)
+    _check(g, pairs, got, ref, name)
     marg = ba.pose_covariances(*K.args(g))
     assert _same_bits((got[0], got[1], got[4][:2]), marg), "cam_cov / obj_cov / status[:2] are the existing entry's, bit for bit"
     assert _same_bits(got, ba.pose_covariances_pairs(*K.args(g), pairs=pairs)), "two calls give the same bits"
 
 
 def test_rel_is_the_camera_block_where_the_object_is_fixed():
-    g, pairs, ref, _ = PK.case("moved_cam_only")
+    g, pairs, ref = _case("moved_cam_only")
     cam, _, cross, rel, _ = ba.pose_covariances_pairs(*K.args(g), pairs=pairs)
-    tol = R.bound(ref) * (1 + 6 * np.abs(PR.adjoint(PK.MOVED)).max()) ** 2
+    pr = ref.pairs(pairs)
     for q in (0, 1):                                     # (camera 0, object 0), (camera 0, object 1)
-        assert np.abs(rel[q] - cam[0]).max() <= tol and not cross[q].any()
+        assert (np.abs(rel[q] - cam[0]) <= MP.tol("rel", pr.M_rel[q]) + MP.tol("sigma", ref.marginals().M_cam[0])).all() and not cross[q].any()
     assert not rel[2].any() and not cross[2].any(), "two fixed objects: 36 zeros exactly"
-    g, _, _, _ = PK.case("5x16")
+    g = MP.graph("5x16")
     g["obj_fixed"][15] = 1
     pairs = PK.pairs_of(g, [(0, 15), (0, 1)])
-    ref, ref_pairs = PK.with_refs(g, pairs)
+    ref = MP.CovRef(g)
     got = ba.pose_covariances_pairs(*K.args(g), pairs=pairs)
-    _check(g, pairs, got, ref, ref_pairs, "5x16 with object 15 fixed")
+    pr = _check(g, pairs, got, ref, "5x16 with object 15 fixed")
     for c in range(1, 5):
         q = c * 16 + 15
         assert tuple(pairs[q]) == (c, 5 + 15)
-        assert not got[2][q].any() and np.abs(got[3][q] - got[0][c]).max() <= R.bound(ref) * (1 + 6 * np.abs(PR.adjoint(PR.vertex_pose(g, c))).max()) ** 2
+        assert not got[2][q].any() and (np.abs(got[3][q] - got[0][c]) <= MP.tol("rel", pr.M_rel[q]) + MP.tol("sigma", ref.marginals().M_cam[c])).all()
 
 
 def test_cross_block_of_a_camera_and_an_object_it_does_not_see():
-    g, pairs, ref, (rcross, _, _) = PK.case("5x16")
+    g, pairs, ref = _case("5x16")
+    pr = ref.pairs(pairs)
+    rcross = pr.cross
     c, o = PK.UNSEEN
     assert not ((g["edge_cam"] == c) & (g["edge_obj"] == o)).any() and not g["cam_fixed"][c]
     q = c * 16 + o
     assert tuple(pairs[q]) == (c, 5 + o)
     cross = ba.pose_covariances_pairs(*K.args(g), pairs=pairs)[2]
     assert np.abs(cross[q]).max() > 0 and np.abs(rcross[q]).max() > 0
-    assert np.abs(cross[q] - rcross[q]).max() <= R.bound(ref)
+    assert (np.abs(cross[q] - rcross[q]) <= MP.tol("cross", pr.M_cross[q])).all()
     # the same pair named object first is the transpose, to the bit
     swapped = ba.pose_covariances_pairs(*K.args(g), pairs=[(5 + o, c), (5 + o, 5 + o)])
     assert np.array_equal(swapped[2][0], cross[q].T)
@@ -114,50 +99,51 @@ def test_cross_block_of_a_camera_and_an_object_it_does_not_see():
 
 def test_every_problem_of_a_batch_that_mixes_the_forms_equals_its_solo_bits_and_a_duplicate_pair_repeats_its_bits():
     names = ("3x2", "moved_1x9", "moved_cam_only", "5x16", "moved_1x17")
-    cases = [PK.case(n) for n in names]
-    lists = [np.vstack([pairs, pairs[:3], pairs[-1:]]) for _, pairs, _, _ in cases]           # duplicates at the end
-    batch = ba.pose_covariances_pairs_batch([ba.Problem(*K.args(g)) for g, _, _, _ in cases], lists)
-    for n, (g, pairs, ref, ref_pairs), lst, got in zip(names, cases, lists, batch):
+    cases = [_case(n) for n in names]
+    lists = [np.vstack([pairs, pairs[:3], pairs[-1:]]) for _, pairs, _ in cases]           # duplicates at the end
+    batch = ba.pose_covariances_pairs_batch([ba.Problem(*K.args(g)) for g, _, _ in cases], lists)
+    for n, (g, pairs, ref), lst, got in zip(names, cases, lists, batch):
         P = len(pairs)
-        _check(g, pairs, (got[0], got[1], got[2][:P], got[3][:P], got[4]), ref, ref_pairs, "mixed " + n)
+        _check(g, pairs, (got[0], got[1], got[2][:P], got[3][:P], got[4]), ref, "mixed " + n)
         assert _same_bits(got, ba.pose_covariances_pairs(*K.args(g), pairs=lst)), n
         for blocks in (got[2], got[3]):
             assert np.array_equal(blocks[P:P + 3], blocks[:3]) and np.array_equal(blocks[P + 3], blocks[P - 1]), n
 
 
 def test_relative_covariances_do_not_depend_on_the_gauge():
-    g0, _ = K.case("3x2")
+    g0 = MP.graph("3x2")
     g1 = {k: v.copy() for k, v in g0.items()}
     g1["cam_fixed"] = np.array([0, 1, 0], np.uint8)
     pairs = PK.pairs_of(g0, [(0, 1), (1, 0)])
-    ref0, ref1 = R.covariances(g0), R.covariances(g1)
-    assert max(ref0["cond"], ref1["cond"]) <= 1e9
+    ref0, ref1 = MP.case("3x2"), MP.CovRef(g1)
+    pr0, pr1 = ref0.pairs(pairs), ref1.pairs(pairs)
     rel0 = ba.pose_covariances_pairs(*K.args(g0), pairs=pairs)[3]
     got1 = ba.pose_covariances_pairs(*K.args(g1), pairs=pairs)
     rel1 = got1[3]
     worst = 0.0
     for q, (a, b) in enumerate(pairs):
-        tol = _rel_tol(g0, a, b, R.bound(ref0)) + _rel_tol(g1, a, b, R.bound(ref1))
-        err = float(np.abs(rel0[q] - rel1[q]).max())
-        worst = max(worst, err / tol)
-        assert err <= tol, (q, a, b, err, tol)
+        tol = MP.tol("rel", pr0.M_rel[q]) + MP.tol("rel", pr1.M_rel[q])
+        err = float((np.abs(rel0[q] - rel1[q]) / tol).max())
+        worst = max(worst, err)
+        assert err <= 1.0, (q, a, b, err)
     print(f"pose_cov_pairs 3x2, camera 0 fixed against camera 1 fixed: difference / summed tolerance {worst:.4f}")
     marg0 = ba.pose_covariances(*K.args(g0))[1][0]
-    assert np.abs(marg0 - got1[1][0]).max() > 1e3 * (R.bound(ref0) + R.bound(ref1)), "the marginal block of object 0 does depend on the gauge"
+    both = MP.tol("sigma", ref0.marginals().M_obj[0]).max() + MP.tol("sigma", ref1.marginals().M_obj[0]).max()
+    assert np.abs(marg0 - got1[1][0]).max() > 1e3 * both, "the marginal block of object 0 does depend on the gauge"
 
 
 @pytest.mark.parametrize("name,o", [("1x8", 3), ("moved_1x8", 3), ("5x16", 7)])
 def test_an_object_without_a_counted_edge_nans_its_pairs_and_the_others_still_meet_the_tolerances(name, o):
-    g = K.case(name)[0] if name in K.CASES else PK.case(name)[0]
+    g = MP.graph(name)
     g["edge_inlier"][g["edge_obj"] == o] = 0
     pairs = PK.pairs_of(g, [(0, 1), (o, 0), (1, o)])
-    ref, ref_pairs = PK.with_refs(g, pairs)
+    ref = MP.CovRef(g)
     nc = len(g["cam_T"])
     hit = np.array([nc + o in (a, b) for a, b in pairs])
-    assert ref_pairs[2] == hit.sum() == nc + 2
+    assert ref.pairs(pairs).n_nan == hit.sum() == nc + 2
     got = ba.pose_covariances_pairs(*K.args(g), pairs=pairs)
     assert np.isnan(got[2][hit]).all() and np.isnan(got[3][hit]).all() and np.isfinite(got[3][~hit]).all() and got[4][2] == nc + 2
-    _check(g, pairs, got, ref, ref_pairs, f"{name} without object {o}")
+    _check(g, pairs, got, ref, f"{name} without object {o}")
 
 
 def _raw_call(g, pair_a, pair_b, n_pair=None):
@@ -172,7 +158,7 @@ def _raw_call(g, pair_a, pair_b, n_pair=None):
 
 
 def test_bad_pairs_and_seventeen_free_objects_are_refused_and_no_pairs_is_the_existing_call():
-    g, _, _, _ = PK.case("3x2")
+    g = MP.graph("3x2")
     for a, b, n, text in (([0], [5], None, "outside"), ([-1], [3], None, "outside"), ([3], [5], None, "outside"), ([0], [1], None, "camera, camera"),
                           ([2], [2], None, "camera, camera"), ([0], [3], -1, "n_pair")):
         rc, err = _raw_call(g, a, b, n)

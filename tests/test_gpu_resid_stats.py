@@ -1,81 +1,26 @@
-"""suo_residual_statistics (csrc/resid_stats.hip behind the pose-covariance kernels) against the finite-difference numpy reference of tests/resid_stats_ref.py, on the
+"""suo_residual_statistics (csrc/resid_stats.hip behind the pose-covariance kernels) against the mp reference of tests/pose_cov_mp_ref.py (CovRef.statistics), on the
 graphs of tests/resid_stats_cases.py.
 
-Tolerances, derived per edge from the reference's own quantities (tolerances() below), never from what the kernels give.  With b = pose_cov_ref.bound(ref) the
-forward bound on every element of Sigma (every input asserts cond <= 1e9 first), S = max|Sigma_ref|, a = the largest absolute row sum of the reference J_e (2 x 12),
-|Om| = |Oxx| + 2 |Oxy| + |Oyy|, eps = 2^-52, h = pose_cov_ref.STEP:
-  dJ    every element of the reference's central-difference Jacobian: 16 eps (1 + |uv|) / h of rounding (two residuals of a handful of operations each, divided by
-        2 h) + 10 a h^2 of truncation (third derivatives of the projection of the order of a)
-  P_e   every element:  b a^2  (Sigma's bound under J . J^T, elementwise)  + 24 dJ S a  (the reference's Jacobian error, 2 x 12 terms)  + 30 eps S a^2  (the rounding
-        of the 12 x 12 quadratic form on either side)
-  lev   tol(P) |Om| + 8 eps |P| |Om|
-  v     dv = 400 eps (1 + a): the rotation matrices through the library's quaternions and the two rigid transforms (points within 2 m), carried by d pi / d p_c <= a
-  chi2  2 dv |Om| |v| + dv^2 |Om| + 8 eps |v|^T |Om| |v|
-  t     with M = Om^-1 + s P, x = M^-1 v, k = tol(P) sum|M^-1|, where k < 1/2:
-        (|x|_1^2 tol(P) + 2 |x|_1 dv + dv^2 sum|M^-1|) / (1 - k)  + 64 eps ((|r00 r11| + |r01 r10|) / det R) |Om v|^T |R^-1| |v|  (the cancellation in det R)
-        Where k >= 1/2 -- an edge of little redundancy in a graph of large cond(H), about one edge in a hundred here -- tol(P), which carries cond(H) max|Sigma| a^2,
-        admits a singular M: the propagation through the 2 x 2 inverse bounds nothing, and the test asserts for that edge what remains (t finite exactly where the
-        reference's is, P and lev to their tolerances).  No case may have more than one edge in ten of this kind.
-  sums  the sum of the members' tolerances + count eps sum|members|;  s0^2: that of sum chi2, divided by dof
+Tolerances, entry by entry, K[buffer] eps M with M the reference's own error scale (its module docstring) and K fixed on the CPU by tests/test_pose_cov_mp_ref.py,
+which also shows every one of them at or below the tolerance this module applied before, and that the tolerance of t is finite on every edge whose t is (no edge is
+exempt) and wider than 1e-6 max(1, |t|) on at most one counted edge in ten:
+  chi2  M_chi2 of tests/ba_phases_ref.py          P_e   (J Sigma) dH (J Sigma)^T through the full rows of Sigma, J's own error, the products' rounding
+  lev   sum (M_P + |P|) |Omega|                   t     through the mp inverse of R = I + s P Omega; P = 0 (both vertices fixed): chi2's
+  sums  the members' M plus their magnitudes; s0^2: that of sum chi2 over dof, plus |s0^2|
 Counts, m, n, dof, status and the NaN pattern are exact.  Observed error-to-tolerance ratios: profiles/resid_stats.txt, and the row of csrc/resid_stats.hip in DESIGN.md's kernel table."""
 import numpy as np
 import pytest
 
 from suo_slam_amd import ba
 from tests import pose_cov_cases as K
-from tests import pose_cov_ref as R
+from tests import pose_cov_mp_ref as MP
 from tests import resid_stats_cases as RK
-from tests import resid_stats_ref as RS
 
 pytestmark = pytest.mark.gpu
 
 EPS = float(np.finfo(np.float64).eps)
 NO_PAIRS = np.zeros((0, 2), np.int32)
 ALL_OUT = ba.RESID_KEYS + ("summary", "status")
-
-
-def tolerances(g, ref, st, fd=True):
-    """per edge: the tolerances of pcov, lev, chi2, t (module docstring); fd=False leaves the reference's finite-difference term out (device against exact algebra)"""
-    E = len(g["edge_cam"])
-    b = R.bound(ref) if ref["H"].shape[0] else 0.0
-    S = float(np.abs(ref["Sigma"]).max()) if ref["H"].shape[0] else 0.0
-    tol = {k: np.zeros(E) for k in ("pcov", "lev", "chi2", "t")}
-    for e in range(E):
-        J, v = st["J"][e], st["v"][e]
-        a = float(np.abs(J).sum(1).max())
-        i = np.abs(g["edge_info"][e])
-        Om = np.array([[g["edge_info"][e][0], g["edge_info"][e][1]], [g["edge_info"][e][1], g["edge_info"][e][2]]])
-        om = float(i[0] + 2 * i[1] + i[2])
-        assert np.abs(g["edge_uv"][e]).max() <= 4 and np.abs(v).max() <= 1
-        dJ = (16 * EPS * (1 + float(np.abs(g["edge_uv"][e]).max())) / R.STEP + 10 * a * R.STEP ** 2) if fd else 0.0
-        dv = 400 * EPS * (1 + a)
-        av = np.abs(v)
-        tol["chi2"][e] = 2 * dv * float((np.abs(Om) @ av).sum()) + dv * dv * om + 8 * EPS * float(av @ np.abs(Om) @ av)
-        if np.isnan(st["edge_lev"][e]):
-            continue
-        tp = b * a * a + 24 * dJ * S * a + 30 * EPS * S * a * a
-        p = st["edge_pcov"][e]
-        P = np.array([[p[0], p[1]], [p[1], p[2]]])
-        tol["pcov"][e] = tp
-        tol["lev"][e] = tp * om + 8 * EPS * float((np.abs(P) * np.abs(Om)).sum())
-        if np.isnan(st["edge_t"][e]):
-            continue
-        s = -1.0 if st["counted"][e] else 1.0
-        Minv = np.linalg.inv(np.linalg.inv(Om) + s * P)
-        x1 = float(np.abs(Minv @ v).sum())
-        k = tp * float(np.abs(Minv).sum())
-        if k >= 0.5:
-            tol["t"][e] = np.inf
-            continue
-        Rm = np.eye(2) + s * P @ Om
-        cancel = (abs(Rm[0, 0] * Rm[1, 1]) + abs(Rm[0, 1] * Rm[1, 0])) / st["det"][e]
-        tol["t"][e] = (x1 * x1 * tp + 2 * x1 * dv + dv * dv * float(np.abs(Minv).sum())) / (1 - k) \
-            + 64 * EPS * cancel * float(np.abs(Om @ v) @ np.abs(np.linalg.inv(Rm)) @ av)
-    return tol
-
-
-def _sum_tol(members, tols):
-    return float(np.sum(tols) + len(members) * EPS * np.abs(members).sum())
 
 
 def _run(g):
@@ -86,61 +31,43 @@ def _same_bits(x, y, keys=ALL_OUT):
     return all(np.array_equal(x[k], y[k], equal_nan=True) for k in keys)
 
 
-def _check(name, g, ref, st, got):
-    """every output against the reference: the NaN pattern, counts and status exactly, the rest to the derived tolerances; returns the worst error / tolerance"""
-    assert ref["cond"] <= 1e9, (name, ref["cond"])
-    RK.far_from_the_threshold(name, g, st)
-    tol = tolerances(g, ref, st)
-    worst = {}
+BUF = {"edge_chi2": "chi2", "edge_pcov": "pcov", "edge_lev": "lev", "edge_t": "t", "cam_stat": "vstat", "obj_stat": "vstat", "summary": "summary"}
 
-    def close(key, a, b, t):
+
+def _check(name, g, cr, got):
+    """every output against the reference (a CovRef): the NaN pattern, counts and status exactly, the rest to K eps M; returns the worst error / tolerance"""
+    st = cr.statistics()
+    RK.far_from_the_threshold(name, g, {"det": st.det, "counted": st.counted})
+    worst = {}
+    for key, buf in BUF.items():
+        a, b = got[key], getattr(st, key)
         assert a.shape == b.shape, (name, key)
         assert np.array_equal(np.isnan(a), np.isnan(b)), (name, key, "the NaN pattern is exact")
-        ok = ~np.isnan(b)
-        err = np.abs(a[ok] - b[ok])
-        tt = np.broadcast_to(t, b.shape)[ok]
-        with np.errstate(invalid="ignore"):
-            worst[key] = float((err / np.where(tt > 0, tt, 1.0)).max()) if err.size else 0.0
-        assert (err <= tt).all(), (name, key, float(err.max()), worst[key])
-
-    close("chi2", got["edge_chi2"], st["edge_chi2"], tol["chi2"])
-    close("pcov", got["edge_pcov"], st["edge_pcov"], tol["pcov"][:, None])
-    close("lev", got["edge_lev"], st["edge_lev"], tol["lev"])
-    close("t", got["edge_t"], st["edge_t"], tol["t"])
-    unbounded = int(np.isinf(tol["t"]).sum())
-    assert 10 * unbounded <= len(tol["t"]), (name, unbounded, "edges whose t the propagated bound does not reach")
-    ec, eo, cnt = g["edge_cam"], g["edge_obj"], st["counted"]
-    for key, idx, n_v in (("cam_stat", ec, len(g["cam_T"])), ("obj_stat", eo, len(g["obj_T"]))):
-        t = np.zeros((n_v, 3))
-        for v in range(n_v):
-            k = np.flatnonzero((idx == v) & cnt)
-            t[v, 1] = _sum_tol(st["edge_chi2"][k], tol["chi2"][k])
-            t[v, 2] = _sum_tol(2 - st["edge_lev"][k], tol["lev"][k])
-        assert np.array_equal(got[key][:, 0], st[key][:, 0]), (name, key, "counts are exact")
-        close(key, got[key], st[key], t)
-    k = np.flatnonzero(cnt)
-    m, n, dof = st["summary"][0], st["summary"][1], st["summary"][4]
+        worst[key] = MP.ratio(a, b, getattr(st, "M_" + key)) / MP.K[buf]
+        assert worst[key] <= 1.0, (name, key, worst[key])
+    for key in ("cam_stat", "obj_stat"):
+        assert np.array_equal(got[key][:, 0], getattr(st, key)[:, 0]), (name, key, "counts are exact")
+    m, n, dof = st.summary[0], st.summary[1], st.summary[4]
     assert list(got["summary"][[0, 1, 4]]) == [m, n, dof], (name, got["summary"], "m, n and dof are exact")
-    t_chi2 = _sum_tol(st["edge_chi2"][k], tol["chi2"][k])
-    t_lev = _sum_tol(st["edge_lev"][k], tol["lev"][k]) if not np.isnan(st["summary"][3]) else 0.0
-    close("summary", got["summary"], st["summary"], np.array([0, 0, t_chi2, t_lev, 0, (t_chi2 / dof + 4 * EPS * abs(st["summary"][5])) if dof > 0 else 0.0]))
-    assert list(got["status"]) == list(st["status"]), (name, got["status"], st["status"])
-    # sum lev = n on the device alone: the algebra's tolerance without the reference's finite-difference term, times m
-    if len(k) and not np.isnan(st["summary"][3]):
-        alone = tolerances(g, ref, st, fd=False)["lev"][k].max() * m
+    assert list(got["status"]) == list(st.status), (name, got["status"], st.status)
+    # sum lev = n on the device alone, and 0 <= lev <= 2 on a counted edge
+    k = np.flatnonzero(st.counted)
+    if len(k) and not np.isnan(st.summary[3]):
+        alone = MP.tol("summary", st.M_summary[3])
         worst["sum lev - n"] = abs(got["summary"][3] - n) / alone
         assert abs(got["summary"][3] - n) <= alone, (name, got["summary"][3], n, alone)
-        assert (got["edge_lev"][k] >= -tol["lev"][k]).all() and (got["edge_lev"][k] <= 2 + tol["lev"][k]).all(), (name, "0 <= lev <= 2 on a counted edge")
-    print(f"resid_stats {name}: E {len(ec)}  m {int(m)}  n {int(n)}  cond {ref['cond']:.2e}  s0^2 {got['summary'][5]:.4f}  error / tolerance: "
+        t_lev = MP.tol("lev", st.M_edge_lev[k])
+        assert (got["edge_lev"][k] >= -t_lev).all() and (got["edge_lev"][k] <= 2 + t_lev).all(), (name, "0 <= lev <= 2 on a counted edge")
+    print(f"resid_stats {name}: E {len(g['edge_cam'])}  m {int(m)}  n {int(n)}  s0^2 {got['summary'][5]:.4f}  error / tolerance: "
           + "  ".join(f"{key} {val:.2e}" for key, val in worst.items()))
     return worst
 
 
 @pytest.mark.parametrize("name", RK.NAMES)
 def test_every_output_meets_the_derived_tolerance_and_two_calls_give_the_same_bits(name):
-    g, ref, st = RK.case(name)
+    g = MP.graph(name)
     got = _run(g)
-    _check(name, g, ref, st, got)
+    _check(name, g, MP.case(name), got)
     # the covariances are the graph entry's on the same problem, bit for bit
     cam, obj, _, _, status = ba.pose_covariances_graph(*K.args(g), pairs=NO_PAIRS)
     assert np.array_equal(got["cam_cov"], cam, equal_nan=True) and np.array_equal(got["obj_cov"], obj, equal_nan=True) and list(got["status"][:2]) == list(status[:2])
@@ -148,23 +75,23 @@ def test_every_output_meets_the_derived_tolerance_and_two_calls_give_the_same_bi
 
 
 def test_the_designed_graphs_take_the_paths_they_were_designed_for():
-    g, _, _ = RK.case("three_edges")
+    g = MP.graph("three_edges")
     got = _run(g)
     cut = RK.designed("three_edges", g)
     assert np.isnan(got["edge_t"][cut]).all() and np.isfinite(got["edge_lev"][cut]).all() and np.isfinite(got["edge_pcov"][cut]).all() and got["status"][3] == 3
-    g, _, _ = RK.case("fixed_pair_3x2")
+    g = MP.graph("fixed_pair_3x2")
     got = _run(g)
     both = (g["edge_cam"] == 0) & (g["edge_obj"] == 1)
     assert both.sum() >= 4 and not got["edge_pcov"][both].any() and not got["edge_lev"][both].any()
     assert np.array_equal(got["edge_t"][both], got["edge_chi2"][both]), "P = 0: t is chi2 to the bit"
-    g, _, _ = RK.case("no_edges")
+    g = MP.graph("no_edges")
     got = _run(g)
     assert np.array_equal(got["summary"][:5], np.zeros(5)) and np.isnan(got["summary"][5]) and list(got["status"]) == [0, 2, 0, 0]
     assert not got["cam_stat"].any() and not got["obj_stat"].any() and got["edge_chi2"].shape == (0,) and np.isnan(got["obj_cov"]).all() and not got["cam_cov"].any()
 
 
 def test_every_problem_of_a_batch_of_all_cases_equals_its_solo_bits():
-    graphs = [RK.case(n)[0] for n in RK.NAMES]
+    graphs = [MP.graph(n) for n in RK.NAMES]
     solo = [_run(g) for g in graphs]
     batch = ba.residual_statistics_batch([ba.Problem(*K.args(g)) for g in graphs])
     for n, a, b in zip(RK.NAMES, batch, solo):
@@ -177,7 +104,7 @@ def test_every_problem_of_a_batch_of_all_cases_equals_its_solo_bits():
 
 @pytest.mark.parametrize("name", ["1x17", "cam_only", "flagged_3x2", "three_edges", "object_out_3x17m", "6x20m"])
 def test_four_times_the_information_scales_every_output_by_a_power_of_two_exactly(name):
-    g, _, _ = RK.case(name)
+    g = MP.graph(name)
     one = _run(g)
     g["edge_info"] = 4.0 * g["edge_info"]
     four = _run(g)
@@ -194,7 +121,7 @@ def test_four_times_the_information_scales_every_output_by_a_power_of_two_exactl
 
 
 def test_statistics_after_optimize_leave_the_problem_unchanged():
-    g, _, _ = RK.case("3x2")
+    g = MP.graph("3x2")
     p = ba.Problem(*K.args(g), its=(10, 10), init_with_outliers=True)
     ba.optimize_batch([p])
     fields = ("cam_T", "obj_T", "cam_fixed", "obj_fixed", "edge_cam", "edge_obj", "edge_camk", "edge_p", "edge_uv", "edge_info", "inlier", "chi2", "stats")
@@ -203,8 +130,7 @@ def test_statistics_after_optimize_leave_the_problem_unchanged():
     for k in fields:
         assert np.array_equal(getattr(p, k), before[k]), k
     state = dict(g, cam_T=p.cam_T.reshape(-1, 3, 4), obj_T=p.obj_T.reshape(-1, 3, 4), edge_inlier=p.inlier)
-    ref = R.covariances(state)
-    _check("3x2 after optimize", state, ref, RS.statistics(state, ref), got)
+    _check("3x2 after optimize", state, MP.CovRef(state), got)
     assert got["summary"][4] > 0 and np.isfinite(got["summary"][5]) and got["summary"][5] > 0, got["summary"]
 
 
