@@ -742,6 +742,17 @@ int suo_debug_pose_oplus(const double* T_in, const double* u, int n, double* T_o
 int suo_debug_pnp_refine(int n_obj, const int* n_pts, const double* xs, const double* ys, double threshold, const int* mode, const double* start_qt,
                          const int* start_idx, const int* sel_in, const int* max_iter, const double* tol, double* out_d, int* out_i, int* sel0_out,
                          int* sel1_out);
+/* Test entry: the minimal solver every lane of the PnP kernel runs per hypothesis (p3p_lambdatwist<double,5>, lambdatwist/lambdatwist.p3p.h; p4p, p4p.cpp:11-60),
+ * through the very p3p_lambdatwist and p4p of csrc/pnp.hip.  HOST arrays, blocking, one launch, one thread per problem in 64-thread workgroups.  A problem is four
+ * points: xs [n][4][3] model points, ys [n][4][2] normalised image points.  Per problem i:
+ *   valid[i]      the number of candidates p3p_lambdatwist returned for points 0, 1, 2 (0 .. 4)
+ *   R[i][4][9]    its rotations, row-major, and t[i][4][3] its translations, in its order, exactly as it wrote them; zero beyond valid[i]
+ *   qt[i][7]      (q w x y z, t) as p4p(xs, ys, {0, 1, 2, 3}) returned it: the candidate with the smallest reprojection error of point 3 among those that put it at
+ *                 z >= 0 (strictly smaller: the first of equals wins), the identity pose when none survives
+ *   status[i]     1 when qt[i] is the identity pose (1, 0, 0, 0, 0, 0, 0) exactly, else 0
+ * Inputs are not screened: degenerate triples, equal bearings and NaN coordinates are the solver's to handle.
+ * Refused with SUO_ERR_ARG, nothing launched, nothing written: n <= 0, a NULL pointer. */
+int suo_debug_p3p(int n, const double* xs, const double* ys, int* valid, double* R, double* t, double* qt, int* status);
 
 /* ---- the partitioned adjustment driven from C (csrc/ba_comm.hip, csrc/ba_drive.hip: optimize_dist) ---------------------------------
  * suo_ba_comm: the one collective the schedule above needs -- an in-place SUM all-reduce of n doubles on a device buffer, ordered on a stream.

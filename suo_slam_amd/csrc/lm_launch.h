@@ -22,6 +22,8 @@ int launch_pnp_batch_counts(int n_obj, const int* offsets, const int* counts, co
 int launch_debug_pnp_refine(int n_obj, const int* offsets, const double* xs, const double* ys, double threshold, const int* mode, const double* start_qt,
                             const int* start_idx, const int* sel_in, const int* max_iter, const double* tol, double* out_d, int* out_i, int* sel0_out,
                             int* sel1_out, hipStream_t s);
+// test entry (suo_debug_p3p): one thread per four-point problem through p3p_lambdatwist and p4p; device pointers, xs [n][4][3], ys [n][4][2]
+int launch_debug_p3p(int n, const double* xs, const double* ys, int* valid, double* R, double* t, double* qt, int* status, hipStream_t s);
 // ---- whole LM runs in one launch: problems_dev = n_problems LmProblem structs (csrc/lm_device.h) in device memory ----
 int launch_lm(const void* problems_dev, int n_problems, int lds_bytes, hipStream_t s);
 int launch_lm_big(const void* problems_dev, int n_problems, int lds_bytes, hipStream_t s);

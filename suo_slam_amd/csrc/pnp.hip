@@ -853,4 +853,34 @@ int launch_debug_pnp_refine(int n_obj, const int* offsets, const double* xs, con
     return SUO_OK;
 }
 
+// test entry (suo_debug_p3p; include/suo_hip.h): one thread per four-point problem through the very p3p_lambdatwist and p4p every lane of pnp_batch_kernel runs
+__global__ __launch_bounds__(64) void debug_p3p_kernel(int n, const double* __restrict__ xs_all, const double* __restrict__ ys_all, int* __restrict__ valid_out,
+                                                       double* __restrict__ R_out, double* __restrict__ t_out, double* __restrict__ qt_out, int* __restrict__ status) {
+    const int i = blockIdx.x * 64 + threadIdx.x;
+    if (i >= n) return;
+    const double* xs = xs_all + 12 * (size_t)i;
+    const double* ys = ys_all + 8 * (size_t)i;
+    double Rs[4][9], Ts[4][3], yh[3][3];
+    for (int k = 0; k < 3; ++k) { yh[k][0] = ys[2 * k]; yh[k][1] = ys[2 * k + 1]; yh[k][2] = 1.0; }
+    const int valid = p3p_lambdatwist(yh[0], yh[1], yh[2], xs, xs + 3, xs + 6, Rs, Ts);
+    valid_out[i] = valid;
+    for (int v = 0; v < 4; ++v) {
+        for (int k = 0; k < 9; ++k) R_out[36 * (size_t)i + 9 * v + k] = v < valid ? Rs[v][k] : 0.0;
+        for (int k = 0; k < 3; ++k) t_out[12 * (size_t)i + 3 * v + k] = v < valid ? Ts[v][k] : 0.0;
+    }
+    const int idx[4] = {0, 1, 2, 3};
+    double q[4], t[3];
+    p4p(xs, ys, idx, q, t);
+    for (int k = 0; k < 4; ++k) qt_out[7 * (size_t)i + k] = q[k];
+    for (int k = 0; k < 3; ++k) qt_out[7 * (size_t)i + 4 + k] = t[k];
+    status[i] = (q[0] == 1 && q[1] == 0 && q[2] == 0 && q[3] == 0 && t[0] == 0 && t[1] == 0 && t[2] == 0) ? 1 : 0;
+}
+
+int launch_debug_p3p(int n, const double* xs, const double* ys, int* valid, double* R, double* t, double* qt, int* status, hipStream_t s) {
+    if (n <= 0) { suo_set_error("suo_debug_p3p: n = %d", n); return SUO_ERR_ARG; }
+    hipLaunchKernelGGL(debug_p3p_kernel, dim3((n + 63) / 64), dim3(64), 0, s, n, xs, ys, valid, R, t, qt, status);
+    SUO_HIP_CHECK(hipGetLastError());
+    return SUO_OK;
+}
+
 }  // namespace suo

@@ -176,6 +176,32 @@ int suo_debug_pnp_refine(int n_obj, const int* n_pts, const double* xs, const do
     return SUO_OK;
 }
 
+// Test entry: the minimal solver of pnp_batch_kernel on its own (include/suo_hip.h).  Everything is checked before anything is allocated or launched.
+int suo_debug_p3p(int n, const double* xs, const double* ys, int* valid, double* R, double* t, double* qt, int* status) {
+    if (n <= 0) { suo_set_error("suo_debug_p3p: n = %d", n); return SUO_ERR_ARG; }
+    if (!xs || !ys || !valid || !R || !t || !qt || !status) { suo_set_error("suo_debug_p3p: null argument"); return SUO_ERR_ARG; }
+    const size_t N = (size_t)n;
+    Layout L;
+    const size_t o_xs = L.take(sizeof(double) * 12 * N), o_ys = L.take(sizeof(double) * 8 * N);
+    const size_t o_R = L.take(sizeof(double) * 36 * N), o_t = L.take(sizeof(double) * 12 * N), o_qt = L.take(sizeof(double) * 7 * N),
+                 o_v = L.take(sizeof(int) * N), o_st = L.take(sizeof(int) * N);
+    char* d = nullptr;
+    SUO_HIP_CHECK(hipMalloc((void**)&d, L.off));
+    struct Free { char* d; ~Free() { (void)hipFree(d); } } guard{d};
+    SUO_HIP_CHECK(hipMemcpy(d + o_xs, xs, sizeof(double) * 12 * N, hipMemcpyHostToDevice));
+    SUO_HIP_CHECK(hipMemcpy(d + o_ys, ys, sizeof(double) * 8 * N, hipMemcpyHostToDevice));
+    int rc = launch_debug_p3p(n, (const double*)(d + o_xs), (const double*)(d + o_ys), (int*)(d + o_v), (double*)(d + o_R), (double*)(d + o_t),
+                              (double*)(d + o_qt), (int*)(d + o_st), nullptr);
+    if (rc != SUO_OK) return rc;
+    SUO_HIP_CHECK(hipDeviceSynchronize());
+    SUO_HIP_CHECK(hipMemcpy(R, d + o_R, sizeof(double) * 36 * N, hipMemcpyDeviceToHost));
+    SUO_HIP_CHECK(hipMemcpy(t, d + o_t, sizeof(double) * 12 * N, hipMemcpyDeviceToHost));
+    SUO_HIP_CHECK(hipMemcpy(qt, d + o_qt, sizeof(double) * 7 * N, hipMemcpyDeviceToHost));
+    SUO_HIP_CHECK(hipMemcpy(valid, d + o_v, sizeof(int) * N, hipMemcpyDeviceToHost));
+    SUO_HIP_CHECK(hipMemcpy(status, d + o_st, sizeof(int) * N, hipMemcpyDeviceToHost));
+    return SUO_OK;
+}
+
 int suo_pnp(const double* xs, const double* ys, int n, double threshold, double* T_out) {
     int st = 0;
     return suo_pnp_batch(1, &n, xs, ys, threshold, 0, 1, T_out, &st, nullptr, nullptr);
