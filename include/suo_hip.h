@@ -942,6 +942,49 @@ int suo_gt_masks(void* mesh_db, int n, const int* model_index, const double* T, 
                  int n_images, const float* depth_test, const int* image_index, double delta,
                  uint8_t* mask /*[n][height][width], may be NULL*/, uint8_t* mask_visib /*may be NULL*/);
 
+/* ---- bop_toolkit's point-set pose errors: ADD, ADI, PROJ --------------------------------
+ * Replaces bop_toolkit_lib/pose_error.py:147-232 (add, adi, proj; misc.py:93-107 project_pts, misc.py:266-276 transform_pts_Rt) over the same mesh database.
+ * Every entry is new; nothing above changes.  With E = [R_est|t_est], G = [R_gt|t_gt] and the model's points p_i, i < P:
+ *   ADD  = (1 / P) sum_i |E p_i - G p_i|                          (mm)
+ *   ADI  = (1 / P) sum_i min_j |G p_i - E p_j|                    (mm)   for every GROUND-TRUTH point the nearest ESTIMATED-pose point: the direction of the
+ *                                                                        toolkit's cKDTree(pts_est).query(pts_gt).  suo_pose_errors' float32 ADD-S above is the
+ *                                                                        reference meter's and is not this.
+ *   PROJ = (1 / P) sum_i |pi(K, E, p_i) - pi(K, G, p_i)|          (px)   pi = (M [p;1])_xy / (M [p;1])_z with M = K [R|t] formed first, divided as given: a
+ *                                                                        point behind the camera keeps its finite value, as in the toolkit.
+ * All arithmetic is fp64 on the float32 points widened exactly; a transformed coordinate is ((r0 x + r1 y) + r2 z) + t, a squared distance (dx^2 + dy^2) + dz^2,
+ * no contraction.  The nearest neighbour is exact (a minimum over all P^2 squared distances, the square root taken once per point).  The sums run in an order
+ * that depends on P alone (point i goes to partial sum i % 256; the 256 partial sums are added by a fixed tree): a pair in a batch has the bits it has alone.
+ * est == gt gives ADD = ADI = PROJ = 0 exactly.
+ * `which` is a bit mask of SUO_POINTS_ADD / _ADI / _PROJ: only ADI costs P^2, and a call that does not ask for it does not pay for it.  An output whose bit
+ * is not set is not written and may be NULL; K [n][9] row-major may be NULL without SUO_POINTS_PROJ.
+ * One stated deviation, as for suo_pose_errors_bop: a pair with a non-finite transformed point (a NaN or overflowing pose) reports +inf for ADD and ADI, a
+ * pair with a non-finite projected distance (z exactly 0) +inf for PROJ.  No input makes the call fault.
+ * model_index[n], T_est / T_gt [n][12] row-major 3x4 (doubles, mm).  Host buffers, blocking.  n = 0 or which = 0 return 0.
+ * SUO_ERR_ARG (nothing launched): a null database or required pointer, n < 0, an unknown bit in which, a model index outside the database. */
+#define SUO_POINTS_ADD 1
+#define SUO_POINTS_ADI 2
+#define SUO_POINTS_PROJ 4
+int suo_pose_errors_points(void* mesh_db, int n, const int* model_index, const double* T_est, const double* T_gt, const double* K, int which,
+                           double* add_out, double* adi_out, double* proj_out);
+
+/* ---- bop_toolkit's mask pose errors from two renders: CUS, COU_BB_PROJ ------------------
+ * What bop_toolkit_lib/pose_error.py:256-286 (cus) and :300-329 (cou_bb_proj) take from the depth images of model_index[i] rendered at T_est[i] and at T_gt[i]
+ * under K[i], width x height (the rules of suo_render_depth, unchanged): with mask_est = depth_est > 0 and mask_gt = depth_gt > 0,
+ *   counts_out [n][2]   pixels of mask_est | mask_gt (union) and of mask_est & mask_gt (intersection);
+ *   box_est, box_gt     [n][4] = [xmin, ymin, xmax - xmin, ymax - ymin] of each mask: no + 1, no clipping (misc.calc_2d_bbox); [-1, -1, -1, -1] for an
+ *                       empty mask.
+ * The quotients are the caller's, in fp64 from these exact integers:  cus = 1 - intersection / float(union), or 1.0 when union is 0;
+ * cou_bb_proj = 1 - misc.iou(box_est, box_gt) (misc.py:236-263).  One stated deviation: the toolkit's cou_bb_proj raises on an empty mask (min() of an empty
+ * array); suo_slam_amd.bop_eval reports 1.0 for it, as cus does.
+ * Both renders of a pair are drawn tile by tile into two z-buffers in LDS and reduced there; neither depth image is written to memory.  The device writes
+ * integers only, reduced per wave, per workgroup and then by one integer atomic per quantity: the values of a pair do not depend on the batch, its order or
+ * the tiling.  Every entry is new; nothing above changes.
+ * Host buffers, blocking.  n = 0 returns 0.  SUO_ERR_ARG with a message, before anything is launched: as for suo_render_depth (a null pointer, non-finite T
+ * or K, a model index out of range, a model without faces, width or height < 1, width * height > 2^28).  More pairs than one launch takes (1024, fewer
+ * with many triangles) are split inside. */
+int suo_pose_errors_masks(void* mesh_db, int n, const int* model_index, const double* T_est, const double* T_gt, const double* K, int width, int height,
+                          long long* counts_out /*[n][2]: union, intersection*/, int* box_est /*[n][4]*/, int* box_gt /*[n][4]*/);
+
 /* ---- SLAM-mode hypothesis scoring------------------------------------------
  * Replaces the per-pair numpy of ObjectSLAM.__estimate_camera_pose's hypothesis loop (lib/object_slam.py:1000-1066) and of
  * __maybe_reinit_objects' inlier counts (:619-690): count_k [ z_k > 0 and chi2_k <= chi2_max ] for n_pairs (pose, detection) pairs in one launch.

@@ -164,6 +164,7 @@ SIGNATURES = {
     "suo_pose_errors": (C.c_int, [VP, C.c_int, VP, VP, VP, VP, VP]),
     "suo_mesh_db_set_symmetries": (C.c_int, [VP, VP, VP]),
     "suo_pose_errors_bop": (C.c_int, [VP, C.c_int, VP, VP, VP, VP, VP, VP]),
+    "suo_pose_errors_points": (C.c_int, [VP, C.c_int, VP, VP, VP, VP, C.c_int, VP, VP, VP]),
     "suo_pose_nees": (C.c_int, [VP, C.c_int, VP, VP, VP, VP, VP, VP, VP, VP, VP]),
     "suo_keypoint_nees": (C.c_int, [VP, C.c_int, VP, VP, VP, VP, VP, VP, VP, VP]),
     "suo_mesh_db_set_faces": (C.c_int, [VP, VP, VP]),
@@ -172,6 +173,7 @@ SIGNATURES = {
     "suo_pose_errors_vsd": (C.c_int, [VP, C.c_int, VP, VP, VP, VP, C.c_int, C.c_int, C.c_int, VP, VP, C.c_double, C.c_int, VP, C.c_int, VP, VP, VP]),
     "suo_gt_info": (C.c_int, [VP, C.c_int, VP, VP, VP, C.c_int, C.c_int, C.c_int, VP, VP, C.c_double, VP, VP, VP]),
     "suo_gt_masks": (C.c_int, [VP, C.c_int, VP, VP, VP, C.c_int, C.c_int, C.c_int, VP, VP, C.c_double, VP, VP]),
+    "suo_pose_errors_masks": (C.c_int, [VP, C.c_int, VP, VP, VP, VP, C.c_int, C.c_int, VP, VP, VP]),
     "suo_slam_store_create": (VP, [C.c_int]),
     "suo_slam_store_destroy": (None, [VP]),
     "suo_slam_store_put": (C.c_int, [VP, C.c_int, C.c_int, VP]),

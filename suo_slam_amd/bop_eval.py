@@ -26,6 +26,16 @@ Opt-in since row N6, with nothing above changed when it is not asked for: a mesh
                                                     scripts/calc_gt_info.py, calc_gt_masks.py   -> HIP, csrc/gt_info.hip (row N7; bop_gt_info.py walks a tree)
     overlapping_sphere_projections(radius, p1, p2)  misc.overlapping_sphere_projections (the gate of eval_calc_errors.py:295-312)
     Bop19Meter(..., depth_loader=..., vsd_delta=15) adds "vsd" (one recall per tau and threshold, eval_bop19.py:178-225) and "ar", the mean of the three.
+
+Beside it since row N4, with nothing above changed: the protocol of scripts/eval_siso.py and the error functions eval_calc_errors.py offers beyond the three:
+
+    BopErrors.point_errors(obj_ids, T_est, T_gt, K, which)      pose_error.add / adi / proj                 -> HIP, csrc/eval_points.hip (suo_pose_errors_points)
+    BopErrors.mask_errors(obj_ids, T_est, T_gt, K, hw)          pose_error.cus / cou_bb_proj                -> HIP, csrc/eval_masks.hip (suo_pose_errors_masks)
+    rotation_error / translation_error                          pose_error.re / te (host numpy)
+    LocalizationMeter(errors, targets, scene_gt, scene_gt_info, error_type, n_top, visib_gt_min, correct_th, ...)
+        .add(...) / .result() / .errors_json(scene_id) / .matches()
+                                                                eval_calc_errors.py:192-388 + eval_calc_scores.py:184-269 for one error type, any n_top, both
+                                                                rules of visib_gt_min; SISO_PARAMS are eval_siso.py's (Evaluator(siso=True), tools/eval_siso.py)
 """
 from __future__ import annotations
 
@@ -98,6 +108,46 @@ def _pack34(T, n):
     return np.ascontiguousarray(np.asarray(T, np.float64).reshape(n, -1, 4)[:, :3, :]).reshape(n, 12)
 
 
+POINT_ERROR_BITS = {"add": 1, "adi": 2, "proj": 4}      # SUO_POINTS_ADD / _ADI / _PROJ of include/suo_hip.h
+
+
+def cus_from_counts(union, inter):
+    """pose_error.cus from the two pixel counts (pose_error.py:281-285): 1 - inter / float(union), 1.0 for an empty union."""
+    return 1.0 - int(inter) / float(union) if union > 0 else 1.0
+
+
+def iou_boxes(bb_a, bb_b):
+    """misc.iou of two boxes (x, y, w, h) as misc.calc_2d_bbox forms them (misc.py:236-263)."""
+    tl_a, br_a = (bb_a[0], bb_a[1]), (bb_a[0] + bb_a[2], bb_a[1] + bb_a[3])
+    tl_b, br_b = (bb_b[0], bb_b[1]), (bb_b[0] + bb_b[2], bb_b[1] + bb_b[3])
+    w_inter = min(br_a[0], br_b[0]) - max(tl_a[0], tl_b[0])
+    h_inter = min(br_a[1], br_b[1]) - max(tl_a[1], tl_b[1])
+    if w_inter > 0 and h_inter > 0:
+        area_inter = w_inter * h_inter
+        return area_inter / float(bb_a[2] * bb_a[3] + bb_b[2] * bb_b[3] - area_inter)
+    return 0.0
+
+
+def cou_bb_from_boxes(box_est, box_gt):
+    """pose_error.cou_bb_proj from the two masks' boxes (pose_error.py:323-329); 1.0 when a mask is empty (box [-1,-1,-1,-1]; the toolkit raises there)."""
+    if box_est[2] < 0 or box_gt[2] < 0:
+        return 1.0
+    return 1.0 - iou_boxes([int(v) for v in box_est], [int(v) for v in box_gt])
+
+
+def rotation_error(R_est, R_gt):
+    """pose_error.re (pose_error.py:187-202): the angle of R_est R_gt^-1 in degrees."""
+    R_est, R_gt = np.asarray(R_est, np.float64).reshape(3, 3), np.asarray(R_gt, np.float64).reshape(3, 3)
+    error_cos = float(0.5 * (np.trace(R_est.dot(np.linalg.inv(R_gt))) - 1.0))
+    error_cos = min(1.0, max(-1.0, error_cos))
+    return 180.0 * math.acos(error_cos) / np.pi
+
+
+def translation_error(t_est, t_gt):
+    """pose_error.te (pose_error.py:205-214): |t_gt - t_est| in the poses' unit."""
+    return np.linalg.norm(np.asarray(t_gt, np.float64).reshape(3, 1) - np.asarray(t_est, np.float64).reshape(3, 1))
+
+
 class BopErrors:
     """Owns a mesh database handle with the models' symmetry transformations.  ``mesh_db``: ``{obj_id: {"points": [P,3] mm, ...}}`` (bop.load_mesh_db);
     ``models_info``: ``{obj_id: {...}}`` (load_models_info).  No CPU fallback: without the HIP library or a GPU this raises."""
@@ -156,6 +206,43 @@ class BopErrors:
         _lib.check(self.lib.suo_pose_errors_bop(self._h, n, idx.ctypes.data, Te.ctypes.data, Tg.ctypes.data, Kn.ctypes.data, mssd.ctypes.data, mspd.ctypes.data),
                    "suo_pose_errors_bop")
         return mssd, mspd
+
+    def point_errors(self, obj_ids, T_est, T_gt, K=None, which=("add", "adi", "proj")):
+        """The toolkit's pose_error.add / adi / proj (row N4; include/suo_hip.h: suo_pose_errors_points) of n (object, estimated pose, ground-truth pose,
+        camera matrix) items: ``{name: float64 [n]}`` for the names in ``which``, mm for add / adi and px for proj.  ``adi`` is the exact mean nearest-neighbour
+        distance from the ground-truth points to the estimated-pose points (the toolkit's direction); only it costs P^2.  ``K`` is needed for proj only."""
+        which = tuple(which)
+        unknown = set(which) - set(POINT_ERROR_BITS)
+        if unknown:
+            raise ValueError(f"point_errors: unknown error {sorted(unknown)}; known: {sorted(POINT_ERROR_BITS)}")
+        if "proj" in which and K is None:
+            raise ValueError("point_errors: proj needs the camera matrix K")
+        n = len(obj_ids)
+        out = {w: np.zeros(n, np.float64) for w in POINT_ERROR_BITS}
+        if n and which:
+            idx = np.array([self._index[int(o)] for o in obj_ids], np.int32)
+            Te, Tg = _pack34(T_est, n), _pack34(T_gt, n)
+            Kn = None if K is None else np.ascontiguousarray(np.broadcast_to(np.asarray(K, np.float64).reshape(-1, 3, 3), (n, 3, 3))).reshape(n, 9)
+            mask = sum(POINT_ERROR_BITS[w] for w in set(which))
+            _lib.check(self.lib.suo_pose_errors_points(self._h, n, idx.ctypes.data, Te.ctypes.data, Tg.ctypes.data, None if Kn is None else Kn.ctypes.data, mask,
+                                                       out["add"].ctypes.data, out["adi"].ctypes.data, out["proj"].ctypes.data), "suo_pose_errors_points")
+        return {w: out[w] for w in which}
+
+    def mask_errors(self, obj_ids, T_est, T_gt, K, hw):
+        """The toolkit's pose_error.cus and cou_bb_proj (row N4; include/suo_hip.h: suo_pose_errors_masks) of n items on images of ``hw`` = (H, W):
+        ``{"cus", "cou_bb_proj": float64 [n], "union", "inter": int64 [n], "box_est", "box_gt": int32 [n,4]}``.  Both poses are rendered on the device and
+        reduced there to integers; the quotients are formed here in fp64.  An empty mask gives cou_bb_proj 1.0 (the toolkit raises)."""
+        n, (H, W) = len(obj_ids), hw
+        counts, be, bg = np.zeros((n, 2), np.int64), np.full((n, 4), -1, np.int32), np.full((n, 4), -1, np.int32)
+        if n:
+            idx = np.array([self._index[int(o)] for o in obj_ids], np.int32)
+            Te, Tg = _pack34(T_est, n), _pack34(T_gt, n)
+            Kn = np.ascontiguousarray(np.broadcast_to(np.asarray(K, np.float64).reshape(-1, 3, 3), (n, 3, 3))).reshape(n, 9)
+            _lib.check(self.lib.suo_pose_errors_masks(self._h, n, idx.ctypes.data, Te.ctypes.data, Tg.ctypes.data, Kn.ctypes.data, int(W), int(H),
+                                                      counts.ctypes.data, be.ctypes.data, bg.ctypes.data), "suo_pose_errors_masks")
+        return {"cus": np.array([cus_from_counts(u, i) for u, i in counts.tolist()], np.float64),
+                "cou_bb_proj": np.array([cou_bb_from_boxes(a, b) for a, b in zip(be.tolist(), bg.tolist())], np.float64),
+                "union": counts[:, 0].copy(), "inter": counts[:, 1].copy(), "box_est": be, "box_gt": bg}
 
     def pose_nees(self, obj_ids, T_est, T_gt, cov):
         """NEES of n (object, estimated pose, ground-truth pose, 6x6 covariance) items against T_ref = T_gt S of the MSSD-minimising symmetry:
@@ -462,3 +549,272 @@ class Bop19Meter:
             out["vsd"] = {"recalls": rec, "ar": float(np.mean(rec))}
             out["ar"] = float(np.mean([out["vsd"]["ar"], out["mssd"]["ar"], out["mspd"]["ar"]]))      # eval_bop19.py:240-241
         return out
+
+
+# ---- the general localisation meter: eval_calc_errors.py + eval_calc_scores.py for one error type (row N4) ----
+ERROR_TYPES = ("vsd", "mssd", "mspd", "ad", "add", "adi", "cus", "proj", "re", "te", "rete")
+CORRECT_TH = {"vsd": [0.3], "mssd": [0.2], "mspd": [10.0], "cus": [0.5], "rete": [5.0, 5.0], "re": [5.0], "te": [5.0], "proj": [5.0], "ad": [0.1], "add": [0.1],
+              "adi": [0.1]}                                  # eval_calc_scores.py:39-51
+NORMALIZED_BY_DIAMETER = ("ad", "add", "adi", "mssd")       # eval_calc_scores.py:54
+NORMALIZED_BY_IM_WIDTH = ("mspd",)                          # eval_calc_scores.py:57
+SISO_PARAMS = dict(error_type="vsd", n_top=1, visib_gt_min=0.1, correct_th=[0.3], vsd_delta=15, vsd_taus=[20.0], vsd_normalized_by_diameter=False)   # scripts/eval_siso.py:26-46
+
+
+def error_signature(error_type, n_top, vsd_delta=None, vsd_tau=None):
+    """misc.get_error_signature (misc.py:334-350): the folder name of one error calculation."""
+    sign = "error=" + error_type + "_ntop=" + str(n_top)
+    if error_type == "vsd":
+        tau = "inf" if vsd_tau == float("inf") else "{:.3f}".format(vsd_tau)
+        sign += "_delta={:.3f}_tau={}".format(vsd_delta, tau)
+    return sign
+
+
+def score_signature(correct_th, visib_gt_min):
+    """misc.get_score_signature (misc.py:353-361)."""
+    return "th=" + "-".join(["{:.3f}".format(t) for t in correct_th]) + "_min-visib={:.3f}".format(visib_gt_min)
+
+
+def match_poses_elements(errs, error_ths, max_ests_count=0, gt_valid=None):
+    """pose_matching.match_poses (pose_matching.py:9-90) for an error of any number of elements: by descending score, each estimate takes the valid,
+    unmatched ground truth that beats the best so far in ALL elements, the thresholds being the first best.  ``errs``: ``[{"est_id", "score", "errors":
+    {gt_id: [e, ...]}}]``.  Returns ``[{"est_id", "gt_id", "score", "error", "error_norm"}]``."""
+    errs_sorted = sorted(errs, key=lambda e: e["score"], reverse=True)
+    if max_ests_count > 0:
+        errs_sorted = errs_sorted[:max_ests_count]
+    n_el = len(error_ths)
+    matches, taken = [], []
+    for e in errs_sorted:
+        best_gt, best = -1, list(error_ths)
+        for gt_id, error in e["errors"].items():
+            if (not gt_valid or gt_valid[gt_id]) and gt_id not in taken and all(error[i] < best[i] for i in range(n_el)):
+                best_gt, best = gt_id, error
+        if best_gt >= 0:
+            taken.append(best_gt)
+            matches.append({"est_id": e["est_id"], "gt_id": best_gt, "score": e["score"], "error": best,
+                            "error_norm": [best[i] / float(error_ths[i]) for i in range(n_el)]})
+    return matches
+
+
+def localization_scores(scene_ids, obj_ids, matches, n_top):
+    """score.calc_localization_scores (score.py:62-157) without the printing: the dictionary eval_calc_scores.py saves as scores_*.json."""
+    insts = {}
+    for m in matches:
+        if m["valid"]:
+            key = (m["obj_id"], m["scene_id"], m["im_id"])
+            insts[key] = insts.get(key, 0) + 1
+    tars, obj_tars, scene_tars = 0, {i: 0 for i in obj_ids}, {i: 0 for i in scene_ids}
+    for (o, s, _), c in insts.items():
+        count = min(n_top, c) if n_top > 0 else c              # score.py:93-96: SiSo counts one target however many instances an image shows
+        tars += count
+        obj_tars[o] += count
+        scene_tars[s] += count
+    tps, obj_tps, scene_tps = 0, {i: 0 for i in obj_ids}, {i: 0 for i in scene_ids}
+    for m in matches:
+        if m["valid"] and m["est_id"] != -1:
+            tps += 1
+            obj_tps[m["obj_id"]] += 1
+            scene_tps[m["scene_id"]] += 1
+    recall = lambda tp, n: tp / float(n) if n else 0.0
+    obj_recalls = {i: recall(obj_tps[i], obj_tars[i]) for i in obj_ids}
+    scene_recalls = {i: float(recall(scene_tps[i], scene_tars[i])) for i in scene_ids}
+    return {"recall": float(recall(tps, tars)), "obj_recalls": obj_recalls, "mean_obj_recall": float(np.mean(list(obj_recalls.values()))),
+            "scene_recalls": scene_recalls, "mean_scene_recall": float(np.mean(list(scene_recalls.values()))),
+            "gt_count": len(matches), "targets_count": int(tars), "tp_count": int(tps)}
+
+
+class LocalizationMeter:
+    """eval_calc_errors.py:192-388 and eval_calc_scores.py:184-269 for ONE error type, in process: collects pose estimates and returns the dictionary of
+    score.calc_localization_scores.  It stands beside Bop19Meter and does not replace it.
+
+    ``errors``: a BopErrors, or anything with ``.models_info`` and the calls the error type needs -- ``.vsd`` (vsd), ``.errors`` (mssd, mspd),
+    ``.point_errors`` (ad, add, adi, proj), ``.mask_errors`` (cus); re / te / rete are formed here.  ``targets``, ``scene_gt``, ``scene_gt_info``: as for
+    Bop19Meter.  Parameters, with the scripts' names:
+        error_type      one of ERROR_TYPES;
+        n_top           estimates scored per (image, object), by descending score: k, 0 = all, -1 = the target's inst_count;
+        visib_gt_min    >= 0: a ground truth is valid when its object is a target of the image and its visib_fract >= this (eval_calc_scores.py:217-223);
+                        -1: per object the inst_count most visible ones (:224-238);
+        correct_th      one threshold per error element (rete has two: a match needs ALL elements below); default CORRECT_TH[error_type];
+        vsd_delta, vsd_taus, vsd_normalized_by_diameter      as for eval_calc_errors.py; results are per tau (``tau_index``);
+        symmetric_obj_ids     the objects for which ``ad`` is adi (add for the others);
+        im_width        for the normalisation of mspd;  im_hw = (H, W) for the renders of cus;  depth_loader(scene_id, im_id) for vsd;
+        scene_ids, obj_ids    the scenes of the split and the objects of the dataset the scores are reported over (default: those of the targets / of
+                        ``errors.models_info``).
+    The script's two shortcuts are applied: vsd / cus of a pair whose sphere projections do not overlap is 1.0, ad / add / adi / mssd of a pair whose
+    centres lie a diameter or more apart is inf, both without a device call."""
+
+    def __init__(self, errors, targets, scene_gt, scene_gt_info, error_type="vsd", n_top=1, visib_gt_min=-1, correct_th=None, vsd_delta=15,
+                 vsd_taus=(20.0,), vsd_normalized_by_diameter=False, symmetric_obj_ids=(), im_width=640, im_hw=None, depth_loader=None, scene_ids=None,
+                 obj_ids=None):
+        if error_type not in ERROR_TYPES:
+            raise ValueError(f"LocalizationMeter: unknown error type {error_type!r}; known: {ERROR_TYPES}")
+        self.errors, self.error_type, self.n_top, self.visib_gt_min = errors, error_type, int(n_top), float(visib_gt_min)
+        self.correct_th = [float(t) for t in (CORRECT_TH[error_type] if correct_th is None else correct_th)]
+        n_el = 2 if error_type == "rete" else 1
+        if len(self.correct_th) != n_el:
+            raise ValueError(f"LocalizationMeter: {error_type} has {n_el} error element(s), correct_th has {len(self.correct_th)}")
+        self.vsd_delta, self.vsd_taus, self.vsd_normalized_by_diameter = vsd_delta, [float(t) for t in vsd_taus], bool(vsd_normalized_by_diameter)
+        self.symmetric_obj_ids = {int(o) for o in symmetric_obj_ids}
+        self.im_width, self.im_hw, self.depth_loader = float(im_width), im_hw, depth_loader
+        if error_type == "vsd" and depth_loader is None:
+            raise ValueError("LocalizationMeter: vsd needs a depth_loader(scene_id, im_id)")
+        if error_type == "cus" and im_hw is None:
+            raise ValueError("LocalizationMeter: cus needs im_hw = (H, W)")
+        self.scene_gt, self.scene_gt_info = scene_gt, scene_gt_info
+        self.targets = {}                                         # scene -> image -> obj -> inst_count, in the file's order
+        for t in targets:
+            self.targets.setdefault(t["scene_id"], {}).setdefault(t["im_id"], {})[t["obj_id"]] = t["inst_count"]
+        self.scene_ids = sorted(self.targets) if scene_ids is None else [int(s) for s in scene_ids]
+        self.obj_ids = sorted(int(o) for o in errors.models_info) if obj_ids is None else [int(o) for o in obj_ids]
+        self.ests = {}                                            # (scene, image, obj) -> [{"score", "T", "K"}]
+        self.n_estimates = 0
+        self._records = None
+
+    @classmethod
+    def from_dataset_tree(cls, errors, split_dir, targets_filename, **kw):
+        """Targets file + the ``scene_gt.json`` / ``scene_gt_info.json`` of every scene it names, read unfiltered; ``kw`` as for the constructor."""
+        with open(targets_filename, "r") as f:
+            targets = json.load(f)
+        scene_gt, scene_gt_info = {}, {}
+        for s in sorted({t["scene_id"] for t in targets}):
+            for name, dst in (("scene_gt.json", scene_gt), ("scene_gt_info.json", scene_gt_info)):
+                with open(os.path.join(split_dir, f"{s:06d}", name), "r") as f:
+                    dst[s] = {int(k): v for k, v in json.load(f).items()}
+        return cls(errors, targets, scene_gt, scene_gt_info, **kw)
+
+    def add(self, scene_id, im_id, obj_id, score, T_est, K):
+        """One line of the results file: pose [3|4,4] object to camera in mm, the image's camera matrix."""
+        T = np.asarray(T_est, np.float64).reshape(-1, 4)[:3, :]
+        self.ests.setdefault((int(scene_id), int(im_id), int(obj_id)), []).append({"score": score, "T": T, "K": np.asarray(K, np.float64).reshape(3, 3)})
+        self._records = None
+
+    # -- eval_calc_errors.py ---------------------------------------------------------------------------------
+    def _device_errors(self, pairs):
+        """Error lists of the pairs that passed the shortcuts: ``pairs`` = [(scene, im, obj, T_est, T_gt, K)]."""
+        et = self.error_type
+        if not pairs:
+            return []
+        objs, Te, Tg, K = [p[2] for p in pairs], np.stack([p[3] for p in pairs]), np.stack([p[4] for p in pairs]), np.stack([p[5] for p in pairs])
+        if et == "vsd":
+            out, images, slot = [], [], {}
+            for p in pairs:
+                if (p[0], p[1]) not in slot:
+                    slot[(p[0], p[1])] = len(images)
+                    images.append((p[0], p[1]))
+            sl = [slot[(p[0], p[1])] for p in pairs]
+            for b in range(0, len(pairs), VSD_PAIRS_PER_CALL):              # the pairs come image by image: a run names a handful of images
+                run = slice(b, b + VSD_PAIRS_PER_CALL)
+                used = sorted(set(sl[run]))
+                depth = [np.asarray(self.depth_loader(*images[i]), np.float32) for i in used]
+                e = self.errors.vsd(objs[run], Te[run], Tg[run], K[run], depth, [used.index(i) for i in sl[run]], delta=self.vsd_delta, taus=self.vsd_taus,
+                                    normalized=self.vsd_normalized_by_diameter)
+                out += np.asarray(e).tolist()
+            return out
+        if et in ("mssd", "mspd"):
+            mssd, mspd = self.errors.errors(objs, Te, Tg, K)
+            return [[e] for e in (mssd if et == "mssd" else mspd).tolist()]
+        if et in ("add", "adi", "proj"):
+            return [[e] for e in self.errors.point_errors(objs, Te, Tg, K, which=(et,))[et].tolist()]
+        if et == "ad":                                                      # eval_calc_errors.py:340-346
+            out = [None] * len(pairs)
+            for name, pick in (("adi", True), ("add", False)):
+                ii = [i for i, o in enumerate(objs) if (o in self.symmetric_obj_ids) == pick]
+                if ii:
+                    e = self.errors.point_errors([objs[i] for i in ii], Te[ii], Tg[ii], K[ii], which=(name,))[name].tolist()
+                    for i, v in zip(ii, e):
+                        out[i] = [v]
+            return out
+        if et == "cus":
+            return [[e] for e in self.errors.mask_errors(objs, Te, Tg, K, self.im_hw)["cus"].tolist()]
+        out = []
+        for te_, tg_ in zip(Te, Tg):
+            re_, tr_ = float(rotation_error(te_[:, :3], tg_[:, :3])), float(translation_error(te_[:, 3], tg_[:, 3]))
+            out.append([re_, tr_] if et == "rete" else [re_] if et == "re" else [tr_])
+        return out
+
+    def error_records(self):
+        """``{scene_id: [{"im_id", "obj_id", "est_id", "score", "errors": {gt_id: [e, ...]}}]}`` in the script's order: what eval_calc_errors.py holds in
+        ``scene_errs`` before it saves (vsd: one element per tau).  Computed once per set of estimates."""
+        if self._records is not None:
+            return self._records
+        et, records, pairs, where = self.error_type, {}, [], []
+        self.n_estimates = 0
+        for s, ims in self.targets.items():
+            records[s] = []
+            for im, objs in ims.items():
+                for o, inst_count in objs.items():
+                    n_top_curr = None if self.n_top == 0 else inst_count if self.n_top == -1 else self.n_top
+                    kept = sorted(enumerate(self.ests.get((s, im, o), [])), key=lambda x: x[1]["score"], reverse=True)[slice(0, n_top_curr)]
+                    self.n_estimates += len(kept)
+                    diameter = self.errors.models_info[o]["diameter"] if et in ("vsd", "cus", "ad", "add", "adi", "mssd") else None
+                    for est_id, est in kept:
+                        row = {"im_id": im, "obj_id": o, "est_id": est_id, "score": est["score"], "errors": {}}
+                        records[s].append(row)
+                        for gt_id, gt in enumerate(self.scene_gt[s][im]):
+                            if gt["obj_id"] != o:
+                                continue
+                            Tg = np.hstack((np.reshape(gt["cam_R_m2c"], (3, 3)), np.reshape(gt["cam_t_m2c"], (3, 1)))).astype(np.float64)
+                            if et in ("vsd", "cus") and not overlapping_sphere_projections(0.5 * diameter, est["T"][:, 3], Tg[:, 3]):
+                                row["errors"][gt_id] = [1.0] * (len(self.vsd_taus) if et == "vsd" else 1)
+                            elif et in ("ad", "add", "adi", "mssd") and not np.linalg.norm(est["T"][:, 3] - Tg[:, 3]) < diameter:
+                                row["errors"][gt_id] = [float("inf")]
+                            else:
+                                row["errors"][gt_id] = None                 # keeps the ground truths in their order
+                                pairs.append((s, im, o, est["T"], Tg, est["K"]))
+                                where.append((row, gt_id))
+        for (row, gt_id), e in zip(where, self._device_errors(pairs)):
+            row["errors"][gt_id] = e
+        self._records = records
+        return records
+
+    def error_sign(self, tau_index=0):
+        return error_signature(self.error_type, self.n_top, vsd_delta=self.vsd_delta, vsd_tau=self.vsd_taus[tau_index] if self.error_type == "vsd" else None)
+
+    def score_sign(self):
+        return score_signature(self.correct_th, self.visib_gt_min)
+
+    def errors_json(self, scene_id, tau_index=0):
+        """The list eval_calc_errors.py saves as ``errors_<scene_id>.json`` (for vsd: the file of tau ``tau_index``)."""
+        pick = (lambda e: [e[tau_index]]) if self.error_type == "vsd" else (lambda e: list(e))
+        return [{"im_id": r["im_id"], "obj_id": r["obj_id"], "est_id": r["est_id"], "score": r["score"], "errors": {g: pick(e) for g, e in r["errors"].items()}}
+                for r in self.error_records()[scene_id]]
+
+    # -- eval_calc_scores.py ---------------------------------------------------------------------------------
+    def valid_gts(self, scene_id, im_id):
+        gts, infos, im_targets = self.scene_gt[scene_id][im_id], self.scene_gt_info[scene_id][im_id], self.targets[scene_id][im_id]
+        if self.visib_gt_min >= 0:
+            return [gt["obj_id"] in im_targets and infos[g]["visib_fract"] >= self.visib_gt_min for g, gt in enumerate(gts)]
+        return valid_gt_mask([gt["obj_id"] for gt in gts], [i["visib_fract"] for i in infos], im_targets)
+
+    def matches(self, tau_index=0):
+        """The list eval_calc_scores.py saves as ``matches_*.json``: one record per ground truth of the target images (pose_matching.match_poses_scene)."""
+        out = []
+        factor = 640.0 / self.im_width
+        for s, ims in self.targets.items():
+            by_im = {}
+            for r in self.errors_json(s, tau_index):
+                if self.error_type in NORMALIZED_BY_DIAMETER:
+                    diameter = float(self.errors.models_info[r["obj_id"]]["diameter"])
+                    r["errors"] = {g: [e / diameter for e in es] for g, es in r["errors"].items()}
+                if self.error_type in NORMALIZED_BY_IM_WIDTH:
+                    r["errors"] = {g: [factor * e for e in es] for g, es in r["errors"].items()}
+                by_im.setdefault(r["im_id"], {}).setdefault(r["obj_id"], []).append(r)
+            for im in ims:
+                gts, valid = self.scene_gt[s][im], self.valid_gts(s, im)
+                im_matches = [{"scene_id": s, "im_id": im, "obj_id": gt["obj_id"], "gt_id": g, "est_id": -1, "score": -1, "error": -1, "error_norm": -1,
+                               "valid": valid[g]} for g, gt in enumerate(gts)]
+                for o in {gt["obj_id"] for gt in gts}:
+                    for m in match_poses_elements(by_im.get(im, {}).get(o, []), self.correct_th, self.n_top, valid):
+                        im_matches[m["gt_id"]].update(est_id=m["est_id"], score=m["score"], error=m["error"], error_norm=m["error_norm"])
+                out += im_matches
+        return out
+
+    def result(self, tau_index=0):
+        """Exactly the dictionary of score.calc_localization_scores: ``recall``, ``obj_recalls``, ``mean_obj_recall``, ``scene_recalls``,
+        ``mean_scene_recall``, ``gt_count``, ``targets_count``, ``tp_count``."""
+        return localization_scores(self.scene_ids, self.obj_ids, self.matches(tau_index), self.n_top)
+
+    def parameters(self, tau_index=0):
+        p = {"error_type": self.error_type, "n_top": self.n_top, "visib_gt_min": self.visib_gt_min, "correct_th": list(self.correct_th)}
+        if self.error_type == "vsd":
+            p.update(vsd_delta=self.vsd_delta, vsd_tau=self.vsd_taus[tau_index], vsd_normalized_by_diameter=self.vsd_normalized_by_diameter)
+        return p

@@ -12,6 +12,8 @@ against the toolkit's own ``inout.load_bop_results`` (tests/golden/make_bop_resu
 
 Everything numeric happens in ``ObjectSLAM`` (HIP network, PnP, bundle adjustment) and ``EvalMeter`` (HIP ADD-S).  ``bop19=True`` adds the
 renderer-free two thirds of the BOP-19 score (row N5): the poses of the CSV also go through ``bop_eval.Bop19Meter`` (HIP MSSD / MSPD, host matching).
+``siso=True`` computes the figure of that hand-off -- the SISO recall of VSD -- in process (row N4): ``bop_eval.LocalizationMeter`` over the HIP rasteriser
+and VSD kernel; tools/eval_siso.py is the same over a results CSV.
 """
 from __future__ import annotations
 
@@ -64,7 +66,7 @@ class Evaluator:
     def __init__(self, dataset, data_root, chkpt_path, nviews=1, no_network_cov=False, detection_type="saved", debug_gt_kp=False,
                  gt_cam_pose=False, no_prior_det=False, debug_saved_only=False, give_all_prior=False, out_dir=None, state_dict=None,
                  do_add=None, seed=666, verbose=False, repo_root=".", run_bop_eval=False, frames_per_call=1, bop19=False, bop19_vsd=False,
-                 consistency=False):
+                 consistency=False, siso=False):
         """``dataset``: "ycbv" | "tless"; ``data_root``: the dataset directory of the BOP tree.  ``out_dir`` defaults to
         the checkpoint's directory like the reference.  ``do_add`` overrides the per-dataset default (the reference
         evaluates ADD only on YCB-V).  ``frames_per_call`` > 1 (single-view evaluation, nviews == 1, only): that many reference views go through
@@ -78,17 +80,34 @@ class Evaluator:
         ``consistency``: also compare the reported uncertainties with the ground truth (consistency.ConsistencyMeter): the NEES of every pose that reaches the
         ADD meter under its ``cov_OtoC`` and the chi2 of that view's keypoints under the network's covariances at the symmetry-resolved ground truth
         (``run()["consistency"]`` and three lines of summary.txt).  The CSV does not change.  With ``frames_per_call`` > 1 it raises ValueError: the batched route
-        carries no ``cov_OtoC``."""
+        carries no ``cov_OtoC``.
+        ``siso``: also report the SISO recall of VSD that bop_toolkit's ``scripts/eval_siso.py`` computes -- the figure the reference reports for T-LESS -- of
+        exactly the poses written to the CSV, in process (row N4): a ``bop_eval.LocalizationMeter`` with that script's parameters (bop_eval.SISO_PARAMS: tau 20
+        not normalised by the diameter, delta of the dataset, threshold 0.3, n_top 1, ground truths with visib_fract >= 0.1).  ``run()["siso"]`` is its
+        ``result()`` plus the parameters, and summary.txt gets one line.  T-LESS only (it needs the targets file); it needs ``depth/`` and
+        ``scene_gt_info.json`` in every scene of the split -- ValueError otherwise.  Without it nothing changes; the subprocess hand-off stays available."""
         cfg = _SETTINGS[dataset]
+        self.siso = bool(siso)
+        if self.siso:
+            if dataset != "tless":
+                raise ValueError(f"siso=True needs a targets file and the {dataset!r} {cfg['split']!r} split has none "
+                                 "(the SISO recall counts the targets of all_target_tless.json)")
+            split_dir = os.path.join(data_root, cfg["split"])
+            scenes = sorted(d for d in os.listdir(split_dir) if os.path.isdir(os.path.join(split_dir, d)))
+            missing = [d for d in scenes if not os.path.isdir(os.path.join(split_dir, d, "depth")) or not os.path.exists(os.path.join(split_dir, d, "scene_gt_info.json"))]
+            if missing:
+                raise ValueError(f"siso=True needs depth/ and scene_gt_info.json in every scene of the {cfg['split']!r} split and scenes {missing} lack one "
+                                 "(bop_gt_info.calc_scene_gt_info writes scene_gt_info.json from the depth images)")
         self.frames_per_call = int(frames_per_call) if nviews == 1 else 1
         self.model_path = out_dir if out_dir is not None else os.path.dirname(chkpt_path or ".")
         self.do_add = cfg["do_add"] if do_add is None else do_add
         if debug_gt_kp:
             detection_type = "gt"                                     # evaluate.py:378-379
         self.dataset = bop.BopDataset(data_root, cfg["split"], bop_dset=dataset, ignore_symmetry=True)
-        mesh = bop.load_mesh_db(os.path.join(data_root, cfg["models"]), faces=bool(bop19 and bop19_vsd))
+        with_faces = bool((bop19 and bop19_vsd) or self.siso)
+        mesh = bop.load_mesh_db(os.path.join(data_root, cfg["models"]), faces=with_faces)
         # what every other consumer saw before: no "faces"
-        self.mesh_db = {o: {k: v for k, v in m.items() if k != "faces"} for o, m in mesh.items()} if bop19 and bop19_vsd else mesh
+        self.mesh_db = {o: {k: v for k, v in m.items() if k != "faces"} for o, m in mesh.items()} if with_faces else mesh
         self.bop_errors = None
         if bop19:
             if self.dataset.targets_filename is None:
@@ -108,6 +127,8 @@ class Evaluator:
                 raise ValueError("consistency=True needs frames_per_call == 1: the batched single-view route carries no cov_OtoC")
             if self.bop_errors is None:
                 self.bop_errors = bop_eval.BopErrors(mesh, bop_eval.load_models_info(os.path.join(data_root, cfg["models"])))
+        if self.siso and self.bop_errors is None:
+            self.bop_errors = bop_eval.BopErrors(mesh, bop_eval.load_models_info(os.path.join(data_root, cfg["models"])))
         self._vsd_delta = bop_eval.VSD_DELTAS[dataset]
         self.debug_saved_only = debug_saved_only
         self.nviews, self.detection_type, self.debug_gt_kp, self.gt_cam_pose = nviews, detection_type, debug_gt_kp, gt_cam_pose
@@ -209,6 +230,12 @@ class Evaluator:
                                                                     vsd_delta=self._vsd_delta)
             else:
                 bop19_meter = bop_eval.Bop19Meter.from_dataset_tree(self.bop_errors, ds.curr_root, ds.targets_filename, im_width)
+        siso_meter = None
+        if self.siso and not self.debug_saved_only:
+            split_scenes = sorted(int(d) for d in os.listdir(ds.curr_root) if d.isdigit() and os.path.isdir(os.path.join(ds.curr_root, d)))
+            siso_meter = bop_eval.LocalizationMeter.from_dataset_tree(
+                self.bop_errors, ds.curr_root, ds.targets_filename, depth_loader=ds.read_depth, scene_ids=split_scenes, obj_ids=sorted(self.mesh_db),
+                symmetric_obj_ids=[o for o, m in self.mesh_db.items() if m["is_symmetric"]], **{**bop_eval.SISO_PARAMS, "vsd_delta": self._vsd_delta})
         if not self.debug_saved_only:
             if self.do_add:
                 meter = EvalMeter(self.mesh_db)
@@ -302,6 +329,8 @@ class Evaluator:
                             csv_lines.append(bop_csv_line(scene_id, view_id, o, res["score"], res["T_OtoC"]))
                             if bop19_meter is not None:
                                 bop19_meter.add(scene_id, view_id, o, res["score"], res["T_OtoC"], ds.data[scene_id][view_id]["K"])
+                            if siso_meter is not None:
+                                siso_meter.add(scene_id, view_id, o, res["score"], res["T_OtoC"], ds.data[scene_id][view_id]["K"])
                     else:
                         self._log(f"NOTE: Could not obtain object pose for object {o}")
                         if meter is not None:                         # the reference updates unconditionally; without ADD there is no meter
@@ -329,6 +358,8 @@ class Evaluator:
                 out["bop19"] = bop19_meter.result()
             if cmeter is not None:
                 out["consistency"] = cmeter.result()
+            if siso_meter is not None:
+                out["siso"] = {**siso_meter.result(), **siso_meter.parameters()}
             out["summary_path"] = os.path.join(outdir, "summary.txt")
             with open(out["summary_path"], "w") as f:
                 if meter is not None:
@@ -355,6 +386,11 @@ class Evaluator:
                     f.write(f"\nConsistency, keypoints: mean chi2 {ck['mean_chi2']:.4f} (2 if consistent), {100 * ck['frac_95']:.2f}% <= {_consistency.CHI2_2_95}, "
                             f"{100 * ck['frac_99']:.2f}% <= {_consistency.CHI2_2_99}; {ck['n']} keypoints, {ck['n_nan']} NaN, "
                             f"{ck['n_skipped']} detections without a covariance\n")
+                if siso_meter is not None:
+                    sp = out["siso"]
+                    f.write(f"\nSISO VSD recall (tau {sp['vsd_tau']:g}, th {sp['correct_th'][0]:g}, visib >= {sp['visib_gt_min']:g}): {sp['recall']:.4f} "
+                            f"({sp['tp_count']} of {sp['targets_count']} targets; mean object recall {sp['mean_obj_recall']:.4f}, "
+                            f"mean scene recall {sp['mean_scene_recall']:.4f}; delta {sp['vsd_delta']} mm)\n")
             out["csv_path"] = os.path.join(outdir, method + ".csv")
             with open(out["csv_path"], "w") as f:
                 f.writelines(csv_lines)
