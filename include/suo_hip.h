@@ -1001,6 +1001,71 @@ void suo_slam_store_destroy(void* store);
 int suo_slam_store_put(void* store, int first_slot, int n, const double* rows_host);
 int suo_slam_score(void* store, int n_pairs, const double* pairs_host, double chi2_max, double kp_std2, int32_t* counts_host);
 
+/* ---- A view's three-panel visualisation (collect_results(no_viz=False)) ------------------------
+ * What lib/object_slam.py:226-274 and lib/utils/utils.py:182-354 (draw_points, bbox_color, make_kp_viz) paint for one view, on the device.  Every entry is
+ * new; nothing above changes.  Everything up to the list of primitives is the reference's own arithmetic and is done by the caller
+ * (suo_slam_amd/viz.py: build_primitives); how cv2 rasterises a primitive cannot be pinned here (no cv2), so each rule below is stated and marked
+ * ORACLE-UNPINNED, as the prior stamp and the VSD rasteriser are.
+ *
+ * Canvas       frame uint8 [H][W][3] BGR on the device; out uint8 [H][3 W][3]: left | centre | right, each panel starting as a copy of the frame.
+ * Colours      a colour is packed b | g << 8 | r << 16.  suo_viz_colours gives the reference's two tables as data: the 41 kp_colors() (kp_config.py:97-102,
+ *              the shuffle under seed 123456 included) and the 30 bbox_color() entries (utils.py:248-251).  The caller indexes the second as the reference
+ *              does, cols[obj_id - 1] with Python's indexing, and refuses obj_id > 30.
+ * Disc         (x, y, r, colour): pixels with dx^2 + dy^2 <= r^2, in integers.                                                          ORACLE-UNPINNED
+ * Keypoint     a black disc of radius r_outer = int(round(1.3 rad)), then a disc of radius r_inner = rad in the keypoint's colour, then its ellipse when
+ *              has_ellipse (rad = 8 from make_kp_viz).  A keypoint whose rounded centre is off the canvas is not in the list at all (utils.py:216-217):
+ *              that is the caller's rule; the device clips whatever it is given.
+ * Ellipse      outline (x, y, A, B, cos phi, sin phi, colour), A and B integer half-axes >= 0: with xr = dx cos + dy sin, yr = -dx sin + dy cos in fp64 and
+ *              inside(a, b) <=> (xr b)^2 + (yr a)^2 <= (a b)^2, the pixel is painted iff inside(A + 1, B + 1) and not (A >= 2 and B >= 2 and
+ *              inside(A - 1, B - 1)).  cos and sin arrive as fp64 from the host; the device uses + - x only, no contraction.               ORACLE-UNPINNED
+ * Box          (x1, y1, x2, y2, colour), thickness 3: pixels inside [x1 - 1, x2 + 1] x [y1 - 1, y2 + 1] and not inside [x1 + 2, x2 - 2] x [y1 + 2, y2 - 2],
+ *              clipped to the canvas.                                                                                                     ORACLE-UNPINNED
+ * Text         putText labels are not drawn (a stated deviation).
+ * Order        primitives overwrite in list order, which is the reference's call order: objects in obj_ids order, keypoints in channel order, per keypoint
+ *              black disc, colour disc, ellipse.  The last hit wins.
+ * Left panel   boxes first.  Then the prior heat: a stamp (channel k, ulx, uly, window x0, x1, y0, y1) contributes float32(w[y - uly] w[x - ulx]) -- the
+ *              table of suo_render_priors: w[i] = exp(-(i - 45)^2 / (2 14^2)), doubled at i = 0 -- at pixels with 0 <= x - ulx < 90, 0 <= y - uly < 90 inside
+ *              the window x0 <= x < x1, y0 <= y < y1 (the object's box window [y1:y2, x1:x2] exactly as Python's slices select it, formed by the caller with
+ *              slice.indices).  Per channel s_k = the float32 sum over the stamps of that channel in list order, clipped to [0, 1];
+ *              prior_c = uint8(trunc(clip(sum_k s_k kp_colour[k][c], 0, 255))) summed in fp64 (exact in any order);
+ *              g = (1868 b + 9617 g + 4899 r + 8192) >> 14 over prior_c (OpenCV's documented 8-bit BGR2GRAY);                                ORACLE-UNPINNED
+ *              in fp32 without contraction p = float(g) / 255, out_c = uint8(trunc((1 - p) img_c + p prior_c)), img being the panel with its boxes.
+ *              The [41][H][W] prior tensor never exists in memory.
+ * Right panel  overlay objects in paint order (far to near: the caller's stable sort on -T_OtoC[2][3]).  Per float32 mesh point p, widened exactly, in fp64:
+ *              X = ((r0 x + r1 y) + r2 z) + t per row, (a, b, c) = K X per row as (k0 X + k1 Y) + k2 Z, u = a / c, v = b / c.  No depth test: the reference
+ *              has none.  A point is skipped when u or v is not finite or |u + 0.5| or |v + 0.5| >= 2^31; its pixel is trunc(u + 0.5), trunc(v + 0.5) toward
+ *              zero (values in (-1, 0) land on 0, as torch's .to(int) does), kept when inside the canvas.  Each object's mask is dilated by a 3 x 3 square,
+ *              nothing entering from outside the canvas, and painted in its colour, later objects over earlier ones.  On the device: an int32 [H][W] owner
+ *              plane takes atomicMax(rank + 1) per point, and the painted object of a pixel is the 3 x 3 maximum of that plane -- order-free and exact.
+ *              (The reference projects in float32; the rule is fp64, and agrees wherever no projected coordinate sits on a pixel boundary.)
+ * One view per call; a batched form is out of scope.  suo_viz_view is stream-ordered and does no host synchronisation: it stages the descriptor in pinned
+ * memory, enqueues one copy, the clearing of the owner plane and two kernels on `stream`, and returns.  The pinned staging is a ring of SUO_VIZ_RING slots: the
+ * caller must not have more than that many views of one handle in flight, and uses one stream per handle at a time.  frame and out are device pointers, out
+ * [H][3 W][3] complete once the stream reaches what is enqueued next; every other array of the descriptor is host memory, free to reuse on return.
+ * SUO_ERR_ARG with a message, before anything is launched: a null handle, descriptor, frame or out; a negative count or a null array with a positive count;
+ * n_kp > SUO_VIZ_MAX_KP (16 objects x 41 keypoints), n_stamp > SUO_VIZ_MAX_KP, n_box > SUO_VIZ_MAX_OBJ, n_overlay > SUO_VIZ_MAX_OBJ (64); a stamp channel
+ * outside [0, 41); a negative radius or half-axis or one above 2^20; a non-finite cos / sin; overlays without a mesh database, or a model index outside it;
+ * suo_viz_create: H or W < 1 or H W >= 2^31. */
+#define SUO_VIZ_MAX_KP 656
+#define SUO_VIZ_MAX_OBJ 64
+#define SUO_VIZ_RING 8
+typedef struct suo_viz suo_viz;
+typedef struct suo_viz_view_desc {
+    const uint8_t* frame;            /* device, [H][W][3] BGR */
+    int n_box;     const int32_t* box;           /* [n_box][5]: x1, y1, x2, y2, colour */
+    int n_stamp;   const int32_t* stamp;         /* [n_stamp][8]: channel, ulx, uly, x0, x1, y0, y1, object (informative) */
+    int n_kp;      const int32_t* kp;            /* [n_kp][8]: x, y, r_outer, r_inner, colour, has_ellipse, A, B */
+    const double* kp_cs;                         /* [n_kp][2]: cos phi, sin phi (read where has_ellipse) */
+    int n_overlay; const int32_t* overlay_model; /* [n_overlay] index into the mesh database, in paint order */
+    const int32_t* overlay_colour;               /* [n_overlay] */
+    const double* overlay_T;                     /* [n_overlay][12] row-major 3x4 object -> camera */
+    const double* overlay_K;                     /* [n_overlay][9] row-major */
+} suo_viz_view_desc;
+int suo_viz_colours(uint8_t* kp_bgr /*[41][3]*/, uint8_t* box_bgr /*[30][3]*/);
+int suo_viz_create(int H, int W, suo_viz** out);
+void suo_viz_destroy(suo_viz* viz);
+int suo_viz_view(suo_viz* viz, const suo_viz_view_desc* view, void* mesh_db /*suo_mesh_db_create's, may be NULL without overlays*/, uint8_t* out_dev, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -178,6 +178,10 @@ SIGNATURES = {
     "suo_slam_store_destroy": (None, [VP]),
     "suo_slam_store_put": (C.c_int, [VP, C.c_int, C.c_int, VP]),
     "suo_slam_score": (C.c_int, [VP, C.c_int, VP, C.c_double, C.c_double, VP]),
+    "suo_viz_colours": (C.c_int, [VP, VP]),
+    "suo_viz_create": (C.c_int, [C.c_int, C.c_int, C.POINTER(VP)]),
+    "suo_viz_destroy": (None, [VP]),
+    "suo_viz_view": (C.c_int, [VP, VP, VP, VP, VP]),
 }
 
 
@@ -202,6 +206,12 @@ class FrameGeomResult(C.Structure):
     _fields_ = [("n_frames", C.c_int), ("n_crops", C.c_int), ("T_pnp", VP), ("T_opt", VP), ("chi2", VP), ("pnp_status", VP),
                 ("pnp_best_inliers", VP), ("pnp_iterations", VP), ("n_kp", VP), ("lm_stats", VP), ("accepted", VP), ("inlier", VP),
                 ("uv", VP), ("cov", VP), ("mask", VP), ("obj_cov", VP)]
+
+
+class VizViewDesc(C.Structure):
+    """ctypes mirror of suo_viz_view_desc."""
+    _fields_ = [("frame", VP), ("n_box", C.c_int), ("box", VP), ("n_stamp", C.c_int), ("stamp", VP), ("n_kp", C.c_int), ("kp", VP), ("kp_cs", VP),
+                ("n_overlay", C.c_int), ("overlay_model", VP), ("overlay_colour", VP), ("overlay_T", VP), ("overlay_K", VP)]
 
 
 def register(extra):

@@ -66,7 +66,7 @@ class Evaluator:
     def __init__(self, dataset, data_root, chkpt_path, nviews=1, no_network_cov=False, detection_type="saved", debug_gt_kp=False,
                  gt_cam_pose=False, no_prior_det=False, debug_saved_only=False, give_all_prior=False, out_dir=None, state_dict=None,
                  do_add=None, seed=666, verbose=False, repo_root=".", run_bop_eval=False, frames_per_call=1, bop19=False, bop19_vsd=False,
-                 consistency=False, siso=False):
+                 consistency=False, siso=False, no_viz=True, viz_cov=False, viz_dir=None):
         """``dataset``: "ycbv" | "tless"; ``data_root``: the dataset directory of the BOP tree.  ``out_dir`` defaults to
         the checkpoint's directory like the reference.  ``do_add`` overrides the per-dataset default (the reference
         evaluates ADD only on YCB-V).  ``frames_per_call`` > 1 (single-view evaluation, nviews == 1, only): that many reference views go through
@@ -85,7 +85,14 @@ class Evaluator:
         exactly the poses written to the CSV, in process (row N4): a ``bop_eval.LocalizationMeter`` with that script's parameters (bop_eval.SISO_PARAMS: tau 20
         not normalised by the diameter, delta of the dataset, threshold 0.3, n_top 1, ground truths with visib_fract >= 0.1).  ``run()["siso"]`` is its
         ``result()`` plus the parameters, and summary.txt gets one line.  T-LESS only (it needs the targets file); it needs ``depth/`` and
-        ``scene_gt_info.json`` in every scene of the split -- ValueError otherwise.  Without it nothing changes; the subprocess hand-off stays available."""
+        ``scene_gt_info.json`` in every scene of the split -- ValueError otherwise.  Without it nothing changes; the subprocess hand-off stays available.
+        ``no_viz=False`` (the reference's default; here the default stays True): every evaluated view's three-panel picture (ObjectSLAM.collect_results(no_viz=False),
+        suo_slam_amd/viz.py) is written to ``viz_dir`` (default ``<out_dir>/<method>/viz_images``) as ``scene_{scene_id}_{j:06d}.png``, j the view's position
+        in its scene, the pictures of an SfM call's views stacked vertically (evaluate.py:202-219); ``viz_cov`` draws the covariance ellipses.  With
+        ``frames_per_call`` > 1 it raises ValueError: the batched route makes no pictures."""
+        self.no_viz, self.viz_dir = bool(no_viz), viz_dir
+        if not self.no_viz and nviews == 1 and int(frames_per_call) > 1:
+            raise ValueError("no_viz=False needs frames_per_call == 1: the batched single-view route makes no pictures")
         cfg = _SETTINGS[dataset]
         self.siso = bool(siso)
         if self.siso:
@@ -137,7 +144,7 @@ class Evaluator:
         self._rng = np.random.RandomState(seed)                       # evaluate.py:386 seeds numpy with 666
         if not debug_saved_only:
             self.object_slam = ObjectSLAM(chkpt_path, self.mesh_db, no_network_cov=no_network_cov, no_prior_det=no_prior_det,
-                                          debug_gt_kp=debug_gt_kp, sfm_mode=nviews > 0, single_view_mode=nviews == 1,
+                                          debug_gt_kp=debug_gt_kp, sfm_mode=nviews > 0, single_view_mode=nviews == 1, viz_cov=viz_cov,
                                           kp_var_thresh=cfg["kp_var_thresh"], bbox_thresh=cfg["bbox_thresh"], bbox_inflate=0.0,
                                           manual_kp_std=cfg["manual_kp_std"], opt_init_with_outliers=cfg["opt_init_with_outliers"],
                                           give_all_prior=give_all_prior, state_dict=state_dict, max_crops=16 * max(1, self.frames_per_call))
@@ -196,11 +203,22 @@ class Evaluator:
             if a is not None:
                 self.object_slam.process_view(*a[0], **a[1])
         if not self.consistency:
-            return self.object_slam.collect_results(last_only=self.nviews < 0, no_viz=True)
-        results = self.object_slam.collect_results(last_only=self.nviews < 0, no_viz=True, covariances=True)
+            return self.object_slam.collect_results(last_only=self.nviews < 0, no_viz=self.no_viz)
+        results = self.object_slam.collect_results(last_only=self.nviews < 0, no_viz=self.no_viz, covariances=True)
         # the reference view's detections, read before the next reset() drops them
         self._view_dets = dict(self.object_slam.detections.get(views_to_proc[0], {}))
         return results
+
+    def _write_viz(self, outdir, scene_id, j, results):
+        """evaluate.py:202-219: the pictures of the call's views (all of them in SfM mode, the last one in SLAM mode) stacked vertically into one PNG."""
+        from PIL import Image
+        view_ids = self.object_slam.view_ids if self.nviews > 0 else [self.object_slam.view_ids[-1]]
+        viz_tot = np.concatenate([results[v]["viz"] for v in view_ids], axis=0)
+        viz_path = self.viz_dir if self.viz_dir is not None else os.path.join(outdir, "viz_images")
+        os.makedirs(viz_path, exist_ok=True)
+        fn = os.path.join(viz_path, f"scene_{scene_id}_{j:06d}.png")
+        Image.fromarray(np.ascontiguousarray(viz_tot[..., ::-1])).save(fn)            # BGR -> RGB
+        self._log("Wrote viz to", fn)
 
     @staticmethod
     def _to4(T):
@@ -294,6 +312,8 @@ class Evaluator:
                     results = self._run_slam(scene_id, views)
                     if len(results) == 0:
                         continue
+                    if not self.no_viz:
+                        self._write_viz(outdir, scene_id, j, results)
                     scene_results.append((view_id, results[view_id]["poses"] if self.nviews > 0 else None, gt_obj_ids))
                     if cmeter is not None:
                         view_dets[view_id] = self._view_dets

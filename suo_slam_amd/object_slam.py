@@ -5,7 +5,7 @@ for the hot path: same public methods, argument order and state dictionaries (``
     ObjectSLAM(chkpt_path, mesh_db, ...)                 object_slam.py:52-57
     reset()                                              :125-153
     process_view(view_id, img, K, obj_ids, bboxes, model_kps, model_kps_masks, kp_masks, uv_gt, cam_pose)  :327-451
-    collect_results(last_only, no_viz, final)            :175-225 (visualisation is out of scope: no_viz only)
+    collect_results(last_only, no_viz, final)            :175-274 (no_viz=False: the three-panel picture, suo_slam_amd/viz.py -> csrc/viz.hip)
     optimize(curr_only)                                  :703-930
     pnp(points_3d, points_2d, camera_matrix)             :25-41
 
@@ -196,6 +196,9 @@ class ObjectSLAM(DeviceRoutes):
         self.opt_init_with_outliers = opt_init_with_outliers
         self.give_all_prior = give_all_prior
         self.verbose = verbose
+        self.viz_cov = bool(viz_cov)           # collect_results(no_viz=False): covariance ellipses on the centre panel (suo_slam_amd/viz.py)
+        self.do_viz_extra = bool(do_viz_extra)  # the paper figures' per-object crops: not built, collect_results(no_viz=False) raises NotImplementedError
+        self._visualizer = None                # viz.Visualizer of the current frame size, made by the first collect_results(no_viz=False)
         # single-view frames: masks -> compaction -> PnP -> acceptance -> graph -> LM as ONE device chain behind the network
         # (suo_slam_amd/frame_geom.py); False = the host route that restates the reference's data flow (three read-backs, Python lists)
         self.device_chain = bool(device_chain)
@@ -272,7 +275,11 @@ class ObjectSLAM(DeviceRoutes):
     # ---------------------------------------------------------------------------------------------
     def collect_results(self, last_only=False, no_viz=True, final=False, covariances=False):
         """object_slam.py:175-225: T_OtoC = T_GtoC @ T_OtoG per view; score = 1 + total inliers.  covariances=True: every pose entry also carries "cov_OtoC", the
-        6x6 covariance of that T_OtoC (pose_covariances(relative=True)), None where T_OtoC is None."""
+        6x6 covariance of that T_OtoC (pose_covariances(relative=True)), None where T_OtoC is None.  no_viz=False (:226-274): every view also carries "viz", the
+        three-panel picture uint8 [H,3W,3] BGR painted on the device (suo_slam_amd/viz.py; ellipses under viz_cov and not no_network_cov).  The default stays
+        no_viz=True, unlike the reference's, and the dict is then exactly what it was."""
+        if not no_viz and self.do_viz_extra:
+            raise NotImplementedError("do_viz_extra (the per-object crops of the paper's figures, object_slam.py:276-325) is not built: DESIGN.md 6")
         if self.slam_mode and self.needs_opt and final:
             t0 = time()
             self.optimize()
@@ -295,7 +302,22 @@ class ObjectSLAM(DeviceRoutes):
                 results[view_id]["poses"][obj_id] = {"T_OtoC": T_OtoC, "score": 1 + n_inl[obj_id]}
                 if covariances:
                     results[view_id]["poses"][obj_id]["cov_OtoC"] = None if T_OtoC is None else rel[(view_id, obj_id)]
+            if not no_viz:
+                results[view_id]["viz"] = self._viz_view(view_id)
         return results
+
+    def _viz_view(self, view_id):
+        """The view's picture: the primitives are the reference's host arithmetic (viz.view_primitives), the painting one stream-ordered device call."""
+        from . import viz
+        img = self.images[view_id]
+        if self._visualizer is None or (self._visualizer.H, self._visualizer.W) != tuple(img.shape[:2]):
+            if self._visualizer is not None:
+                self._visualizer.close()
+            self._visualizer = viz.Visualizer(self.mesh_db, img.shape[0], img.shape[1])
+        frame = self._frame_dev if self._frame_key == (id(img), getattr(img, "shape", None)) else None      # the frame _frame_on_device uploaded, when it is this view's
+        if frame is None or not hasattr(frame, "is_cuda") or not frame.is_cuda or tuple(frame.shape) != tuple(img.shape) or str(frame.dtype) != "torch.uint8":
+            frame = img
+        return self._visualizer.render(frame, viz.view_primitives(self, view_id))
 
     # ---------------------------------------------------------------------------------------------
     @_on_stream
