@@ -381,6 +381,12 @@ int suo_pnp(const double* xs, const double* ys, int n, double threshold, double*
  *     caller advanced `seed` by their number from frame to frame (what ObjectSLAM does between process_view calls).
  *     do_lm = 0 stops after PnP + acceptance (SLAM tracking continues on the host: camera hypotheses :975-1072).
  *     At most 16 crops per frame when do_lm (one wave per object, csrc/lm_frame.hip).
+ *     Singular covariances (DEVIATION: the reference's np.linalg.inv raises LinAlgError on the exactly singular ones, :827, and hands g2o whatever it returns for
+ *     the others): with use_cov, a keypoint whose float32 covariance [[a, b], [c, d]] gives a det = a d - b c in fp64 (products exact, one rounding) that is not
+ *     finite or is <= 0 is not a measurement.  The chain treats it as masked out: it is not a PnP point, not a graph edge, does not count in n_kp and reads
+ *     back as mask = 0, whatever mask_dev said (suo_keypoint_masks lets a zero variance through: sqrt(0) < 2 kp_var_thresh).  An invertible covariance is
+ *     untouched, bit for bit.  With use_cov = 0 the covariance is not read and the keypoint stays.  The host-array route (suo_pnp_batch + suo_optimize with
+ *     information matrices the caller inverted, ObjectSLAM(device_chain=False)) keeps np.linalg.inv and its exception.
  *   suo_frame_geom_fetch: waits for that launch and points `out` into the context's pinned read-back block (valid until the next launch):
  *     per crop T_pnp [16] (row-major 4x4; pnp_status 1 = identity = failure), accepted, T_opt [12] (refined T_OtoC, = PnP pose when not
  *     refined), n_kp, and per keypoint SLOT (crop * 41 + position among the crop's valid keypoints, i.e. the order of the reference's
@@ -753,6 +759,16 @@ int suo_debug_pnp_refine(int n_obj, const int* n_pts, const double* xs, const do
  * Inputs are not screened: degenerate triples, equal bearings and NaN coordinates are the solver's to handle.
  * Refused with SUO_ERR_ARG, nothing launched, nothing written: n <= 0, a NULL pointer. */
 int suo_debug_p3p(int n, const double* xs, const double* ys, int* valid, double* R, double* t, double* qt, int* status);
+/* Test entry: the pose graph fg_prep_kernel and fg_build_kernel (csrc/frame_geom.hip) staged on the device in the context's last suo_frame_geom_launch, as the LM
+ * kernel read it.  Waits for that launch, then copies the device arrays to HOST buffers, blocking; any output pointer may be NULL.  L = crops of the launch,
+ * F = its frames, SLOT layout: crop l owns slots l * 41 .. l * 41 + 40 and fills the first n_kp[l] of them with its valid keypoints in mask order; the slots behind
+ * them are not written by the launch (they hold what an earlier launch of the context left, zeros in a fresh one).
+ *   xs [L][41][3] model points, ys [L][41][2] normalised image points (the PnP problem), edge_uv [L][41][2] measurements, edge_k [L][41][4] fx, fy, cx, cy,
+ *   edge_info [L][41][3] (xx, xy, yy), pair_start / pair_end [L] edge range of the crop's pair relative to its FRAME's first slot (start = lane * 41, end = start +
+ *   n_kp for an accepted crop, = start for a rejected one), obj_fixed [L] = !accepted, problem_header [F][4] = n_cam, n_obj, n_edge, n_pair of each frame's LmProblem.
+ * SUO_ERR_ARG when nothing was launched. */
+int suo_debug_frame_geom_staged(suo_frame_geom* g, double* xs, double* ys, double* edge_uv, double* edge_k, double* edge_info, int* pair_start, int* pair_end,
+                                unsigned char* obj_fixed, int* problem_header);
 
 /* ---- the partitioned adjustment driven from C (csrc/ba_comm.hip, csrc/ba_drive.hip: optimize_dist) ---------------------------------
  * suo_ba_comm: the one collective the schedule above needs -- an in-place SUM all-reduce of n doubles on a device buffer, ordered on a stream.

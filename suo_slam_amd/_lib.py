@@ -128,6 +128,7 @@ SIGNATURES = {
     "suo_debug_pnp_refine": (C.c_int, [C.c_int, VP, VP, VP, C.c_double, VP, VP, VP, VP, VP, VP, VP, VP, VP, VP]),
     "suo_debug_p3p": (C.c_int, [C.c_int, VP, VP, VP, VP, VP, VP, VP]),
     "suo_debug_lm_routes": (C.c_int, [VP, C.c_int, VP, VP]),
+    "suo_debug_frame_geom_staged": (C.c_int, [VP] * 10),
     "suo_ba_comm_rccl_unique_id": (C.c_int, [VP]),
     "suo_ba_comm_create_rccl": (C.c_int, [VP, C.c_int, C.c_int, C.POINTER(VP)]),
     "suo_ba_comm_create_local": (C.c_int, [C.c_int, C.POINTER(VP)]),

@@ -8,7 +8,8 @@
 //
 //   fg_prep_kernel      wave per crop: ballot-compacts the valid keypoints (mask order = the reference's boolean indexing), widens
 //                       uv / model points to fp64, normalises uv with the host-inverted K_bbox (ys, PnP input), inverts the 2x2
-//                       covariances (information of the graph edges), copies uv / cov / mask into the read-back block
+//                       covariances (information of the graph edges), copies uv / cov / mask into the read-back block; with use_cov a
+//                       keypoint whose covariance has no positive finite determinant counts as masked out (include/suo_hip.h)
 //   pnp_batch_kernel    csrc/pnp.hip, unchanged arithmetic; point counts read from the device (`counts`)
 //   fg_build_kernel     wave per frame: acceptance (pose found, T[2,3] > 0.5 diameter, >= 4 keypoints), then the frame's pose graph as
 //                       the LmProblem the LM kernels take -- fixed identity camera, one vertex per accepted crop initialised with its PnP
@@ -60,7 +61,17 @@ struct FgArrays {                       // device pointers into the context's ar
 __global__ __launch_bounds__(64) void fg_prep_kernel(FgArrays A, const float* __restrict__ uv, const float* __restrict__ cov,
                                                      const uint8_t* __restrict__ mask, const float* __restrict__ model_kps, int use_cov) {
     const int g = blockIdx.x, k = threadIdx.x;
-    const bool valid = k < NUM_KP && mask[g * NUM_KP + k] != 0;
+    bool valid = k < NUM_KP && mask[g * NUM_KP + k] != 0;
+    // A covariance without a positive finite determinant is not a measurement (the reference's np.linalg.inv raises on the singular ones, :827; d / 0 here
+    // would put NaN into every frame-wide sum of the LM kernel): with use_cov the keypoint is masked out BEFORE the ballot -- it leaves the PnP set, the graph,
+    // n_kp, and reads back as mask 0.  Products of two float32 are exact in fp64, so det is rounded once.
+    double a = 0.0, bb = 0.0, c = 0.0, d = 0.0, det = 1.0;
+    if (valid && use_cov) {
+        const int i = g * NUM_KP + k;
+        a = (double)cov[4 * i]; bb = (double)cov[4 * i + 1]; c = (double)cov[4 * i + 2]; d = (double)cov[4 * i + 3];
+        det = a * d - bb * c;
+        valid = det > 0.0 && det < __builtin_huge_val();
+    }
     const unsigned long long b = __ballot(valid);
     const int pos = __popcll(b & ((1ull << k) - 1ull));
     const int n = __popcll(b);
@@ -81,11 +92,7 @@ __global__ __launch_bounds__(64) void fg_prep_kernel(FgArrays A, const float* __
         A.edge_uv[2 * e] = u; A.edge_uv[2 * e + 1] = v;
         for (int t = 0; t < 4; ++t) A.edge_k[4 * e + t] = A.camk[4 * g + t];
         double ixx = 1.0, ixy = 0.0, iyy = 1.0;                    // Inf = np.eye(2) without network covariance (:825)
-        if (use_cov) {
-            const double a = (double)cov[4 * i], bb = (double)cov[4 * i + 1], c = (double)cov[4 * i + 2], d = (double)cov[4 * i + 3];
-            const double det = a * d - bb * c;
-            ixx = d / det; iyy = a / det; ixy = 0.5 * (-bb / det + -c / det);
-        }
+        if (use_cov) { ixx = d / det; iyy = a / det; ixy = 0.5 * (-bb / det + -c / det); }
         A.edge_info[3 * e] = ixx; A.edge_info[3 * e + 1] = ixy; A.edge_info[3 * e + 2] = iyy;
     }
     if (k == 0) {
@@ -341,6 +348,33 @@ int suo_frame_geom_device_result(suo_frame_geom* c, suo_frame_geom_result* r) {
 int suo_frame_geom_ready(suo_frame_geom* c) {
     if (!c || !c->launched) return 1;
     return hipEventQuery(c->done) == hipSuccess ? 1 : 0;
+}
+
+// Test entry: what fg_prep_kernel / fg_build_kernel staged for the LM kernel in the last launch, copied from the device arrays as they lie (slots beyond a crop's
+// count keep whatever an earlier launch left there).
+int suo_debug_frame_geom_staged(suo_frame_geom* c, double* xs, double* ys, double* edge_uv, double* edge_k, double* edge_info, int* pair_start, int* pair_end,
+                                unsigned char* obj_fixed, int* problem_header) {
+    if (!c) { suo_set_error("suo_debug_frame_geom_staged: null argument"); return SUO_ERR_ARG; }
+    if (!c->launched) { suo_set_error("suo_debug_frame_geom_staged: nothing launched"); return SUO_ERR_ARG; }
+    SUO_HIP_CHECK(hipEventSynchronize(c->done));
+    const size_t L = c->L, E = L * NUM_KP;
+    auto get = [](void* dst, const void* src, size_t bytes) { return dst ? hipMemcpy(dst, src, bytes, hipMemcpyDeviceToHost) : hipSuccess; };
+    SUO_HIP_CHECK(get(xs, c->A.xs, sizeof(double) * 3 * E));
+    SUO_HIP_CHECK(get(ys, c->A.ys, sizeof(double) * 2 * E));
+    SUO_HIP_CHECK(get(edge_uv, c->A.edge_uv, sizeof(double) * 2 * E));
+    SUO_HIP_CHECK(get(edge_k, c->A.edge_k, sizeof(double) * 4 * E));
+    SUO_HIP_CHECK(get(edge_info, c->A.edge_info, sizeof(double) * 3 * E));
+    SUO_HIP_CHECK(get(pair_start, c->A.pair_start, sizeof(int) * L));
+    SUO_HIP_CHECK(get(pair_end, c->A.pair_end, sizeof(int) * L));
+    SUO_HIP_CHECK(get(obj_fixed, c->A.obj_fixed, L));
+    if (problem_header) {
+        std::vector<LmProblem> P(c->n_frames);
+        SUO_HIP_CHECK(hipMemcpy(P.data(), c->A.problems, sizeof(LmProblem) * c->n_frames, hipMemcpyDeviceToHost));
+        for (int f = 0; f < c->n_frames; ++f) {
+            problem_header[4 * f] = P[f].n_cam; problem_header[4 * f + 1] = P[f].n_obj; problem_header[4 * f + 2] = P[f].n_edge; problem_header[4 * f + 3] = P[f].n_pair;
+        }
+    }
+    return SUO_OK;
 }
 
 }  // extern "C"

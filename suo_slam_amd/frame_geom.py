@@ -90,13 +90,30 @@ class FrameGeometry:
         _lib.check(self._lib.suo_frame_geom_fetch(self._h, C.byref(r)), "suo_frame_geom_fetch")
         return np.ctypeslib.as_array(C.cast(r.obj_cov, C.POINTER(C.c_double)), shape=(r.n_crops, 6, 6)).copy()
 
+    def staged(self):
+        """Test read-out (suo_debug_frame_geom_staged): the device-resident pose graph of the last launch in slot layout -- xs [L,41,3], ys [L,41,2],
+        edge_uv [L,41,2], edge_k [L,41,4], edge_info [L,41,3], pair_start / pair_end [L], obj_fixed [L] bool, header [F,4] = n_cam, n_obj, n_edge, n_pair.
+        Slots beyond a crop's n_kp are whatever an earlier launch left there."""
+        r = _lib.FrameGeomResult()
+        _lib.check(self._lib.suo_frame_geom_fetch(self._h, C.byref(r)), "suo_frame_geom_fetch")
+        L, F = r.n_crops, r.n_frames
+        out = {"xs": np.zeros((L, NUM_KP, 3)), "ys": np.zeros((L, NUM_KP, 2)), "edge_uv": np.zeros((L, NUM_KP, 2)), "edge_k": np.zeros((L, NUM_KP, 4)),
+               "edge_info": np.zeros((L, NUM_KP, 3)), "pair_start": np.zeros(L, np.int32), "pair_end": np.zeros(L, np.int32),
+               "obj_fixed": np.zeros(L, np.uint8), "header": np.zeros((F, 4), np.int32)}
+        _lib.check(self._lib.suo_debug_frame_geom_staged(self._h, *[a.ctypes.data for a in out.values()]), "suo_debug_frame_geom_staged")
+        out["obj_fixed"] = out["obj_fixed"].astype(bool)
+        return out
+
     def ready(self):
         return bool(self._lib.suo_frame_geom_ready(self._h))
 
     def fetch(self, copy=True):
         """Wait for the launch; dict of numpy arrays (views into the pinned block unless copy): T_pnp [L,4,4], pnp_status [L], accepted
         [L] bool, T_opt [L,3,4], n_kp [L], inlier [L,41] bool / chi2 [L,41] in SLOT order (first n_kp[l] entries of row l = the crop's
-        valid keypoints in mask order), uv [L,41,2], cov [L,41,2,2], mask [L,41] bool, lm_stats [F,4], pnp_iterations, pnp_best_inliers."""
+        valid keypoints in mask order), uv [L,41,2], cov [L,41,2,2], mask [L,41] bool, lm_stats [F,4], pnp_iterations, pnp_best_inliers.
+        inlier slots beyond n_kp[l] are 1 (every launch resets all 41); chi2 slots beyond n_kp[l], and every chi2 slot of a crop that was not accepted
+        or of a do_lm = False launch, are UNSPECIFIED: they keep what an earlier launch of the context left there.  mask is what the chain used: with
+        use_cov a keypoint whose covariance has no positive finite determinant reads back as False (include/suo_hip.h: suo_frame_geom_launch)."""
         r = _lib.FrameGeomResult()
         _lib.check(self._lib.suo_frame_geom_fetch(self._h, C.byref(r)), "suo_frame_geom_fetch")
         L, F = r.n_crops, r.n_frames

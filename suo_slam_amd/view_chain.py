@@ -428,8 +428,8 @@ class DeviceRoutes:
             puv = torch.empty((Lb, NUM_KP, 2), dtype=torch.float32, device=dev)
             pmk = torch.empty((Lb, NUM_KP), dtype=torch.uint8, device=dev)
             vout = torch.empty(32, dtype=torch.float64, device=dev)
-            # ---- vote + priors, on the stream, behind pass A's PnP
-            _lib.check(lib.suo_slam_vote(La, ra_dev.T_pnp, ra_dev.accepted, ra_dev.n_kp, P(pa.uv_dev), P(pa.pred["cov"]), P(pa.masks_dev), P(pa.kps_dev),
+            # ---- vote + priors, on the stream, behind pass A's PnP (the masks as the chain used them: without the keypoints it dropped for a singular covariance)
+            _lib.check(lib.suo_slam_vote(La, ra_dev.T_pnp, ra_dev.accepted, ra_dev.n_kp, P(pa.uv_dev), P(pa.pred["cov"]), ra_dev.mask, P(pa.kps_dev),
                                          P(pb.block_dev), Lb, P(pb.kps_dev), P(pb.class_mask_dev), int(not self.no_network_cov), float(self.manual_kp_std) ** 2,
                                          CHI2_2DOF_95, 4, P(puv), P(pmk), P(vout), C.c_void_p(_lib.current_stream_ptr())), "suo_slam_vote")
             if self._vote_pin is None:

@@ -89,7 +89,7 @@ def _launch(fg, frames, seed, its=(10, 10, 40, 40), use_cov=True, do_lm=True):
     return fg.fetch()
 
 
-@pytest.mark.parametrize("n_obj,use_cov", [(8, True), (8, False), (5, True), (16, True), (1, True)])
+@pytest.mark.parametrize("n_obj,use_cov", [(8, True), (8, False), (5, True), (16, True), (1, True), (9, True)])
 def test_chain_equals_the_host_array_entry_points_bit_for_bit(n_obj, use_cov):
     rng = np.random.default_rng(100 + n_obj + use_cov)
     fg = FrameGeometry(16, 1)
