@@ -958,6 +958,31 @@ int suo_gt_masks(void* mesh_db, int n, const int* model_index, const double* T, 
                  int n_images, const float* depth_test, const int* image_index, double delta,
                  uint8_t* mask /*[n][height][width], may be NULL*/, uint8_t* mask_visib /*may be NULL*/);
 
+/* ---- model statistics: 3-D box and diameter ------------------------------------------
+ * What bop_toolkit's scripts/calc_model_info.py computes for models_info.json (min_*, size_*, diameter; misc.py:279-293 calc_pts_diameter), for n items
+ * model_index[i] of the mesh database, on its float32 points widened exactly to fp64.  Every entry is new; nothing above changes.
+ *   box        min_c = min_i p_ic,  size_c = max_i p_ic - min_c: one fp64 subtraction.  -0 orders below +0: a zero minimum of an axis that holds both zeros
+ *              is -0.0 (the toolkit's numpy reports whichever it meets first -- a stated deviation; size_c is the same number either way).
+ *   diameter   d^2(i, j) = ((dx dx + dy dy) + dz dz) with dx = p_ix - p_jx and so on: fp64 with + - x only, in exactly that association, no contraction and
+ *              no fma.  diameter = sqrt(max_{i <= j} d^2), one correctly rounded sqrt at the end -- sqrt is monotone, so this is the toolkit's maximum of
+ *              square roots bit for bit.  The pair (i, i) counts: a one-point model has diameter 0.0.  Exact brute force over all pairs: no fp32 filter,
+ *              no pruning.
+ *   pair       with pair_out, the pair i <= j whose d^2(i, j) equals the maximum with the lowest i, then the lowest j (point indices within the model).
+ *              NULL skips the work.
+ *   non-finite a model with any NaN or Inf coordinate gets flags bit 0, NaN in all seven outputs and the pair (-1, -1); every other item of the call is
+ *              unaffected.  Finite float32 coordinates cannot overflow fp64 here: a finite model always has finite results.  No input makes the call fault.
+ * Every value is a minimum or maximum of numbers that do not depend on where they are formed (integer atomics on order-preserving bit patterns): an item's
+ * results do not depend on the launch geometry, on the batch or on its place in it.  One launch set a call, whatever n: a box pass, a pass over the tiles
+ * (item, i-tile, j-tile at or above it) of all items in one list, and with pair_out a pass that rescans only the tiles whose maximum equals the item's.
+ * Host buffers, blocking; runs on the database's stream under its lock; its scratch grows only.  n = 0 returns 0.  SUO_ERR_ARG with a message, nothing launched
+ * and no output written: a null database, n < 0, null model_index or info_out with n > 0, a model index outside the database, a model without points.
+ * suo_model_info_tiles: the j-tile and i-tile of the tile pass, in points (the sizes at which a model takes another path through it; for tests). */
+int suo_model_info(void* mesh_db, int n, const int* model_index,
+                   double* info_out /*[n][7]: min_x, min_y, min_z, size_x, size_y, size_z, diameter*/,
+                   int* pair_out    /*[n][2] or NULL: the point indices of a diametral pair*/,
+                   int* flags_out   /*[n] or NULL: bit 0 = a non-finite coordinate*/);
+void suo_model_info_tiles(int* tile, int* itile);
+
 /* ---- bop_toolkit's point-set pose errors: ADD, ADI, PROJ --------------------------------
  * Replaces bop_toolkit_lib/pose_error.py:147-232 (add, adi, proj; misc.py:93-107 project_pts, misc.py:266-276 transform_pts_Rt) over the same mesh database.
  * Every entry is new; nothing above changes.  With E = [R_est|t_est], G = [R_gt|t_gt] and the model's points p_i, i < P:

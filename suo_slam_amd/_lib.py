@@ -174,6 +174,8 @@ SIGNATURES = {
     "suo_pose_errors_vsd": (C.c_int, [VP, C.c_int, VP, VP, VP, VP, C.c_int, C.c_int, C.c_int, VP, VP, C.c_double, C.c_int, VP, C.c_int, VP, VP, VP]),
     "suo_gt_info": (C.c_int, [VP, C.c_int, VP, VP, VP, C.c_int, C.c_int, C.c_int, VP, VP, C.c_double, VP, VP, VP]),
     "suo_gt_masks": (C.c_int, [VP, C.c_int, VP, VP, VP, C.c_int, C.c_int, C.c_int, VP, VP, C.c_double, VP, VP]),
+    "suo_model_info": (C.c_int, [VP, C.c_int, VP, VP, VP, VP]),
+    "suo_model_info_tiles": (None, [c_i32p, c_i32p]),
     "suo_pose_errors_masks": (C.c_int, [VP, C.c_int, VP, VP, VP, VP, C.c_int, C.c_int, VP, VP, VP]),
     "suo_slam_store_create": (VP, [C.c_int]),
     "suo_slam_store_destroy": (None, [VP]),

@@ -141,13 +141,21 @@ def load_ply_mesh(path):
         return pts.astype(np.float32), np.ascontiguousarray(faces, np.int32)
 
 
-def load_mesh_db(model_dir, faces=False):
+def load_mesh_db(model_dir, faces=False, compute_info=False):
     """``{obj_id: {"is_symmetric", "continuous_sym", "diameter", "points"}}`` from ``models_info.json`` +
     ``obj_%06d.ply`` (mesh_database.py:17-45).  ``points`` is a float32 numpy array [P,3] in mm; ``EvalMeter`` uploads
     it to the GPU once (the reference keeps a CUDA tensor here).  ``faces=True`` adds ``"faces"``, int32 [F,3] vertex
-    indices, for the VSD renderer (bop_eval.BopErrors); the other entries are the same either way."""
-    with open(os.path.join(model_dir, "models_info.json"), "r") as f:
-        model_info = json.load(f)
+    indices, for the VSD renderer (bop_eval.BopErrors); the other entries are the same either way.
+    ``compute_info=True`` (off by default: nothing changes): a missing ``models_info.json`` stands for one entry per
+    ``obj_%06d.ply`` with no symmetries, and an object whose entry lacks ``diameter`` has it computed on the device
+    from the points (bop_model_info.model_info, row N8).  Nothing is written to disk."""
+    info_path = os.path.join(model_dir, "models_info.json")
+    if compute_info and not os.path.exists(info_path):
+        from . import bop_model_info
+        model_info = {str(o): {} for o in bop_model_info.model_ids(model_dir)}
+    else:
+        with open(info_path, "r") as f:
+            model_info = json.load(f)
     mesh_db = {}
     for key, info in model_info.items():
         obj_id = int(key)
@@ -160,11 +168,17 @@ def load_mesh_db(model_dir, faces=False):
         mesh_db[obj_id] = {
             "is_symmetric": len(info.get("symmetries_discrete", [])) > 0 or len(cont) > 0,
             "continuous_sym": cont if len(cont) > 0 else [],
-            "diameter": info["diameter"],
+            "diameter": info.get("diameter") if compute_info else info["diameter"],
             "points": pts,
         }
         if faces:
             mesh_db[obj_id]["faces"] = tris
+    if compute_info:
+        missing = [o for o, e in mesh_db.items() if e["diameter"] is None]
+        if missing:
+            from . import bop_model_info
+            for o, e in bop_model_info.model_info(mesh_db, missing).items():
+                mesh_db[o]["diameter"] = e["diameter"]
     return mesh_db
 
 
