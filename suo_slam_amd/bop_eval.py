@@ -36,6 +36,11 @@ Beside it since row N4, with nothing above changed: the protocol of scripts/eval
         .add(...) / .result() / .errors_json(scene_id) / .matches()
                                                                 eval_calc_errors.py:192-388 + eval_calc_scores.py:184-269 for one error type, any n_top, both
                                                                 rules of visib_gt_min; SISO_PARAMS are eval_siso.py's (Evaluator(siso=True), tools/eval_siso.py)
+
+Written once, for everything above: stage_pairs / stage_images (what every BopErrors method and consistency.py hand to C: model indices, [n,12] poses, [n,9]
+camera matrices; the test images of a call stacked and re-indexed), _Meter (the base of both meters: targets index, add, from_dataset_tree and _walk -- scene ->
+image -> object -> kept estimates -> ground truths, in the scripts' order), projections_overlap / centres_within (the two shortcut gates), vsd_runs (runs of
+VSD_PAIRS_PER_CALL pairs, each with exactly the images it names) and match_poses_elements (the greedy rule; match_poses is its one-element form).
 """
 from __future__ import annotations
 
@@ -102,10 +107,34 @@ def load_models_info(model_dir):
 
 
 # ---- errors on the device ---------------------------------------------------------------------------------
-def _pack34(T, n):
-    if hasattr(T, "detach"):
-        T = T.detach().cpu().numpy()
-    return np.ascontiguousarray(np.asarray(T, np.float64).reshape(n, -1, 4)[:, :3, :]).reshape(n, 12)
+def _numpy(x):
+    return x.detach().cpu().numpy() if hasattr(x, "detach") else x
+
+
+def pack_poses(T, n):
+    """float64 [n,12], C-contiguous: the rows [R|t] of n poses [n,3|4,4], torch or numpy."""
+    return np.ascontiguousarray(np.asarray(_numpy(T), np.float64).reshape(n, -1, 4)[:, :3, :]).reshape(n, 12) if n else np.zeros((0, 12), np.float64)
+
+
+def stage_pairs(index, obj_ids, K, *poses):
+    """What every C entry over the mesh database takes, staged once: ``(n, idx, K, *poses)`` with ``idx`` int32 [n] the model indices of ``obj_ids`` under
+    ``index`` ({obj_id: model index}; an unknown object is a KeyError), ``K`` float64 [n,9] from one [3,3] or [n,3,3] (None stays None) and every pose
+    [n,3|4,4] as pack_poses gives it.  All C-contiguous; no device."""
+    n = len(obj_ids)
+    idx = np.array([index[int(o)] for o in obj_ids], np.int32)
+    if K is not None:
+        K = np.ascontiguousarray(np.broadcast_to(np.asarray(_numpy(K), np.float64).reshape(-1, 3, 3), (n, 3, 3))).reshape(n, 9)
+    return (n, idx, K) + tuple(pack_poses(T, n) for T in poses)
+
+
+def stage_images(depth_images, image_index):
+    """The test images a call names, stacked and re-indexed: ``(float32 [k,H,W] of the images ``image_index`` names, in ascending order of their index;
+    int32 [n] indices into that stack)``."""
+    image_index = [int(i) for i in image_index]
+    used = sorted(set(image_index))
+    test = np.ascontiguousarray(np.stack([np.asarray(depth_images[i], np.float32) for i in used]))
+    assert test.ndim == 3, "the depth images of a call must have one size"
+    return test, np.array([used.index(i) for i in image_index], np.int32)
 
 
 POINT_ERROR_BITS = {"add": 1, "adi": 2, "proj": 4}      # SUO_POINTS_ADD / _ADI / _PROJ of include/suo_hip.h
@@ -196,13 +225,10 @@ class BopErrors:
 
     def errors(self, obj_ids, T_est, T_gt, K):
         """(MSSD[n] in mm, MSPD[n] in px) of n (object, estimated pose, ground-truth pose, camera matrix) items; poses [n,3|4,4], K [n,3,3] or one [3,3]."""
-        n = len(obj_ids)
+        n, idx, Kn, Te, Tg = stage_pairs(self._index, obj_ids, K, T_est, T_gt)
         mssd, mspd = np.zeros(n, np.float64), np.zeros(n, np.float64)
         if n == 0:
             return mssd, mspd
-        idx = np.array([self._index[int(o)] for o in obj_ids], np.int32)
-        Te, Tg = _pack34(T_est, n), _pack34(T_gt, n)
-        Kn = np.ascontiguousarray(np.broadcast_to(np.asarray(K, np.float64).reshape(-1, 3, 3), (n, 3, 3))).reshape(n, 9)
         _lib.check(self.lib.suo_pose_errors_bop(self._h, n, idx.ctypes.data, Te.ctypes.data, Tg.ctypes.data, Kn.ctypes.data, mssd.ctypes.data, mspd.ctypes.data),
                    "suo_pose_errors_bop")
         return mssd, mspd
@@ -217,12 +243,9 @@ class BopErrors:
             raise ValueError(f"point_errors: unknown error {sorted(unknown)}; known: {sorted(POINT_ERROR_BITS)}")
         if "proj" in which and K is None:
             raise ValueError("point_errors: proj needs the camera matrix K")
-        n = len(obj_ids)
+        n, idx, Kn, Te, Tg = stage_pairs(self._index, obj_ids, K, T_est, T_gt)
         out = {w: np.zeros(n, np.float64) for w in POINT_ERROR_BITS}
         if n and which:
-            idx = np.array([self._index[int(o)] for o in obj_ids], np.int32)
-            Te, Tg = _pack34(T_est, n), _pack34(T_gt, n)
-            Kn = None if K is None else np.ascontiguousarray(np.broadcast_to(np.asarray(K, np.float64).reshape(-1, 3, 3), (n, 3, 3))).reshape(n, 9)
             mask = sum(POINT_ERROR_BITS[w] for w in set(which))
             _lib.check(self.lib.suo_pose_errors_points(self._h, n, idx.ctypes.data, Te.ctypes.data, Tg.ctypes.data, None if Kn is None else Kn.ctypes.data, mask,
                                                        out["add"].ctypes.data, out["adi"].ctypes.data, out["proj"].ctypes.data), "suo_pose_errors_points")
@@ -232,12 +255,9 @@ class BopErrors:
         """The toolkit's pose_error.cus and cou_bb_proj (row N4; include/suo_hip.h: suo_pose_errors_masks) of n items on images of ``hw`` = (H, W):
         ``{"cus", "cou_bb_proj": float64 [n], "union", "inter": int64 [n], "box_est", "box_gt": int32 [n,4]}``.  Both poses are rendered on the device and
         reduced there to integers; the quotients are formed here in fp64.  An empty mask gives cou_bb_proj 1.0 (the toolkit raises)."""
-        n, (H, W) = len(obj_ids), hw
+        (n, idx, Kn, Te, Tg), (H, W) = stage_pairs(self._index, obj_ids, K, T_est, T_gt), hw
         counts, be, bg = np.zeros((n, 2), np.int64), np.full((n, 4), -1, np.int32), np.full((n, 4), -1, np.int32)
         if n:
-            idx = np.array([self._index[int(o)] for o in obj_ids], np.int32)
-            Te, Tg = _pack34(T_est, n), _pack34(T_gt, n)
-            Kn = np.ascontiguousarray(np.broadcast_to(np.asarray(K, np.float64).reshape(-1, 3, 3), (n, 3, 3))).reshape(n, 9)
             _lib.check(self.lib.suo_pose_errors_masks(self._h, n, idx.ctypes.data, Te.ctypes.data, Tg.ctypes.data, Kn.ctypes.data, int(W), int(H),
                                                       counts.ctypes.data, be.ctypes.data, bg.ctypes.data), "suo_pose_errors_masks")
         return {"cus": np.array([cus_from_counts(u, i) for u, i in counts.tolist()], np.float64),
@@ -258,11 +278,8 @@ class BopErrors:
     def render_depth(self, obj_ids, T, K, hw):
         """float32 [n,H,W] depth images (mm, 0 where nothing is drawn) of the objects under poses [n,3|4,4] and K [n,3,3] or one [3,3]; ``hw`` = (H, W).
         The rules are those of include/suo_hip.h (suo_render_depth)."""
-        n, (H, W) = len(obj_ids), hw
+        (n, idx, Kn, Tn), (H, W) = stage_pairs(self._index, obj_ids, K, T), hw
         out = np.zeros((n, int(H), int(W)), np.float32)
-        idx = np.array([self._index[int(o)] for o in obj_ids], np.int32)
-        Tn = _pack34(T, n) if n else np.zeros((0, 12))
-        Kn = np.ascontiguousarray(np.broadcast_to(np.asarray(K, np.float64).reshape(-1, 3, 3), (n, 3, 3))).reshape(n, 9)
         _lib.check(self.lib.suo_render_depth(self._h, n, idx.ctypes.data, Tn.ctypes.data, Kn.ctypes.data, int(W), int(H), out.ctypes.data), "suo_render_depth")
         return out
 
@@ -270,42 +287,29 @@ class BopErrors:
         """VSD errors [n, len(taus)] of n (object, estimated pose, ground-truth pose, camera matrix, test depth image) items: ``depth_images`` a sequence of
         float32 [H,W] in mm, ``image_index[n]`` into it.  Both poses are rendered on the device; a call takes VSD_PAIRS_PER_CALL pairs with the images they
         name.  ``return_counts``: also int64 [n, 2 + len(taus)] union, intersection and cost per tau."""
-        n = len(obj_ids)
+        n, idx, Kn, Te, Tg = stage_pairs(self._index, obj_ids, K, T_est, T_gt)
         taus = np.ascontiguousarray(taus, np.float64)
         errors, counts = np.ones((n, len(taus)), np.float64), np.zeros((n, 2 + len(taus)), np.int64)
         if n:
-            idx = np.array([self._index[int(o)] for o in obj_ids], np.int32)
-            Te, Tg = _pack34(T_est, n), _pack34(T_gt, n)
-            Kn = np.ascontiguousarray(np.broadcast_to(np.asarray(K, np.float64).reshape(-1, 3, 3), (n, 3, 3))).reshape(n, 9)
             diam = np.array([float(self.models_info[int(o)]["diameter"]) for o in obj_ids], np.float64)
-            image_index = [int(i) for i in image_index]
-            H, W = np.asarray(depth_images[image_index[0]]).shape
+            image_index = list(image_index)
+            H, W = np.asarray(depth_images[int(image_index[0])]).shape
         for b in range(0, n, VSD_PAIRS_PER_CALL):
             sl = slice(b, min(n, b + VSD_PAIRS_PER_CALL))
-            used = sorted(set(image_index[sl]))
-            test = np.ascontiguousarray(np.stack([np.asarray(depth_images[i], np.float32) for i in used]))
+            test, ii = stage_images(depth_images, image_index[sl])
             assert test.shape[1:] == (H, W), "the depth images of a call must have one size"
-            ii = np.array([used.index(i) for i in image_index[sl]], np.int32)
             m = sl.stop - sl.start
             e, c = np.zeros((m, len(taus)), np.float64), np.zeros((m, 2 + len(taus)), np.int64)
             i_, te, tg, kk, dd = (np.ascontiguousarray(a[sl]) for a in (idx, Te, Tg, Kn, diam))
-            _lib.check(self.lib.suo_pose_errors_vsd(self._h, m, i_.ctypes.data, te.ctypes.data, tg.ctypes.data, kk.ctypes.data, int(W), int(H), len(used),
+            _lib.check(self.lib.suo_pose_errors_vsd(self._h, m, i_.ctypes.data, te.ctypes.data, tg.ctypes.data, kk.ctypes.data, int(W), int(H), len(test),
                                                     test.ctypes.data, ii.ctypes.data, float(delta), len(taus), taus.ctypes.data, int(bool(normalized)),
                                                     dd.ctypes.data, e.ctypes.data, c.ctypes.data), "suo_pose_errors_vsd")
             errors[sl], counts[sl] = e, c
         return (errors, counts) if return_counts else errors
 
     def _gt_args(self, obj_ids, T_gt, K, depth_images, image_index):
-        n = len(obj_ids)
-        idx = np.array([self._index[int(o)] for o in obj_ids], np.int32)
-        Tn = _pack34(T_gt, n)
-        Kn = np.ascontiguousarray(np.broadcast_to(np.asarray(K, np.float64).reshape(-1, 3, 3), (n, 3, 3))).reshape(n, 9)
-        image_index = [int(i) for i in image_index]
-        used = sorted(set(image_index))
-        test = np.ascontiguousarray(np.stack([np.asarray(depth_images[i], np.float32) for i in used]))
-        assert test.ndim == 3, "the depth images of a call must have one size"
-        ii = np.array([used.index(i) for i in image_index], np.int32)
-        return n, idx, Tn, Kn, test, ii
+        n, idx, Kn, Tn = stage_pairs(self._index, obj_ids, K, T_gt)
+        return (n, idx, Tn, Kn) + stage_images(depth_images, image_index)
 
     def gt_info(self, obj_ids, T_gt, K, depth_images, image_index, delta=15):
         """What scripts/calc_gt_info.py writes per ground-truth instance (row N7; include/suo_hip.h: suo_gt_info): a list of dictionaries with the toolkit's
@@ -381,17 +385,9 @@ def valid_gt_mask(im_gt_obj_ids, im_visib_fract, im_targets):
 def match_poses(errs, threshold, gt_valid):
     """Greedy matching of the estimates of one (image, object) to its ground truths (pose_matching.match_poses with one error element and
     max_ests_count <= 0): by descending score, each estimate takes the valid, unmatched ground truth with the smallest error strictly below the threshold.
-    ``errs``: ``[{"est_id", "score", "errors": {gt_id: error}}]``.  Returns ``[(est_id, gt_id, error)]``."""
-    matches, taken = [], []
-    for e in sorted(errs, key=lambda e: e["score"], reverse=True):
-        best_gt, best = -1, threshold
-        for gt_id, err in e["errors"].items():
-            if gt_valid[gt_id] and gt_id not in taken and err < best:
-                best_gt, best = gt_id, err
-        if best_gt >= 0:
-            taken.append(best_gt)
-            matches.append((e["est_id"], best_gt, best))
-    return matches
+    ``errs``: ``[{"est_id", "score", "errors": {gt_id: error}}]``.  Returns ``[(est_id, gt_id, error)]``.  The rule itself is match_poses_elements'."""
+    one = [{"est_id": e["est_id"], "score": e["score"], "errors": {g: (err,) for g, err in e["errors"].items()}} for e in errs]
+    return [(m["est_id"], m["gt_id"], m["error"][0]) for m in match_poses_elements(one, (threshold,), 0, gt_valid)]
 
 
 def match_poses_image(im_gt_obj_ids, gt_valid, im_errs, threshold):
@@ -403,29 +399,52 @@ def match_poses_image(im_gt_obj_ids, gt_valid, im_errs, threshold):
     return est
 
 
-class Bop19Meter:
-    """Collects pose estimates and turns them into the MSSD and MSPD recalls of eval_bop19.py.
+# ---- what the two meters share: collection, the pair walk, the two shortcut gates, the VSD runs ----------
+def projections_overlap(diameter, T_est, T_gt):
+    """The gate of vsd and cus (eval_calc_errors.py:295-312): a pair whose sphere projections do not overlap is 1.0 without a device call."""
+    return overlapping_sphere_projections(0.5 * diameter, T_est[:, 3], T_gt[:, 3])
 
-    ``errors``: a BopErrors (or anything with ``.errors(obj_ids, T_est, T_gt, K)``, ``.models_info`` and ``.max_sym_disc_step``);
-    ``targets``: the list of the targets file (``{"scene_id", "im_id", "obj_id", "inst_count"}``); ``scene_gt`` / ``scene_gt_info``:
-    ``{scene_id: {im_id: [ground truths of scene_gt.json / scene_gt_info.json, unfiltered]}}``; ``im_width``: width of the split's images in pixels."""
 
-    def __init__(self, errors, targets, scene_gt, scene_gt_info, im_width, depth_loader=None, vsd_delta=15):
-        """``depth_loader(scene_id, im_id)`` -> float32 [H,W] depth in mm (BopDataset.read_depth): with it ``result()`` also carries VSD (``errors`` then
-        needs ``.vsd``, a BopErrors over a mesh database with faces) and the mean of the three terms; without it nothing changes."""
-        self.errors = errors
-        self.depth_loader, self.vsd_delta = depth_loader, vsd_delta
-        self.im_width = float(im_width)
-        self.scene_gt, self.scene_gt_info = scene_gt, scene_gt_info
+def centres_within(diameter, T_est, T_gt):
+    """The gate of mssd, ad, add and adi (eval_calc_errors.py:314-323): a pair whose centres lie a diameter or more apart is inf without a device call."""
+    return bool(np.linalg.norm(T_est[:, 3] - T_gt[:, 3]) < diameter)
+
+
+def _stacked(pairs):
+    """``(obj_ids, T_est [n,3,4], T_gt [n,3,4], K [n,3,3])`` of pairs ``[(scene, im, obj, T_est, T_gt, K)]``."""
+    return [p[2] for p in pairs], np.stack([p[3] for p in pairs]), np.stack([p[4] for p in pairs]), np.stack([p[5] for p in pairs])
+
+
+def vsd_runs(errors, depth_loader, pairs, **kw):
+    """``errors.vsd`` over pairs ``[(scene, im, obj, T_est, T_gt, K)]`` in runs of VSD_PAIRS_PER_CALL (read at call time): the pairs come image by image, so
+    a run names a handful of images.  Exactly those are loaded, in the order they were first seen among all pairs, and the run's ``image_index`` counts
+    into them.  ``kw``: delta, taus, normalized.  Returns the error lists, one per pair."""
+    slot, out, per_call = {}, [], VSD_PAIRS_PER_CALL
+    slots = [slot.setdefault((p[0], p[1]), len(slot)) for p in pairs]
+    images = list(slot)
+    for b in range(0, len(pairs), per_call):
+        used = sorted(set(slots[b:b + per_call]))
+        depth = [np.asarray(depth_loader(*images[i]), np.float32) for i in used]
+        out += np.asarray(errors.vsd(*_stacked(pairs[b:b + per_call]), depth, [used.index(i) for i in slots[b:b + per_call]], **kw)).tolist()
+    return out
+
+
+class _Meter:
+    """Collection and the pair walk of Bop19Meter and LocalizationMeter.  ``targets``: the list of the targets file (``{"scene_id", "im_id", "obj_id",
+    "inst_count"}``); ``scene_gt`` / ``scene_gt_info``: ``{scene_id: {im_id: [ground truths of scene_gt.json / scene_gt_info.json, unfiltered]}}``."""
+
+    def __init__(self, errors, targets, scene_gt, scene_gt_info):
+        self.errors, self.scene_gt, self.scene_gt_info = errors, scene_gt, scene_gt_info
         self.targets = {}                                         # scene -> image -> obj -> inst_count, in the file's order
         for t in targets:
             self.targets.setdefault(t["scene_id"], {}).setdefault(t["im_id"], {})[t["obj_id"]] = t["inst_count"]
         self.ests = {}                                            # (scene, image, obj) -> [{"score", "T", "K"}]
-        self.n_estimates = 0                                      # the estimates that were scored (top inst_count of a target), after result()
+        self.n_estimates = 0                                      # the estimates that were scored (the top n of a target), after a walk
 
     @classmethod
-    def from_dataset_tree(cls, errors, split_dir, targets_filename, im_width, depth_loader=None, vsd_delta=15):
-        """Targets file + the ``scene_gt.json`` / ``scene_gt_info.json`` of every scene it names, read unfiltered."""
+    def from_dataset_tree(cls, errors, split_dir, targets_filename, *args, **kw):
+        """Targets file + the ``scene_gt.json`` / ``scene_gt_info.json`` of every scene it names, read unfiltered; ``args``, ``kw`` as for the constructor
+        behind ``scene_gt_info``."""
         with open(targets_filename, "r") as f:
             targets = json.load(f)
         scene_gt, scene_gt_info = {}, {}
@@ -433,71 +452,73 @@ class Bop19Meter:
             for name, dst in (("scene_gt.json", scene_gt), ("scene_gt_info.json", scene_gt_info)):
                 with open(os.path.join(split_dir, f"{s:06d}", name), "r") as f:
                     dst[s] = {int(k): v for k, v in json.load(f).items()}
-        return cls(errors, targets, scene_gt, scene_gt_info, im_width, depth_loader=depth_loader, vsd_delta=vsd_delta)
+        return cls(errors, targets, scene_gt, scene_gt_info, *args, **kw)
 
     def add(self, scene_id, im_id, obj_id, score, T_est, K):
         """One line of the results file: pose [3|4,4] object to camera in mm, the image's camera matrix."""
         T = np.asarray(T_est, np.float64).reshape(-1, 4)[:3, :]
         self.ests.setdefault((int(scene_id), int(im_id), int(obj_id)), []).append({"score": score, "T": T, "K": np.asarray(K, np.float64).reshape(3, 3)})
 
-    def error_table(self):
-        """eval_calc_errors.py:196-325 for both error types: ``{scene: {im: {obj: [{"est_id", "score", "errors": {gt_id: (mssd, mspd)}}]}}}``, raw errors
-        (mm, px).  MSSD of a pair whose centres lie a diameter or more apart is inf without a device call."""
-        table, pairs = {}, []
+    def _walk(self, n_top):
+        """Scene -> image -> object of the targets, in the file's order, -> the kept estimates by descending score (eval_calc_errors.py:232-262: ``n_top``
+        k, 0 = all, -1 = the target's inst_count): yields ``(scene, im, obj, est_id, est, [(gt_id, T_gt [3,4])])`` with the ground truths of that object in
+        the image, in their order.  Counts the kept estimates into ``n_estimates``."""
         self.n_estimates = 0
         for s, ims in self.targets.items():
             for im, objs in ims.items():
                 for o, inst_count in objs.items():
-                    kept = top_estimates(self.ests.get((s, im, o), []), inst_count)
+                    kept = top_estimates(self.ests.get((s, im, o), []), None if n_top == 0 else inst_count if n_top == -1 else n_top)
                     self.n_estimates += len(kept)
-                    diameter = self.errors.models_info[o]["diameter"]
+                    gts = [(g, np.hstack((np.reshape(gt["cam_R_m2c"], (3, 3)), np.reshape(gt["cam_t_m2c"], (3, 1)))).astype(np.float64))
+                           for g, gt in enumerate(self.scene_gt[s][im]) if kept and gt["obj_id"] == o]
                     for est_id, est in kept:
-                        row = {"est_id": est_id, "score": est["score"], "errors": {}}
-                        table.setdefault(s, {}).setdefault(im, {}).setdefault(o, []).append(row)
-                        for gt_id, gt in enumerate(self.scene_gt[s][im]):
-                            if gt["obj_id"] != o:
-                                continue
-                            Tg = np.hstack((np.reshape(gt["cam_R_m2c"], (3, 3)), np.reshape(gt["cam_t_m2c"], (3, 1)))).astype(np.float64)
-                            overlap = np.linalg.norm(est["T"][:, 3] - Tg[:, 3]) < diameter
-                            pairs.append((row, gt_id, o, est["T"], Tg, est["K"], bool(overlap)))
+                        yield s, im, o, est_id, est, gts
+
+
+class Bop19Meter(_Meter):
+    """Collects pose estimates and turns them into the MSSD and MSPD recalls of eval_bop19.py.  Its own: ONE ``errors.errors`` call that serves both MSSD
+    and MSPD, and the ten thresholds.  ``errors``: a BopErrors (or anything with ``.errors(obj_ids, T_est, T_gt, K)``, ``.models_info`` and
+    ``.max_sym_disc_step``); ``targets``, ``scene_gt``, ``scene_gt_info``: as for _Meter; ``im_width``: width of the split's images in pixels."""
+
+    def __init__(self, errors, targets, scene_gt, scene_gt_info, im_width, depth_loader=None, vsd_delta=15):
+        """``depth_loader(scene_id, im_id)`` -> float32 [H,W] depth in mm (BopDataset.read_depth): with it ``result()`` also carries VSD (``errors`` then
+        needs ``.vsd``, a BopErrors over a mesh database with faces) and the mean of the three terms; without it nothing changes."""
+        super().__init__(errors, targets, scene_gt, scene_gt_info)
+        self.depth_loader, self.vsd_delta = depth_loader, vsd_delta
+        self.im_width = float(im_width)
+
+    def _table(self, gated):
+        """The walk as the nested table of both error types: ``(table, pairs, where)`` with ``where[k] = (row, gt_id)`` of ``pairs[k]``.  ``gated(est, Tg,
+        diameter)``: None to send the pair to the device, else the value a shortcut gives it at once."""
+        table, pairs, where = {}, [], []
+        for s, im, o, est_id, est, gts in self._walk(-1):
+            row = {"est_id": est_id, "score": est["score"], "errors": {}}
+            table.setdefault(s, {}).setdefault(im, {}).setdefault(o, []).append(row)
+            for gt_id, Tg in gts:
+                value = gated(est, Tg, self.errors.models_info[o]["diameter"])
+                if value is None:
+                    pairs.append((s, im, o, est["T"], Tg, est["K"]))
+                    where.append((row, gt_id))
+                else:
+                    row["errors"][gt_id] = value
+        return table, pairs, where
+
+    def error_table(self):
+        """eval_calc_errors.py:196-325 for both error types: ``{scene: {im: {obj: [{"est_id", "score", "errors": {gt_id: (mssd, mspd)}}]}}}``, raw errors
+        (mm, px).  MSSD of a pair whose centres lie a diameter or more apart is inf without a device call (MSPD has no shortcut: every pair is sent)."""
+        table, pairs, where = self._table(lambda est, Tg, diameter: None)
         if pairs:
-            mssd, mspd = self.errors.errors([p[2] for p in pairs], np.stack([p[3] for p in pairs]), np.stack([p[4] for p in pairs]),
-                                            np.stack([p[5] for p in pairs]))
-            for (row, gt_id, _, _, _, _, overlap), e3, e2 in zip(pairs, mssd.tolist(), mspd.tolist()):
-                row["errors"][gt_id] = (e3 if overlap else float("inf"), e2)
+            mssd, mspd = self.errors.errors(*_stacked(pairs))
+            for (row, gt_id), p, e3, e2 in zip(where, pairs, mssd.tolist(), mspd.tolist()):
+                row["errors"][gt_id] = (e3 if centres_within(self.errors.models_info[p[2]]["diameter"], p[3], p[4]) else float("inf"), e2)
         return table
 
     def vsd_table(self, taus=VSD_TAUS):
         """eval_calc_errors.py:196-325 for the error type ``vsd``: the table of error_table with ``errors: {gt_id: [e per tau]}`` (already normalised by the
         diameter inside the error).  A pair whose sphere projections do not overlap gets 1.0 for every tau without a device call (:295-312)."""
-        table, pairs, images, slot = {}, [], [], {}
-        for s, ims in self.targets.items():
-            for im, objs in ims.items():
-                for o, inst_count in objs.items():
-                    radius = 0.5 * self.errors.models_info[o]["diameter"]
-                    for est_id, est in top_estimates(self.ests.get((s, im, o), []), inst_count):
-                        row = {"est_id": est_id, "score": est["score"], "errors": {}}
-                        table.setdefault(s, {}).setdefault(im, {}).setdefault(o, []).append(row)
-                        for gt_id, gt in enumerate(self.scene_gt[s][im]):
-                            if gt["obj_id"] != o:
-                                continue
-                            Tg = np.hstack((np.reshape(gt["cam_R_m2c"], (3, 3)), np.reshape(gt["cam_t_m2c"], (3, 1)))).astype(np.float64)
-                            if not overlapping_sphere_projections(radius, est["T"][:, 3], Tg[:, 3]):
-                                row["errors"][gt_id] = [1.0] * len(taus)
-                                continue
-                            if (s, im) not in slot:
-                                slot[(s, im)] = len(images)
-                                images.append((s, im))
-                            pairs.append((row, gt_id, o, est["T"], Tg, est["K"], slot[(s, im)]))
-        # device calls over runs of pairs that share few images: the pairs come image by image, so a run of VSD_PAIRS_PER_CALL names a handful
-        for b in range(0, len(pairs), VSD_PAIRS_PER_CALL):
-            run = pairs[b:b + VSD_PAIRS_PER_CALL]
-            used = sorted({p[6] for p in run})
-            depth = [np.asarray(self.depth_loader(*images[i]), np.float32) for i in used]
-            errs = self.errors.vsd([p[2] for p in run], np.stack([p[3] for p in run]), np.stack([p[4] for p in run]), np.stack([p[5] for p in run]),
-                                   depth, [used.index(p[6]) for p in run], delta=self.vsd_delta, taus=taus, normalized=True)
-            for (row, gt_id, *_), e in zip(run, np.asarray(errs).tolist()):
-                row["errors"][gt_id] = e
+        table, pairs, where = self._table(lambda est, Tg, diameter: None if projections_overlap(diameter, est["T"], Tg) else [1.0] * len(taus))
+        for (row, gt_id), e in zip(where, vsd_runs(self.errors, self.depth_loader, pairs, delta=self.vsd_delta, taus=taus, normalized=True)):
+            row["errors"][gt_id] = e
         return table
 
     def normalised(self, table):
@@ -577,7 +598,7 @@ def score_signature(correct_th, visib_gt_min):
 def match_poses_elements(errs, error_ths, max_ests_count=0, gt_valid=None):
     """pose_matching.match_poses (pose_matching.py:9-90) for an error of any number of elements: by descending score, each estimate takes the valid,
     unmatched ground truth that beats the best so far in ALL elements, the thresholds being the first best.  ``errs``: ``[{"est_id", "score", "errors":
-    {gt_id: [e, ...]}}]``.  Returns ``[{"est_id", "gt_id", "score", "error", "error_norm"}]``."""
+    {gt_id: [e, ...]}}]``.  Returns ``[{"est_id", "gt_id", "score", "error", "error_norm"}]``.  The one place the greedy rule is written."""
     errs_sorted = sorted(errs, key=lambda e: e["score"], reverse=True)
     if max_ests_count > 0:
         errs_sorted = errs_sorted[:max_ests_count]
@@ -622,9 +643,10 @@ def localization_scores(scene_ids, obj_ids, matches, n_top):
             "gt_count": len(matches), "targets_count": int(tars), "tp_count": int(tps)}
 
 
-class LocalizationMeter:
+class LocalizationMeter(_Meter):
     """eval_calc_errors.py:192-388 and eval_calc_scores.py:184-269 for ONE error type, in process: collects pose estimates and returns the dictionary of
-    score.calc_localization_scores.  It stands beside Bop19Meter and does not replace it.
+    score.calc_localization_scores.  It shares with Bop19Meter the collection of estimates, the reading of a dataset tree, the pair walk with its top-n
+    cut, the two shortcut gates, the VSD runs and the greedy matching rule; its own are the choice of one error type and the scripts' records and scores.
 
     ``errors``: a BopErrors, or anything with ``.models_info`` and the calls the error type needs -- ``.vsd`` (vsd), ``.errors`` (mssd, mspd),
     ``.point_errors`` (ad, add, adi, proj), ``.mask_errors`` (cus); re / te / rete are formed here.  ``targets``, ``scene_gt``, ``scene_gt_info``: as for
@@ -647,7 +669,8 @@ class LocalizationMeter:
                  obj_ids=None):
         if error_type not in ERROR_TYPES:
             raise ValueError(f"LocalizationMeter: unknown error type {error_type!r}; known: {ERROR_TYPES}")
-        self.errors, self.error_type, self.n_top, self.visib_gt_min = errors, error_type, int(n_top), float(visib_gt_min)
+        super().__init__(errors, targets, scene_gt, scene_gt_info)
+        self.error_type, self.n_top, self.visib_gt_min = error_type, int(n_top), float(visib_gt_min)
         self.correct_th = [float(t) for t in (CORRECT_TH[error_type] if correct_th is None else correct_th)]
         n_el = 2 if error_type == "rete" else 1
         if len(self.correct_th) != n_el:
@@ -659,32 +682,12 @@ class LocalizationMeter:
             raise ValueError("LocalizationMeter: vsd needs a depth_loader(scene_id, im_id)")
         if error_type == "cus" and im_hw is None:
             raise ValueError("LocalizationMeter: cus needs im_hw = (H, W)")
-        self.scene_gt, self.scene_gt_info = scene_gt, scene_gt_info
-        self.targets = {}                                         # scene -> image -> obj -> inst_count, in the file's order
-        for t in targets:
-            self.targets.setdefault(t["scene_id"], {}).setdefault(t["im_id"], {})[t["obj_id"]] = t["inst_count"]
         self.scene_ids = sorted(self.targets) if scene_ids is None else [int(s) for s in scene_ids]
         self.obj_ids = sorted(int(o) for o in errors.models_info) if obj_ids is None else [int(o) for o in obj_ids]
-        self.ests = {}                                            # (scene, image, obj) -> [{"score", "T", "K"}]
-        self.n_estimates = 0
         self._records = None
 
-    @classmethod
-    def from_dataset_tree(cls, errors, split_dir, targets_filename, **kw):
-        """Targets file + the ``scene_gt.json`` / ``scene_gt_info.json`` of every scene it names, read unfiltered; ``kw`` as for the constructor."""
-        with open(targets_filename, "r") as f:
-            targets = json.load(f)
-        scene_gt, scene_gt_info = {}, {}
-        for s in sorted({t["scene_id"] for t in targets}):
-            for name, dst in (("scene_gt.json", scene_gt), ("scene_gt_info.json", scene_gt_info)):
-                with open(os.path.join(split_dir, f"{s:06d}", name), "r") as f:
-                    dst[s] = {int(k): v for k, v in json.load(f).items()}
-        return cls(errors, targets, scene_gt, scene_gt_info, **kw)
-
     def add(self, scene_id, im_id, obj_id, score, T_est, K):
-        """One line of the results file: pose [3|4,4] object to camera in mm, the image's camera matrix."""
-        T = np.asarray(T_est, np.float64).reshape(-1, 4)[:3, :]
-        self.ests.setdefault((int(scene_id), int(im_id), int(obj_id)), []).append({"score": score, "T": T, "K": np.asarray(K, np.float64).reshape(3, 3)})
+        super().add(scene_id, im_id, obj_id, score, T_est, K)
         self._records = None
 
     # -- eval_calc_errors.py ---------------------------------------------------------------------------------
@@ -693,22 +696,9 @@ class LocalizationMeter:
         et = self.error_type
         if not pairs:
             return []
-        objs, Te, Tg, K = [p[2] for p in pairs], np.stack([p[3] for p in pairs]), np.stack([p[4] for p in pairs]), np.stack([p[5] for p in pairs])
         if et == "vsd":
-            out, images, slot = [], [], {}
-            for p in pairs:
-                if (p[0], p[1]) not in slot:
-                    slot[(p[0], p[1])] = len(images)
-                    images.append((p[0], p[1]))
-            sl = [slot[(p[0], p[1])] for p in pairs]
-            for b in range(0, len(pairs), VSD_PAIRS_PER_CALL):              # the pairs come image by image: a run names a handful of images
-                run = slice(b, b + VSD_PAIRS_PER_CALL)
-                used = sorted(set(sl[run]))
-                depth = [np.asarray(self.depth_loader(*images[i]), np.float32) for i in used]
-                e = self.errors.vsd(objs[run], Te[run], Tg[run], K[run], depth, [used.index(i) for i in sl[run]], delta=self.vsd_delta, taus=self.vsd_taus,
-                                    normalized=self.vsd_normalized_by_diameter)
-                out += np.asarray(e).tolist()
-            return out
+            return vsd_runs(self.errors, self.depth_loader, pairs, delta=self.vsd_delta, taus=self.vsd_taus, normalized=self.vsd_normalized_by_diameter)
+        objs, Te, Tg, K = _stacked(pairs)
         if et in ("mssd", "mspd"):
             mssd, mspd = self.errors.errors(objs, Te, Tg, K)
             return [[e] for e in (mssd if et == "mssd" else mspd).tolist()]
@@ -736,31 +726,19 @@ class LocalizationMeter:
         ``scene_errs`` before it saves (vsd: one element per tau).  Computed once per set of estimates."""
         if self._records is not None:
             return self._records
-        et, records, pairs, where = self.error_type, {}, [], []
-        self.n_estimates = 0
-        for s, ims in self.targets.items():
-            records[s] = []
-            for im, objs in ims.items():
-                for o, inst_count in objs.items():
-                    n_top_curr = None if self.n_top == 0 else inst_count if self.n_top == -1 else self.n_top
-                    kept = sorted(enumerate(self.ests.get((s, im, o), [])), key=lambda x: x[1]["score"], reverse=True)[slice(0, n_top_curr)]
-                    self.n_estimates += len(kept)
-                    diameter = self.errors.models_info[o]["diameter"] if et in ("vsd", "cus", "ad", "add", "adi", "mssd") else None
-                    for est_id, est in kept:
-                        row = {"im_id": im, "obj_id": o, "est_id": est_id, "score": est["score"], "errors": {}}
-                        records[s].append(row)
-                        for gt_id, gt in enumerate(self.scene_gt[s][im]):
-                            if gt["obj_id"] != o:
-                                continue
-                            Tg = np.hstack((np.reshape(gt["cam_R_m2c"], (3, 3)), np.reshape(gt["cam_t_m2c"], (3, 1)))).astype(np.float64)
-                            if et in ("vsd", "cus") and not overlapping_sphere_projections(0.5 * diameter, est["T"][:, 3], Tg[:, 3]):
-                                row["errors"][gt_id] = [1.0] * (len(self.vsd_taus) if et == "vsd" else 1)
-                            elif et in ("ad", "add", "adi", "mssd") and not np.linalg.norm(est["T"][:, 3] - Tg[:, 3]) < diameter:
-                                row["errors"][gt_id] = [float("inf")]
-                            else:
-                                row["errors"][gt_id] = None                 # keeps the ground truths in their order
-                                pairs.append((s, im, o, est["T"], Tg, est["K"]))
-                                where.append((row, gt_id))
+        et, records, pairs, where = self.error_type, {s: [] for s in self.targets}, [], []
+        for s, im, o, est_id, est, gts in self._walk(self.n_top):
+            row = {"im_id": im, "obj_id": o, "est_id": est_id, "score": est["score"], "errors": {}}
+            records[s].append(row)
+            for gt_id, Tg in gts:
+                if et in ("vsd", "cus") and not projections_overlap(self.errors.models_info[o]["diameter"], est["T"], Tg):
+                    row["errors"][gt_id] = [1.0] * (len(self.vsd_taus) if et == "vsd" else 1)
+                elif et in ("ad", "add", "adi", "mssd") and not centres_within(self.errors.models_info[o]["diameter"], est["T"], Tg):
+                    row["errors"][gt_id] = [float("inf")]
+                else:
+                    row["errors"][gt_id] = None                 # keeps the ground truths in their order
+                    pairs.append((s, im, o, est["T"], Tg, est["K"]))
+                    where.append((row, gt_id))
         for (row, gt_id), e in zip(where, self._device_errors(pairs)):
             row["errors"][gt_id] = e
         self._records = records

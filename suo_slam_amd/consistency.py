@@ -13,6 +13,7 @@ from __future__ import annotations
 import numpy as np
 
 from . import _lib
+from .bop_eval import pack_poses, stage_pairs
 
 # Quantiles of the chi2 distribution (0.95, 0.99): six degrees of freedom for a pose (standard tables: 12.5916, 16.8119), two for a keypoint (-2 ln 0.05 = 5.9915;
 # -2 ln 0.01 = 9.2103, kept as the reference's own literal 9.210, plot_cov.py:145).
@@ -20,22 +21,14 @@ CHI2_6_95, CHI2_6_99 = 12.5916, 16.8119
 CHI2_2_95, CHI2_2_99 = 5.9915, 9.210
 
 
-def _pack34(T, n):
-    if hasattr(T, "detach"):
-        T = T.detach().cpu().numpy()
-    return np.ascontiguousarray(np.asarray(T, np.float64).reshape(n, -1, 4)[:, :3, :]).reshape(n, 12)
-
-
 def pose_nees(errors, obj_ids, T_est, T_gt, cov):
     """n (object, estimated pose, ground-truth pose, 6x6 covariance) items; poses [n,3|4,4], cov [n,6,6] with rows / columns [omega, upsilon] of the left update
     (ba.pose_covariances, collect_results(covariances=True)["cov_OtoC"]), all lengths in the unit of the mesh database.
     Returns ``{"nees" [n], "xi" [n,6], "sym_index" [n] (-1: a non-finite pose), "T_ref" [n,3,4], "n_nan"}``."""
-    n = len(obj_ids)
+    n, idx, _, Te, Tg = stage_pairs(errors._index, obj_ids, None, T_est, T_gt)
     nees, xi, sym, T_ref = np.zeros(n), np.zeros((n, 6)), np.zeros(n, np.int32), np.zeros((n, 3, 4))
     status = np.zeros(1, np.int32)
     if n:
-        idx = np.array([errors._index[int(o)] for o in obj_ids], np.int32)
-        Te, Tg = _pack34(T_est, n), _pack34(T_gt, n)
         cv = np.ascontiguousarray(np.asarray(cov, np.float64).reshape(n, 36))
         _lib.check(errors.lib.suo_pose_nees(errors._h, n, idx.ctypes.data, Te.ctypes.data, Tg.ctypes.data, cv.ctypes.data, nees.ctypes.data, xi.ctypes.data,
                                             sym.ctypes.data, T_ref.ctypes.data, status.ctypes.data), "suo_pose_nees")
@@ -47,7 +40,7 @@ def keypoint_nees(errors, dets, T_ref):
     view_chain.py both fill them) at the poses T_ref [n,3|4,4].  A detection with ``cov_pred is None`` is skipped and counted.
     Returns ``{"chi2": [array [k] or None per detection], "err": [array [k,2] or None], "n_skipped"}``."""
     n = len(dets)
-    T = _pack34(T_ref, n) if n else np.zeros((0, 12))
+    T = pack_poses(T_ref, n)
     use = [i for i, d in enumerate(dets) if d.get("cov_pred") is not None]
     chi2, err = [None] * n, [None] * n
     if use:

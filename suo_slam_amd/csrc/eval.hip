@@ -135,15 +135,47 @@ __global__ __launch_bounds__(EV_BLOCK) void eval_finalize_kernel(EvalArgs a) {
     }
 }
 
-int ensure_scratch(MeshDb* db, size_t bytes) {
-    if (bytes <= db->scratch_cap) return SUO_OK;
-    size_t ncap = (std::max(bytes, db->scratch_cap * 2) + 4095) & ~(size_t)4095;
-    if (db->scratch_dev) (void)hipFree(db->scratch_dev);
-    if (db->scratch_host) (void)hipHostFree(db->scratch_host);
-    db->scratch_dev = nullptr; db->scratch_host = nullptr; db->scratch_cap = 0;
-    SUO_HIP_CHECK(hipMalloc((void**)&db->scratch_dev, ncap));
-    SUO_HIP_CHECK(hipHostMalloc((void**)&db->scratch_host, ncap, hipHostMallocDefault));
-    db->scratch_cap = ncap;
+int grow_buffer(char** dev, char** host, size_t* cap, size_t bytes) {
+    if (bytes <= *cap) return SUO_OK;
+    const size_t ncap = (std::max(bytes, *cap * 2) + 4095) & ~(size_t)4095;
+    if (*dev) (void)hipFree(*dev);
+    if (host && *host) (void)hipHostFree(*host);
+    *dev = nullptr; *cap = 0;
+    if (host) *host = nullptr;
+    SUO_HIP_CHECK(hipMalloc((void**)dev, ncap));
+    if (host) SUO_HIP_CHECK(hipHostMalloc((void**)host, ncap, hipHostMallocDefault));
+    *cap = ncap;
+    return SUO_OK;
+}
+
+int ensure_scratch(MeshDb* db, size_t bytes) { return grow_buffer(&db->scratch_dev, &db->scratch_host, &db->scratch_cap, bytes); }
+
+int check_model_index(const char* who, const MeshDb* db, int n, const int* model_index, int* pmax) {
+    int most = 0;
+    for (int i = 0; i < n; ++i) {
+        const int m = model_index[i];
+        if (m < 0 || m >= db->n_models) { suo_set_error("%s: model_index[%d]=%d out of range", who, i, m); return SUO_ERR_ARG; }
+        most = std::max(most, db->off[m + 1] - db->off[m]);
+    }
+    if (pmax) *pmax = most;
+    return SUO_OK;
+}
+
+int stage_pairs_locked(MeshDb* db, int n, const int* model_index, const double* T_est, const double* T_gt, const double* K, size_t total_bytes, PairBlock* out) {
+    // staged block: Te[n][12] | Tg[n][12] | K[n][9] | model[n]; what lies behind it, up to total_bytes, is the caller's
+    const size_t o_te = 0, o_tg = (size_t)n * 96, o_k = o_tg + (size_t)n * 96, o_model = o_k + (size_t)n * 72;
+    int rc;
+    if ((rc = ensure_scratch(db, total_bytes))) return rc;
+    memcpy(db->scratch_host + o_te, T_est, (size_t)n * 96);
+    memcpy(db->scratch_host + o_tg, T_gt, (size_t)n * 96);
+    double* Kh = (double*)(db->scratch_host + o_k);
+    if (K) memcpy(Kh, K, (size_t)n * 72);
+    else for (int i = 0; i < n; ++i) for (int e = 0; e < 9; ++e) Kh[(size_t)i * 9 + e] = e % 4 == 0 ? 1.0 : 0.0;      // no projection asked for: any camera does
+    memcpy(db->scratch_host + o_model, model_index, (size_t)n * 4);
+    out->staged = pair_block_bytes(n);
+    SUO_HIP_CHECK(hipMemcpyAsync(db->scratch_dev, db->scratch_host, out->staged, hipMemcpyHostToDevice, db->stream));
+    out->Te = (const double*)(db->scratch_dev + o_te); out->Tg = (const double*)(db->scratch_dev + o_tg); out->K = (const double*)(db->scratch_dev + o_k);
+    out->model = (const int*)(db->scratch_dev + o_model);
     return SUO_OK;
 }
 
@@ -200,18 +232,14 @@ extern "C" int suo_pose_errors(void* h, int n, const int* model_index, const flo
     MeshDb* db = (MeshDb*)h;
     if (!db || n < 0 || (n > 0 && (!model_index || !T_pred || !T_gt || !add || !adds))) { suo_set_error("suo_pose_errors: bad argument"); return SUO_ERR_ARG; }
     if (n == 0) return SUO_OK;
-    int pmax = 0;
-    for (int i = 0; i < n; ++i) {
-        if (model_index[i] < 0 || model_index[i] >= db->n_models) { suo_set_error("suo_pose_errors: model_index[%d]=%d out of range", i, model_index[i]); return SUO_ERR_ARG; }
-        pmax = std::max(pmax, db->off[model_index[i] + 1] - db->off[model_index[i]]);
-    }
+    int pmax = 0, rc;
+    if ((rc = check_model_index("suo_pose_errors", db, n, model_index, &pmax))) return rc;
     std::lock_guard<std::mutex> lk(db->mu);
     const int stride = (pmax + 63) & ~63;
     // staged block: model[n] | Tp[n][12] | Tg[n][12]   then device-only: mind2[n][stride] | out[n][2]
     const size_t o_model = 0, o_tp = (n * sizeof(int) + 15) & ~(size_t)15, o_tg = o_tp + (size_t)n * 48, staged = o_tg + (size_t)n * 48;
     const size_t o_out = staged, o_min = (o_out + (size_t)n * 8 + 255) & ~(size_t)255, total = o_min + (size_t)n * stride * 4;
-    int rc = ensure_scratch(db, total);
-    if (rc) return rc;
+    if ((rc = ensure_scratch(db, total))) return rc;
     memcpy(db->scratch_host + o_model, model_index, n * sizeof(int));
     memcpy(db->scratch_host + o_tp, T_pred, (size_t)n * 48);
     memcpy(db->scratch_host + o_tg, T_gt, (size_t)n * 48);

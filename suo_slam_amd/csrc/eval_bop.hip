@@ -197,25 +197,16 @@ int bop_maxima_enqueue_locked(MeshDb* db, const char* who, int n, const int* mod
         pmax = std::max(pmax, db->off[mi + 1] - db->off[mi]);
         smax = std::max(smax, db->sym_off[mi + 1] - db->sym_off[mi]);
     }
-    // staged block: Te[n][12] | Tg[n][12] | K[n][9] | model[n]   then device-only: out[n][2] | flags[n] | smax[n][stride][2]
-    const size_t o_te = 0, o_tg = (size_t)n * 96, o_k = o_tg + (size_t)n * 96, o_model = o_k + (size_t)n * 72, staged = (o_model + (size_t)n * 4 + 15) & ~(size_t)15;
-    const size_t o_out = staged, o_flags = o_out + (size_t)n * 16, o_smax = (o_flags + (size_t)n * 4 + 255) & ~(size_t)255;
+    // the staged pair block (stage_pairs_locked; K == NULL: MSPD not asked for)   then device-only: out[n][2] | flags[n] | smax[n][stride][2]
+    const size_t o_out = pair_block_bytes(n), o_flags = o_out + (size_t)n * 16, o_smax = (o_flags + (size_t)n * 4 + 255) & ~(size_t)255;
     const size_t end = o_smax + (size_t)n * smax * 16;
     const size_t o_extra = extra ? (end + 255) & ~(size_t)255 : end;
-    const size_t total = o_extra + extra;
-    if ((rc = ensure_scratch(db, total))) return rc;
-    memcpy(db->scratch_host + o_te, T_est, (size_t)n * 96);
-    memcpy(db->scratch_host + o_tg, T_gt, (size_t)n * 96);
-    double* Kh = (double*)(db->scratch_host + o_k);
-    if (K) memcpy(Kh, K, (size_t)n * 72);
-    else for (int i = 0; i < n; ++i) for (int e = 0; e < 9; ++e) Kh[(size_t)i * 9 + e] = e % 4 == 0 ? 1.0 : 0.0;      // MSPD not asked for: any camera does
-    memcpy(db->scratch_host + o_model, model_index, (size_t)n * 4);
-    SUO_HIP_CHECK(hipMemcpyAsync(db->scratch_dev, db->scratch_host, staged, hipMemcpyHostToDevice, db->stream));
+    PairBlock B;
+    if ((rc = stage_pairs_locked(db, n, model_index, T_est, T_gt, K, o_extra + extra, &B))) return rc;
     SUO_HIP_CHECK(hipMemsetAsync(db->scratch_dev + o_flags, 0, end - o_flags, db->stream));                             // +0.0: the identity of max over d^2 >= 0
     BopArgs a;
     a.pts = db->pts_dev; a.off = db->off_dev; a.sym = db->sym_dev; a.soff = db->sym_off_dev;
-    a.Te = (const double*)(db->scratch_dev + o_te); a.Tg = (const double*)(db->scratch_dev + o_tg); a.K = (const double*)(db->scratch_dev + o_k);
-    a.model = (const int*)(db->scratch_dev + o_model);
+    a.Te = B.Te; a.Tg = B.Tg; a.K = B.K; a.model = B.model;
     a.out = (double*)(db->scratch_dev + o_out); a.flags = (unsigned*)(db->scratch_dev + o_flags); a.smax = (unsigned long long*)(db->scratch_dev + o_smax);
     a.stride = smax;
     // symmetry chunks: as many as bring the grid to BE_WG_TARGET workgroups, of 4..BE_SCH symmetries each (below 4 a workgroup's set-up of its points outweighs its loop)
@@ -237,11 +228,10 @@ extern "C" int suo_pose_errors_bop(void* h, int n, const int* model_index, const
     MeshDb* db = (MeshDb*)h;
     if (!db || n < 0 || (n > 0 && (!model_index || !T_est || !T_gt || (mspd && !K)))) { suo_set_error("suo_pose_errors_bop: bad argument"); return SUO_ERR_ARG; }
     if (n == 0) return SUO_OK;
-    for (int i = 0; i < n; ++i)
-        if (model_index[i] < 0 || model_index[i] >= db->n_models) { suo_set_error("suo_pose_errors_bop: model_index[%d]=%d out of range", i, model_index[i]); return SUO_ERR_ARG; }
+    int rc;
+    if ((rc = check_model_index("suo_pose_errors_bop", db, n, model_index, nullptr))) return rc;
     if (!mssd && !mspd) return SUO_OK;
     std::lock_guard<std::mutex> lk(db->mu);
-    int rc;
     BopLayout L;
     if ((rc = bop_maxima_enqueue_locked(db, "suo_pose_errors_bop", n, model_index, T_est, T_gt, K, 0, &L))) return rc;
     const size_t o_out = L.o_out, o_flags = L.o_flags;

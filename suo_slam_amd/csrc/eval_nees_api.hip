@@ -19,15 +19,14 @@ extern "C" int suo_pose_nees(void* h, int n, const int* model_index, const doubl
     for (int i = 0; i < n; ++i)
         if (model_index[i] < 0) { suo_set_error("suo_pose_nees: model_index[%d]=%d out of range", i, model_index[i]); return SUO_ERR_ARG; }
     if (!db) { suo_set_error("suo_pose_nees: null mesh database"); return SUO_ERR_ARG; }
-    for (int i = 0; i < n; ++i)
-        if (model_index[i] >= db->n_models) { suo_set_error("suo_pose_nees: model_index[%d]=%d out of range", i, model_index[i]); return SUO_ERR_ARG; }
+    int rc;
+    if ((rc = check_model_index("suo_pose_nees", db, n, model_index, nullptr))) return rc;
     if (status) status[0] = 0;
     if (n == 0) return SUO_OK;
     std::lock_guard<std::mutex> lk(db->mu);
     // the caller's part of the scratch: cov[n][36] (staged) | nees[n] | xi[n][6] | T_ref[n][12] | sym_index[n]
     const size_t o_cov = 0, o_nees = (size_t)n * 288, o_xi = o_nees + (size_t)n * 8, o_tref = o_xi + (size_t)n * 48, o_sym = o_tref + (size_t)n * 96, extra = o_sym + (size_t)n * 4;
     BopLayout L;
-    int rc;
     if ((rc = bop_maxima_enqueue_locked(db, "suo_pose_nees", n, model_index, T_est, T_gt, nullptr, extra, &L))) return rc;
     char* xh = db->scratch_host + L.o_extra;
     char* xd = db->scratch_dev + L.o_extra;

@@ -165,29 +165,17 @@ extern "C" int suo_pose_errors_points(void* h, int n, const int* model_index, co
         return SUO_ERR_ARG;
     }
     if (n == 0 || !which) return SUO_OK;
-    int pmax = 0;
-    for (int i = 0; i < n; ++i) {
-        if (model_index[i] < 0 || model_index[i] >= db->n_models) { suo_set_error("suo_pose_errors_points: model_index[%d]=%d out of range", i, model_index[i]); return SUO_ERR_ARG; }
-        pmax = std::max(pmax, db->off[model_index[i] + 1] - db->off[model_index[i]]);
-    }
+    int pmax = 0, rc;
+    if ((rc = check_model_index("suo_pose_errors_points", db, n, model_index, &pmax))) return rc;
     std::lock_guard<std::mutex> lk(db->mu);
     const int stride = w_adi ? (pmax + 63) & ~63 : 0;
-    // staged block: Te[n][12] | Tg[n][12] | K[n][9] | model[n]   then device-only: out[n][3] | mind2[n][stride]
-    const size_t o_te = 0, o_tg = (size_t)n * 96, o_k = o_tg + (size_t)n * 96, o_model = o_k + (size_t)n * 72, staged = (o_model + (size_t)n * 4 + 15) & ~(size_t)15;
-    const size_t o_out = staged, o_min = (o_out + (size_t)n * 24 + 255) & ~(size_t)255, total = o_min + (size_t)n * stride * 8;
-    int rc;
-    if ((rc = ensure_scratch(db, total))) return rc;
-    memcpy(db->scratch_host + o_te, T_est, (size_t)n * 96);
-    memcpy(db->scratch_host + o_tg, T_gt, (size_t)n * 96);
-    double* Kh = (double*)(db->scratch_host + o_k);
-    if (K) memcpy(Kh, K, (size_t)n * 72);
-    else for (int i = 0; i < n; ++i) for (int e = 0; e < 9; ++e) Kh[(size_t)i * 9 + e] = e % 4 == 0 ? 1.0 : 0.0;        // PROJ not asked for: any camera does
-    memcpy(db->scratch_host + o_model, model_index, (size_t)n * 4);
-    SUO_HIP_CHECK(hipMemcpyAsync(db->scratch_dev, db->scratch_host, staged, hipMemcpyHostToDevice, db->stream));
+    // the staged pair block (stage_pairs_locked; K == NULL: PROJ not asked for)   then device-only: out[n][3] | mind2[n][stride]
+    const size_t o_out = pair_block_bytes(n), o_min = (o_out + (size_t)n * 24 + 255) & ~(size_t)255, total = o_min + (size_t)n * stride * 8;
+    PairBlock B;
+    if ((rc = stage_pairs_locked(db, n, model_index, T_est, T_gt, K, total, &B))) return rc;
     PointsArgs a;
     a.pts = db->pts_dev; a.off = db->off_dev;
-    a.Te = (const double*)(db->scratch_dev + o_te); a.Tg = (const double*)(db->scratch_dev + o_tg); a.K = (const double*)(db->scratch_dev + o_k);
-    a.model = (const int*)(db->scratch_dev + o_model);
+    a.Te = B.Te; a.Tg = B.Tg; a.K = B.K; a.model = B.model;
     a.out = (double*)(db->scratch_dev + o_out); a.mind2 = (unsigned long long*)(db->scratch_dev + o_min);
     a.stride = stride; a.which = which; a.splits = 1;
     if (w_adi) {

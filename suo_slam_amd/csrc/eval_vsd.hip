@@ -131,12 +131,7 @@ static int vsd_run_locked(MeshDb* db, int n, int width, int height, const float*
     const size_t o_cnt = staged, total = o_cnt + (size_t)n * nc * 8, test_bytes = (size_t)n_images * hw * 4;
     int rc;
     if ((rc = ensure_scratch(db, total))) return rc;
-    if (test_bytes > db->test_cap) {
-        if (db->test_dev) (void)hipFree(db->test_dev);
-        db->test_dev = nullptr; db->test_cap = 0;
-        SUO_HIP_CHECK(hipMalloc((void**)&db->test_dev, test_bytes));
-        db->test_cap = test_bytes;
-    }
+    if ((rc = grow_buffer(&db->test_dev, nullptr, &db->test_cap, test_bytes))) return rc;
     memcpy(db->scratch_host + o_k, K, (size_t)n * 72);
     memcpy(db->scratch_host + o_tau, taus, (size_t)n_taus * 8);
     double* dh = (double*)(db->scratch_host + o_diam);
@@ -196,12 +191,7 @@ extern "C" int suo_vsd_from_depth(int n, int width, int height, const float* dep
     if (!db) { suo_set_error("suo_vsd_from_depth: no stream"); return SUO_ERR_HIP; }
     std::lock_guard<std::mutex> lk(db->mu);
     const size_t bytes = (size_t)n * height * width * sizeof(float);
-    if (2 * bytes > db->img_cap) {
-        if (db->img_dev) (void)hipFree(db->img_dev);
-        db->img_dev = nullptr; db->img_cap = 0;
-        SUO_HIP_CHECK(hipMalloc((void**)&db->img_dev, 2 * bytes));
-        db->img_cap = 2 * bytes;
-    }
+    if ((rc = grow_buffer(&db->img_dev, nullptr, &db->img_cap, 2 * bytes))) return rc;
     SUO_HIP_CHECK(hipMemcpyAsync(db->img_dev, depth_est, bytes, hipMemcpyHostToDevice, db->stream));
     SUO_HIP_CHECK(hipMemcpyAsync(db->img_dev + bytes, depth_gt, bytes, hipMemcpyHostToDevice, db->stream));
     std::vector<int> re(n), rg(n);

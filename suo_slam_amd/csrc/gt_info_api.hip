@@ -73,12 +73,7 @@ static int gt_info_run(const char* who, int mult, MeshDb* db, int n, const int* 
     if (mult == 1 && !mask && !mask_visib) return SUO_OK;
 
     const size_t test_bytes = (size_t)n_images * hw * 4;
-    if (test_bytes > db->test_cap) {
-        if (db->test_dev) (void)hipFree(db->test_dev);
-        db->test_dev = nullptr; db->test_cap = 0;
-        SUO_HIP_CHECK(hipMalloc((void**)&db->test_dev, test_bytes));
-        db->test_cap = test_bytes;
-    }
+    if ((rc = grow_buffer(&db->test_dev, nullptr, &db->test_cap, test_bytes))) return rc;
     SUO_HIP_CHECK(hipMemcpyAsync(db->test_dev, depth_test, test_bytes, hipMemcpyHostToDevice, db->stream));
     for (size_t c = 0; c + 1 < cut.size(); ++c) {
         const int b = cut[c], m = cut[c + 1] - cut[c];

@@ -1,5 +1,8 @@
-// The mesh database behind suo_mesh_db_create: shared by the ADD / ADD-S kernels (csrc/eval.hip, row N1) and the BOP-19
-// MSSD / MSPD kernels (csrc/eval_bop.hip, row N5).
+// The mesh database behind suo_mesh_db_create and what its entries share on the host.  Shared by the ADD / ADD-S kernels (csrc/eval.hip, row N1), the BOP-19
+// MSSD / MSPD kernels (csrc/eval_bop.hip, row N5) and the NEES entries over them (csrc/eval_nees_api.hip), the rasteriser and VSD (csrc/raster.hip,
+// csrc/eval_vsd.hip, row N6), ADD / ADI / PROJ and CUS (csrc/eval_points.hip, csrc/eval_masks.hip, row N4), gt_info (csrc/gt_info_api.hip, row N7) and
+// models_info (csrc/model_info_api.hip, row N8).  The database's buffers, their one growth rule, the range check of model_index and the staged block of a
+// call's pairs are declared here and defined once, in csrc/eval.hip.
 #pragma once
 #include <mutex>
 #include <vector>
@@ -32,7 +35,20 @@ struct MeshDb {
     std::mutex mu;
 };
 
-int ensure_scratch(MeshDb* db, size_t bytes);     // csrc/eval.hip
+// csrc/eval.hip.  What the entries over the database share before their kernels:
+// grow_buffer: a grow-only device buffer, with a pinned host twin when host is not null; a re-growth at least doubles, rounded up to 4 KB.  Every grow-only
+// buffer above goes through it; ensure_scratch is grow_buffer on the scratch pair.
+// check_model_index: SUO_ERR_ARG with "<who>: model_index[i]=m out of range" for the first index outside the database; *pmax (may be null) the most points
+// of a model named.
+// stage_pairs_locked: the staged block of a call's pairs -- both poses, the camera matrix and the model index of each, laid out where it is defined -- at
+// offset 0 of a scratch of total_bytes (>= pair_block_bytes(n), the block's 16-byte-aligned size; the rest is the caller's), K == NULL staged as the
+// identity, and its one upload enqueued on db->stream.  *out names the four arrays on the device.  Caller holds db->mu and has checked the arguments.
+struct PairBlock { const double* Te; const double* Tg; const double* K; const int* model; size_t staged; };
+inline size_t pair_block_bytes(int n) { return ((size_t)n * (96 + 96 + 72 + 4) + 15) & ~(size_t)15; }
+int grow_buffer(char** dev, char** host, size_t* cap, size_t bytes);
+int ensure_scratch(MeshDb* db, size_t bytes);
+int check_model_index(const char* who, const MeshDb* db, int n, const int* model_index, int* pmax);
+int stage_pairs_locked(MeshDb* db, int n, const int* model_index, const double* T_est, const double* T_gt, const double* K, size_t total_bytes, PairBlock* out);
 
 // csrc/eval_bop.hip.  The arguments of bop_errors_kernel / bop_errors_min_kernel.
 struct BopArgs {
@@ -61,9 +77,7 @@ int bop_maxima_enqueue_locked(MeshDb* db, const char* who, int n, const int* mod
 // float32 depth and *rbox_dev [n][4] the renders' clipped pixel boxes (x0, y0, x1, y1; x0 > x1: nothing drawn), both valid until the next render.
 // render_setup_locked: the first half of a render, shared with csrc/gt_info_api.hip -- stages the n renders and enqueues raster_setup_kernel; *args then
 // names the triangle records and the renders' pixel boxes on the device (args->out is left null: the tile pass and its epilogue are the caller's).
-// grow_buffer: a grow-only device buffer, with a pinned host twin when host is not null.
 struct RasterArgs;
-int grow_buffer(char** dev, char** host, size_t* cap, size_t bytes);
 int render_setup_locked(MeshDb* db, const char* who, int n, const int* model_index, const double* T, const double* K, int width, int height, RasterArgs* args);
 int check_render_args(const char* who, MeshDb* db, int n, const int* model_index, const double* T, const double* K, int width, int height);
 int render_depth_locked(MeshDb* db, int n, const int* model_index, const double* T, const double* K, int width, int height, float** img_dev, int** rbox_dev);

@@ -25,16 +25,11 @@ extern "C" int suo_model_info(void* h, int n, const int* model_index, double* in
     if (n < 0) { suo_set_error("suo_model_info: n = %d is negative", n); return SUO_ERR_ARG; }
     if (n == 0) return SUO_OK;
     if (!model_index || !info_out) { suo_set_error("suo_model_info: null model_index or info_out"); return SUO_ERR_ARG; }
-    int pmax = 0;
-    for (int i = 0; i < n; ++i) {
-        const int m = model_index[i];
-        if (m < 0 || m >= db->n_models) { suo_set_error("suo_model_info: model_index[%d]=%d out of range", i, m); return SUO_ERR_ARG; }
-        const int P = db->off[m + 1] - db->off[m];
-        if (P < 1) { suo_set_error("suo_model_info: model %d has no points", m); return SUO_ERR_ARG; }
-        pmax = std::max(pmax, P);
-    }
+    int pmax = 0, rc;
+    if ((rc = check_model_index("suo_model_info", db, n, model_index, &pmax))) return rc;
+    for (int i = 0; i < n; ++i)
+        if (db->off[model_index[i] + 1] - db->off[model_index[i]] < 1) { suo_set_error("suo_model_info: model %d has no points", model_index[i]); return SUO_ERR_ARG; }
     std::lock_guard<std::mutex> lk(db->mu);
-    int rc;
     // staged, in this order: first[n + 1] | dmax[n] | pairkey[n] | model[n] | flags[n] | box[n][6]   then, with the pair, written by the device: tmax[total]
     const size_t o_first = 0, o_dmax = o_first + (size_t)(n + 1) * 8, o_key = o_dmax + (size_t)n * 8, o_model = o_key + (size_t)n * 8, o_flags = o_model + (size_t)n * 4,
                  o_box = o_flags + (size_t)n * 4, staged = (o_box + (size_t)n * 24 + 15) & ~(size_t)15;

@@ -116,19 +116,6 @@ __global__ __launch_bounds__(RS_BLOCK) void raster_tile_kernel(RasterArgs a) {
     }
 }
 
-int grow_buffer(char** dev, char** host, size_t* cap, size_t bytes) {
-    if (bytes <= *cap) return SUO_OK;
-    const size_t ncap = (std::max(bytes, *cap * 2) + 4095) & ~(size_t)4095;
-    if (*dev) (void)hipFree(*dev);
-    if (host && *host) (void)hipHostFree(*host);
-    *dev = nullptr; *cap = 0;
-    if (host) *host = nullptr;
-    SUO_HIP_CHECK(hipMalloc((void**)dev, ncap));
-    if (host) SUO_HIP_CHECK(hipHostMalloc((void**)host, ncap, hipHostMallocDefault));
-    *cap = ncap;
-    return SUO_OK;
-}
-
 int check_render_args(const char* who, MeshDb* db, int n, const int* model_index, const double* T, const double* K, int width, int height) {
     if (!db || n < 0 || width < 1 || height < 1 || (n > 0 && (!model_index || !T || !K))) { suo_set_error("%s: bad argument", who); return SUO_ERR_ARG; }
     if (n > 65535 || (long long)width * height > (1LL << 28)) { suo_set_error("%s: %d renders of %d x %d exceed one call", who, n, width, height); return SUO_ERR_ARG; }
