@@ -90,6 +90,12 @@ int launch_conv3x3_wino_f16x2_fused_dma(const ConvArgs& a, hipStream_t s, int ti
 // Kernel and launcher: csrc/conv_wino_x3_skip_dma.hip.
 bool conv3x3_wino_f16x2_skip_dma() { return env_switch("SUO_WINO_SKIP_DMA", 1) != 0; }
 int launch_conv3x3_wino_f16x2_fused_up_skip_dma(const ConvArgs& a, hipStream_t s, int tiles);
+// The LDS-DMA form's tail with the next block's conv1 runs its 1x1 stages in ONE pass over the 128-pixel tile (the kernel's comment: ONEP): W3 and the next W1
+// are streamed once per tile, not once per 64-pixel pass.  SUO_WINO_TAIL_ONE_PASS=0 (supported switch, include/suo_hip.h; read when a launch is issued, like
+// SUO_WINO_HALO_DMA): the two passes (A/B, tests/test_gpu_wino_tail_one_pass.py: bit for bit the same).  The other tails have no such form
+// (profiles/REJECTED.md); with SUO_WINO_HALO_DMA=0 none has.  Kernel and launcher: csrc/conv_wino_x3_one_pass.hip.
+bool conv3x3_wino_f16x2_tail_one_pass() { return env_switch("SUO_WINO_TAIL_ONE_PASS", 1) != 0; }
+int launch_conv3x3_wino_f16x2_fused_next_one_pass(const ConvArgs& a, hipStream_t s, int tiles);
 
 // a.Wp = weights packed by pack_wino_weight_bf16x3 / _f16x2 (uint16 under a float pointer); 128 -> 128 or 64 -> 64 channels
 template <int NP>
@@ -129,7 +135,7 @@ int launch_conv3x3_wino_f16x2_fused(const ConvArgs& a, hipStream_t s) {
         // (with an up-sampled addend the kernel would need 14-23 registers more than the 256 a two-workgroup-per-CU kernel has: it spilled and measured
         //  SLOWER than the two launches, profiles/REJECTED.md -- not built; csrc/net.hip does not ask for it)
         if (a.up) { suo_set_error("conv3x3_wino_f16x2_fused: the next block's conv1 cannot ride on a tail with an up-sampled addend"); return SUO_ERR_ARG; }
-        if (dma) return launch_conv3x3_wino_f16x2_fused_dma(a, s, tiles);
+        if (dma) return conv3x3_wino_f16x2_tail_one_pass() ? launch_conv3x3_wino_f16x2_fused_next_one_pass(a, s, tiles) : launch_conv3x3_wino_f16x2_fused_dma(a, s, tiles);
         hipLaunchKernelGGL((wino3x3_x3_kernel<true, false, true, 4, 2, true>), dim3(tiles), dim3(256), 0, s, a);
     } else if (conv3x3_wino_f16x2_w8(tiles)) {
         if (a.up) hipLaunchKernelGGL((wino3x3_x3_kernel<true, true, true, 4, 2, false, false, true>), dim3(tiles), dim3(512), 0, s, a);

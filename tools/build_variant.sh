@@ -8,7 +8,7 @@ C=$ROOT/suo_slam_amd/csrc
 V=$ROOT/suo_slam_amd/variants
 mkdir -p $V
 FL="--offload-arch=gfx950 -O3 -std=c++17 -fPIC -ffp-contract=off -DSUO_TUNING"     # the tuning knobs of csrc/tune.h read the environment in these builds only
-VAR="conv conv_wino conv_wino_x3 conv_wino_x3_dma conv_wino_x3_skip_dma gemm_persist gemm_bf16x3 conv_small res_small res_small_x3 stem_x3 lm_frame lm_frame2 lm_dist ba_stage ba_api ba_ctx ba_drive net net_weights misc"
+VAR="conv conv_wino conv_wino_x3 conv_wino_x3_dma conv_wino_x3_skip_dma conv_wino_x3_one_pass gemm_persist gemm_bf16x3 conv_small res_small res_small_x3 stem_x3 lm_frame lm_frame2 lm_dist ba_stage ba_api ba_ctx ba_drive net net_weights misc"
 for f in $VAR; do /opt/rocm/bin/hipcc $FL "$@" -c $C/$f.hip -o $V/${f}_$NAME.o & done
 wait
 OBJS=""

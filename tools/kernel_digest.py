@@ -18,7 +18,7 @@ from concurrent.futures import ThreadPoolExecutor
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 CSRC = os.path.join(ROOT, "suo_slam_amd", "csrc")
-FILES = ["conv.hip", "conv_wino.hip", "conv_wino_x3.hip", "conv_wino_x3_dma.hip", "conv_wino_x3_skip_dma.hip", "gemm_bf16x3.hip", "gemm_persist.hip",
+FILES = ["conv.hip", "conv_wino.hip", "conv_wino_x3.hip", "conv_wino_x3_dma.hip", "conv_wino_x3_skip_dma.hip", "conv_wino_x3_one_pass.hip", "gemm_bf16x3.hip", "gemm_persist.hip",
          "res_small.hip", "res_small_x3.hip", "stem_x3.hip"]
 HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
 FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-ffp-contract=off", "--cuda-device-only", "-S",
