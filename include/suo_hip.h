@@ -12,7 +12,7 @@
  * pointers; `stream` is a hipStream_t passed as void* (NULL = internal stream + blocking).
  * All work is stream-ordered; the library never reads or writes host memory behind *_dev names.
  *
- * Runtime switches.  The library reads TWELVE environment variables that select between forms whose results the test suite holds against each other
+ * Runtime switches.  The library reads THIRTEEN environment variables that select between forms whose results the test suite holds against each other
  * (csrc/tune.h: env_switch), and one path -- SUO_RCCL_LIB, the RCCL library of suo_ba_comm_create_rccl when the process holds none yet; nothing else in the
  * environment changes what it does:
  *     SUO_WINO_BF16X3=0      networks are built on the fp32 matrix pipe (SUO_PIPE_F32)                      read when a network is created
@@ -32,6 +32,9 @@
  *     SUO_WINO_TAIL_ONE_PASS=0 the LDS-DMA form's fused tail with the next block's conv1 runs its 1x1 stages in two     as SUO_WINO_HALO_DMA (without which there is
  *                            passes of 64 pixels instead of one pass over the 128-pixel tile                         no such form)
  *                            (csrc/conv_wino_x3_one_pass.hip; bit for bit the same)
+ *     SUO_GEMM_WAVES_1X4=0   the fp16 1x1 GEMMs on 128 x 128 tiles and the lin -> head chain's first stage keep their four  as SUO_WINO_W8: when a launch is issued; fixed
+ *                            waves as 2 x 2 instead of side by side, each weight fragment requested once per workgroup     in a network's graph when it is captured
+ *                            (csrc/gemm_bf16x3.hip: W14; bit for bit the same)
  * The thresholds and A/B knobs behind the measurements of DESIGN.md / profiles/REJECTED.md (SUO_TUNE in csrc/tune.h: launch-size thresholds, tile choices, kernel
  * selections) are compiled to their defaults; only the variant builds of tools/build_variant.sh (-DSUO_TUNING) read them from the environment.  The host side above
  * the ABI has its own, in suo_slam_amd/: SUO_HIP_LIB (path of the library), SUO_BA_GRAPH / SUO_BA_HOST_SCHEDULE / SUO_FORCE_COLLECTIVES (ba_dist.py),

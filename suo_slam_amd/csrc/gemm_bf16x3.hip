@@ -88,9 +88,17 @@ void pack_gemm_weight_f16x2(const float* W, int N, int K, uint16_t* out, float* 
 // RB: 32-row blocks per wave -- 2: 128-row tiles; 1: 64-row tiles, for launches that would otherwise be fewer tiles than two per CU (the one-frame call)
 // NP: operand planes -- 3: three bf16 terms, six MFMAs per product block (csrc/bf16x3.h); 2: two fp16 terms, three MFMAs (csrc/f16x2.h: activations enter times
 //     2^S2_XSHIFT, the weights' rows times 2^t_n, the epilogue multiplies by g.oscale[n]; g.range_flag is raised when an activation leaves fp16's range)
-template <bool PRO, bool DUAL, bool RES, bool POOL, int NCB = 2, int RB = 2, int NP = 3>
+// W14 (fp16 form, 128 x 128 tiles): the four waves side by side, 1 x 4 -- wave w owns n-tile w (32 columns) over all 128 rows (4 x 1 accumulators).  The 2 x 2 form's
+//     waves (wm = 0, wn) and (wm = 1, wn) request the same weight fragments, 16 KB per k-step and workgroup through the CU's one vector-memory path for 8 KB of
+//     distinct data; here every fragment is requested once (two 16-byte loads per lane and k-step instead of four) and a wave reads twice the A fragments from LDS
+//     (eight ds_read_b128 instead of four).  Ring depth, request order, the MFMAs of an accumulator and their order are those of 2 x 2: every output and the range
+//     flag are bit for bit the same (tests/test_gpu_gemm_wave_layout.py).  POOL: both image rows of the tile are then in one wave (row blocks 0, 1 / 2, 3), the
+//     vertical maximum stays in registers.  SUO_GEMM_WAVES_1X4=0 keeps 2 x 2 (gemm_waves_1x4 below); measurements: profiles/gemm_wave_layout.txt
+template <bool PRO, bool DUAL, bool RES, bool POOL, int NCB = 2, int RB = 2, int NP = 3, bool W14 = false>
 __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(NP == 2 ? SUO_X3_F16_WAVES : 2))) void gemm_bf16x3_kernel(const GemmArgs g, const uint16_t* __restrict__ Wp) {
     static_assert(RB == 2 || !POOL, "the pooled epilogue is laid out for 128-row tiles");
+    static_assert(!W14 || (NP == 2 && NCB == 2 && RB == 2), "the 1 x 4 wave layout is built for the fp16 form's 128 x 128 tiles");
+    constexpr int RBW = W14 ? 2 * RB : RB, NCW = W14 ? NCB / 2 : NCB;         // 32-row / 32-column blocks of a wave
     constexpr int X3_BM = 64 * RB, X3_NR = X3_BM / X3_RPP;                    // rows of the tile; staging passes
     static_assert(X3_NR >= 1, "64-row tiles need the 16-wide k-step");
     constexpr int PLANE = X3_BM * X3_PITCH;                                   // bf16 elements of one plane
@@ -100,7 +108,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(NP == 2 ? S
     __shared__ __attribute__((aligned(16))) float P[2][512];                  // prologue scale / shift (K1 <= 512)
     const int tid = threadIdx.x, lane = tid & 63;
     const int w = __builtin_amdgcn_readfirstlane(tid >> 6);
-    const int wm = w >> 1, wn = w & 1;
+    const int wm = W14 ? 0 : w >> 1, wn = W14 ? w : w & 1;
     const int M = g.M, K = g.K1 + (DUAL ? g.K2 : 0), ldo = g.ldo;
     const float xs = NP == 2 ? s2_xscale(g.xscale) : 1.f;                   // the site's activation factor 2^s (csrc/f16x2.h)
     if (PRO) {
@@ -139,7 +147,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(NP == 2 ? S
     const int wvoff = lane * 16;
     f32x4 araw[X3_ASLOTS][X3_NR];
     constexpr int BSL = NP == 2 ? SUO_X3_F16_BSLOTS : X3_BSLOTS;          // weight k-groups in flight
-    u32x4 braw[BSL][NCB][NP];
+    u32x4 braw[BSL][NCW][NP];
     auto requestA = [&](int ks, int slot) {
         if (!DUAL || ks < ns1) {
 #pragma unroll
@@ -151,10 +159,10 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(NP == 2 ? S
     };
     auto requestB = [&](int kg, int slot) {                                   // kg: 16-wide k-group
 #pragma unroll
-        for (int cb = 0; cb < NCB; ++cb)
+        for (int cb = 0; cb < NCW; ++cb)
 #pragma unroll
             for (int p = 0; p < NP; ++p)
-                braw[slot][cb][p] = __builtin_bit_cast(u32x4, buf_load(w_srd, wvoff + p * 1024, ((kg * NBT + 2 * NCB * tn + NCB * wn + cb) * NP) * 1024));
+                braw[slot][cb][p] = __builtin_bit_cast(u32x4, buf_load(w_srd, wvoff + p * 1024, ((kg * NBT + 2 * NCB * tn + NCW * wn + cb) * NP) * 1024));
     };
     float xmax = 0.f;                                                         // NP = 2: largest scaled magnitude this lane split (range guard)
     auto split_store = [&](int ks, int slot, int stage) {
@@ -180,11 +188,11 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(NP == 2 ? S
             split_store4<NP, PLANE>(&As[(X3_RPP * i + ar) * X3_PITCH + 4 * aq], x[0], x[1], x[2], x[3]);
         }
     };
-    f32x16 acc[RB][NCB];
+    f32x16 acc[RBW][NCW];
 #pragma unroll
-    for (int i = 0; i < RB; ++i)
+    for (int i = 0; i < RBW; ++i)
 #pragma unroll
-        for (int j = 0; j < NCB; ++j)
+        for (int j = 0; j < NCW; ++j)
 #pragma unroll
             for (int r = 0; r < 16; ++r) acc[i][j][r] = 0.f;
     const int ngroups = nsteps * X3_GH;
@@ -203,13 +211,13 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(NP == 2 ? S
             __syncthreads();                                                  // stage u & 1 complete; every wave is past its reads of the other stage
             // this step's A fragments are requested first: their LDS latency passes under the split of the next step's activations
             const uint16_t* As = &S[u & 1][0];
-            bf16x8 af[X3_GH][RB][NP];
+            bf16x8 af[X3_GH][RBW][NP];
 #pragma unroll
             for (int h = 0; h < X3_GH; ++h)
 #pragma unroll
                 for (int p = 0; p < NP; ++p)
 #pragma unroll
-                    for (int rb = 0; rb < RB; ++rb) af[h][rb][p] = *(const bf16x8*)&As[p * PLANE + (32 * RB * wm + 32 * rb + (lane & 31)) * X3_PITCH + ko + 16 * h];
+                    for (int rb = 0; rb < RBW; ++rb) af[h][rb][p] = *(const bf16x8*)&As[p * PLANE + (32 * RBW * wm + 32 * rb + (lane & 31)) * X3_PITCH + ko + 16 * h];
             __builtin_amdgcn_sched_barrier(0);
             if (ks + 1 < nsteps) split_store(ks + 1, (u + 1) % X3_ASLOTS, (u + 1) & 1);
             requestA(ks + X3_ASLOTS < nsteps ? ks + X3_ASLOTS : nsteps - 1, u);
@@ -217,18 +225,18 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(NP == 2 ? S
             for (int h = 0; h < X3_GH; ++h) {
                 // weights of this k-group out of their ring slot, then the slot's next request
                 const int slot = (u * X3_GH + h) % BSL, kg = ks * X3_GH + h;
-                u32x4 bw[NCB][NP];
+                u32x4 bw[NCW][NP];
 #pragma unroll
-                for (int cb = 0; cb < NCB; ++cb)
+                for (int cb = 0; cb < NCW; ++cb)
 #pragma unroll
                     for (int p = 0; p < NP; ++p) bw[cb][p] = braw[slot][cb][p];
                 requestB(kg + BSL < ngroups ? kg + BSL : ngroups - 1, slot);
 #pragma unroll
                 for (int t = 0; t < split_terms<NP>(); ++t)             // the cross terms, smallest first (csrc/mma_ops.h)
 #pragma unroll
-                    for (int rb = 0; rb < RB; ++rb)
+                    for (int rb = 0; rb < RBW; ++rb)
 #pragma unroll
-                        for (int cb = 0; cb < NCB; ++cb) acc[rb][cb] = split_mma<NP>(t, af[h][rb], bw[cb], acc[rb][cb]);
+                        for (int cb = 0; cb < NCW; ++cb) acc[rb][cb] = split_mma<NP>(t, af[h][rb], bw[cb], acc[rb][cb]);
             }
             __builtin_amdgcn_sched_barrier(0);
         }
@@ -237,14 +245,16 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(NP == 2 ? S
     if constexpr (NP == 2) s2_raise(g.range_flag, xmax);
     float* T = reinterpret_cast<float*>(&S[0][0]) + w * (32 * 36);
     f32x4* PX = reinterpret_cast<f32x4*>(reinterpret_cast<float*>(&S[0][0]) + 4 * 32 * 36);      // POOL: 16 KB behind the four patches
-    f32x4 hold[POOL ? 2 : 1][POOL ? 2 : 1][POOL ? 4 : 1];
+    f32x4 hold[POOL ? 2 : 1][POOL ? NCW : 1][POOL ? 4 : 1];                  // POOL: image row 0's horizontal maxima (2 x 2: of the waves wm = 0)
+    const __amdgpu_buffer_rsrc_t p14_srd = make_srd(POOL && W14 ? g.pool_out : nullptr, POOL && W14 ? (size_t)(M >> 2) * ldo * sizeof(float) : 0);      // (W14 stores the pooled rows in the loop below)
+    const int prow14 = POOL && W14 ? (pool_base / g.pool_W >> 1) * (g.pool_W >> 1) + ((pool_base % g.pool_W) >> 1) : 0;      // pooled pixel of tile row 0, as prow0 below
     const __amdgpu_buffer_rsrc_t o_srd = make_srd((POOL && !g.out) ? (float*)g.pool_out : g.out, (POOL && !g.out) ? 0 : (size_t)M * ldo * sizeof(float));
     const __amdgpu_buffer_rsrc_t r_srd = make_srd(RES ? g.R : g.out, RES ? (size_t)M * g.ldr * sizeof(float) : 0);
 #pragma unroll
-    for (int rb = 0; rb < RB; ++rb)
+    for (int rb = 0; rb < RBW; ++rb)
 #pragma unroll
-        for (int cb = 0; cb < NCB; ++cb) {
-            const int col = BN * tn + 32 * NCB * wn + 32 * cb + (lane & 7) * 4;
+        for (int cb = 0; cb < NCW; ++cb) {
+            const int col = BN * tn + 32 * NCW * wn + 32 * cb + (lane & 7) * 4;
             f32x4 bv = f32x4{0.f, 0.f, 0.f, 0.f};
             if (g.bias) bv = *(const f32x4*)(g.bias + col);
             f32x4 osc = f32x4{1.f, 1.f, 1.f, 1.f};
@@ -253,7 +263,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(NP == 2 ? S
             if (RES) {
 #pragma unroll
                 for (int k = 0; k < 4; ++k) {
-                    const int row = pixel_of(32 * RB * wm + 32 * rb + (lane >> 3) + 8 * k);
+                    const int row = pixel_of(32 * RBW * wm + 32 * rb + (lane >> 3) + 8 * k);
                     rv[k] = buf_load(r_srd, row < M ? (row * g.ldr + col) * 4 : BUF_OOB, 0);
                 }
             }
@@ -262,7 +272,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(NP == 2 ? S
             __builtin_amdgcn_wave_barrier();
 #pragma unroll
             for (int k = 0; k < 4; ++k) {
-                const int row = pixel_of(32 * RB * wm + 32 * rb + (lane >> 3) + 8 * k);
+                const int row = pixel_of(32 * RBW * wm + 32 * rb + (lane >> 3) + 8 * k);
                 f32x4 o = patch_row4(T, lane, k);
                 if constexpr (NP == 2) o *= osc;                              // back to scale: an exact power of two per column
                 o += bv;
@@ -277,13 +287,22 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(NP == 2 ? S
 #pragma unroll
                     for (int q = 0; q < 4; ++q)
                         hm[q] = fmaxf(o[q], __int_as_float(__builtin_amdgcn_mov_dpp(__float_as_int(o[q]), 0x128, 0xf, 0xf, false)));
-                    if (wm == 0) hold[rb][cb][k] = hm;
+                    if constexpr (W14) {                                   // row blocks 0, 1 = image row 0, blocks 2, 3 = image row 1 of the same columns
+                        if (rb < 2) hold[rb & 1][cb][k] = hm;
+                        else if (!(lane & 8)) {
+                            f32x4 v;
+#pragma unroll
+                            for (int q = 0; q < 4; ++q) v[q] = fmaxf(hold[rb & 1][cb][k][q], hm[q]);
+                            const int j = 32 * (rb & 1) + (lane >> 3) + 8 * k;      // even: the pair (j, j + 1)
+                            buf_store(v, p14_srd, ((prow14 + (j >> 1)) * ldo + col) * 4);
+                        }
+                    } else if (wm == 0) hold[rb][cb][k] = hm;
                     else if (!(lane & 8)) PX[(((wn * 2 + rb) * 2 + cb) * 4 + k) * 32 + (lane >> 4) * 8 + (lane & 7)] = hm;
                 }
             }
             __builtin_amdgcn_wave_barrier();
         }
-    if (POOL) {
+    if (POOL && !W14) {
         __syncthreads();
         if (wm == 0 && !(lane & 8)) {
             const __amdgpu_buffer_rsrc_t p_srd = make_srd(g.pool_out, (size_t)(M >> 2) * ldo * sizeof(float));
@@ -315,6 +334,8 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(NP == 2 ? S
 //   stage 2: acc2 (64 rows x 64 columns, one 32 x 32 block per wave) += Y-half (K = 128, eight k-steps) x W2 -- over the two halves in ascending k: bit-identical to the
 //            fp16 GEMM launched on the stored tensor;  epilogue: per-channel rescale + bias, NCHW store of the first n_valid channels.
 // LDS 18 + 32 KB, three workgroups per CU like the plain fp16 GEMM.
+// W14: stage 1's waves side by side like gemm_bf16x3_kernel's W14 -- wave w owns n-tile w of the half over both 32-row blocks (2 x 1 accumulators), every W1 fragment is
+// requested once per workgroup; Y and stage 2 (one 32 x 32 block per wave, 2 x 2) are as they were.  Bit for bit the 2 x 2 form's result and flag.
 struct GemmChainArgs {
     const float* A; int lda, M;                           // [M, 256] rows
     const float* bias1; const float* osc1;                // [256]: stage 1 (BatchNorm folded), its per-column factors
@@ -324,6 +345,7 @@ struct GemmChainArgs {
     const float* xs1; const float* xs2;                   // the activation factors 2^s of the two sites (lin's input, tmpOut's input; nullptr: 2^S2_XSHIFT)
 };
 
+template <bool W14>
 __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(3))) void gemm_chain_head_kernel(const GemmChainArgs g, const uint16_t* __restrict__ W1, const uint16_t* __restrict__ W2) {
     static_assert(X3_BK == 16, "written for the 16-wide k-step");
     constexpr int NP = 2, NCB = 2, BM = 64, K1 = 256, N1 = 256, NBT1 = N1 / 32, NB2 = 2;
@@ -334,7 +356,9 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(3))) void g
     __shared__ __attribute__((aligned(16))) uint16_t Y[NP][BM * 128];         // relu(y1) * 16 of the current half: [plane][row][16 chunks of 8, chunk ^ (row & 15)]
     const int tid = threadIdx.x, lane = tid & 63;
     const int w = __builtin_amdgcn_readfirstlane(tid >> 6);
-    const int wm = w >> 1, wn = w & 1;
+    const int wm = w >> 1, wn = w & 1;                                        // stage 2's block of the wave
+    constexpr int RBW = W14 ? 2 : 1, NCW = W14 ? 1 : NCB;                     // stage 1: 32-row / 32-column blocks of a wave,
+    const int wm1 = W14 ? 0 : wm, wn1 = W14 ? w : wn;                         //          and which
     const int M = g.M;
     const float xs1 = s2_xscale(g.xs1), xs2 = s2_xscale(g.xs2);
     int bid = xcd_block_id();          // XCD-aware tile order
@@ -354,14 +378,14 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(3))) void g
     for (int r = 0; r < 16; ++r) acc2[r] = 0.f;
     for (int tn = 0; tn < 2; ++tn) {
         f32x4 araw[X3_ASLOTS];
-        u32x4 braw[BSL][NCB][NP];
+        u32x4 braw[BSL][NCW][NP];
         auto requestA = [&](int ks, int slot) { araw[slot] = buf_load(a_srd, avoff, ks * X3_BK * 4); };
         auto requestB = [&](int kg, int slot) {
 #pragma unroll
-            for (int cb = 0; cb < NCB; ++cb)
+            for (int cb = 0; cb < NCW; ++cb)
 #pragma unroll
                 for (int p = 0; p < NP; ++p)
-                    braw[slot][cb][p] = __builtin_bit_cast(u32x4, buf_load(w1_srd, wvoff + p * 1024, ((kg * NBT1 + 2 * NCB * tn + NCB * wn + cb) * NP) * 1024));
+                    braw[slot][cb][p] = __builtin_bit_cast(u32x4, buf_load(w1_srd, wvoff + p * 1024, ((kg * NBT1 + 2 * NCB * tn + NCW * wn1 + cb) * NP) * 1024));
         };
         auto split_store = [&](int slot, int stage) {
             uint16_t* As = &S[stage][0];
@@ -371,11 +395,13 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(3))) void g
             xmax = s2_track(s2_track(xmax, x[0], x[1]), x[2], x[3]);
             split_store4<NP, PLANE>(&As[ar * X3_PITCH + 4 * aq], x[0], x[1], x[2], x[3]);
         };
-        f32x16 acc[NCB];
+        f32x16 acc[RBW][NCW];
 #pragma unroll
-        for (int j = 0; j < NCB; ++j)
+        for (int i = 0; i < RBW; ++i)
 #pragma unroll
-            for (int r = 0; r < 16; ++r) acc[j][r] = 0.f;
+            for (int j = 0; j < NCW; ++j)
+#pragma unroll
+                for (int r = 0; r < 16; ++r) acc[i][j][r] = 0.f;
 #pragma unroll
         for (int u = 0; u < X3_ASLOTS; ++u) requestA(u, u);
 #pragma unroll
@@ -387,23 +413,27 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(3))) void g
                 const int ks = ks0 + u;
                 __syncthreads();
                 const uint16_t* As = &S[u & 1][0];
-                bf16x8 af[NP];
+                bf16x8 af[RBW][NP];
 #pragma unroll
-                for (int p = 0; p < NP; ++p) af[p] = *(const bf16x8*)&As[p * PLANE + (32 * wm + (lane & 31)) * X3_PITCH + ko];
+                for (int p = 0; p < NP; ++p)
+#pragma unroll
+                    for (int rb = 0; rb < RBW; ++rb) af[rb][p] = *(const bf16x8*)&As[p * PLANE + (32 * RBW * wm1 + 32 * rb + (lane & 31)) * X3_PITCH + ko];
                 __builtin_amdgcn_sched_barrier(0);
                 if (ks + 1 < nsteps) split_store((u + 1) % X3_ASLOTS, (u + 1) & 1);
                 requestA(ks + X3_ASLOTS < nsteps ? ks + X3_ASLOTS : nsteps - 1, u);
                 const int slot = u % BSL;
-                u32x4 bw[NCB][NP];
+                u32x4 bw[NCW][NP];
 #pragma unroll
-                for (int cb = 0; cb < NCB; ++cb)
+                for (int cb = 0; cb < NCW; ++cb)
 #pragma unroll
                     for (int p = 0; p < NP; ++p) bw[cb][p] = braw[slot][cb][p];
                 requestB(ks + BSL < nsteps ? ks + BSL : nsteps - 1, slot);
 #pragma unroll
                 for (int t = 0; t < split_terms<NP>(); ++t)
 #pragma unroll
-                    for (int cb = 0; cb < NCB; ++cb) acc[cb] = split_mma<NP>(t, af, bw[cb], acc[cb]);
+                    for (int rb = 0; rb < RBW; ++rb)
+#pragma unroll
+                        for (int cb = 0; cb < NCW; ++cb) acc[rb][cb] = split_mma<NP>(t, af[rb], bw[cb], acc[rb][cb]);
                 __builtin_amdgcn_sched_barrier(0);
             }
         }
@@ -416,15 +446,17 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(3))) void g
             for (int p = 0; p < NP; ++p) b2[kk][p] = __builtin_bit_cast(u32x4, buf_load(w2_srd, wvoff + p * 1024, (((8 * tn + kk) * NB2 + wn) * NP) * 1024));
         float* T = reinterpret_cast<float*>(&S[0][0]) + w * (32 * 36);
 #pragma unroll
-        for (int cb = 0; cb < NCB; ++cb) {
-            const int lcol = 32 * NCB * wn + 32 * cb + (lane & 7) * 4;       // column within the half
+        for (int rb = 0; rb < RBW; ++rb)
+#pragma unroll
+        for (int cb = 0; cb < NCW; ++cb) {
+            const int lcol = 32 * NCW * wn1 + 32 * cb + (lane & 7) * 4;      // column within the half
             const f32x4 bv = *(const f32x4*)(g.bias1 + 128 * tn + lcol), osc = *(const f32x4*)(g.osc1 + 128 * tn + lcol);
 #pragma unroll
-            for (int r = 0; r < 16; ++r) T[patch_at(r, lane)] = acc[cb][r];
+            for (int r = 0; r < 16; ++r) T[patch_at(r, lane)] = acc[rb][cb][r];
             __builtin_amdgcn_wave_barrier();
 #pragma unroll
             for (int k = 0; k < 4; ++k) {
-                const int row = 32 * wm + (lane >> 3) + 8 * k;               // row of the tile
+                const int row = 32 * RBW * wm1 + 32 * rb + (lane >> 3) + 8 * k;      // row of the tile
                 f32x4 o = patch_row4(T, lane, k);
                 o *= osc;
                 o += bv;
@@ -470,6 +502,11 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(3))) void g
     }
 }
 
+// The fp16 form's 128 x 128 tiles and the chain's stage 1 run their four waves side by side (the kernels' comments: W14).  SUO_GEMM_WAVES_1X4=0 (supported switch,
+// include/suo_hip.h; read when a launch is issued, like SUO_WINO_SKIP_DMA -- a network's captured graph keeps the form it was captured with): 2 x 2 (A/B,
+// tests/test_gpu_gemm_wave_layout.py: bit for bit the same).  64-row and 64-column tiles and the bf16x3 form have the 2 x 2 layout only.
+bool gemm_waves_1x4() { return env_switch("SUO_GEMM_WAVES_1X4", 1) != 0; }
+
 bool gemm_chain_head_takes(int M, int lda, int n_valid, int hw) {
     return M > 0 && M % 64 == 0 && lda % 4 == 0 && n_valid > 0 && n_valid <= 64 && hw > 0 && hw % 64 == 0 && M % hw == 0 && (size_t)M * lda * 4 < ((size_t)1 << 31);
 }
@@ -482,7 +519,8 @@ int launch_gemm_chain_head(const float* A, int lda, int M, const uint16_t* W1h, 
         return SUO_ERR_ARG;
     }
     GemmChainArgs g = {A, lda, M, bias1, osc1, bias2, osc2, out, n_valid, hw, range_flag, xs1, xs2};
-    hipLaunchKernelGGL(gemm_chain_head_kernel, dim3(M / 64), dim3(256), 0, s, g, W1h, W2h);
+    if (gemm_waves_1x4()) hipLaunchKernelGGL(gemm_chain_head_kernel<true>, dim3(M / 64), dim3(256), 0, s, g, W1h, W2h);
+    else hipLaunchKernelGGL(gemm_chain_head_kernel<false>, dim3(M / 64), dim3(256), 0, s, g, W1h, W2h);
     SUO_HIP_CHECK(hipGetLastError());
     return SUO_OK;
 }
@@ -513,11 +551,19 @@ static int launch_gemm_split(const GemmArgs& g, const uint16_t* Wx3, hipStream_t
                                    else if (n64) hipLaunchKernelGGL((gemm_bf16x3_kernel<P_, D_, R_, false, 1, 2, NP>), dim3(tiles), dim3(256), 0, s, g, Wx3); \
                                    else if (rows64) hipLaunchKernelGGL((gemm_bf16x3_kernel<P_, D_, R_, false, 2, 1, NP>), dim3(tiles), dim3(256), 0, s, g, Wx3); \
                                    else hipLaunchKernelGGL((gemm_bf16x3_kernel<P_, D_, R_, false, 2, 2, NP>), dim3(tiles), dim3(256), 0, s, g, Wx3); } while (0)
+#define X3_LAUNCH14(P_, D_, R_) do { if constexpr (NP == 2) { if (g.pool_out) hipLaunchKernelGGL((gemm_bf16x3_kernel<P_, D_, R_, true, 2, 2, 2, true>), dim3(tiles), dim3(256), 0, s, g, Wx3); \
+                                     else hipLaunchKernelGGL((gemm_bf16x3_kernel<P_, D_, R_, false, 2, 2, 2, true>), dim3(tiles), dim3(256), 0, s, g, Wx3); } } while (0)
     const bool res = g.R != nullptr;
-    if (g.pro_scale) { if (res) X3_LAUNCH(true, false, true); else X3_LAUNCH(true, false, false); }
+    if (NP == 2 && !n64 && !rows64 && gemm_waves_1x4()) {                    // the fp16 form's 128 x 128 tiles: the waves side by side
+        if (g.pro_scale) { if (res) X3_LAUNCH14(true, false, true); else X3_LAUNCH14(true, false, false); }
+        else if (g.K2) { if (res) X3_LAUNCH14(false, true, true); else X3_LAUNCH14(false, true, false); }
+        else { if (res) X3_LAUNCH14(false, false, true); else X3_LAUNCH14(false, false, false); }
+    }
+    else if (g.pro_scale) { if (res) X3_LAUNCH(true, false, true); else X3_LAUNCH(true, false, false); }
     else if (g.K2) { if (res) X3_LAUNCH(false, true, true); else X3_LAUNCH(false, true, false); }
     else { if (res) X3_LAUNCH(false, false, true); else X3_LAUNCH(false, false, false); }
 #undef X3_LAUNCH
+#undef X3_LAUNCH14
     SUO_HIP_CHECK(hipGetLastError());
     return SUO_OK;
 }
